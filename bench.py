@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|2b|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|2b|3|4|5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, and prints one JSON line (`value`,
+`ms_per_step` = milliseconds per timed step, ...).  `--full` adds the side figures described below
+(rooflines, kernel groups, eager and alternative-schedule loops, CPU baselines, the `also` block of
+the other configurations).  `--dump-outputs DIR` writes what the last timed step computed (configs
+2 / 2b) as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared array by array.
 
 With N > 1 and no WORLD_SIZE in the environment the script re-launches itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank
@@ -95,9 +101,20 @@ def parse(argv=None):
     ap.add_argument("--graph-steps", type=int, default=8,
                     help="steps captured per hipGraph (a replay boundary costs ~5 us): 8 at EVERY N, so that the first "
                          "step of a scaling curve measures the gradient exchange, not a change of graph shape")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side figures: CPU baselines (all configurations) and, at configs 2 / 2b, the "
+                         "per-kernel-group times and rooflines, the eager step, the rulebook build, the round-4, "
+                         "steady-state, cache-warm and one-step-per-replay loops and (config 2, N = 1) the compact "
+                         "block of the other configurations.  Off: the run times the headline loop and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="configs 2 / 2b: after the timed steps write what the last timed step computed (the layer's "
+                         "output features, the input-feature and weight gradients) as DIR/<name>.npy, float32, at most "
+                         "64 MB in all (a fixed, seeded sample of rows beyond that)")
     args = ap.parse_args(argv)
     if args.cold:
         args.scenes = max(args.scenes, 4)
+    if args.dump_outputs and args.config not in ("2", "2b"):
+        ap.error("--dump-outputs is implemented for configs 2 and 2b")
     return args
 
 
@@ -127,7 +144,8 @@ def maybe_spawn(args, argv) -> None:
         raise SystemExit(0)
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC (RCCL across processes)
-    os.execvpe(cmd[0], cmd, env)
+    import subprocess                                      # a child process, not exec: the launcher stays the parent
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 # ------------------------------------------------------------------ helpers
@@ -218,6 +236,29 @@ def roofline_obj(group, ab, ms, kernel, traffic=None, extra=None):
     if extra:
         r.update(extra)
     return r
+
+
+DUMP_BYTES = 60_000_000        # data bytes of --dump-outputs (64 MB in all with the .npy headers, with room to spare)
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """Writes every tensor of `arrays` (name -> tensor) as <path>/<name>.npy in float32.  When the float32 total exceeds
+    `budget`, every array keeps the same fraction of its rows (dim 0), a fixed sample (numpy seed 0, ascending row order),
+    so that two builds given the same arguments write the same rows.  Returns name -> {shape, rows_sampled}."""
+    arrs = {k: v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float32)
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(path, exist_ok=True)
+    info = {}
+    for name, a in arrs.items():
+        rows = None
+        if total > budget and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, a.shape[0] * budget // total)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        info[name] = {"shape": list(a.shape), "rows_sampled": None if rows is None else int(rows.shape[0])}
+    return info
 
 
 class Dist:
@@ -530,7 +571,7 @@ def run_layer(args, D: Dist):
             return ops.build_rulebook(sc.indices, 1, sc.shape, [3] * 3, [1] * 3, [1] * 3, [1] * 3, [0] * 3,
                                       True, do_sort=conv_mod.MODULE_DO_SORT)[0]
         torch.cuda.synchronize()
-        if si == 0:                      # rulebook build: timed separately (wall, incl. enqueue)
+        if si == 0 and args.full:        # rulebook build: timed separately (wall, incl. enqueue)
             for _ in range(5):
                 t0 = time.perf_counter()
                 build()
@@ -544,12 +585,18 @@ def run_layer(args, D: Dist):
     n = scenes[0].n
     bucket = GradBucket(net.parameters()) if D.multi else None   # fp16 gradient, reduced in place
 
-    def compute(sc):
+    def compute(sc, keep=None):
+        """One step; `keep` (a dict) receives what the step hands its caller: output features, dX, dW."""
         net.weight.grad = None
         sc.feats.grad = None
         y = net(sc.x)
         y.features.backward(sc.dout)
+        if keep is not None:
+            keep.update(out_features=y.features.detach(), grad_features=sc.feats.grad, grad_weight=net.weight.grad)
 
+    # what the last step of each captured graph hands its caller (tensors of the graph's pool, rewritten by every
+    # replay), and what the last step run so far handed it: --dump-outputs writes the latter after the timed steps
+    outs_of, last_out = {}, [None]
     launch = "eager"
     fwd_dispatched = {}   # forward launches per kernel family inside the timed graph's capture
     graphs = None         # one step per replay, one graph per scene
@@ -574,7 +621,7 @@ def run_layer(args, D: Dist):
             for sc in scenes:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                    compute(sc)
+                    compute(sc, outs_of.setdefault(id(g), {}))
                 graphs.append(g)
                 graph_grads.append(net.weight.grad)   # each graph writes dW into its own pool buffer
             if U > 1:
@@ -582,7 +629,7 @@ def run_layer(args, D: Dist):
                 lc0 = {k: _lib_count(k) for k in ("igemm_ws", "igemm_v4")}
                 with torch.cuda.graph(graph_u, capture_error_mode=CAPTURE_MODE):
                     for u in range(U):
-                        compute(scenes[u % S])
+                        compute(scenes[u % S], outs_of.setdefault(id(graph_u), {}) if u == U - 1 else None)
                         dws_a.append(net.weight.grad)
                 # which forward kernel the TIMED graph holds (the library's own record of what it dispatched while
                 # the graph was captured -- not the class state seen afterwards: round-5 ADVICE)
@@ -591,7 +638,7 @@ def run_layer(args, D: Dist):
                     graph_b = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph_b, capture_error_mode=CAPTURE_MODE):
                         for u in range(U):
-                            compute(scenes[u % S])
+                            compute(scenes[u % S], outs_of.setdefault(id(graph_b), {}) if u == U - 1 else None)
                             dws_b.append(net.weight.grad)
                 else:
                     graph_w = torch.cuda.CUDAGraph()
@@ -605,7 +652,7 @@ def run_layer(args, D: Dist):
                     dws = []
                     with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
                         for u in range(r):
-                            compute(scenes[u % S])
+                            compute(scenes[u % S], outs_of.setdefault(id(g), {}) if u == r - 1 else None)
                             dws.append(net.weight.grad)
                     rem_graphs[r] = (g, dws)
             launch = "hipgraph"
@@ -614,6 +661,7 @@ def run_layer(args, D: Dist):
                   file=sys.stderr)
             graphs = graph_u = graph_w = graph_b = None
             graph_grads, rem_graphs = [], {}
+            outs_of.clear()
             torch.cuda.synchronize()
     if graph_u is None:
         U = 1
@@ -628,8 +676,10 @@ def run_layer(args, D: Dist):
         if graphs is not None:
             graphs[i].replay()
             net.weight.grad = graph_grads[i]                       # the dW this replay produced
+            last_out[0] = outs_of[id(graphs[i])]
         else:
-            compute(scenes[i])
+            last_out[0] = {}
+            compute(scenes[i], last_out[0])
         if bucket is not None:
             bucket.all_reduce(average=True)                        # one RCCL call per step
 
@@ -664,6 +714,7 @@ def run_layer(args, D: Dist):
             if h.pending:
                 main.wait_event(h.reduced)           # its previous bucket has been reduced: buffers are free
             h.graph.replay()
+            last_out[0] = outs_of[id(h.graph)]
             h.done.record(main)
             with torch.cuda.stream(side_ar):
                 side_ar.wait_event(h.done)
@@ -698,15 +749,21 @@ def run_layer(args, D: Dist):
         elif gu is not None:
             for _ in range(k // U):
                 gu.replay()
+            if k >= U and not warm:
+                last_out[0] = outs_of[id(gu)]
             k = k % U
             if not warm and k in rem_graphs:
                 rem_graphs[k][0].replay()
+                last_out[0] = outs_of[id(rem_graphs[k][0])]
                 k = 0
         for _ in range(k):
             step(warm)
 
     run_steps(args.prewarm)              # untimed, stated in config.prewarm_steps; the contract's W + K follow
     elapsed = timed_region(D, run_steps, args.warmup, args.steps)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything below replays the graphs again
+        dumped = dump_outputs(args.dump_outputs, last_out[0])
     # The timed region above is what the contract asks for; its wall clock holds a FIXED cost of ~30-40 us (first
     # graph launch until the first kernel runs + the wake-up of the final synchronize: fitted over K = 20 / 40 / 80 /
     # 160, profiles/r04_experiments.md), i.e. 7 % of a 20-step region and 0.1 % of a 2000-step one.  The same loop over a
@@ -715,7 +772,7 @@ def run_layer(args, D: Dist):
     # driver's line).  That shaped the measurement around a 20-step run and put a protocol kink between N = 1 and N = 2
     # (ADVICE / VERDICT r4), so `value` is back on the plain schedule; the same figure is kept here for comparison.
     round4 = None
-    if not D.multi and graph_u is not None and 1 <= args.steps <= 40 and args.steps != U:
+    if args.full and not D.multi and graph_u is not None and 1 <= args.steps <= 40 and args.steps != U:
         try:
             gk = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gk, capture_error_mode=CAPTURE_MODE):
@@ -736,7 +793,7 @@ def run_layer(args, D: Dist):
         except Exception as e:                                        # a side figure must not cost the headline
             round4 = {"error": f"{type(e).__name__}: {e}"[:200]}
     steady = None
-    if not D.multi and args.steps < 400:
+    if args.full and not D.multi and args.steps < 400:
         k_steady = U * max(1, 400 // U)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -747,7 +804,7 @@ def run_layer(args, D: Dist):
                   "value": round(sum(sc.n for sc in scenes) / S * k_steady / dt, 1),
                   "note": "same loop, same graphs, more steps: the fixed cost of a timed region amortised"}
     warm_ms = None
-    if not D.multi and S > 1:             # the same K steps on ONE scene (Infinity-Cache-resident)
+    if args.full and not D.multi and S > 1:   # the same K steps on ONE scene (Infinity-Cache-resident)
         run_steps(min(args.warmup, 50), warm=True)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -755,7 +812,7 @@ def run_layer(args, D: Dist):
         torch.cuda.synchronize()
         warm_ms = (time.perf_counter() - t1) / args.steps * 1e3
     single_replay_ms = None
-    if graph_u is not None and not D.multi:   # the rotating K steps with one step per replay, for reference
+    if args.full and graph_u is not None and not D.multi:   # the rotating K steps, one step per replay, for reference
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -788,6 +845,42 @@ def run_layer(args, D: Dist):
     value = n_total * args.steps / elapsed
     if rank != 0:
         return None
+
+    s = scenes[0].feats.element_size()
+    P = sum(sc.P for sc in scenes) / S
+    dt = args.dtype
+    layout_info = None
+    if scenes[0].rb.layout is not None:
+        head = scenes[0].rb.layout[:4].cpu().tolist()
+        layout_info = {"class": "regrouped" if head[0] else "identity", "rows_with_a_neighbour": head[1]}
+    cfg_name = "configs[1]" if args.config == "2" and kind == "uniform" else f"config {args.config}"
+    result = {
+        "metric": METRIC, "value": value, "unit": "voxels/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": f"SubMConv3d 3x3x3 C={C}->{K} {dt}, {int(n_mean)} {kind} voxels/scene in "
+                               f"{scenes[0].shape[2]}x{scenes[0].shape[1]}x{scenes[0].shape[0]} (BASELINE {cfg_name}), "
+                               f"{S} distinct scenes per GPU visited round-robin, rulebook reused via indice_key",
+                   "voxels_per_gpu": int(n_mean), "pairs_per_voxel": round(P / n_mean, 4), "launch": launch,
+                   "steps_per_replay": U if launch == "hipgraph" else None, "scenes_rotated": S,
+                   "rulebook_source": "net(x): the module's own build, default environment" if args.sort == "auto"
+                                      else f"net(x) with SPCONV_DO_SORT={'1' if args.sort == 'on' else '0'}",
+                   "rows_layout": layout_info, "mask_sort": scenes[0].rb.argsort_fwd is not None,
+                   "forward_launches_in_timed_graph": fwd_dispatched or None,
+                   "prewarm_steps": args.prewarm, "gradient_exchange_check": exchange_check,
+                   "parallelism": f"dp{world}",
+                   "ranks_seen": ranks_seen,
+                   "dist_backend": D.backend if D.multi else None,
+                   "gradient_exchange": None if not D.multi else (
+                       f"one flat-bucket all-reduce (average) of the {U} dW of a replay ({U} x {net.weight.numel() * s} B) "
+                       f"on a side stream, overlapped with the next replay (two graphs with their own gradient "
+                       f"buffers alternate)" if overlap is not None else "blocking all-reduce of dW after every step")},
+    }
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped,
+                                    "step": "the last timed step (rank 0): output features, dX, dW"}
+    if not args.full:
+        return result
 
     # ---- per-kernel-group device time (HIP events on the launch stream), cold and warm -------
     w = net.weight.detach()
@@ -856,19 +949,14 @@ def run_layer(args, D: Dist):
     t_sort_dev = None
     if scenes[0].rb.argsort_fwd is not None:      # mask sort + tile-order table copies: once per rulebook
         t_sort_dev = round(event_time_ms(lambda i: ops.sort_rulebook(scenes[0].rb), iters=10, warm=2), 4)
-    t_layout_dev, layout_info = None, None
+    t_layout_dev = None
     if scenes[0].rb.layout is not None:           # the rows layout alone (count -> scan -> scatter), part of every build
         t_layout_dev = round(event_time_ms(lambda i: ops.rows_layout(scenes[0].rb), iters=10, warm=2), 4)
-        head = scenes[0].rb.layout[:4].cpu().tolist()
-        layout_info = {"class": "regrouped" if head[0] else "identity", "rows_with_a_neighbour": head[1]}
-    s = scenes[0].feats.element_size()
-    P = sum(sc.P for sc in scenes) / S
     ab = algorithmic_bytes(n_mean, n_mean, C, K, 27, s)
     # stricter count for the fused backward launch: dout is read once for both gradients
     # (dout + feat + din + pair table + Native lists of P pairs + W + dW)
     strict = {"fwd": ab["fwd"], "bwd": s * n_mean * K + 2 * s * n_mean * C + 4 * 27 * n_mean + 8 * P
               + 2 * s * 27 * C * K}
-    dt = args.dtype
     ops.poll_class(scenes[0].rb)
     dense_fwd = bool(getattr(scenes[0].rb.layout, "_spx_dense", False)) and C == 64 and K == 64
     if fwd_dispatched:
@@ -893,28 +981,7 @@ def run_layer(args, D: Dist):
         return {k: {"ms": round(v, 5), "algorithmic_MB": round(ab[k] / 1e6, 3),
                     "GBps": round(ab[k] / (v * 1e-3) / 1e9, 1)} for k, v in t.items()}
     total_bytes = ab["fwd"] + ab["bwd"]
-    cfg_name = "configs[1]" if args.config == "2" and kind == "uniform" else f"config {args.config}"
-    result = {
-        "metric": METRIC, "value": value, "unit": "voxels/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": f"SubMConv3d 3x3x3 C={C}->{K} {dt}, {int(n_mean)} {kind} voxels/scene in "
-                               f"{scenes[0].shape[2]}x{scenes[0].shape[1]}x{scenes[0].shape[0]} (BASELINE {cfg_name}), "
-                               f"{S} distinct scenes per GPU visited round-robin, rulebook reused via indice_key",
-                   "voxels_per_gpu": int(n_mean), "pairs_per_voxel": round(P / n_mean, 4), "launch": launch,
-                   "steps_per_replay": U if launch == "hipgraph" else None, "scenes_rotated": S,
-                   "rulebook_source": "net(x): the module's own build, default environment" if args.sort == "auto"
-                                      else f"net(x) with SPCONV_DO_SORT={'1' if args.sort == 'on' else '0'}",
-                   "rows_layout": layout_info, "mask_sort": scenes[0].rb.argsort_fwd is not None,
-                   "forward_launches_in_timed_graph": fwd_dispatched or None,
-                   "prewarm_steps": args.prewarm, "gradient_exchange_check": exchange_check,
-                   "parallelism": f"dp{world}",
-                   "ranks_seen": ranks_seen,
-                   "dist_backend": D.backend if D.multi else None,
-                   "gradient_exchange": None if not D.multi else (
-                       f"one flat-bucket all-reduce (average) of the {U} dW of a replay ({U} x {net.weight.numel() * s} B) "
-                       f"on a side stream, overlapped with the next replay (two graphs with their own gradient "
-                       f"buffers alternate)" if overlap is not None else "blocking all-reduce of dW after every step")},
+    result.update({
         "roofline": r_cold, "roofline_cold": r_cold, "roofline_warm": r_warm,
         "kernels": ktable(t_cold), "kernels_warm": ktable(t_warm),
         "kernels_note": "each group is timed alone (its own hipGraph, rotating over the scenes); in a step the "
@@ -938,8 +1005,8 @@ def run_layer(args, D: Dist):
         "rulebook_device_ms": round(t_rule_dev, 4),
         "rows_layout_device_ms": t_layout_dev,
         "mask_sort_device_ms": t_sort_dev,
-    }
-    if world == 1 and not args.no_cpu_baseline:
+    })
+    if world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_layer(scenes[0].idx_np, scenes[0].shape, C, K, seed=1)
     return result
 
@@ -1025,7 +1092,7 @@ def run_int8(args, D: Dist):
                       "parallelism": f"dp{D.world}", "ranks_seen": ranks_seen},
            "roofline": r, "roofline_cold": r,
            "roofline_warm": roofline_obj("fwd", ab, t_warm, r["kernel"], None, {"memory_level": "Infinity Cache"})}
-    if D.world == 1 and not args.no_cpu_baseline:
+    if D.world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_int8(scenes[0][0], scenes[0][1], C, K)
     return res
 
@@ -1082,8 +1149,7 @@ def run_net(args, D: Dist):
     def run_steps(k):
         for _ in range(k):
             step()
-    warm = min(args.warmup, 20)
-    steps = min(args.steps, 200)
+    warm, steps = args.warmup, args.steps
     elapsed = timed_region(D, run_steps, warm, steps)
     eager_st_ms = None
     if not D.multi:          # the eager step with the autograd engine on the calling thread (run_layer: the recipe)
@@ -1161,7 +1227,7 @@ def run_net(args, D: Dist):
         res["eager_ms_per_step"] = eager_ms
     if eager_st_ms is not None:
         res["eager_ms_per_step_single_thread_autograd"] = eager_st_ms
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         t, done = cpu_baseline_net(recs)
         frac_layers = done / len(recs)
         res["cpu_baseline"] = {"value": n_mean / t * frac_layers if done < len(recs) else n_mean / t,
@@ -1312,7 +1378,7 @@ def run_infer(args, D: Dist):
                 ind, f, _ = data[cnt[0] % S]
                 cnt[0] += 1
                 net(spconv.SparseConvTensor(f, ind, shape, bs))
-    warm, steps = min(args.warmup, 20), min(args.steps, 200)
+    warm, steps = args.warmup, args.steps
     t_eager = timed_region(D, eager_steps, warm, steps)
     bounds = {k: int(v * 1.1) + 1 for k, v in seen.items()}
     n_max = max(d[0].shape[0] for d in data)
@@ -1406,6 +1472,7 @@ def also_block(args, D: Dist):
     for cfg in ("2b", "5", "3", "4", "4i"):
         a = copy.copy(args)
         a.config, a.no_cpu_baseline, a.voxels, a.channels, a.scene = cfg, True, None, None, None
+        a.dump_outputs = None                               # the headline's outputs only
         a.scenes = min(args.scenes, 4)
         a.steps = min(args.steps, 400 if cfg in ("2b", "5") else 40)
         a.warmup = min(args.warmup, 40 if cfg in ("2b", "5") else 8)
@@ -1524,7 +1591,7 @@ def main(argv=None):
         result = run_infer(args, D)
     else:
         result = run_net(args, D)
-    if D.rank == 0 and D.world == 1 and args.config == "2" and not args.no_also:
+    if D.rank == 0 and D.world == 1 and args.config == "2" and args.full and not args.no_also:
         result["also"] = also_block(args, D)
         # the same, compact, inside the object the driver's record keeps whole
         result["roofline"]["also"] = {

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ def _run(args, extra_env=None, timeout=420):
 
 
 def test_bench_single_gpu_contract(cuda):
-    r = _run(["--steps", "20", "--warmup", "8", "--no-cpu-baseline", "--scenes", "4"])
+    r = _run(["--steps", "20", "--warmup", "8", "--no-cpu-baseline", "--scenes", "4", "--full"])
     assert r["n_gpus"] == 1 and r["steps"] == 20 and r["warmup"] == 8
     # the same replay structure at every N: 8 steps per graph, no untimed steps beyond --warmup; round
     # 4's schedule (one K-step graph behind 400 pre-warm steps) rides along as a side figure
@@ -39,6 +40,40 @@ def test_bench_single_gpu_contract(cuda):
     for cfg, c in r["also"].items():
         assert "error" not in c, (cfg, c)
         assert c["value"] > 0 and c["ms_per_step"] > 0 and 0 < c["roofline"]["frac"] < 1.0
+
+
+def test_bench_plain_run_times_only_the_headline_and_dumps_outputs(cuda, tmp_path):
+    """Without --full the line holds the headline and no side figure; --dump-outputs writes the last timed step's
+    output features, dX and dW, and matches the same step run eagerly on the same inputs (scene 3 of 4 after 20 steps)."""
+    r = _run(["--steps", "20", "--warmup", "8", "--scenes", "4", "--dump-outputs", str(tmp_path)])
+    assert r["steps"] == 20 and r["warmup"] == 8 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["unit"] == "voxels/s" and r["higher_is_better"] is True and r["dtype"] == "f16"
+    for side in ("also", "cpu_baseline", "roofline", "kernels", "round4_protocol", "steady_state", "rulebook_ms"):
+        assert side not in r, side
+    n = r["config"]["voxels_per_gpu"]
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("out_features", "grad_features", "grad_weight")}
+    assert got["out_features"].shape == (n, 64) and got["grad_features"].shape == (n, 64)
+    assert got["grad_weight"].shape == (64, 3, 3, 3, 64)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0 for a in got.values())
+    assert sum(os.path.getsize(tmp_path / f"{k}.npy") for k in got) <= 64_000_000
+    # the same step, eager, in this process: bench.run_layer's inputs for scene 3 (20 = 2 x 8 + 4 steps rotating over
+    # 4 scenes end on scene 3), weights from torch.manual_seed(0)
+    import torch
+    import bench
+    import spconv_amd.pytorch as spconv
+    idx, shape = bench.make_scene("uniform", 100_000, seed=3)
+    torch.manual_seed(0)
+    net = spconv.SubMConv3d(64, 64, 3, bias=False, indice_key="bench").to(cuda, torch.float16)
+    g = torch.Generator(device="cpu").manual_seed(1234 + 3)
+    feats = (torch.rand((idx.shape[0], 64), generator=g) * 2 - 1).to(cuda, torch.float16).requires_grad_(True)
+    dout = ((torch.rand((idx.shape[0], 64), generator=g) * 2 - 1) * 0.2).to(cuda, torch.float16)
+    y = net(spconv.SparseConvTensor(feats, torch.from_numpy(idx).to(cuda), shape, 1))
+    y.features.backward(dout)
+    want = {"out_features": y.features, "grad_features": feats.grad, "grad_weight": net.weight.grad}
+    for k, w in want.items():
+        w = w.detach().float().cpu().numpy()
+        assert w.shape == got[k].shape, k
+        assert np.abs(got[k] - w).max() <= 2e-3 * np.abs(w).max(), k
 
 
 def test_bench_gpus_2_spawns_two_ranks(cuda):

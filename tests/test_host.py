@@ -190,6 +190,30 @@ def test_bench_gpus_flag_becomes_a_launcher(tmp_path):
         del os.environ["WORLD_SIZE"]
 
 
+def test_bench_dump_outputs_float32_within_budget_and_repeatable(tmp_path):
+    """bench.dump_outputs: float32 .npy per array; over the budget every array keeps the same fixed, seeded rows, so two
+    runs (two builds) write the same sample.  --full is off by default; --dump-outputs is refused where not implemented."""
+    import bench
+    a = torch.arange(4000 * 8, dtype=torch.float64).reshape(4000, 8)
+    b = torch.linspace(-1, 1, 1000 * 8, dtype=torch.float16).reshape(1000, 8)
+    info = bench.dump_outputs(tmp_path / "small", {"a": a, "b": b})
+    assert info == {"a": {"shape": [4000, 8], "rows_sampled": None}, "b": {"shape": [1000, 8], "rows_sampled": None}}
+    got = np.load(tmp_path / "small" / "a.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, a.float().numpy())
+    budget = 40_000                                   # 160 000 B of float32 in all -> a quarter of the rows
+    for d in ("r1", "r2"):
+        info = bench.dump_outputs(tmp_path / d, {"a": a, "b": b}, budget=budget)
+        assert info["a"]["rows_sampled"] == 1000 and info["b"]["rows_sampled"] == 250
+        assert sum(np.load(tmp_path / d / f"{k}.npy").nbytes for k in "ab") <= budget
+    for k in "ab":
+        assert np.array_equal(np.load(tmp_path / "r1" / f"{k}.npy"), np.load(tmp_path / "r2" / f"{k}.npy"))
+    rows = np.load(tmp_path / "r1" / "a.npy")[:, 0] / 8
+    assert np.all(np.diff(rows) > 0)                  # ascending original row order
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    with pytest.raises(SystemExit):
+        bench.parse(["--config", "4", "--dump-outputs", str(tmp_path)])
+
+
 def test_kernel_timer_api_and_debug_dump(tmp_path, monkeypatch):
     """spconv/tools.py:23-78 surface; on a box without a GPU the timer is inert like the reference's
     CPU-only build.  SPCONV_DEBUG_SAVE_PATH pickles what a failing call was given."""

@@ -282,31 +282,23 @@ def test_oracle_rulebook_equals_reference_digests_at_baseline_sizes():
 
 
 def test_oracle_rulebook_equals_live_reference_library():
-    """Randomised sweep against oracle/_ref/libspconv_ref.so when it is present."""
+    """Randomised sweep against the reference's own rulebook code: the digests of what it made of the 40 seeded cases
+    (tests/golden/ref_live_digests.json, make_ref_live_golden.py) on every box, and oracle/_ref/libspconv_ref.so itself
+    where it is present."""
     from oracle import ref
-    if not ref.available():
-        pytest.skip("oracle/_ref not built here (needs /root/reference: make -C oracle ref)")
-    from spconv_amd.utils import synthetic
-    rng = np.random.default_rng(2024)
-    for trial in range(40):
-        nd = int(rng.integers(1, 5))
-        shape = [int(v) for v in rng.integers(6, 20 if nd > 2 else 60, nd)]
-        bs = int(rng.integers(1, 4))
-        n = int(min(rng.integers(1, 800), np.prod(shape) // 2))
-        subm = bool(rng.integers(0, 2))
-        transposed = (not subm) and bool(rng.integers(0, 3) == 0)
-        ksize = [int(v) for v in (rng.choice([1, 3, 5], nd) if subm else rng.integers(1, 4, nd))]
-        stride = [1] * nd if subm else [int(v) for v in rng.integers(1, 4, nd)]
-        dil = [int(v) for v in rng.integers(1, 3, nd)]
-        pad = [int(v) for v in rng.integers(0, 3, nd)]
-        idx = synthetic.uniform_scene(shape, n, bs, seed=trial)
-        try:
-            want = ref.get_indice_pairs(idx, bs, shape, ksize, stride, pad, dil, None, subm, transposed)
-        except (ValueError, RuntimeError):
+    from golden import ref_live_digests, rulebook_sweep_cases
+    stored = ref_live_digests()["rulebook_sweep"]
+    live = ref.available()
+    for trial, (idx, bs, shape, ksize, stride, pad, dil, subm, transposed) in enumerate(rulebook_sweep_cases()):
+        if stored[trial] is None:                     # the reference refuses the case
             continue
         got = oracle.get_indice_pairs(idx, bs, shape, ksize, stride, pad, dil, None, subm, transposed)
-        for a, b in zip(got[:3], want[:3]):
-            np.testing.assert_array_equal(a, b, err_msg=f"trial {trial}: {shape} k{ksize} s{stride} p{pad} d{dil}")
+        msg = f"trial {trial}: {shape} k{ksize} s{stride} p{pad} d{dil}"
+        assert [digest(a) for a in got[:3]] == stored[trial], msg
+        if live:
+            want = ref.get_indice_pairs(idx, bs, shape, ksize, stride, pad, dil, None, subm, transposed)
+            for a, b in zip(got[:3], want[:3]):
+                np.testing.assert_array_equal(a, b, err_msg=msg)
 
 
 def test_gather_scatter_add_equal_reference_executed_vectors():
@@ -336,22 +328,20 @@ def test_gather_scatter_add_equal_reference_executed_vectors():
 
 
 def test_native_conv_loop_with_the_reference_gather_code():
-    """The per-offset driver loop (ops.py:962-986, 1225-1252 restated) run twice: with oracle.cpp's
-    gather / scatter-add and with the reference's own GatherCPU code switched in (oracle/_ref, when
-    present).  Forward, input gradient and weight gradient must be identical bit for bit."""
+    """The per-offset driver loop (ops.py:962-986, 1225-1252 restated) with oracle.cpp's gather / scatter-add: forward,
+    input gradient and weight gradient equal bit for bit (a) the digests of the same loop with the reference's own
+    GatherCPU code switched in, on dyadic values (tests/golden/ref_live_digests.json), on every box, and (b) where
+    oracle/_ref is present, that loop run live on random values."""
     from oracle import ref
+    from golden import native_loop_cases, ref_live_digests
+    stored = ref_live_digests()["native_loop"]
+    for key, out_inds, pair, num, subm, f, w, g in native_loop_cases(dyadic=True):
+        y = oracle.indice_conv(f, w, pair, num, out_inds.shape[0], subm=subm)
+        din, dw = oracle.indice_conv_backward(f, w, g, pair, num, subm=subm)
+        assert [digest(t.numpy()) for t in (y, din, dw)] == stored[key], key
     if not ref.available():
-        pytest.skip("oracle/_ref not built here (needs /root/reference: make -C oracle ref)")
-    from spconv_amd.utils import synthetic
-    rng = np.random.default_rng(5)
-    for subm, stride in ((True, 1), (False, 2)):
-        shape, bs, C, K = [14, 15, 16], 2, 5, 7
-        idx = synthetic.uniform_scene(shape, 700, bs, seed=3)
-        out_inds, pair, num, _ = oracle.get_indice_pairs(idx, bs, shape, [3] * 3, [stride] * 3, [1] * 3, [1] * 3,
-                                                         None, subm, False)
-        f = torch.from_numpy(rng.uniform(-1, 1, (idx.shape[0], C)).astype(np.float32))
-        w = torch.from_numpy(rng.uniform(-1, 1, (K, 3, 3, 3, C)).astype(np.float32))
-        g = torch.from_numpy(rng.uniform(-1, 1, (out_inds.shape[0], K)).astype(np.float32))
+        return
+    for key, out_inds, pair, num, subm, f, w, g in native_loop_cases(dyadic=False):
         res = []
         for use_ref in (False, True):
             oracle.use_reference_gather(use_ref)
@@ -362,7 +352,7 @@ def test_native_conv_loop_with_the_reference_gather_code():
                 oracle.use_reference_gather(False)
             res.append((y, din, dw))
         for a, b in zip(*res):
-            assert torch.equal(a, b)
+            assert torch.equal(a, b), key
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -434,25 +424,22 @@ def test_global_pool_rearrange_reference_executed_vector():
 
 
 def test_section_8f_restatements_equal_the_live_reference_library():
-    """Where oracle/_ref exists (this container; it travels to the GPU box): fresh seeds against the library."""
+    """The voxeliser and the max-pool loops on fresh seeds against the reference's own code: the digests of what it
+    made of them (tests/golden/ref_live_digests.json) on every box, and oracle/_ref itself where it is present."""
     from oracle import ref
-    if not ref.available():
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    rng = np.random.default_rng(8)
-    for seed in range(3):
-        pts = rng.uniform((-1, -5, -3, 0), (9, 5, 3, 1), (3000, 4)).astype(np.float32)
-        pts[:1500, :3] = pts[:1500, :3] * 0.03 + np.float32(2.0)
-        vs, cr, grid = [0.2, 0.1, 0.1], [-2, -4, 0, 2, 4, 8], [20, 80, 80]
-        for mean in (False, True):
-            a = oracle.point2voxel(pts, vs, cr, grid, 900 + 2000 * seed, 4, mean, reference_quirks=True)
-            b = ref.point2voxel(pts, vs, cr, grid, 900 + 2000 * seed, 4, mean)
-            for x, y in zip(a, b):
-                np.testing.assert_array_equal(x, y)
-    idx = scene([16, 16, 16], 1200, 2, 5)
-    _, pair, num, _ = oracle.get_indice_pairs(idx, 2, [16] * 3, [2] * 3, [2] * 3, [0] * 3, [1] * 3, None, False, False)
-    n_out = int(pair[1].max()) + 1
-    f = (rng.integers(-64, 65, (idx.shape[0], 5)) / 64.0).astype(np.float32)
-    dout = (rng.integers(-32, 33, (n_out, 5)) / 64.0).astype(np.float32)
+    from golden import ref_live_digests, section_8f_inputs
+    stored = ref_live_digests()
+    live = ref.available()
+    p2v, (pair, num, n_out, f, dout) = section_8f_inputs()
+    for (pts, vs, cr, grid, cap), want in zip(p2v, stored["point2voxel"]):
+        for mean, w in zip((False, True), want):
+            a = oracle.point2voxel(pts, vs, cr, grid, cap, 4, mean, reference_quirks=True)
+            assert digest(*a) == w, (cap, mean)
+            if live:
+                for x, y in zip(a, ref.point2voxel(pts, vs, cr, grid, cap, 4, mean)):
+                    np.testing.assert_array_equal(x, y)
     out, bwd = oracle.indice_maxpool_native(f, pair, num, n_out)
-    np.testing.assert_array_equal(out, ref.indice_maxpool(f, pair, num, n_out))
-    np.testing.assert_array_equal(bwd(dout), ref.indice_maxpool_backward(f, out, dout, pair, num))
+    assert [digest(out), digest(bwd(dout))] == stored["maxpool"]
+    if live:
+        np.testing.assert_array_equal(out, ref.indice_maxpool(f, pair, num, n_out))
+        np.testing.assert_array_equal(bwd(dout), ref.indice_maxpool_backward(f, out, dout, pair, num))

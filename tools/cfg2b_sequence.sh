@@ -7,7 +7,7 @@ T=${1:-r06}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 export TMPDIR=/tmp
 mkdir -p $O
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/$O/seq_${T}_cfg2b -o bench -- python $R/bench.py --config 2b --steps 40 --warmup 10 --no-cpu-baseline --no-also > $R/$O/${T}_cfg2b_seq.log 2>&1)
+(cd "$TMPDIR" && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/$O/seq_${T}_cfg2b -o bench -- python $R/bench.py --config 2b --steps 40 --warmup 10 --no-cpu-baseline --no-also --full > $R/$O/${T}_cfg2b_seq.log 2>&1)
 f=$(find $O/seq_${T}_cfg2b -name "*kernel_trace.csv" | head -1)
 [ -n "$f" ] && { echo "# tree: $(cat BUILD_STAMP 2>/dev/null || echo unknown)"; python tools/step_sequence.py "$f" igemm_ws_kernel; } > $O/${T}_cfg2b_sequence.txt 2>&1
 python - "$f" <<'PY' >> $O/${T}_cfg2b_sequence.txt

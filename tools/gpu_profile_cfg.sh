@@ -5,7 +5,7 @@ TAG=$1; KEY=$2; shift 2
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 R=$GRAFT_REPO_ROOT
-CMD="python $R/bench.py --steps 40 --warmup 10 --no-graph --no-cpu-baseline --no-also $@"
+CMD="python $R/bench.py --steps 40 --warmup 10 --no-graph --no-cpu-baseline --no-also --full $@"
 (cd /tmp && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_${TAG}_stats -o bench -- $CMD > $R/gpurun_out/rocprof_${TAG}_stats.log 2>&1); echo "stats rc=$?"
 (cd /tmp && timeout 200 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $R/gpurun_out/prof_${TAG}_fetch -o bench -- $CMD > $R/gpurun_out/rocprof_${TAG}_fetch.log 2>&1); echo "fetch rc=$?"
 (cd /tmp && timeout 200 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $R/gpurun_out/prof_${TAG}_write -o bench -- $CMD > $R/gpurun_out/rocprof_${TAG}_write.log 2>&1); echo "write rc=$?"

@@ -11,7 +11,7 @@ mkdir -p $O
 echo "rc=$?" >> $O/${T}_pytest.txt
 tail -4 $O/${T}_pytest.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-(time timeout -k 10 900 python bench.py --steps 20 --warmup 5) > $O/${T}_bench_driver.json 2> $O/${T}_bench_driver.err
+(time timeout -k 10 900 python bench.py --steps 20 --warmup 5 --full) > $O/${T}_bench_driver.json 2> $O/${T}_bench_driver.err
 echo "bench rc=$?"
 bash tools/cfg4_kernels.sh $T > /dev/null 2>&1
 SPCONV_AMD_CONV_ORDER=first_seen bash tools/cfg4_kernels.sh ${T}_first_seen > /dev/null 2>&1
