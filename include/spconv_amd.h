@@ -72,7 +72,17 @@ int spx_set_option(const char *name_h, int value);
  * "igemm_bwd" (fused dgrad + wgrad launch), "igemm_bwd_rows" (one-gather backward), "igemm_i8_stream", "generic";
  * -1 for an unknown name.  The role of the reference's tuner record (which algorithm a layer was given:
  * ConvTunerSimple, csrc/sparse/convops.py:919-1466): lets a test or a benchmark say which kernel a call REALLY took
- * when the choice depends on an asynchronously read density class.  Host only. */
+ * when the choice depends on an asynchronously read density class.
+ * Keys with a '/' count one template INSTANCE (dt: f16 | bf16 | i8 | f32):
+ *   igemm_v4/<COUT>/<MB>/<dt>/<fwd|bt>/<NKS>/<PK>   forward / dgrad gather-GEMM tile (bt: transposed weight reads)
+ *   igemm_bwd/<COUT>/<MB>/<dt>/<NKS>/<PK>           fused dgrad + wgrad launch
+ *   igemm_ws/<dt>                                  weight-stationary kernel (forward and dgrad)
+ *   igemm_bwd_rows/<C>/<K>/<dt>/<W8>               rows walk of narrow layers (W8: 0 | 1, eight waves)
+ *   wgrad_tr/<dt>/<SL>, wgrad_f32                  weight gradient, first stage (SL: 2 | 4 | 8 live slots per row)
+ *   wgrad_mfma/<dt>, wgrad_generic/<dt>            weight gradient, fallback kernels
+ *   generic/<dt>, gen1/<COUT>/<dt>                 one-thread-per-output and first-generation gather-GEMM
+ * COUT in {16, 32, 64, 128, 256}, NKS in {1, 2}, PK in {1, 2, 4, 8, 16, 32}.  A well-formed key of an instance that is
+ * never built counts 0; anything else is unknown.  Host only. */
 long long spx_launch_count(const char *family_h);
 
 /* dst[r] = src[r] followed by zeros: rows of src_row_bytes bytes widened to dst_row_bytes (both even), one launch.  The

@@ -31,6 +31,83 @@ std::mutex g_option_mutex;
 }  // namespace
 
 std::atomic<long long> g_launches[kFamCount];
+std::atomic<long long> g_inst_launches[inst::kCount];
+
+namespace {
+// "f16" | "bf16" | "i8" | "f32" -> the kernels' DT code, or -1
+int parse_dt(const char *t) {
+  static const char *names[inst::kDts] = {"f16", "bf16", "i8", "f32"};
+  for (int i = 0; i < inst::kDts; ++i)
+    if (strcmp(t, names[i]) == 0) return i;
+  return -1;
+}
+
+// a decimal token, or -1
+int parse_int(const char *t) {
+  if (!*t || strlen(t) > 6) return -1;
+  int v = 0;
+  for (; *t; ++t) {
+    if (*t < '0' || *t > '9') return -1;
+    v = v * 10 + (*t - '0');
+  }
+  return v;
+}
+
+// slot of an instance key (spx_launch_count), or -1
+int instance_slot(const char *key) {
+  char buf[96];
+  if (strlen(key) >= sizeof(buf)) return -1;
+  strcpy(buf, key);
+  const char *tok[8];
+  int n = 0;
+  for (char *c = buf, *start = buf;; ++c) {
+    if (*c == '/' || *c == 0) {
+      if (n == 8) return -1;
+      const bool end = *c == 0;
+      *c = 0;
+      tok[n++] = start;
+      start = c + 1;
+      if (end) break;
+    }
+  }
+  const char *fam = tok[0];
+  auto is = [&](const char *name, int ntok) { return strcmp(fam, name) == 0 && n == ntok; };
+  auto cout_ok = [](int c) { return inst::cout_slot(c) >= 0; };
+  if (is("igemm_v4", 7)) {
+    const int cout = parse_int(tok[1]), mb = parse_int(tok[2]), dt = parse_dt(tok[3]);
+    const int bt = strcmp(tok[4], "bt") == 0 ? 1 : (strcmp(tok[4], "fwd") == 0 ? 0 : -1);
+    const int nks = parse_int(tok[5]), pk = parse_int(tok[6]);
+    if (!cout_ok(cout) || (mb != 1 && mb != 2) || dt < 0 || bt < 0 || (nks != 1 && nks != 2) || inst::pk_slot(pk) < 0)
+      return -1;
+    return inst::v4(cout, mb, dt, bt == 1, nks, pk);
+  }
+  if (is("igemm_bwd", 6)) {
+    const int cout = parse_int(tok[1]), mb = parse_int(tok[2]), dt = parse_dt(tok[3]);
+    const int nks = parse_int(tok[4]), pk = parse_int(tok[5]);
+    if (!cout_ok(cout) || (mb != 1 && mb != 2) || dt < 0 || (nks != 1 && nks != 2) || inst::pk_slot(pk) < 0) return -1;
+    return inst::bwd(cout, mb, dt, nks, pk);
+  }
+  if (is("igemm_ws", 2)) return parse_dt(tok[1]) < 0 ? -1 : inst::ws(parse_dt(tok[1]));
+  if (is("igemm_bwd_rows", 5)) {
+    const int c = parse_int(tok[1]), k = parse_int(tok[2]), dt = parse_dt(tok[3]), w8 = parse_int(tok[4]);
+    if ((c != 16 && c != 32) || (k != 16 && k != 32) || dt < 0 || (w8 != 0 && w8 != 1)) return -1;
+    return inst::bwd_rows(c, k, dt, w8 == 1);
+  }
+  if (is("wgrad_tr", 3)) {
+    const int dt = parse_dt(tok[1]), sl = parse_int(tok[2]);
+    return dt < 0 || inst::sl_slot(sl) < 0 ? -1 : inst::wgrad_tr(dt, sl);
+  }
+  if (is("wgrad_f32", 1)) return inst::kWgradF32;
+  if (is("wgrad_mfma", 2)) return parse_dt(tok[1]) < 0 ? -1 : inst::wgrad_mfma(parse_dt(tok[1]));
+  if (is("wgrad_generic", 2)) return parse_dt(tok[1]) < 0 ? -1 : inst::wgrad_generic(parse_dt(tok[1]));
+  if (is("generic", 2)) return parse_dt(tok[1]) < 0 ? -1 : inst::generic(parse_dt(tok[1]));
+  if (is("gen1", 3)) {
+    const int cout = parse_int(tok[1]), dt = parse_dt(tok[2]);
+    return !cout_ok(cout) || dt < 0 ? -1 : inst::gen1(cout, dt);
+  }
+  return -1;
+}
+}  // namespace
 
 int option_int(const char *name, int dflt) {
   {
@@ -66,7 +143,8 @@ long long spx_launch_count(const char *family_h) {
   if (!family_h) return -1;
   for (int i = 0; i < spx::kFamCount; ++i)
     if (strcmp(names[i], family_h) == 0) return spx::g_launches[i].load(std::memory_order_relaxed);
-  return -1;
+  const int slot = spx::instance_slot(family_h);
+  return slot < 0 ? -1 : spx::g_inst_launches[slot].load(std::memory_order_relaxed);
 }
 
 int spx_version(void) { return 1000; }

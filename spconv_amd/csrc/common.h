@@ -117,6 +117,52 @@ namespace spx {
 enum LaunchFamily { kFamV4 = 0, kFamWs, kFamBwdFused, kFamBwdRows, kFamI8Stream, kFamGeneric, kFamStage2, kFamStage2Batch, kFamCount };
 extern std::atomic<long long> g_launches[kFamCount];
 inline void count_launch(LaunchFamily f) { g_launches[f].fetch_add(1, std::memory_order_relaxed); }
+
+// Per-INSTANCE counters (the keys with a '/' of spx_launch_count): one flat table, each template instance a slot whose
+// index is a constant expression of its template parameters, so a launch site adds one relaxed increment and formats
+// nothing.  dt codes are the kernels' DT parameter: 0 f16, 1 bf16, 2 i8, 3 f32.  common.cpp parses the keys.
+namespace inst {
+constexpr int cout_slot(int c) { return c == 16 ? 0 : c == 32 ? 1 : c == 64 ? 2 : c == 128 ? 3 : c == 256 ? 4 : -1; }
+constexpr int pk_slot(int pk) {
+  return pk == 1 ? 0 : pk == 2 ? 1 : pk == 4 ? 2 : pk == 8 ? 3 : pk == 16 ? 4 : pk == 32 ? 5 : -1;
+}
+constexpr int sl_slot(int sl) { return sl == 2 ? 0 : sl == 4 ? 1 : sl == 8 ? 2 : -1; }
+constexpr int kCouts = 5, kDts = 4, kPks = 6;
+constexpr int kV4 = 0;                                                    // COUT x MB x dt x BT x NKS x PK
+constexpr int kBwd = kV4 + kCouts * 2 * kDts * 2 * 2 * kPks;              // COUT x MB x dt x NKS x PK
+constexpr int kWs = kBwd + kCouts * 2 * kDts * 2 * kPks;                  // dt
+constexpr int kBwdRows = kWs + kDts;                                      // C x K x dt x W8
+constexpr int kWgradTr = kBwdRows + 2 * 2 * kDts * 2;                     // dt x SL
+constexpr int kWgradF32 = kWgradTr + kDts * 3;
+constexpr int kWgradMfma = kWgradF32 + 1;                                 // dt
+constexpr int kWgradGeneric = kWgradMfma + kDts;                          // dt
+constexpr int kGeneric = kWgradGeneric + kDts;                            // dt
+constexpr int kGen1 = kGeneric + kDts;                                    // COUT x dt
+constexpr int kCount = kGen1 + kCouts * kDts;
+
+constexpr int v4(int cout, int mb, int dt, bool bt, int nks, int pk) {
+  return kV4 + ((((cout_slot(cout) * 2 + (mb - 1)) * kDts + dt) * 2 + (bt ? 1 : 0)) * 2 + (nks - 1)) * kPks + pk_slot(pk);
+}
+constexpr int bwd(int cout, int mb, int dt, int nks, int pk) {
+  return kBwd + (((cout_slot(cout) * 2 + (mb - 1)) * kDts + dt) * 2 + (nks - 1)) * kPks + pk_slot(pk);
+}
+constexpr int ws(int dt) { return kWs + dt; }
+constexpr int bwd_rows(int c, int k, int dt, bool w8) {
+  return kBwdRows + (((c == 32 ? 1 : 0) * 2 + (k == 32 ? 1 : 0)) * kDts + dt) * 2 + (w8 ? 1 : 0);
+}
+constexpr int wgrad_tr(int dt, int sl) { return kWgradTr + dt * 3 + sl_slot(sl); }
+constexpr int wgrad_mfma(int dt) { return kWgradMfma + dt; }
+constexpr int wgrad_generic(int dt) { return kWgradGeneric + dt; }
+constexpr int generic(int dt) { return kGeneric + dt; }
+constexpr int gen1(int cout, int dt) { return kGen1 + cout_slot(cout) * kDts + dt; }
+}  // namespace inst
+
+extern std::atomic<long long> g_inst_launches[inst::kCount];
+template <int I>
+inline void count_inst() {
+  static_assert(I >= 0 && I < inst::kCount, "instance counter slot");
+  g_inst_launches[I].fetch_add(1, std::memory_order_relaxed);
+}
 }  // namespace spx
 
 // ---- row orders (rowsort.hip) ---------------------------------------------------------------------

@@ -728,13 +728,16 @@ int run_gather_gemm_single(const GemmParams &p, int dtype, hipStream_t s) {
   const long long total = static_cast<long long>(p.n_dst) * p.COUT;
   const dim3 grid(static_cast<unsigned>((total + kThreads - 1) / kThreads));
   count_launch(kFamGeneric);
-  if (dtype == SPX_F32)
+  if (dtype == SPX_F32) {
+    count_inst<inst::generic(3)>();
     hipLaunchKernelGGL(gather_gemm_generic_kernel<float>, grid, dim3(kThreads), 0, s, p);
-  else if (dtype == SPX_F16)
+  } else if (dtype == SPX_F16) {
+    count_inst<inst::generic(0)>();
     hipLaunchKernelGGL(gather_gemm_generic_kernel<h16>, grid, dim3(kThreads), 0, s, p);
-  else if (dtype == SPX_BF16)
+  } else if (dtype == SPX_BF16) {
+    count_inst<inst::generic(1)>();
     hipLaunchKernelGGL(gather_gemm_generic_kernel<b16>, grid, dim3(kThreads), 0, s, p);
-  else {
+  } else {
     set_error("unsupported dtype %d", dtype);
     return -1;
   }
@@ -1132,17 +1135,24 @@ static int igemm_wgrad_impl(const void *feat, const void *dout, void *dw, const 
     const dim3 grid(static_cast<unsigned>(q.G) * ntile);
     const size_t lds = 2 * 2 * kW2J * 128;    // two stages x two operand tiles
     const int sl = (C <= 16 && K <= 16) ? 2 : ((C <= 32 && K <= 32) ? 4 : 8);   // live 16-byte slots per row
-    if (dtype == SPX_F32)
+#define SPX_WGRAD_TR(BF, SL)                                                                 \
+  do {                                                                                       \
+    count_inst<inst::wgrad_tr(BF ? 1 : 0, SL)>();                                            \
+    hipLaunchKernelGGL((wgrad_tr_kernel<BF, SL>), grid, dim3(kThreads), lds, s, q);          \
+  } while (0)
+    if (dtype == SPX_F32) {
+      count_inst<inst::kWgradF32>();
       hipLaunchKernelGGL(wgrad_f32_kernel, grid, dim3(kThreads), 2 * kW3J * kW3Stride * sizeof(float), s, q);
-    else if (dtype == SPX_F16) {
-      if (sl == 2) hipLaunchKernelGGL((wgrad_tr_kernel<false, 2>), grid, dim3(kThreads), lds, s, q);
-      else if (sl == 4) hipLaunchKernelGGL((wgrad_tr_kernel<false, 4>), grid, dim3(kThreads), lds, s, q);
-      else hipLaunchKernelGGL((wgrad_tr_kernel<false, 8>), grid, dim3(kThreads), lds, s, q);
+    } else if (dtype == SPX_F16) {
+      if (sl == 2) SPX_WGRAD_TR(false, 2);
+      else if (sl == 4) SPX_WGRAD_TR(false, 4);
+      else SPX_WGRAD_TR(false, 8);
     } else {
-      if (sl == 2) hipLaunchKernelGGL((wgrad_tr_kernel<true, 2>), grid, dim3(kThreads), lds, s, q);
-      else if (sl == 4) hipLaunchKernelGGL((wgrad_tr_kernel<true, 4>), grid, dim3(kThreads), lds, s, q);
-      else hipLaunchKernelGGL((wgrad_tr_kernel<true, 8>), grid, dim3(kThreads), lds, s, q);
+      if (sl == 2) SPX_WGRAD_TR(true, 2);
+      else if (sl == 4) SPX_WGRAD_TR(true, 4);
+      else SPX_WGRAD_TR(true, 8);
     }
+#undef SPX_WGRAD_TR
     return launch_reduce2(q, dw, dtype, ntile, s, stage2_job);
   }
   {
@@ -1160,17 +1170,22 @@ static int igemm_wgrad_impl(const void *feat, const void *dout, void *dw, const 
     constexpr int max_grid = 1024;
     const dim3 grid(static_cast<unsigned>(bound < max_grid ? bound : max_grid));
     const size_t lds = 2 * kWT * kWJ * 2;
-    if (mfma && dtype == SPX_F16)
+    if (mfma && dtype == SPX_F16) {
+      count_inst<inst::wgrad_mfma(0)>();
       hipLaunchKernelGGL(wgrad_mfma_kernel<false>, grid, dim3(kThreads), lds, s, p);
-    else if (mfma)
+    } else if (mfma) {
+      count_inst<inst::wgrad_mfma(1)>();
       hipLaunchKernelGGL(wgrad_mfma_kernel<true>, grid, dim3(kThreads), lds, s, p);
-    else if (dtype == SPX_F32)
+    } else if (dtype == SPX_F32) {
+      count_inst<inst::wgrad_generic(3)>();
       hipLaunchKernelGGL(wgrad_generic_kernel<float>, grid, dim3(kThreads), 0, s, p);
-    else if (dtype == SPX_F16)
+    } else if (dtype == SPX_F16) {
+      count_inst<inst::wgrad_generic(0)>();
       hipLaunchKernelGGL(wgrad_generic_kernel<h16>, grid, dim3(kThreads), 0, s, p);
-    else if (dtype == SPX_BF16)
+    } else if (dtype == SPX_BF16) {
+      count_inst<inst::wgrad_generic(1)>();
       hipLaunchKernelGGL(wgrad_generic_kernel<b16>, grid, dim3(kThreads), 0, s, p);
-    else
+    } else
       SPX_CHECK(false, "unsupported dtype %d", dtype);
     SPX_LAUNCH_CHECK();
   }

@@ -384,10 +384,13 @@ int launch_bwd(const GemmParams &p, const Wgrad2Params &q, int n_wgrad_blocks, h
   pl.lpt = p.tile_order && n_dgrad + n_wgrad_blocks > 1024;           // (see launch_v4)
   count_launch(kFamBwdFused);
 #define SPX_LAUNCH_BWD(NKSV, PKV)                                                                                  \
-  hipLaunchKernelGGL((igemm_bwd_kernel<COUT, MB, DT, NKSV, PKV>), dim3(n_dgrad + n_wgrad_blocks), dim3(kThreads),  \
-                     (bwd_smem_bytes<COUT, MB, DT>()), s, p.A, p.B, p.mask, p.argsort, p.pair, p.n_dst,           \
-                     p.n_src, p.CIN, p.kv, p.identity_k, v4_flags(pl), rr,                                        \
-                     wgrad_first ? ~n_wgrad_blocks : n_dgrad, q)
+  do {                                                                                                               \
+    count_inst<inst::bwd(COUT, MB, DT, NKSV, PKV)>();                                                                \
+    hipLaunchKernelGGL((igemm_bwd_kernel<COUT, MB, DT, NKSV, PKV>), dim3(n_dgrad + n_wgrad_blocks), dim3(kThreads),  \
+                       (bwd_smem_bytes<COUT, MB, DT>()), s, p.A, p.B, p.mask, p.argsort, p.pair, p.n_dst,           \
+                       p.n_src, p.CIN, p.kv, p.identity_k, v4_flags(pl), rr,                                        \
+                       wgrad_first ? ~n_wgrad_blocks : n_dgrad, q);                                                 \
+  } while (0)
   const int pk = v4_pack(p, DT, DT == 3 ? 4 : 2, true);   // dgrad's reduction rows are the dout channels
   if constexpr (DT == 0 || DT == 1) {
     if (pk == 32) SPX_LAUNCH_BWD(2, 32);

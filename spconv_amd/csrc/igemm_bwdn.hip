@@ -427,7 +427,10 @@ int spx_igemm_bwd_rows(const void *feat, const void *dout, const void *weight_t,
   // and are no longer instantiated: every instantiation of this kernel runs without scratch
   count_launch(kFamBwdRows);
 #define SPX_BWDN(BF, CC, KK, W8)                                                                                \
-  hipLaunchKernelGGL((bwdn_kernel<BF, CC, KK, W8>), dim3(G), dim3(W8 ? 512 : 256), smem, s, p)
+  do {                                                                                                          \
+    count_inst<inst::bwd_rows(CC, KK, BF ? 1 : 0, W8)>();                                                       \
+    hipLaunchKernelGGL((bwdn_kernel<BF, CC, KK, W8>), dim3(G), dim3(W8 ? 512 : 256), smem, s, p);               \
+  } while (0)
   const bool bf = dtype == SPX_BF16;
   if (C == 16 && K == 16) { if (bf) SPX_BWDN(true, 16, 16, true); else SPX_BWDN(false, 16, 16, true); }
   else if (C == 16 && K == 32) { if (bf) SPX_BWDN(true, 16, 32, false); else SPX_BWDN(false, 16, 32, false); }

@@ -270,6 +270,7 @@ constexpr size_t gemm_smem_bytes() {
 template <int COUT, bool BF16>
 int launch_gather_gemm(const GemmParams &p, hipStream_t s) {
   const int ntiles = div_up(p.n_dst, kTileM);
+  count_inst<inst::gen1(COUT, BF16 ? 1 : 0)>();
   if (p.strideD == 1)
     hipLaunchKernelGGL((gather_gemm_mfma_kernel<COUT, BF16, false>), dim3(ntiles), dim3(kThreads),
                        gemm_smem_bytes<COUT>(), s, p);

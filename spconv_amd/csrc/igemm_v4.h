@@ -855,9 +855,12 @@ int launch_v4(const GemmParams &p, hipStream_t s) {
   const int pk = v4_pack(p, DT, es);         // ... <= 32 / 16 bytes: 2 / 4 offsets per step (igemm_v4_body, PK)
   count_launch(kFamV4);
 #define SPX_LAUNCH_V4(BTV, NKSV, PKV)                                                                \
-  hipLaunchKernelGGL((igemm_v4_kernel<COUT, MB, DT, BTV, NKSV, PKV>), dim3(napp + ntiles), dim3(kThreads),   \
-                     (v4_smem_bytes<COUT, MB, DT>()), s, p.A, p.B, p.mask, p.argsort, p.pair, p.n_dst,  \
-                     p.n_src, p.CIN, p.kv, p.identity_k, v4_flags(q), r)
+  do {                                                                                                 \
+    count_inst<inst::v4(COUT, MB, DT, BTV, NKSV, PKV)>();                                              \
+    hipLaunchKernelGGL((igemm_v4_kernel<COUT, MB, DT, BTV, NKSV, PKV>), dim3(napp + ntiles), dim3(kThreads), \
+                       (v4_smem_bytes<COUT, MB, DT>()), s, p.A, p.B, p.mask, p.argsort, p.pair, p.n_dst,  \
+                       p.n_src, p.CIN, p.kv, p.identity_k, v4_flags(q), r);                            \
+  } while (0)
   if (p.grid_out) *p.grid_out = (p.stats && DT != 2 && p.strideD == 1 && !p.acc_mode) ? napp + ntiles : 0;
   if (DT == 2 || p.strideD == 1) {
     if constexpr (DT == 0 || DT == 1) {

@@ -401,6 +401,7 @@ int launch_ws_one(const WsArgs &a, hipStream_t s, int *grid_out) {
   WsArgs q = a;
   q.ntiles = div_up(a.n_dst, NW * 32);
   count_launch(kFamWs);
+  count_inst<inst::ws(BF16 ? 1 : 0)>();
   hipLaunchKernelGGL(kern, dim3(q.ntiles), dim3(NW * 64), lds, s, q);
   if (grid_out) *grid_out = q.stats ? q.ntiles : 0;
   SPX_LAUNCH_CHECK();
