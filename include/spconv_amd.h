@@ -40,7 +40,11 @@ extern "C" {
 
 typedef void *spx_stream_t; /* hipStream_t */
 
-enum spx_dtype { SPX_F32 = 0, SPX_F16 = 1, SPX_BF16 = 2, SPX_I8 = 3 };
+/* SPX_F64: float64 tensors of spx_igemm_fwd / _fwd_stats / _dgrad / _wgrad / _bwd, spx_bias_act_inplace and the four
+ * pooling entries.  Their own kernels (csrc/igemm_f64.hip: v_mfma_f64_16x16x4_f64, float64 accumulation throughout) take
+ * any channel count, any kernel volume in one launch and every table form, and need no scratch except the weight
+ * gradient's (spx_igemm_wgrad_ws_bytes_dtype). */
+enum spx_dtype { SPX_F32 = 0, SPX_F16 = 1, SPX_BF16 = 2, SPX_I8 = 3, SPX_F64 = 4 };
 
 /* tv::gemm::Activation subset used by the path (csrc/sparse/inference.py:26-146) */
 enum spx_act { SPX_ACT_NONE = 0, SPX_ACT_RELU = 1, SPX_ACT_SIGMOID = 2, SPX_ACT_LEAKY_RELU = 3 };
@@ -82,7 +86,13 @@ int spx_set_option(const char *name_h, int value);
  *   wgrad_mfma/<dt>, wgrad_generic/<dt>            weight gradient, fallback kernels
  *   generic/<dt>, gen1/<COUT>/<dt>                 one-thread-per-output and first-generation gather-GEMM
  * COUT in {16, 32, 64, 128, 256}, NKS in {1, 2}, PK in {1, 2, 4, 8, 16, 32}.  A well-formed key of an instance that is
- * never built counts 0; anything else is unknown.  Host only. */
+ * never built counts 0; anything else is unknown.
+ * float64 (SPX_F64) has a family and keys of its own, outside the dt vocabulary above:
+ *   igemm_f64                                      every float64 gather-GEMM launch (forward and dgrad)
+ *   igemm_f64/fwd, igemm_f64/dgrad                 the same, by role
+ *   wgrad_f64                                      float64 weight gradient, first stage
+ *   pool/f64                                       float64 pooling (max / avg, forward / backward)
+ * Host only. */
 long long spx_launch_count(const char *family_h);
 
 /* dst[r] = src[r] followed by zeros: rows of src_row_bytes bytes widened to dst_row_bytes (both even), one launch.  The
@@ -305,6 +315,8 @@ size_t spx_igemm_acc_bytes(int n_dst, int cout, int kv);
  *   pair [kv, n_out]; mask [n_out, W] or NULL; argsort [n_out] or NULL
  *   identity_k: offset whose pair is the identity (SubM centre, kv/2) or -1
  *   bias [K] (dtype) or NULL; act: spx_act (inference epilogue, conv.py:463-490)
+ *   dtype: SPX_F32 / SPX_F16 / SPX_BF16 / SPX_F64 (float64: any C and K, any kv in one launch, ws unused; the
+ *   SPX_OUT_CACHED and SPX_DENSE_HINT bits are accepted and ignored)
  * Every row of `out` is written (no pre-zeroing needed, cf. convops.py:2128-2134). */
 int spx_igemm_fwd(const void *feat, const void *weight, void *out, const int32_t *pair,
                   const uint32_t *mask, const int32_t *argsort, int tile_order, int n_in, int n_out,
@@ -318,7 +330,7 @@ int spx_igemm_fwd(const void *feat, const void *weight, void *out, const int32_t
  * ROUNDED output values, i.e. of what a normalisation layer behind the convolution reads), rows >= *n_live (device,
  * static-shape tensors; NULL = every row) not counted.  *slots_used_h (host) = number of records written = the
  * launch's workgroup count, or 0 when the kernel that was dispatched leaves none (bias / activation in the epilogue,
- * kernel volumes > 32, generic kernels): spx_batchnorm_fwd_stats then starts at its merge step instead of reading the
+ * kernel volumes > 32, generic kernels, SPX_F64): spx_batchnorm_fwd_stats then starts at its merge step instead of reading the
  * rows again for a statistics pass.  `stats` holds stats_slots >= spx_igemm_fwd_stats_slots(n_out) records.
  * The reference leaves BatchNorm to torch on the feature matrix (spconv/pytorch/modules.py:127-168): two extra passes
  * over every activation; this removes the first of them. */
@@ -407,7 +419,8 @@ size_t spx_igemm_dgrad_ws_bytes(int C, int K, int kv, int dtype);
  * (convops.py:2245-2440, ops.py:1667-1896):
  *   din[i,:] = sum_k [pair_bwd[k][i] >= 0] dout[pair_bwd[k][i],:] * W[:,k,:]
  * For SubM pass subm=1 with the FORWARD pair/mask (mirror symmetry
- * pair_bwd[k] == pair_fwd[kv-1-k]; the reference's reverse_mask, convops.py:2327-2345). */
+ * pair_bwd[k] == pair_fwd[kv-1-k]; the reference's reverse_mask, convops.py:2327-2345).
+ * dtype: SPX_F32 / SPX_F16 / SPX_BF16 / SPX_F64, as spx_igemm_fwd. */
 int spx_igemm_dgrad(const void *dout, const void *weight, void *din, const int32_t *pair,
                     const uint32_t *mask, const int32_t *argsort, int tile_order, int n_out, int n_in,
                     int C, int K, int kv, int dtype, int subm, void *ws, size_t ws_bytes,
@@ -415,6 +428,10 @@ int spx_igemm_dgrad(const void *dout, const void *weight, void *din, const int32
 
 /* Scratch for wgrad (per-workgroup fp32 partials + room for a work plan). */
 size_t spx_igemm_wgrad_ws_bytes(int n_in, int C, int K, int kv);
+/* The same for a given dtype: SPX_F64 needs float64 partial tiles (one per offset, fixed chunk of its pair list and
+ * 64 x 64 tile of dW), which the query above cannot express; the other dtypes return spx_igemm_wgrad_ws_bytes.  Also
+ * the scratch of spx_igemm_bwd. */
+size_t spx_igemm_wgrad_ws_bytes_dtype(int n_in, int C, int K, int kv, int dtype);
 
 /* Work plan of wgrad: the list of (offset, chunk-of-pairs) items that exist for a
  * rulebook, so the wgrad grid holds no empty workgroups.  It depends only on
@@ -430,7 +447,9 @@ int spx_wgrad_plan(const int32_t *num_per_loc, int n_in, int kv, int subm, int32
  * over the Native lists; deterministic two-stage reduction (no atomics).
  *   dw KRSC [K, kv, C] in `dtype`, fully overwritten.
  *   subm=1: centre offset is the identity over all rows and offsets k > kv/2 use
- *   num_per_loc[kv-1-k] (ops.py:962-968). */
+ *   num_per_loc[kv-1-k] (ops.py:962-968).
+ *   dtype SPX_F64: float64 partial tiles over fixed chunks of each list, summed in chunk order by a second launch (no
+ *   atomics, bit-identical between calls); any kv; `plan` is not read; ws as spx_igemm_wgrad_ws_bytes_dtype. */
 int spx_igemm_wgrad(const void *feat, const void *dout, void *dw, const int32_t *pair_native,
                     const int32_t *num_per_loc, const int32_t *plan, int n_in, int n_out, int C,
                     int K, int kv, int dtype, int subm, void *ws, size_t ws_bytes,
@@ -455,7 +474,8 @@ int spx_igemm_bwd_rows(const void *feat, const void *dout, const void *weight_t,
  * indice_conv_backward as a whole (pytorch/ops.py:1667-1896,1103-1447), which also return both
  * gradients from one call.  pair / mask / argsort are the dgrad table (the FORWARD table for
  * SubM), pair_native / num_per_loc / plan as for spx_igemm_wgrad, ws as spx_igemm_wgrad_ws_bytes.
- * Shapes the fused kernel does not cover fall back to the two separate calls internally. */
+ * Shapes the fused kernel does not cover fall back to the two separate calls internally; so does SPX_F64 (ws as
+ * spx_igemm_wgrad_ws_bytes_dtype). */
 int spx_igemm_bwd(const void *feat, const void *dout, const void *weight, void *din, void *dw,
                   const int32_t *pair, const uint32_t *mask, const int32_t *argsort, int tile_order,
                   const int32_t *pair_native, const int32_t *num_per_loc, const int32_t *plan,
@@ -471,7 +491,8 @@ int spx_igemm_bwd(const void *feat, const void *dout, const void *weight, void *
  * alive and must not read dw.  A call whose shapes take a path without a second stage (empty scene, odd channel counts)
  * completes dw at once and leaves an empty record, which the batch call skips.  Results are bit-identical to the
  * undeferred calls (same kernel body, same summation order).  The reference returns din and dw from one blocking
- * call (pytorch/ops.py:1667-1896); its split-K reduction is part of that call. */
+ * call (pytorch/ops.py:1667-1896); its split-K reduction is part of that call.  SPX_F64 is rejected (no deferred stage:
+ * use spx_igemm_bwd / spx_igemm_wgrad). */
 #define SPX_STAGE2_JOB_BYTES 64
 int spx_igemm_bwd_deferred(const void *feat, const void *dout, const void *weight, void *din, void *dw,
                            const int32_t *pair, const uint32_t *mask, const int32_t *argsort, int tile_order,
@@ -488,7 +509,7 @@ int spx_wgrad_stage2_batch(const void *jobs, int njobs, spx_stream_t stream);
 int spx_stage2_job_retarget(void *stage2_job, void *dw);
 
 /* In-place epilogues for callers that keep bias/activation separate
- * (InferenceOps.bias_add_act_inplace etc., csrc/sparse/inference.py:26-146). */
+ * (InferenceOps.bias_add_act_inplace etc., csrc/sparse/inference.py:26-146).  dtype: SPX_F32 / F16 / BF16 / F64. */
 int spx_bias_act_inplace(void *out, const void *bias, int n, int K, int dtype, int act,
                          float act_alpha, spx_stream_t stream);
 
@@ -505,7 +526,7 @@ int spx_bias_act_inplace(void *out, const void *bias, int n, int K, int dtype, i
  *   max backward: din[i] = sum of dout[o] over the outputs o with out[o] == feat[i].
  *   avg forward: mean over the valid pairs, count_out [n_out] (or NULL) receives their number.
  *   avg backward: din[i] = sum_o dout[o] / count[o].
- * dtypes: f32 / f16 / bf16, plus int8 for the max forward. */
+ * dtypes: f32 / f16 / bf16 / f64 (float64 sums), plus int8 for the max forward. */
 int spx_maxpool_fwd(const void *feat, void *out, const int32_t *pair_fwd, const uint32_t *mask,
                     int n_out, int C, int kv, int dtype, int init_zero, spx_stream_t stream);
 int spx_maxpool_bwd(const void *feat, const void *out, const void *dout, void *din,

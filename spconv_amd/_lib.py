@@ -92,6 +92,7 @@ SIGNATURES = {
     "spx_igemm_dgrad_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "spx_igemm_dgrad": (ctypes.c_int, [vp] * 6 + [ctypes.c_int] * 8 + [vp, ctypes.c_size_t, vp]),
     "spx_igemm_wgrad_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "spx_igemm_wgrad_ws_bytes_dtype": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "spx_wgrad_plan_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "spx_wgrad_plan": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "spx_igemm_wgrad": (ctypes.c_int, [vp] * 6 + [ctypes.c_int] * 7 + [vp, ctypes.c_size_t, vp]),
@@ -133,7 +134,7 @@ SIGNATURES = {
                                             ctypes.c_int, ctypes.c_float, vp]),
 }
 
-DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_I8 = 0, 1, 2, 3
+DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_I8, DTYPE_F64 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_LEAKY_RELU = 0, 1, 2, 3
 
 _lib: Optional[ctypes.CDLL] = None

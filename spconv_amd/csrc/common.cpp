@@ -32,6 +32,7 @@ std::mutex g_option_mutex;
 
 std::atomic<long long> g_launches[kFamCount];
 std::atomic<long long> g_inst_launches[inst::kCount];
+std::atomic<long long> g_f64_launches[kF64Count];
 
 namespace {
 // "f16" | "bf16" | "i8" | "f32" -> the kernels' DT code, or -1
@@ -107,6 +108,15 @@ int instance_slot(const char *key) {
   }
   return -1;
 }
+
+// counter of a float64 key (spx_launch_count), or null
+std::atomic<long long> *f64_counter(const char *key) {
+  if (strcmp(key, "igemm_f64/fwd") == 0) return &g_f64_launches[kF64Fwd];
+  if (strcmp(key, "igemm_f64/dgrad") == 0) return &g_f64_launches[kF64Dgrad];
+  if (strcmp(key, "wgrad_f64") == 0) return &g_f64_launches[kF64Wgrad];
+  if (strcmp(key, "pool/f64") == 0) return &g_f64_launches[kF64Pool];
+  return nullptr;
+}
 }  // namespace
 
 int option_int(const char *name, int dflt) {
@@ -139,10 +149,11 @@ const char *spx_last_error(void) { return spx::g_error.c_str(); }
 
 long long spx_launch_count(const char *family_h) {
   static const char *names[spx::kFamCount] = {"igemm_v4", "igemm_ws", "igemm_bwd", "igemm_bwd_rows", "igemm_i8_stream",
-                                              "generic", "wgrad_stage2", "wgrad_stage2_batch"};
+                                              "generic", "wgrad_stage2", "wgrad_stage2_batch", "igemm_f64"};
   if (!family_h) return -1;
   for (int i = 0; i < spx::kFamCount; ++i)
     if (strcmp(names[i], family_h) == 0) return spx::g_launches[i].load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::f64_counter(family_h)) return c->load(std::memory_order_relaxed);
   const int slot = spx::instance_slot(family_h);
   return slot < 0 ? -1 : spx::g_inst_launches[slot].load(std::memory_order_relaxed);
 }

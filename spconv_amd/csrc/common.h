@@ -114,7 +114,8 @@ inline Geom make_geom(int ndim, int batch, const int *in_dims, const int *out_di
 
 // ---- launch counters (diagnostics: which kernel family a call dispatched; spx_launch_count) --------
 namespace spx {
-enum LaunchFamily { kFamV4 = 0, kFamWs, kFamBwdFused, kFamBwdRows, kFamI8Stream, kFamGeneric, kFamStage2, kFamStage2Batch, kFamCount };
+enum LaunchFamily { kFamV4 = 0, kFamWs, kFamBwdFused, kFamBwdRows, kFamI8Stream, kFamGeneric, kFamStage2, kFamStage2Batch,
+                    kFamF64, kFamCount };
 extern std::atomic<long long> g_launches[kFamCount];
 inline void count_launch(LaunchFamily f) { g_launches[f].fetch_add(1, std::memory_order_relaxed); }
 
@@ -163,6 +164,12 @@ inline void count_inst() {
   static_assert(I >= 0 && I < inst::kCount, "instance counter slot");
   g_inst_launches[I].fetch_add(1, std::memory_order_relaxed);
 }
+
+// float64 kernels (igemm_f64.hip, pool.hip): a table of their own, outside the dt vocabulary of the instances above.
+// Keys igemm_f64/fwd, igemm_f64/dgrad, wgrad_f64, pool/f64.
+enum F64Inst { kF64Fwd = 0, kF64Dgrad, kF64Wgrad, kF64Pool, kF64Count };
+extern std::atomic<long long> g_f64_launches[kF64Count];
+inline void count_f64(F64Inst i) { g_f64_launches[i].fetch_add(1, std::memory_order_relaxed); }
 }  // namespace spx
 
 // ---- row orders (rowsort.hip) ---------------------------------------------------------------------

@@ -664,7 +664,7 @@ bias_act_kernel(T *__restrict__ out, const T *__restrict__ bias, long long total
   store_f(out + gid, apply_act(v, act, alpha));
 }
 
-int elem_bytes(int dtype) { return dtype == SPX_F32 ? 4 : (dtype == SPX_I8 ? 1 : 2); }
+int elem_bytes(int dtype) { return dtype == SPX_F64 ? 8 : (dtype == SPX_F32 ? 4 : (dtype == SPX_I8 ? 1 : 2)); }
 
 bool mfma_ok(int dtype, int cin, int cout, int kv, const uint32_t *mask) {
   if (dtype != SPX_F16 && dtype != SPX_BF16 && dtype != SPX_F32) return false;
@@ -925,6 +925,8 @@ static int igemm_fwd_impl(const void *feat, const void *weight, void *out, const
   p.act = act & 0xff;
   if (act & SPX_OUT_CACHED) p.dbg = 0x400;       // plain result stores: the next launch reads the rows
   p.act_alpha = act_alpha;
+  // float64: its own kernel for every width, kernel volume and table form; no scratch, no statistics (*slots_used_h = 0)
+  if (dtype == SPX_F64) return run_gather_gemm_f64(p, false, static_cast<hipStream_t>(stream));
   if (ws && ws_bytes >= spx_igemm_acc_bytes(n_out, K, kv) && kv > 32) p.acc = static_cast<float *>(ws);
   if (stats && kv <= 32 && !bias && p.act == SPX_ACT_NONE) {   // (the training-mode call: plain rows)
     p.stats = stats;
@@ -1026,6 +1028,7 @@ int spx_igemm_dgrad(const void *dout, const void *weight, void *din, const int32
   GemmParams p = dgrad_params(dout, weight, din, pair, mask, argsort, n_out, n_in, C, K, kv, subm);
   p.dense_hint = (tile_order & SPX_DENSE_HINT) ? 1 : 0;
   apply_rows_layout(p, tile_order & ~SPX_DENSE_HINT);
+  if (dtype == SPX_F64) return run_gather_gemm_f64(p, true, static_cast<hipStream_t>(stream));
   if (ws && ws_bytes >= spx_igemm_acc_bytes(n_in, C, kv) && kv > 32) p.acc = static_cast<float *>(ws);
   return run_gather_gemm(p, dtype, static_cast<hipStream_t>(stream));
 }
@@ -1056,6 +1059,10 @@ int spx_wgrad_plan(const int32_t *num_per_loc, int n_in, int kv, int subm, int32
   return 0;
 }
 
+size_t spx_igemm_wgrad_ws_bytes_dtype(int n_in, int C, int K, int kv, int dtype) {
+  return dtype == SPX_F64 ? wgrad_f64_ws_bytes(n_in, C, K, kv) : spx_igemm_wgrad_ws_bytes(n_in, C, K, kv);
+}
+
 size_t spx_igemm_wgrad_ws_bytes(int n_in, int C, int K, int kv) {
   const int chunk = wgrad_chunk(n_in);
   const size_t nchunks = div_up(n_in > 0 ? n_in : 1, chunk);
@@ -1072,6 +1079,15 @@ static int igemm_wgrad_impl(const void *feat, const void *dout, void *dw, const 
                             spx_stream_t stream, void *stage2_job) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   SPX_CHECK(dw && C > 0 && K > 0, "null tensor pointer");
+  if (dtype == SPX_F64) {                                     // float64: any kernel volume, no plan, no deferral
+    SPX_CHECK(kv >= 1, "bad kernel volume %d", kv);
+    SPX_CHECK(!stage2_job, "float64 weight gradients have no deferred second stage");
+    if (n_in == 0 || n_out == 0) {
+      SPX_HIP(hipMemsetAsync(dw, 0, static_cast<size_t>(K) * kv * C * elem_bytes(dtype), s));
+      return 0;
+    }
+    return wgrad_f64(feat, dout, dw, pair_native, num_per_loc, n_in, C, K, kv, subm, ws, ws_bytes, s);
+  }
   SPX_CHECK(kv >= 1 && kv <= 128, "kernel volume %d not supported by wgrad (max 128)", kv);
   if (n_in == 0 || n_out == 0) {                              // no pairs: the gradient is zero
     SPX_HIP(hipMemsetAsync(dw, 0, static_cast<size_t>(K) * kv * C * elem_bytes(dtype), s));
@@ -1223,6 +1239,15 @@ static int igemm_bwd_impl(const void *feat, const void *dout, const void *weight
   SPX_CHECK(feat && dout && weight && din && dw && ws, "null tensor pointer");
   SPX_CHECK(pair_native && num_per_loc, "Native pair lists and counts are required");
   SPX_CHECK(pair || kv == 1, "pair table required");
+  if (dtype == SPX_F64) {                  // float64: the input gradient, then the weight gradient (no fused launch)
+    SPX_CHECK(!stage2_job, "float64 backward has no deferred second stage (use spx_igemm_bwd)");
+    SPX_CHECK(ws_bytes >= wgrad_f64_ws_bytes(n_in, C, K, kv),
+              "workspace too small for the float64 weight gradient (spx_igemm_wgrad_ws_bytes_dtype)");
+    if (spx_igemm_dgrad(dout, weight, din, pair, mask, argsort, tile_order, n_out, n_in, C, K, kv, dtype, subm,
+                        nullptr, 0, stream))
+      return -2;
+    return wgrad_f64(feat, dout, dw, pair_native, num_per_loc, n_in, C, K, kv, subm, ws, ws_bytes, s);
+  }
   SPX_CHECK(ws_bytes >= spx_igemm_wgrad_ws_bytes(n_in, C, K, kv), "workspace too small");
   constexpr int fuse = 1;                  // (dgrad + wgrad in one launch: settled A/B)
   GemmParams p = dgrad_params(dout, weight, din, pair, mask, argsort, n_out, n_in, C, K, kv, subm);
@@ -1298,6 +1323,7 @@ int spx_igemm_wgrad_deferred(const void *feat, const void *dout, void *dw, const
                              int K, int kv, int dtype, int subm, void *ws, size_t ws_bytes,
                              spx_stream_t stream, void *stage2_job) {
   SPX_CHECK(stage2_job, "stage2_job is required");
+  SPX_CHECK(dtype != SPX_F64, "float64 weight gradients have no deferred second stage (use spx_igemm_wgrad)");
   memset(stage2_job, 0, SPX_STAGE2_JOB_BYTES);
   return igemm_wgrad_impl(feat, dout, dw, pair_native, num_per_loc, plan, n_in, n_out, C, K, kv, dtype, subm, ws,
                           ws_bytes, stream, stage2_job);
@@ -1309,6 +1335,7 @@ int spx_igemm_bwd_deferred(const void *feat, const void *dout, const void *weigh
                            int n_in, int n_out, int C, int K, int kv, int dtype, int subm, void *ws,
                            size_t ws_bytes, spx_stream_t stream, void *stage2_job) {
   SPX_CHECK(stage2_job, "stage2_job is required");
+  SPX_CHECK(dtype != SPX_F64, "float64 backward has no deferred second stage (use spx_igemm_bwd)");
   memset(stage2_job, 0, SPX_STAGE2_JOB_BYTES);
   return igemm_bwd_impl(feat, dout, weight, din, dw, pair, mask, argsort, tile_order, pair_native, num_per_loc, plan, n_in,
                         n_out, C, K, kv, dtype, subm, ws, ws_bytes, stream, stage2_job);
@@ -1369,6 +1396,7 @@ int spx_bias_act_inplace(void *out, const void *bias, int n, int K, int dtype, i
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long long total = static_cast<long long>(n) * K;
   if (total == 0) return 0;
+  if (dtype == SPX_F64) return bias_act_f64(out, bias, n, K, act, act_alpha, s);
   const dim3 grid(static_cast<unsigned>((total + kThreads - 1) / kThreads));
   if (dtype == SPX_F32)
     hipLaunchKernelGGL(bias_act_kernel<float>, grid, dim3(kThreads), 0, s, static_cast<float *>(out),

@@ -273,6 +273,12 @@ int launch_gather_gemm_gen1(const GemmParams &p, bool bf16, hipStream_t s);
 // igemm_ws.hip: weight-stationary gather-GEMM for dense neighbourhoods (forward and dgrad)
 bool ws_ok(const GemmParams &p, int dtype);
 int launch_gather_gemm_ws(const GemmParams &p, int dtype, hipStream_t s);
+// igemm_f64.hip: float64 forward / dgrad gather-GEMM, weight gradient (two launches) and epilogue
+int run_gather_gemm_f64(const GemmParams &p, bool dgrad, hipStream_t s);
+size_t wgrad_f64_ws_bytes(int n_in, int C, int K, int kv);
+int wgrad_f64(const void *feat, const void *dout, void *dw, const int32_t *pair_native, const int32_t *num_per_loc,
+              int n_in, int C, int K, int kv, int subm, void *ws, size_t ws_bytes, hipStream_t s);
+int bias_act_f64(void *out, const void *bias, int n, int K, int act, float act_alpha, hipStream_t s);
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));

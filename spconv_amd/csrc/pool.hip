@@ -5,7 +5,9 @@
 // pool).  Pure bandwidth kernels: one thread owns a 16-byte piece of one output row, walks the
 // offsets present for that row (set bits of the rulebook mask word when there is one, every
 // offset otherwise), gathers the source pieces as full-width loads and reduces in registers;
-// every row is written exactly once, no atomics.
+// every row is written exactly once, no atomics.  float64 tensors accumulate in float64.
+#include <type_traits>
+
 #include "common.h"
 
 namespace spx {
@@ -26,18 +28,29 @@ struct PoolParams {
   int n_dst, C, kv, init_zero;
 };
 
+// to_f / from_f convert to and from the accumulation type Acc: float, double for double tensors (their sums stay
+// float64 all the way)
 template <typename T> struct Elem;
+template <> struct Elem<double> {
+  typedef double Acc;
+  static __device__ __forceinline__ double to_f(double v) { return v; }
+  static __device__ __forceinline__ double from_f(double v) { return v; }
+  static __device__ __forceinline__ double lowest() { return -1.7976931348623157e+308; }
+};
 template <> struct Elem<float> {
+  typedef float Acc;
   static __device__ __forceinline__ float to_f(float v) { return v; }
   static __device__ __forceinline__ float from_f(float v) { return v; }
   static __device__ __forceinline__ float lowest() { return -3.402823466e+38f; }
 };
 template <> struct Elem<_Float16> {
+  typedef float Acc;
   static __device__ __forceinline__ float to_f(_Float16 v) { return static_cast<float>(v); }
   static __device__ __forceinline__ _Float16 from_f(float v) { return static_cast<_Float16>(v); }
   static __device__ __forceinline__ _Float16 lowest() { return static_cast<_Float16>(-65504.f); }
 };
 template <> struct Elem<__bf16> {
+  typedef float Acc;
   static __device__ __forceinline__ float to_f(__bf16 v) { return static_cast<float>(v); }
   static __device__ __forceinline__ __bf16 from_f(float v) { return static_cast<__bf16>(v); }
   static __device__ __forceinline__ __bf16 lowest() {
@@ -45,6 +58,7 @@ template <> struct Elem<__bf16> {
   }
 };
 template <> struct Elem<int8_t> {
+  typedef float Acc;
   static __device__ __forceinline__ float to_f(int8_t v) { return static_cast<float>(v); }
   static __device__ __forceinline__ int8_t from_f(float v) { return static_cast<int8_t>(v); }
   static __device__ __forceinline__ int8_t lowest() { return -128; }
@@ -78,6 +92,7 @@ __global__ void __launch_bounds__(kBlock) pool_kernel(PoolParams p) {
   if (gid >= static_cast<long long>(p.n_dst) * pieces) return;
   const int r = static_cast<int>(gid / pieces), c = static_cast<int>(gid % pieces) * V;
   typedef Piece<T, V> P;
+  typedef typename Elem<T>::Acc Acc;
   const T *src = static_cast<const T *>(p.src);
   T *dst = static_cast<T *>(p.dst);
   if (OP == kMaxFwd) {
@@ -86,7 +101,7 @@ __global__ void __launch_bounds__(kBlock) pool_kernel(PoolParams p) {
     // (pytorch/ops.py:1910, maxpool.py:36-60).
     P cur;
 #pragma unroll
-    for (int e = 0; e < V; ++e) cur.v[e] = p.init_zero ? Elem<T>::from_f(0.f) : Elem<T>::lowest();
+    for (int e = 0; e < V; ++e) cur.v[e] = p.init_zero ? Elem<T>::from_f(Acc(0)) : Elem<T>::lowest();
     bool any = false;
     for_each_pair(p, r, [&](int, int idx) {
       const P in = *reinterpret_cast<const P *>(src + static_cast<size_t>(idx) * p.C + c);
@@ -99,15 +114,15 @@ __global__ void __launch_bounds__(kBlock) pool_kernel(PoolParams p) {
     // created it): zeros, like every other padding row, not the lowest value
     if (!any) {
 #pragma unroll
-      for (int e = 0; e < V; ++e) cur.v[e] = Elem<T>::from_f(0.f);
+      for (int e = 0; e < V; ++e) cur.v[e] = Elem<T>::from_f(Acc(0));
     }
     *reinterpret_cast<P *>(dst + static_cast<size_t>(r) * p.C + c) = cur;
   } else if (OP == kMaxBwd) {
     // maxpool.py:142-209: din[i] = sum of dout[o] over the outputs whose maximum this input is
     const P in = *reinterpret_cast<const P *>(static_cast<const T *>(p.feat) + static_cast<size_t>(r) * p.C + c);
-    float acc[V];
+    Acc acc[V];
 #pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    for (int e = 0; e < V; ++e) acc[e] = 0;
     for_each_pair(p, r, [&](int, int o) {
       const P out = *reinterpret_cast<const P *>(static_cast<const T *>(p.out) + static_cast<size_t>(o) * p.C + c);
       const P d = *reinterpret_cast<const P *>(src + static_cast<size_t>(o) * p.C + c);
@@ -121,9 +136,9 @@ __global__ void __launch_bounds__(kBlock) pool_kernel(PoolParams p) {
     *reinterpret_cast<P *>(dst + static_cast<size_t>(r) * p.C + c) = res;
   } else if (OP == kAvgFwd) {
     // maxpool.py:211-260: mean over the valid pairs, 0 for a row without pairs
-    float acc[V];
+    Acc acc[V];
 #pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    for (int e = 0; e < V; ++e) acc[e] = 0;
     int count = 0;
     for_each_pair(p, r, [&](int, int idx) {
       const P in = *reinterpret_cast<const P *>(src + static_cast<size_t>(idx) * p.C + c);
@@ -132,7 +147,7 @@ __global__ void __launch_bounds__(kBlock) pool_kernel(PoolParams p) {
       ++count;
     });
     if (p.count_out && c == 0) p.count_out[r] = count;
-    const float inv = count > 0 ? 1.f / static_cast<float>(count) : 0.f;
+    const Acc inv = count > 0 ? Acc(1) / static_cast<Acc>(count) : Acc(0);
     P res;
 #pragma unroll
     for (int e = 0; e < V; ++e) res.v[e] = Elem<T>::from_f(acc[e] * inv);
@@ -141,13 +156,13 @@ __global__ void __launch_bounds__(kBlock) pool_kernel(PoolParams p) {
     // gradient of the mean: din[i] = sum_o dout[o] / count[o].  (The reference kernel,
     // maxpool.py:262-300, MULTIPLIES by count[o]; that is not the derivative of its own
     // forward -- DESIGN.md.  SPCONV_AMD_REFERENCE_QUIRKS=1 reproduces it: quirk_mul.)
-    float acc[V];
+    Acc acc[V];
 #pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    for (int e = 0; e < V; ++e) acc[e] = 0;
     for_each_pair(p, r, [&](int, int o) {
       const P d = *reinterpret_cast<const P *>(src + static_cast<size_t>(o) * p.C + c);
       const int cnt = p.count[o];
-      const float inv = p.quirk_mul ? static_cast<float>(cnt) : (cnt > 0 ? 1.f / static_cast<float>(cnt) : 0.f);
+      const Acc inv = p.quirk_mul ? static_cast<Acc>(cnt) : (cnt > 0 ? Acc(1) / static_cast<Acc>(cnt) : Acc(0));
 #pragma unroll
       for (int e = 0; e < V; ++e) acc[e] += Elem<T>::to_f(d.v[e]) * inv;
     });
@@ -162,6 +177,7 @@ template <typename T, int OP>
 int launch_pool(const PoolParams &p, hipStream_t s) {
   constexpr int V = 16 / static_cast<int>(sizeof(T));
   if (p.n_dst == 0) return 0;
+  if (std::is_same<T, double>::value) count_f64(kF64Pool);     // (counted where the launch happens, like the others)
   if (p.C % V == 0) {
     const long long total = static_cast<long long>(p.n_dst) * (p.C / V);
     hipLaunchKernelGGL((pool_kernel<T, V, OP>), dim3(static_cast<unsigned>((total + kBlock - 1) / kBlock)),
@@ -179,6 +195,7 @@ template <int OP>
 int dispatch_pool(const PoolParams &p, int dtype, hipStream_t s) {
   switch (dtype) {
     case SPX_F32: return launch_pool<float, OP>(p, s);
+    case SPX_F64: return launch_pool<double, OP>(p, s);
     case SPX_F16: return launch_pool<_Float16, OP>(p, s);
     case SPX_BF16: return launch_pool<__bf16, OP>(p, s);
     case SPX_I8:

@@ -53,7 +53,7 @@ Your Conv Params:
     dilation={}"""
 
 _DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16,
-           torch.bfloat16: _lib.DTYPE_BF16}
+           torch.bfloat16: _lib.DTYPE_BF16, torch.float64: _lib.DTYPE_F64}
 
 
 class Activation:
@@ -935,6 +935,9 @@ def igemm_fwd(features: torch.Tensor, filters: torch.Tensor, pair: torch.Tensor,
     K0, C0 = filters.shape[0], filters.shape[-1]
     assert features.shape[1] == C0, "channel size mismatch"
     kv = filters.numel() // (K0 * C0)
+    if features.dtype == torch.float64:
+        return _igemm_fwd_f64(L, features, filters, pair, mask, argsort, n_out, identity_k, bias, act_type,
+                              act_alpha, tile_order, kv)
     # Shapes the MFMA kernels are not instantiated for (a backbone's first layer has 3-5 input
     # channels; widths like 48 or 96) are zero-padded to the next supported shape instead of
     # falling to the one-thread-per-output generic kernel (two orders of magnitude slower): the
@@ -979,6 +982,22 @@ def igemm_fwd(features: torch.Tensor, filters: torch.Tensor, pair: torch.Tensor,
     return out if K == K0 else out[:, :K0].contiguous()
 
 
+def _igemm_fwd_f64(L, features, filters, pair, mask, argsort, n_out, identity_k, bias, act_type, act_alpha,
+                   tile_order, kv):
+    """float64 forward (csrc/igemm_f64.hip): every width and kernel volume as it is -- no padding, no scratch, no
+    BatchNorm statistics out of the epilogue (a sink stays empty and the normalisation layer runs its own pass)."""
+    K, C = filters.shape[0], filters.shape[-1]
+    features, filters = features.contiguous(), filters.contiguous()
+    out = torch.empty((n_out, K), dtype=features.dtype, device=features.device)
+    if bias is not None:
+        bias = bias.to(features.dtype).contiguous()
+    _lib.check(L.spx_igemm_fwd(features.data_ptr(), filters.data_ptr(), out.data_ptr(), _ptr(pair), _ptr(mask),
+                               _ptr(argsort), int(tile_order), features.shape[0], n_out, C, K, kv,
+                               _lib.DTYPE_F64, identity_k, _ptr(bias), int(act_type), float(act_alpha), None, 0,
+                               _stream(features)))
+    return out
+
+
 @_on_device
 def igemm_dgrad(out_bp: torch.Tensor, filters: torch.Tensor, pair: torch.Tensor,
                 mask: Optional[torch.Tensor], argsort: Optional[torch.Tensor], n_in: int,
@@ -988,10 +1007,12 @@ def igemm_dgrad(out_bp: torch.Tensor, filters: torch.Tensor, pair: torch.Tensor,
     L = _lib.load()
     K0, C0 = filters.shape[0], filters.shape[-1]
     kv = filters.numel() // (K0 * C0)
-    # same padding rule as igemm_fwd: here K is the reduction length and C the output width
+    # same padding rule as igemm_fwd: here K is the reduction length and C the output width (float64: none)
     K = -(-K0 // _lane_mult(out_bp.dtype)) * _lane_mult(out_bp.dtype)
     C = _round_cout(C0) if kv <= 128 else C0
-    if C and (C != C0 or K != K0):
+    if out_bp.dtype == torch.float64:
+        C, K = C0, K0
+    elif C and (C != C0 or K != K0):
         out_bp = _pad_last(out_bp, K)
         filters = _pad_first(_pad_last(filters, C), K)
     else:
@@ -1000,11 +1021,13 @@ def igemm_dgrad(out_bp: torch.Tensor, filters: torch.Tensor, pair: torch.Tensor,
     filters = filters.contiguous()
     din = torch.empty((n_in, C), dtype=out_bp.dtype, device=out_bp.device)
     code = _dtype_code(out_bp)
-    ws = _ws(max(L.spx_igemm_dgrad_ws_bytes(C, K, kv, code), L.spx_igemm_acc_bytes(n_in, C, kv)), out_bp.device)
+    # (float64 needs no scratch: the fp32 partial sums of the grouped kernel volumes > 32 belong to the MFMA kernels)
+    ws = None if code == _lib.DTYPE_F64 else _ws(max(L.spx_igemm_dgrad_ws_bytes(C, K, kv, code),
+                                                     L.spx_igemm_acc_bytes(n_in, C, kv)), out_bp.device)
     _lib.check(L.spx_igemm_dgrad(out_bp.data_ptr(), filters.data_ptr(), din.data_ptr(), _ptr(pair),
                                  _ptr(mask), _ptr(argsort), _with_dense_hint(int(tile_order), argsort, mask), out_bp.shape[0],
                                  n_in, C, K, kv, code,
-                                 int(subm), ws.data_ptr(), ws.numel(), _stream(out_bp)))
+                                 int(subm), _ptr(ws), 0 if ws is None else ws.numel(), _stream(out_bp)))
     return din if C == C0 else din[:, :C0].contiguous()
 
 
@@ -1056,12 +1079,16 @@ def igemm_wgrad(features: torch.Tensor, out_bp: torch.Tensor, filters_shape, nat
         return _wgrad_in_groups(features, out_bp, filters_shape, native, num_per_loc, subm, kv)
     m = _lane_mult(features.dtype)
     C, K = -(-C0 // m) * m, -(-K0 // m) * m          # the MFMA wgrad needs whole lane pieces
+    f64 = features.dtype == torch.float64
+    if f64:                                          # (float64: any width as it is)
+        C, K = C0, K0
     features = _pad_last(features, C).contiguous()
     out_bp = _pad_last(out_bp, K).contiguous()
     n_in = native.shape[2]
     shape = (K,) + tuple(filters_shape[1:-1]) + (C,)
     dw = torch.empty(shape, dtype=features.dtype, device=features.device)
-    ws = _ws(L.spx_igemm_wgrad_ws_bytes(n_in, C, K, kv), features.device)
+    ws = _ws(L.spx_igemm_wgrad_ws_bytes_dtype(n_in, C, K, kv, _lib.DTYPE_F64) if f64
+             else L.spx_igemm_wgrad_ws_bytes(n_in, C, K, kv), features.device)
     _lib.check(L.spx_igemm_wgrad(features.data_ptr(), out_bp.data_ptr(), dw.data_ptr(),
                                  native.data_ptr(), num_per_loc.data_ptr(), _ptr(plan), n_in,
                                  out_bp.shape[0], C, K, kv, _dtype_code(features), int(subm),
@@ -1173,7 +1200,8 @@ def igemm_bwd(features: torch.Tensor, out_bp: torch.Tensor, filters: torch.Tenso
         return _igemm_bwd_rows(features, out_bp, filters, table, mask, subm, need_din, K0, C0, kvf)
     if native is None:
         native, num_per_loc, plan = lists()
-    if not need_din or K0 % m or C0 not in _MFMA_COUT or kvf > 32:      # (kv > 32: dgrad in groups of 32 offsets)
+    if (not need_din or K0 % m or C0 not in _MFMA_COUT or kvf > 32      # (kv > 32: dgrad in groups of 32 offsets)
+            or out_bp.dtype == torch.float64):                          # (float64: dgrad + wgrad, no fused launch)
         din = igemm_dgrad(out_bp, filters, table, mask, argsort, features.shape[0], subm,
                           tile_order=tile_order) if need_din else None
         return din, igemm_wgrad(features, out_bp, filters.shape, native, num_per_loc, subm, plan)
