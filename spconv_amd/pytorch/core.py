@@ -29,12 +29,19 @@ class ConvAlgo(Enum):
 class Rulebook:
     """All artefacts of one rulebook, as produced by ``ops.build_rulebook``.
 
-    pair_fwd  [kv, n_out] int32: input row feeding output row o through offset k, or -1
-    pair_bwd  [kv, n_in ] int32: output row fed by input row i through offset k, or -1
-                (SubM: None unless requested; pair_bwd[k] == pair_fwd[kv-1-k])
-    mask_fwd  [n_out, W] int32 (bit k <=> pair_fwd[k][o] >= 0), mask_bwd [n_in, W]
-    pair_native [2, kv, n_in] int32 + num_per_loc [kv]: ConvAlgo.Native lists, identical
-                to the reference CPU path (csrc/sparse/indices.py:1639-1778)
+    Tables: pair_fwd [kv, n_out] int32 (input row feeding output row o through offset k, or -1), pair_bwd [kv, n_in]
+      (output row fed by input row i; SubM: None unless requested, pair_bwd[k] == pair_fwd[kv-1-k]), mask_fwd [n_out, W]
+      (bit k <=> pair_fwd[k][o] >= 0), mask_bwd [n_in, W]; pair_native [2, kv, n_in] + num_per_loc [kv], the
+      ConvAlgo.Native lists of the reference CPU path (csrc/sparse/indices.py:1639-1778), derived from the tables on
+      first use when the build left them out; out_indices, n_in, n_out, kv, subm; wgrad_plan (lazily, ops._plan_of).
+    Geometry of the two row sets (set_geometry): in_indices, in_shape, out_shape, batch_size.
+    Row orders (_rulebook): layout (rows layout of a SubM rulebook: int32 blob of spx_subm_layout, or None);
+      argsort_fwd / argsort_bwd + sorted_tables {"fwd" / "bwd": (pair, mask)} (explicit mask sort: the order and copies of
+      the tables in that tile order); rankmap (rank map of the OUTPUT level of a sorted-order strided build, or None).
+    Density class (_rulebook._set_class): sparse_class (None = not measured yet), heavy_rows (rows with a neighbour), _class_req
+      (pending asynchronous read of the class word), pred_key (the module that owns this rulebook).
+    Static-shape counters (device int32, None otherwise): n_out_dev [2] = {distinct outputs found, hash-table overflow},
+      rows >= the count are dead; in_n_live_dev / out_n_live_dev [1] = live rows of the input / output row sets.
     """
 
     def __init__(self, out_indices, pair_fwd, pair_bwd, mask_fwd, mask_bwd, pair_native,
@@ -51,36 +58,29 @@ class Rulebook:
         self.n_out = n_out
         self.kv = kv
         self.subm = subm
-        self.argsort_fwd = argsort_fwd
-        self.argsort_bwd = argsort_bwd
-        self.wgrad_plan = None          # built lazily by ops._plan_of
+        self.wgrad_plan = None
         self._native_swapped = None
-        # geometry of the two row sets (set by ops.build_rulebook)
         self.in_indices = None
         self.in_shape = None
         self.out_shape = None
         self.batch_size = 1
-        # rows layout of a SubM rulebook (ops.rows_layout: int32 blob of spx_subm_layout -- class word,
-        # row order, mask words and pair table in tile order), None without one
         self.layout = None
-        # copies of the tables in mask-sorted tile order (ops.sort_rulebook): [pair, mask] per
-        # direction, None while unsorted; sort_decided: the automatic mode looked at this rulebook
+        self.argsort_fwd = argsort_fwd
+        self.argsort_bwd = argsort_bwd
         self.sorted_tables = {}
-        self.sort_decided = False
-        # density class (ops.sparse_neighbourhoods): None = not measured yet
+        self.rankmap = None
         self.sparse_class = None
         self.heavy_rows = 0
-        # asynchronous read of the class word (ops.poll_class): the pending request, and whose rulebook this is
         self._class_req = None
         self.pred_key = None
-        # rank map of the OUTPUT level (a sorted-order strided build, ops._build_sorted), or None
-        self.rankmap = None
-        # static-shape build (ops.build_rulebook(static_num_out=...)): device int32 [2] =
-        # {distinct outputs found, hash-table overflow}; rows >= the count are dead.  None otherwise.
         self.n_out_dev = None
-        # live-row counts (device int32 [1] or None = all) of the input / output row sets
         self.in_n_live_dev = None
         self.out_n_live_dev = None
+
+    def set_geometry(self, in_indices, in_shape, out_shape, batch_size: int, pred_key=None) -> None:
+        """What the build knows about the two row sets, and whose rulebook this is (once per build)."""
+        self.in_indices, self.in_shape, self.out_shape = in_indices, list(in_shape), list(out_shape)
+        self.batch_size, self.pred_key = batch_size, pred_key
 
     def _ensure_native(self) -> None:
         """Inference builds only the dense tables; the ConvAlgo.Native lists (consumed by wgrad

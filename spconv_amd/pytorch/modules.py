@@ -102,7 +102,7 @@ class SparseSequential(SparseModule):
                                   and getattr(module, "bias", None) is None and module.training
                                   and not module._forward_hooks and not nxt._forward_hooks
                                   and not nxt._forward_pre_hooks)
-                    with ops.output_stays_cached():     # the normalisation reads the rows next (ops._OUT_CACHED)
+                    with ops.output_stays_cached():     # the normalisation reads the rows next (SPX_OUT_CACHED)
                         if fuse_stats:
                             with ops.collect_bn_stats() as conv_stats:
                                 input = module(input)

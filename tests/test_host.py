@@ -581,3 +581,19 @@ def test_autograd_engine_rule_of_the_package_import(monkeypatch):
     calls.clear()
     monkeypatch.setenv("SPCONV_AMD_AUTOGRAD_THREADS", "keep")
     assert spconv._autograd_on_the_calling_thread() == "kept" and calls == []
+
+
+def test_ops_facade_keeps_every_name_callers_reach_through_it():
+    """ops.py is a facade over private modules: what bench.py, tests/, tools/, __graft_entry__.py and the other modules
+    of the package reach as `ops.<name>` stays there (switches that are assigned through it included)."""
+    names = """Activation BN_EPILOGUE StatsSink _BWD_ROWS _BWD_ROWS_OCC _CLS0_ATTR _DTYPES _LAYOUT_SKIP _POOL_CODES
+        _SORTED_MAX_CELLS_PER_ROW _defer_passes _dense_rows _dtype_code _igemm_bwd_rows _native_from_table _on_device
+        _plan_of _pred_get _rankmap_of _sorted_pays _stream _table_from_native _with_dense_hint attach_rank_map
+        attach_rulebook bias_act_inplace build_rulebook collect_bn_stats current_stats_sink deferred_wgrad
+        get_conv_output_size get_deconv_output_size get_indice_pairs get_indice_pairs_implicit_gemm global_pool_rearrange
+        igemm_bwd igemm_dgrad igemm_fwd igemm_fwd_int8 igemm_wgrad implicit_gemm implicit_gemm_backward
+        indice_avgpool_implicit_gemm indice_avgpool_implicit_gemm_backward indice_conv indice_conv_backward indice_maxpool
+        indice_maxpool_backward indice_maxpool_implicit_gemm indice_maxpool_implicit_gemm_backward key_argsort layout_views
+        mask_argsort output_stays_cached poll_class record_voxel_count_ rows_backward_expected rows_layout rulebook_of
+        sort_rulebook sparse_neighbourhoods tables_of wgrad_plan""".split()
+    assert [n for n in names if not hasattr(ops, n)] == []
