@@ -73,12 +73,15 @@ int spx_set_option(const char *name_h, int value);
 
 /* Diagnostics: how many launches of a kernel family this process has enqueued (or captured) so far -- "igemm_v4" (128 /
  * 64-row gather-GEMM tiles), "igemm_ws" (weight-stationary 512-row workgroups of dense C = K = 64 layers),
- * "igemm_bwd" (fused dgrad + wgrad launch), "igemm_bwd_rows" (one-gather backward), "igemm_i8_stream", "generic";
+ * "igemm_v4w" (column-blocked launches of layers wider than 256 channels), "igemm_bwd" (fused dgrad + wgrad launch),
+ * "igemm_bwd_rows" (one-gather backward), "igemm_i8_stream", "generic";
  * -1 for an unknown name.  The role of the reference's tuner record (which algorithm a layer was given:
  * ConvTunerSimple, csrc/sparse/convops.py:919-1466): lets a test or a benchmark say which kernel a call REALLY took
  * when the choice depends on an asynchronously read density class.
  * Keys with a '/' count one template INSTANCE (dt: f16 | bf16 | i8 | f32):
  *   igemm_v4/<COUT>/<MB>/<dt>/<fwd|bt>/<NKS>/<PK>   forward / dgrad gather-GEMM tile (bt: transposed weight reads)
+ *   igemm_v4w/128/<dt>/<fwd|bt>/<NKS>/<PK>          the same, column-blocked (output widths beyond 256: 128-column x
+ *                                                  64-row tiles; PK in {1, 2, 4}, PK > 1 with NKS 1 and a 16-bit dt; i8: fwd)
  *   igemm_bwd/<COUT>/<MB>/<dt>/<NKS>/<PK>           fused dgrad + wgrad launch
  *   igemm_ws/<dt>                                  weight-stationary kernel (forward and dgrad)
  *   igemm_bwd_rows/<C>/<K>/<dt>/<W8>               rows walk of narrow layers (W8: 0 | 1, eight waves)
@@ -304,7 +307,16 @@ int spx_table_to_native(const int32_t *table, int subm, int kv, int n, int32_t *
  * run as ceil(kv / 32) launches of the MFMA kernel whose partial sums travel through an fp32
  * [n_dst, cout] scratch: pass spx_igemm_acc_bytes() bytes as `ws` to spx_igemm_fwd (n_dst = n_out,
  * cout = K) / spx_igemm_dgrad (n_dst = n_in, cout = C).  0 for kv <= 32; without the scratch such
- * layers take the generic (one thread per output) kernel. */
+ * layers take the generic (one thread per output) kernel.
+ *
+ * Output widths (K of spx_igemm_fwd / _stats / _int8, C of spx_igemm_dgrad and of the dgrad half of spx_igemm_bwd): the
+ * MFMA kernels run 16 / 32 / 64 / 128 / 256 and, beyond 256, every multiple of 128 -- one column-blocked launch
+ * (igemm_wide.hip) for every table form, with the scratch row stride the full width; tensors beyond its 32-bit buffer
+ * offsets (2 GiB per operand) take the generic kernel at these widths, tables by row or a rows layout (there is no
+ * first-generation instance beyond 256 columns).  Other widths take the generic
+ * kernel (float) or are refused (int8): callers zero-pad (the Python drivers do).  The reduction side only has to be a
+ * whole number of 16-byte lane pieces.  Launches beyond 256 columns leave no BatchNorm statistics
+ * (spx_igemm_fwd_stats: *slots_used_h = 0), and the fused backward stays at C <= 128. */
 size_t spx_igemm_acc_bytes(int n_dst, int cout, int kv);
 
 /* Output-stationary implicit GEMM (atomics-free):
@@ -330,7 +342,7 @@ int spx_igemm_fwd(const void *feat, const void *weight, void *out, const int32_t
  * ROUNDED output values, i.e. of what a normalisation layer behind the convolution reads), rows >= *n_live (device,
  * static-shape tensors; NULL = every row) not counted.  *slots_used_h (host) = number of records written = the
  * launch's workgroup count, or 0 when the kernel that was dispatched leaves none (bias / activation in the epilogue,
- * kernel volumes > 32, generic kernels, SPX_F64): spx_batchnorm_fwd_stats then starts at its merge step instead of reading the
+ * kernel volumes > 32, widths beyond 256, generic kernels, SPX_F64): spx_batchnorm_fwd_stats then starts at its merge step instead of reading the
  * rows again for a statistics pass.  `stats` holds stats_slots >= spx_igemm_fwd_stats_slots(n_out) records.
  * The reference leaves BatchNorm to torch on the feature matrix (spconv/pytorch/modules.py:127-168): two extra passes
  * over every activation; this removes the first of them. */
@@ -349,7 +361,7 @@ int spx_igemm_fwd_stats(const void *feat, const void *weight, void *out, const i
  *   out_dtype SPX_I8: clip(round_half_even(v), -128, 127);  SPX_F16 / SPX_BF16 / SPX_F32: v
  *   feat int8 [n_in, C], weight int8 KRSC [K, kv, C], scale / bias fp32 [K] (or NULL = 1 / 0),
  *   add int8 [n_out, K] or NULL (the module passes add_scale = add_q_scale / output_scale).
- * C must be a multiple of 16, K one of 16/32/64/128/256, kv <= 32 (the reference's int8 kernels
+ * C must be a multiple of 16, K one of 16/32/64/128/256 or a multiple of 128 beyond, kv <= 32 (the reference's int8 kernels
  * need C, K % 16 == 0 as well, test/test_all_algo.py:376-377). */
 int spx_igemm_fwd_int8(const void *feat, const void *weight, void *out, const int32_t *pair,
                        const uint32_t *mask, const int32_t *argsort, int n_in, int n_out, int C,

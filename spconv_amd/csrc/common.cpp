@@ -82,6 +82,13 @@ int instance_slot(const char *key) {
       return -1;
     return inst::v4(cout, mb, dt, bt == 1, nks, pk);
   }
+  if (is("igemm_v4w", 6)) {                   // igemm_v4w/128/<dt>/<fwd|bt>/<nks>/<pk>
+    const int nt = parse_int(tok[1]), dt = parse_dt(tok[2]);
+    const int bt = strcmp(tok[3], "bt") == 0 ? 1 : (strcmp(tok[3], "fwd") == 0 ? 0 : -1);
+    const int nks = parse_int(tok[4]), pk = parse_int(tok[5]);
+    if (nt != 128 || bt < 0 || !inst::v4w_exists(dt, bt == 1, nks, pk)) return -1;
+    return inst::v4w(dt, bt == 1, nks, pk);
+  }
   if (is("igemm_bwd", 6)) {
     const int cout = parse_int(tok[1]), mb = parse_int(tok[2]), dt = parse_dt(tok[3]);
     const int nks = parse_int(tok[4]), pk = parse_int(tok[5]);
@@ -149,7 +156,8 @@ const char *spx_last_error(void) { return spx::g_error.c_str(); }
 
 long long spx_launch_count(const char *family_h) {
   static const char *names[spx::kFamCount] = {"igemm_v4", "igemm_ws", "igemm_bwd", "igemm_bwd_rows", "igemm_i8_stream",
-                                              "generic", "wgrad_stage2", "wgrad_stage2_batch", "igemm_f64"};
+                                              "generic", "wgrad_stage2", "wgrad_stage2_batch", "igemm_f64",
+                                              "igemm_v4w"};
   if (!family_h) return -1;
   for (int i = 0; i < spx::kFamCount; ++i)
     if (strcmp(names[i], family_h) == 0) return spx::g_launches[i].load(std::memory_order_relaxed);

@@ -115,7 +115,7 @@ inline Geom make_geom(int ndim, int batch, const int *in_dims, const int *out_di
 // ---- launch counters (diagnostics: which kernel family a call dispatched; spx_launch_count) --------
 namespace spx {
 enum LaunchFamily { kFamV4 = 0, kFamWs, kFamBwdFused, kFamBwdRows, kFamI8Stream, kFamGeneric, kFamStage2, kFamStage2Batch,
-                    kFamF64, kFamCount };
+                    kFamF64, kFamV4w, kFamCount };
 extern std::atomic<long long> g_launches[kFamCount];
 inline void count_launch(LaunchFamily f) { g_launches[f].fetch_add(1, std::memory_order_relaxed); }
 
@@ -139,7 +139,9 @@ constexpr int kWgradMfma = kWgradF32 + 1;                                 // dt
 constexpr int kWgradGeneric = kWgradMfma + kDts;                          // dt
 constexpr int kGeneric = kWgradGeneric + kDts;                            // dt
 constexpr int kGen1 = kGeneric + kDts;                                    // COUT x dt
-constexpr int kCount = kGen1 + kCouts * kDts;
+constexpr int kV4w = kGen1 + kCouts * kDts;                               // dt x BT x NKS x PK (1, 2, 4)
+constexpr int kWidePks = 3;
+constexpr int kCount = kV4w + kDts * 2 * 2 * kWidePks;
 
 constexpr int v4(int cout, int mb, int dt, bool bt, int nks, int pk) {
   return kV4 + ((((cout_slot(cout) * 2 + (mb - 1)) * kDts + dt) * 2 + (bt ? 1 : 0)) * 2 + (nks - 1)) * kPks + pk_slot(pk);
@@ -156,6 +158,15 @@ constexpr int wgrad_mfma(int dt) { return kWgradMfma + dt; }
 constexpr int wgrad_generic(int dt) { return kWgradGeneric + dt; }
 constexpr int generic(int dt) { return kGeneric + dt; }
 constexpr int gen1(int cout, int dt) { return kGen1 + cout_slot(cout) * kDts + dt; }
+// column-blocked launches (igemm_wide.hip; the tile is 128 columns x 64 rows).  Instances that exist: pk 2 / 4 with
+// nks 1 and a 16-bit type only; int8 forward only.
+constexpr bool v4w_exists(int dt, bool bt, int nks, int pk) {
+  return dt >= 0 && dt < kDts && (nks == 1 || nks == 2) && (pk == 1 || ((pk == 2 || pk == 4) && nks == 1 && dt <= 1)) &&
+         !(dt == 2 && bt);
+}
+constexpr int v4w(int dt, bool bt, int nks, int pk) {
+  return kV4w + ((dt * 2 + (bt ? 1 : 0)) * 2 + (nks - 1)) * kWidePks + pk_slot(pk);
+}
 }  // namespace inst
 
 extern std::atomic<long long> g_inst_launches[inst::kCount];

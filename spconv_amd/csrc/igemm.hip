@@ -671,7 +671,10 @@ bool mfma_ok(int dtype, int cin, int cout, int kv, const uint32_t *mask) {
   if (cin % (dtype == SPX_F32 ? 4 : 8) != 0) return false;     // 16-byte lane pieces
   if (kv > 128) return false;                                  // 33 .. 128: groups of 32 offsets
   (void)mask;
-  return cout == 16 || cout == 32 || cout == 64 || cout == 128 || cout == 256;
+  if (cout == 16 || cout == 32 || cout == 64 || cout == 128 || cout == 256) return true;
+  // beyond 256: the column-blocked launch (igemm_wide.hip); SPX_WIDE = 0 keeps the generic kernel (A/B runs:
+  // tools/bench_wide.py -- the tables must then be the row-order ones: tables in tile order are an error on that kernel)
+  return wide_cout(cout) && option_int("SPX_WIDE", 1) != 0;
 }
 
 
@@ -714,7 +717,9 @@ int run_gather_gemm_single(const GemmParams &p, int dtype, hipStream_t s) {
   if (dtype == SPX_F32 && f32_mfma && mfma_ok(dtype, p.CIN, p.COUT, p.kv, p.mask) && v4_ok(p, 4, 4) &&
       (p.kv <= 32 || grouped))
     return dispatch_gather_gemm_f32(p, s);
-  if (dtype != SPX_F32 && mfma_ok(dtype, p.CIN, p.COUT, p.kv, p.mask) && (p.kv <= 32 || grouped))
+  // (widths beyond 256 have no first-generation instance: past the 32-bit buffer offsets they keep the generic kernel)
+  if (dtype != SPX_F32 && mfma_ok(dtype, p.CIN, p.COUT, p.kv, p.mask) && (p.kv <= 32 || grouped) &&
+      (!wide_cout(p.COUT) || v4_ok(p)))
     return dtype == SPX_BF16 ? dispatch_gather_gemm_bf16(p, s) : dispatch_gather_gemm<false>(p, s);
   if (p.cls) {                     // (as above: the generic kernel reads the tables by row)
     GemmParams q = p;
@@ -973,8 +978,8 @@ int spx_igemm_fwd_int8(const void *feat, const void *weight, void *out, const in
   SPX_CHECK(pair || kv == 1, "pair table required");
   // the reference has the same restriction (test/test_all_algo.py:376-377)
   SPX_CHECK(C % 16 == 0, "int8 needs in_channels %% 16 == 0, got %d", C);
-  SPX_CHECK(K == 16 || K == 32 || K == 64 || K == 128 || K == 256,
-            "int8 supports out_channels 16/32/64/128/256, got %d", K);
+  SPX_CHECK(K == 16 || K == 32 || K == 64 || K == 128 || K == 256 || wide_cout(K),
+            "int8 supports out_channels 16/32/64/128/256 or a multiple of 128 beyond, got %d", K);
   SPX_CHECK(kv <= 32, "int8 supports kernel volumes up to 32, got %d", kv);
   SPX_CHECK(out_dtype == SPX_I8 || out_dtype == SPX_F16 || out_dtype == SPX_BF16 || out_dtype == SPX_F32,
             "bad output dtype %d", out_dtype);

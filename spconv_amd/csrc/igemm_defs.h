@@ -75,6 +75,7 @@ struct GemmParams {
   float *stats;
   const int32_t *n_live;
   int *grid_out;
+  int n0;                 // (device side) first output column of the workgroup: column-blocked launches, igemm_wide.hip
 };
 
 // appendix workgroups of a fused backward launch, whose dgrad half shares the chip's 1024 workgroup slots with the
@@ -268,6 +269,11 @@ int dispatch_gather_gemm_f32(const GemmParams &p, hipStream_t s);               
 int dispatch_bwd_f32(const GemmParams &p, const Wgrad2Params &q, int n_wgrad_blocks, hipStream_t s);
 int launch_gather_gemm_int8(const GemmParams &p, bool rows64, hipStream_t s);                        // igemm_i8.hip
 
+// igemm_wide.hip: the column-blocked direct-fragment gather-GEMM for output widths beyond 256 (multiples of 128);
+// dt = the kernels' DT code (0 f16, 1 bf16, 2 int8, 3 fp32)
+constexpr int kWideNT = 128;
+inline bool wide_cout(int cout) { return cout > 256 && cout % kWideNT == 0; }
+int launch_gather_gemm_wide(const GemmParams &p, int dt, hipStream_t s);
 // igemm_gen1.hip: first-generation gather-GEMM (tensors beyond 32-bit buffer offsets)
 int launch_gather_gemm_gen1(const GemmParams &p, bool bf16, hipStream_t s);
 // igemm_ws.hip: weight-stationary gather-GEMM for dense neighbourhoods (forward and dgrad)

@@ -13,6 +13,7 @@ int dispatch_gather_gemm_f32(const GemmParams &p, hipStream_t s) {
     case 128: return launch_v4<128, 2, 3>(p, s);
     case 256: return launch_v4<256, 1, 3>(p, s);
   }
+  if (wide_cout(p.COUT)) return launch_gather_gemm_wide(p, 3, s);
   return -1;
 }
 

@@ -20,6 +20,7 @@ int launch_gather_gemm_int8(const GemmParams &p, bool rows64, hipStream_t s) {
     case 128: return rows64 ? launch_v4<128, 1, 2>(p, s) : launch_v4<128, 2, 2>(p, s);
     case 256: return launch_v4<256, 1, 2>(p, s);
   }
+  if (wide_cout(p.COUT)) return launch_gather_gemm_wide(p, 2, s);
   return -1;
 }
 

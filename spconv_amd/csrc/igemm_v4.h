@@ -42,7 +42,10 @@ __device__ unsigned long long g_timeline[kTlMaxWg * kTlSlots];
 
 
 
-template <int COUT, int MB, int DT, bool BT, int NKS = 2, int PK = 1>
+// WIDE: COUT is the width of the launch's column block only (igemm_wide.hip) -- the rows of `out`, of the fp32 scratch
+// and of the int8 `add` operand are p.COUT wide, and the block's first column p.n0 moves the weight slice and the
+// per-channel vectors.  !WIDE: both are compile-time constants (p.COUT == COUT, n0 == 0), the code is what it was.
+template <int COUT, int MB, int DT, bool BT, int NKS = 2, int PK = 1, bool WIDE = false>
 __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block);
 __device__ __forceinline__ void unpack_gemm_args(GemmParams &p, const void *argA, const void *argB,
                                                  const uint32_t *arg_mask, const int32_t *arg_argsort,
@@ -119,21 +122,21 @@ __device__ __forceinline__ void unpack_gemm_args(GemmParams &p, const void *argA
 // main tiles of igemm_i8_sparse_kernel): lds_sb = [2][COUT] fp32 per-channel scale | bias
 template <int COUT, int MB>
 __device__ __forceinline__ void i8_epilogue(const GemmParams &p, i32x4 (&acc)[COUT / 16][MB], const int (&grow)[MB],
-                                            int lgrp, const float *lds_sb) {
+                                            int lgrp, const float *lds_sb, int ldo = COUT, int n0 = 0) {
   constexpr int NB = COUT / 16, CPL = NB * 4;
   // int8 inference epilogue (reference numerics: test/test_all_algo.py:272-287):
   //   v = acc_i32 * scale[k] + bias[k] + add[o][k] * add_scale;  v = act(v)
   //   int8 out: clip(round_half_even(v), -128, 127);  f16 / f32 out: v
   const int oes = p.out_dtype == SPX_I8 ? 1 : (p.out_dtype == SPX_F32 ? 4 : 2);
   const __amdgpu_buffer_rsrc_t rO =
-      make_rsrc(p.out, static_cast<uint32_t>(p.n_dst) * static_cast<uint32_t>(COUT * oes));
+      make_rsrc(p.out, static_cast<uint32_t>(p.n_dst) * static_cast<uint32_t>(ldo * oes));
   const __amdgpu_buffer_rsrc_t rAdd =
-      make_rsrc(p.add, p.add ? static_cast<uint32_t>(p.n_dst) * COUT : 0u);
+      make_rsrc(p.add, p.add ? static_cast<uint32_t>(p.n_dst) * ldo : 0u);
   uint32_t rowoff[MB];
   uint32_t addw[MB][CPL / 4];
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) {
-    rowoff[mb] = grow[mb] < 0 ? kOob : static_cast<uint32_t>(grow[mb]) * COUT + lgrp * CPL;
+    rowoff[mb] = grow[mb] < 0 ? kOob : static_cast<uint32_t>(grow[mb]) * ldo + n0 + lgrp * CPL;
     load_dwords<CPL / 4>(addw[mb], rAdd, rowoff[mb]);   // zeros when there is no residual input
   }
   // four channels (one output dword of an int8 row) at a time keeps the live set small
@@ -219,7 +222,7 @@ __device__ __forceinline__ void i8_epilogue(const GemmParams &p, i32x4 (&acc)[CO
 // ahead of the mask exchange) -- the same load instructions per offset, a fraction of the steps, barriers and pair-word
 // trips (~1 us of kernel time per step and launch on the 400 k-row level of config 4).  Sums of a row associate
 // differently than with one offset per step: the same values to fp32 rounding, not bit for bit.
-template <int COUT, int MB, int DT, bool BT, int NKS, int PK>
+template <int COUT, int MB, int DT, bool BT, int NKS, int PK, bool WIDE>
 __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
   constexpr bool BF16 = DT == 1, I8 = DT == 2, F32 = DT == 3;
   constexpr bool XK = PK >= 8;                          // both pieces of a step packed
@@ -230,6 +233,8 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
   constexpr int ES = I8 ? 1 : (F32 ? 4 : 2);            // bytes per element
   static_assert(!(I8 && BT), "int8 is forward only");
   constexpr int NB = COUT / 16;
+  const int ldo = WIDE ? p.COUT : COUT;                 // row stride of out / acc / add (elements)
+  const int n0 = WIDE ? p.n0 : 0;                       // first output column of this workgroup
   constexpr int TM = 64 * MB;                           // rows per workgroup: 4 waves x MB x 16
   // 16-byte weight vectors staged per thread: [COUT][128 B] row-wise (forward), or the
   // transposing read of dgrad (pairs of reduction rows x 8 channels for 16-bit, one reduction
@@ -275,7 +280,7 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
     const int cls = *(cptr_t)(p.cls);
     app_m = *(cptr_t)(p.cls + 1);
     if (!cls) {
-      if constexpr (!I8 && !BT) if (p.stats) wg_bn_stats_empty<COUT>(p.stats, block, static_cast<int>(gridDim.x));
+      if constexpr (!I8 && !BT && !WIDE) if (p.stats) wg_bn_stats_empty<COUT>(p.stats, block, static_cast<int>(gridDim.x));
       return;
     }
     // The M rows of the appendix are dealt to the launch's napp appendix workgroups in whole 16-row blocks, h rows
@@ -287,7 +292,7 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
     const int groups = p.app_budget > 0 ? min(napp, p.app_budget) : napp;
     const int h = min(TM, (((app_m + groups - 1) / groups) + 15) & ~15);
     if (block * h >= app_m) {
-      if constexpr (!I8 && !BT) if (p.stats) wg_bn_stats_empty<COUT>(p.stats, block, static_cast<int>(gridDim.x));
+      if constexpr (!I8 && !BT && !WIDE) if (p.stats) wg_bn_stats_empty<COUT>(p.stats, block, static_cast<int>(gridDim.x));
       return;
     }
 #pragma unroll
@@ -388,7 +393,7 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
       const int n = r0 + 32 * j;
       // PK: 16-byte slot `slot` of the stage row holds slot % GL of the row of offset slot / GL (slots 4 .. 7: nothing)
       const int sl = T == 1 ? slot : slot % GL;
-      const uint32_t o = static_cast<uint32_t>(n) * static_cast<uint32_t>(p.strideN) * ES + sl * 16u;
+      const uint32_t o = static_cast<uint32_t>(n0 + n) * static_cast<uint32_t>(p.strideN) * ES + sl * 16u;
       bgrp[j] = T == 1 ? 0 : slot / GL;
       boff[j] = (n < COUT && (T == 1 || XK || slot < 4)) ? o : kOob;
       boff_tail[j] = sl * 16 < ctail ? 0u : kOob;
@@ -401,7 +406,7 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
       const int n = F32 ? j * 32 + slot * 4 : (j >> 1) * 64 + slot * 8;
       // PK: reduction position d of the stage = position d % (8 GL) of the row of offset d / (8 GL) (d >= 32: nothing)
       const int dl = T == 1 ? d : d % (8 * GL);
-      const uint32_t o = (static_cast<uint32_t>(dl) * static_cast<uint32_t>(p.strideD) + n) * ES;
+      const uint32_t o = (static_cast<uint32_t>(dl) * static_cast<uint32_t>(p.strideD) + n0 + n) * ES;
       bgrp[j] = T == 1 ? 0 : (d / (8 * GL)) & 7;
       boff[j] = (n < COUT && (T == 1 || XK || d < 32)) ? o : kOob;
       boff_tail[j] = dl * ES < ctail ? 0u : kOob;
@@ -584,7 +589,7 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
   if constexpr (I8) {
     const float *bias_f = static_cast<const float *>(p.bias);
     for (int c = tid; c < 2 * COUT; c += kThreads)
-      lds_sb[c] = c < COUT ? (p.scale ? p.scale[c] : 1.f) : (bias_f ? bias_f[c - COUT] : 0.f);
+      lds_sb[c] = c < COUT ? (p.scale ? p.scale[n0 + c] : 1.f) : (bias_f ? bias_f[n0 + c - COUT] : 0.f);
   }
   __syncthreads();
   SPX_STAMP(2);   // mask words arrived, tile mask exchanged
@@ -717,24 +722,24 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
   if constexpr (!I8) {
     // bias/activation; fp32 -> 16 bit with packed converts, or fp32 as it is
     const bool plain = p.bias == nullptr && p.act == SPX_ACT_NONE;   // uniform: training path
-    const __amdgpu_buffer_rsrc_t rO = make_rsrc(p.out, static_cast<uint32_t>(p.n_dst) * (COUT * ES));
+    const __amdgpu_buffer_rsrc_t rO = make_rsrc(p.out, static_cast<uint32_t>(p.n_dst) * (ldo * ES));
     float bv[CPL];
 #pragma unroll
     for (int q = 0; q < CPL; ++q) bv[q] = 0.f;
     if (p.bias) {
 #pragma unroll
       for (int q = 0; q < CPL; ++q) {
-        if constexpr (F32) bv[q] = static_cast<const float *>(p.bias)[lgrp * CPL + q];
-        else bv[q] = to_float<BF16>(static_cast<const uint16_t *>(p.bias)[lgrp * CPL + q]);
+        if constexpr (F32) bv[q] = static_cast<const float *>(p.bias)[n0 + lgrp * CPL + q];
+        else bv[q] = to_float<BF16>(static_cast<const uint16_t *>(p.bias)[n0 + lgrp * CPL + q]);
       }
     }
     if (p.acc_mode) {
       // one group of a kernel volume > 32: partial sums come from / go to the fp32 scratch; bias and
       // activation apply with the last group only (acc_mode bit 1 clear)
-      const __amdgpu_buffer_rsrc_t rS = make_rsrc(p.acc, static_cast<uint32_t>(p.n_dst) * (COUT * 4));
+      const __amdgpu_buffer_rsrc_t rS = make_rsrc(p.acc, static_cast<uint32_t>(p.n_dst) * (ldo * 4));
 #pragma unroll
       for (int mb = 0; mb < MB; ++mb) {
-        const uint32_t so = grow[mb] < 0 ? kOob : static_cast<uint32_t>(grow[mb]) * (COUT * 4) + lgrp * (CPL * 4);
+        const uint32_t so = grow[mb] < 0 ? kOob : static_cast<uint32_t>(grow[mb]) * (ldo * 4) + (n0 + lgrp * CPL) * 4;
         uint32_t prev[CPL];
         if (p.acc_mode & 1) load_dwords<CPL>(prev, rS, so);
 #pragma unroll
@@ -769,7 +774,7 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
         }
       }
       const uint32_t vo = grow[mb] < 0 ? kOob
-                                       : static_cast<uint32_t>(grow[mb]) * (COUT * ES) + lgrp * (CPL * ES);
+                                       : static_cast<uint32_t>(grow[mb]) * (ldo * ES) + (n0 + lgrp * CPL) * ES;
       // non-temporal stores: the rows are not read again by this launch, and lines left dirty in the L2 /
       // Infinity Cache are written back at the kernel boundary and push the next scene's inputs out
       // (cfg 2 step 37.4 -> 33.6 us; sc1 stores 41.9; neutral on the fixture and inside the backbone)
@@ -778,7 +783,7 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
     }
     // BatchNorm statistics of the rows this workgroup stores (spx_igemm_fwd_stats; the host asks for them on plain
     // launches only: no bias, no activation) -- of the ROUNDED values, i.e. of what the normalisation layer will read
-    if constexpr (!BT) {
+    if constexpr (!BT && !WIDE) {
       if (p.stats) {
         const int st_live = p.n_live ? *p.n_live : 0x7fffffff;
         __syncthreads();      // every wave is past its last read of the weight stages: the LDS is free
@@ -787,7 +792,7 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
       }
     }
   } else {
-    i8_epilogue<COUT, MB>(p, acc, grow, lgrp, lds_sb);
+    i8_epilogue<COUT, MB>(p, acc, grow, lgrp, lds_sb, ldo, n0);
   }
   SPX_STAMP(6);   // stores issued
 #ifdef SPX_TIMELINE
@@ -1086,6 +1091,7 @@ int dispatch_gather_gemm(const GemmParams &p, hipStream_t s) {
       case 128: return mb == 1 ? launch_v4<128, 1, BF16 ? 1 : 0>(p, s) : launch_v4<128, 2, BF16 ? 1 : 0>(p, s);
       case 256: return launch_v4<256, 1, BF16 ? 1 : 0>(p, s);
     }
+    if (wide_cout(p.COUT)) return launch_gather_gemm_wide(p, BF16 ? 1 : 0, s);      // igemm_wide.hip
   }
   if (p.cls) {                     // a rows layout is a hint: the first-generation kernel reads the tables by row
     GemmParams q = p;

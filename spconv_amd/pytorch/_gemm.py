@@ -139,12 +139,16 @@ def _lane_mult(dtype: torch.dtype) -> int:
     return 4 if dtype == torch.float32 else 16 if dtype == torch.int8 else 8
 
 
+_WIDE_TILE = 128        # column block of the wide launches (csrc/igemm_wide.hip: kWideNT)
+
+
 def _round_cout(c: int) -> int:
-    """Smallest output width the MFMA kernels are instantiated for (0: none, generic kernel)."""
+    """Smallest output width the MFMA kernels run: an instantiated width up to 256, the next multiple of the column
+    block beyond (csrc/igemm_wide.hip: one column-blocked launch, at most 127 zero columns)."""
     for v in _MFMA_COUT:
         if c <= v:
             return v
-    return 0
+    return -(-c // _WIDE_TILE) * _WIDE_TILE
 
 
 def _pad_last(t: torch.Tensor, to: int) -> torch.Tensor:
@@ -174,11 +178,12 @@ def _pad_first(t: torch.Tensor, to: int) -> torch.Tensor:
 @functools.lru_cache(maxsize=None)       # (a pure function of five small values, asked for every launch)
 def _padded_ck(dtype: torch.dtype, role: str, C0: int, K0: int, kv: int):
     """THE padding rule: the (C, K) a driver runs filters [K0, kv, C0] in.  The MFMA kernels take reduction lengths in
-    whole 16-byte lane pieces and the output widths of _MFMA_COUT.  Shapes they are not instantiated for (a backbone's
-    first layer has 3-5 input channels; widths like 48 or 96) are zero-padded to the next supported shape instead of
-    falling to the one-thread-per-output generic kernel (two orders of magnitude slower): the extra columns cost a few
-    bytes per row and contribute exact zeros; the driver slices them off its result.  role "fwd" reduces over C into K
-    columns, "dgrad" over K into C columns; "wgrad" has both as lane dimensions."""
+    whole 16-byte lane pieces and the output widths of _MFMA_COUT; beyond 256 columns the column-blocked launch takes
+    every multiple of 128 (float and int8 alike).  Shapes they are not instantiated for (a backbone's first layer has
+    3-5 input channels; widths like 48, 96 or 320) are zero-padded to the next supported shape instead of falling to the
+    one-thread-per-output generic kernel: the extra columns cost a few bytes per row and contribute exact zeros; the
+    driver slices them off its result.  Only kernel volumes beyond 128 keep the generic kernel, and their shape.  role
+    "fwd" reduces over C into K columns, "dgrad" over K into C columns; "wgrad" has both as lane dimensions."""
     if dtype == torch.float64:                  # csrc/igemm_f64.hip runs every width as it is
         return C0, K0
     lane = _lane_mult(dtype)
@@ -186,10 +191,6 @@ def _padded_ck(dtype: torch.dtype, role: str, C0: int, K0: int, kv: int):
         return -(-C0 // lane) * lane, -(-K0 // lane) * lane
     red, out = (C0, K0) if role == "fwd" else (K0, C0)
     width = _round_cout(out) if (kv <= 128 or dtype == torch.int8) else out     # (kv > 128: the grouped kernel, any width)
-    if not width:                               # wider than every instantiation:
-        if dtype != torch.int8:
-            return C0, K0                       # the generic kernel takes the shape as it is
-        width = out
     red = -(-red // lane) * lane
     return (red, width) if role == "fwd" else (width, red)
 
@@ -228,7 +229,7 @@ def igemm_fwd(features: torch.Tensor, filters: torch.Tensor, pair: torch.Tensor,
     act = int(act_type) | (_OUT_CACHED if getattr(_out_policy, "cached", False) else 0)
     sink = getattr(_stats_req, "sink", None)
     if (sink is not None and sink.records is None and bias is None and int(act_type) == Activation.None_
-            and K == K0 and kv <= 32 and n_out > 0):
+            and K == K0 and K <= _MFMA_COUT[-1] and kv <= 32 and n_out > 0):    # (wide layers leave no statistics)
         slots = int(L.spx_igemm_fwd_stats_slots(n_out))
         # [field][channel][workgroup] over the `used` workgroups of the launch (igemm_defs.h bn_record_store): a flat buffer
         records = torch.empty((3 * K * slots,), dtype=torch.float32, device=features.device)

@@ -558,10 +558,10 @@ def tables_of(rb: Rulebook, which: str, cout: int = 64):
     over the output rows, "bwd": pair_bwd over the input rows).  tile_order 0: tables by row (argsort,
     if any, permutes the rows); 1: copies in tile order (explicit mask sort); 2: `argsort` is the rows
     layout blob and pair / mask the row-order tables (the device picks).  `cout`: output width of the
-    GEMM (widths beyond the MFMA instantiations take the generic kernel, which reads the tables by row)."""
+    GEMM (every width reaches a kernel that takes all three forms; kernel volumes beyond 32 read the tables by row)."""
     pair, mask, order = ((rb.pair_fwd, rb.mask_fwd, rb.argsort_fwd) if which == "fwd"
                          else (rb.pair_bwd, rb.mask_bwd, rb.argsort_bwd))
-    if cout > _MFMA_COUT[-1] or rb.kv > 32:
+    if rb.kv > 32:
         return pair, mask, None, 0
     st = rb.sorted_tables.get(which)
     if order is not None and st is not None:
