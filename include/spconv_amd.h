@@ -606,7 +606,10 @@ int spx_hash_items(void *table_keys, void *table_vals, int capacity, int key_byt
  * spconv/pytorch/modules.py:131-145; SparseBatchNorm / SparseReLU, :147-185).  These two calls do
  * the same arithmetic (torch.nn.BatchNorm1d semantics: biased variance to normalise, unbiased for
  * the running estimate, `momentum`, `eps`, optional affine) as three streaming launches per pass.
- *   x, y, dy, dx      [n, C] row-major, dtype f16 / bf16 / f32, C a multiple of 8 (f32: 4), C <= 256
+ *   x, y, dy, dx      [n, C] row-major, dtype f16 / bf16 / f32, C a multiple of 8 (f32: 4), C <= 65536.
+ *                     Beyond 256 channels the row-streaming launches run over column blocks of 256 channels
+ *                     (the last may be narrower); each channel is summed in the order the 256-wide kernel
+ *                     sums it on a contiguous copy of its column block, so the results agree bit for bit
  *   weight, bias      [C] or NULL;  running_mean / running_var [C] or NULL (updated in place when
  *                     training, read when not)
  *   save_mean / save_invstd [C] fp32: batch statistics for the backward pass (training)

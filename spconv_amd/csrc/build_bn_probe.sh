@@ -2,6 +2,7 @@
 # Measurement build of norm.hip with SPX_BN_PROBE (SPX_BN_PHASES picks which launches of a BatchNorm call are issued, so
 # that tools/bn_probe.py can time each alone): lib/libspconv_amd_bnprobe.so, selected with SPX_LIB.  Product build
 # (csrc/build.sh) first: the other objects are linked from it.
+# The switch covers the column-blocked launches of matrices wider than 256 channels too (tools/bn_probe.py --wide).
 set -e
 cd "$(dirname "$0")"
 OUT=../lib

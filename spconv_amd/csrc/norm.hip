@@ -13,6 +13,13 @@
 // merged with Chan's parallel update, so cancellation is bounded by the spread inside ~400 rows.
 // Semantics are torch.nn.BatchNorm1d's: biased variance for normalisation, unbiased for the running
 // estimate, `momentum`, `eps`, affine weight / bias (may be NULL).
+//
+// Matrices wider than kT = 256 channels run the same four row-streaming kernels over column blocks of kT channels
+// (the last one may be narrower): blockIdx.y is the column block, a piece lives at row * (C / VPL) + block_piece0 +
+// piece.  Inside its block a workgroup does what the <= kT kernel does on a [n, Cb] matrix -- the same row partition,
+// the same walk per thread, the same reduction -- so every channel of a wide matrix is summed in the order the kT-wide
+// kernel sums it on a contiguous copy of that column block, and the results agree bit for bit.  WIDE = false is the
+// kernel of before (one column block at pitch C), launched on a one-dimensional grid.
 #include "common.h"
 
 namespace spx {
@@ -103,6 +110,27 @@ __device__ __forceinline__ int live_rows(const int32_t *n_live, int n) {
   return v < 0 ? 0 : (v < n ? v : n);
 }
 
+// The channels [c0, c0 + Cb) a workgroup works on: all C of them, or column block blockIdx.y of a wide matrix.
+// P = 16-byte pieces of a row inside the block, Prow = pieces of a whole row (the pitch), piece0 = c0 / VPL.
+struct ColBlock {
+  int c0, Cb, P, Prow, piece0;
+};
+template <int VPL, bool WIDE>
+__device__ __forceinline__ ColBlock col_block(int C) {
+  ColBlock b;
+  b.Prow = C / VPL;
+  if (WIDE) {
+    b.c0 = static_cast<int>(blockIdx.y) * kT;
+    b.Cb = min(kT, C - b.c0);
+  } else {
+    b.c0 = 0;
+    b.Cb = C;
+  }
+  b.P = b.Cb / VPL;
+  b.piece0 = b.c0 / VPL;
+  return b;
+}
+
 // A block owns rows [r0, r1); thread t reads the 16-byte piece (t % P) of rows r0 + t / P + i * (kT / P),
 // P = pieces per row = C / VPL (a power of two <= 64 is not required: kT / P rows per sweep, threads past
 // (kT / P) * P idle).
@@ -183,18 +211,21 @@ __device__ __forceinline__ void piece_reduce(float (&a)[VPL], float (&b)[VPL], i
 
 // partial[0][c][b] = rows of block b, [1][c][b] = mean, [2][c][b] = M2 (sum of squared deviations): field-major, then
 // channel, then block -- the merge reads each field of a channel as one contiguous run (igemm_defs.h bn_record_store)
-template <int DT>
+template <int DT, bool WIDE>
 __global__ void __launch_bounds__(kT)
 bn_partial_kernel(const u32x4 *__restrict__ x, int n, int C, float *__restrict__ partial,
                   const int32_t *__restrict__ n_live) {
   constexpr int VPL = Vec<DT>::VPL;
   __shared__ float lds[2][kT][VPL + 1];
-  const int P = C / VPL;
+  const ColBlock blk = col_block<VPL, WIDE>(C);
+  const int P = blk.P;
+  const size_t pitch = blk.Prow;
+  x += blk.piece0;                                        // (the block's first piece of row 0)
   const RowSplit s = row_split(live_rows(n_live, n), P, gridDim.x);
   float shift[VPL], sum[VPL], sq[VPL];
 #pragma unroll
   for (int i = 0; i < VPL; ++i) shift[i] = sum[i] = sq[i] = 0.f;
-  if (s.active && s.r0 < s.r1) Vec<DT>::unpack(x[static_cast<size_t>(s.r0) * P + s.piece], shift);
+  if (s.active && s.r0 < s.r1) Vec<DT>::unpack(x[static_cast<size_t>(s.r0) * pitch + s.piece], shift);
   if (s.active) {
     // eight rows of loads in flight per thread (a block owns 64-390 rows: one trip; without this a thread's loads were
     // a chain of memory round trips); rows past the block's end are predicated, not branched around
@@ -204,7 +235,7 @@ bn_partial_kernel(const u32x4 *__restrict__ x, int n, int C, float *__restrict__
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int ru = r + u * s.rows_per_sweep;
-        v[u] = ru < s.r1 ? x[static_cast<size_t>(ru) * P + s.piece] : u32x4{0u, 0u, 0u, 0u};
+        v[u] = ru < s.r1 ? x[static_cast<size_t>(ru) * pitch + s.piece] : u32x4{0u, 0u, 0u, 0u};
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -226,19 +257,19 @@ bn_partial_kernel(const u32x4 *__restrict__ x, int n, int C, float *__restrict__
     for (int i = 0; i < VPL; ++i) sum[i] = sq[i] = 0.f;
   }
   float a, b;
-  piece_reduce<VPL>(sum, sq, P, C, s.rows_per_sweep, lds, a, b);
-  // threads 0 .. C-1: one channel each
-  if (threadIdx.x < C) {
+  piece_reduce<VPL>(sum, sq, P, blk.Cb, s.rows_per_sweep, lds, a, b);
+  // threads 0 .. Cb-1: one channel each
+  if (threadIdx.x < blk.Cb) {
     const int piece = threadIdx.x / VPL, e = threadIdx.x % VPL;
     const float cnt = static_cast<float>(s.r1 - s.r0);
     // the shift of channel c is the block's first row, read again by this thread
     float sh = 0.f;
     if (s.r0 < s.r1) {
       float f[VPL];
-      Vec<DT>::unpack(x[static_cast<size_t>(s.r0) * P + piece], f);
+      Vec<DT>::unpack(x[static_cast<size_t>(s.r0) * pitch + piece], f);
       sh = f[e];
     }
-    const size_t G = gridDim.x, c = threadIdx.x;
+    const size_t G = gridDim.x, c = blk.c0 + threadIdx.x;
     partial[c * G + blockIdx.x] = cnt;
     partial[(C + c) * G + blockIdx.x] = cnt > 0.f ? sh + a / cnt : 0.f;
     partial[(2 * static_cast<size_t>(C) + c) * G + blockIdx.x] = cnt > 0.f ? b - a * a / cnt : 0.f;
@@ -313,7 +344,11 @@ bn_finalize_kernel(const float *__restrict__ partial, int G, int C, float eps, f
 // y = x * scale[c] + shift[c] (scale = invstd * w, shift = b - mean * scale), optional ReLU.  The two
 // coefficient vectors are computed once per block into LDS.  stat_is_var: `stat2` holds a variance
 // (inference with the running estimate, dtype pdt like `stat1`) instead of the saved fp32 1 / std.
-template <int DT>
+// WIDE: the workgroups of column block blockIdx.y stream that block's pieces; a thread keeps one piece (threadIdx.x %
+// P) and walks rows blockIdx.x * (kT / P) + threadIdx.x / P + i * gridDim.x * (kT / P), so the kT / P rows of a sweep
+// are runs of whole 16-byte pieces (a full block of a 16-bit row: four 128-byte lines) and the thread's channels --
+// hence its coefficients -- never change.
+template <int DT, bool WIDE>
 __global__ void __launch_bounds__(kT)
 bn_apply_kernel(const u32x4 *__restrict__ x, u32x4 *__restrict__ y, long long pieces, int C,
                 const void *__restrict__ stat1, const void *__restrict__ stat2,
@@ -321,6 +356,43 @@ bn_apply_kernel(const u32x4 *__restrict__ x, u32x4 *__restrict__ y, long long pi
                 int stat_is_var, int relu, const int32_t *__restrict__ n_live, int n) {
   constexpr int VPL = Vec<DT>::VPL;
   __shared__ __attribute__((aligned(16))) float l_sc[kT], l_sh[kT];
+  const ColBlock blk = col_block<VPL, WIDE>(C);
+  if (WIDE) {
+    const int rps = kT / blk.P, piece = threadIdx.x % blk.P, lane_row = threadIdx.x / blk.P;
+    const bool active = lane_row < rps;
+    const long long step = static_cast<long long>(gridDim.x) * rps;
+    long long r = static_cast<long long>(blockIdx.x) * rps + lane_row;
+    x += blk.piece0 + piece;
+    y += blk.piece0 + piece;
+    u32x4 v = active && r < n ? x[r * blk.Prow] : u32x4{0u, 0u, 0u, 0u};       // (before the prologue, as below)
+    if (threadIdx.x < blk.Cb) {
+      const int c = blk.c0 + threadIdx.x;
+      const float mean = stat_is_var ? ldp(stat1, pdt, c) : static_cast<const float *>(stat1)[c];
+      const float is = stat_is_var ? rsqrtf(ldp(stat2, pdt, c) + eps) : static_cast<const float *>(stat2)[c];
+      const float sc = is * (weight ? ldp(weight, pdt, c) : 1.f);
+      l_sc[threadIdx.x] = sc;
+      l_sh[threadIdx.x] = (bias ? ldp(bias, pdt, c) : 0.f) - mean * sc;
+    }
+    __syncthreads();
+    if (!active) return;
+    const int live = live_rows(n_live, n), c0 = piece * VPL;
+    while (r < n) {
+      const long long nxt = r + step;
+      const u32x4 vn = nxt < n ? x[nxt * blk.Prow] : u32x4{0u, 0u, 0u, 0u};
+      float f[VPL];
+      Vec<DT>::unpack(v, f);
+#pragma unroll
+      for (int e = 0; e < VPL; ++e) {
+        float o = f[e] * l_sc[c0 + e] + l_sh[c0 + e];
+        if (relu) o = o > 0.f ? o : 0.f;
+        f[e] = r < live ? o : 0.f;
+      }
+      __builtin_nontemporal_store(Vec<DT>::pack(f), &y[r * blk.Prow]);
+      v = vn;
+      r = nxt;
+    }
+    return;
+  }
   // the first piece of this thread is asked for BEFORE the coefficients are put together: its latency runs under the
   // prologue's (parameter loads -> LDS -> barrier), not behind it
   long long i = static_cast<long long>(blockIdx.x) * kT + threadIdx.x;
@@ -361,7 +433,7 @@ bn_apply_kernel(const u32x4 *__restrict__ x, u32x4 *__restrict__ y, long long pi
 // thread were as many requests as the rows themselves on a small level).
 constexpr int kBwdBatch = 8;
 
-template <int DT>
+template <int DT, bool WIDE>
 __global__ void __launch_bounds__(kT)
 bn_bwd_partial_kernel(const u32x4 *__restrict__ x, const u32x4 *__restrict__ dy, int n, int C,
                       const float *__restrict__ mean, const float *__restrict__ invstd,
@@ -370,7 +442,11 @@ bn_bwd_partial_kernel(const u32x4 *__restrict__ x, const u32x4 *__restrict__ dy,
   constexpr int VPL = Vec<DT>::VPL;
   __shared__ float lds[2][kT][VPL + 1];
   __shared__ __attribute__((aligned(16))) float l_a[kT], l_b[kT], l_w[kT], l_bias[kT];
-  const int P = C / VPL;
+  const ColBlock blk = col_block<VPL, WIDE>(C);
+  const int P = blk.P;
+  const size_t pitch = blk.Prow;
+  x += blk.piece0;
+  dy += blk.piece0;
   const RowSplit s = row_split(live_rows(n_live, n), P, gridDim.x);
   constexpr int U = kBwdBatch;
   u32x4 vx[U], vg[U];
@@ -379,16 +455,16 @@ bn_bwd_partial_kernel(const u32x4 *__restrict__ x, const u32x4 *__restrict__ dy,
   for (int u = 0; u < U; ++u) {
     const int ru = r + u * s.rows_per_sweep;
     const bool ok = s.active && ru < s.r1;
-    vx[u] = ok ? x[static_cast<size_t>(ru) * P + s.piece] : u32x4{0u, 0u, 0u, 0u};
-    vg[u] = ok ? dy[static_cast<size_t>(ru) * P + s.piece] : u32x4{0u, 0u, 0u, 0u};
+    vx[u] = ok ? x[static_cast<size_t>(ru) * pitch + s.piece] : u32x4{0u, 0u, 0u, 0u};
+    vg[u] = ok ? dy[static_cast<size_t>(ru) * pitch + s.piece] : u32x4{0u, 0u, 0u, 0u};
   }
-  if (threadIdx.x < C) {
-    const int c = threadIdx.x;
+  if (threadIdx.x < blk.Cb) {
+    const int t = threadIdx.x, c = blk.c0 + t;           // (LDS by the channel inside the block)
     const float is = invstd[c];
-    l_a[c] = is;
-    l_b[c] = -mean[c] * is;
-    l_w[c] = weight ? ldp(weight, pdt, c) : 1.f;
-    l_bias[c] = bias ? ldp(bias, pdt, c) : 0.f;
+    l_a[t] = is;
+    l_b[t] = -mean[c] * is;
+    l_w[t] = weight ? ldp(weight, pdt, c) : 1.f;
+    l_bias[t] = bias ? ldp(bias, pdt, c) : 0.f;
   }
   __syncthreads();
   float s1[VPL], s2[VPL], ca[VPL], cb[VPL], w[VPL], bb[VPL];
@@ -424,17 +500,17 @@ bn_bwd_partial_kernel(const u32x4 *__restrict__ x, const u32x4 *__restrict__ dy,
         for (int u = 0; u < U; ++u) {
           const int ru = r + u * s.rows_per_sweep;
           const bool ok = ru < s.r1;
-          vx[u] = ok ? x[static_cast<size_t>(ru) * P + s.piece] : u32x4{0u, 0u, 0u, 0u};
-          vg[u] = ok ? dy[static_cast<size_t>(ru) * P + s.piece] : u32x4{0u, 0u, 0u, 0u};
+          vx[u] = ok ? x[static_cast<size_t>(ru) * pitch + s.piece] : u32x4{0u, 0u, 0u, 0u};
+          vg[u] = ok ? dy[static_cast<size_t>(ru) * pitch + s.piece] : u32x4{0u, 0u, 0u, 0u};
         }
       }
     }
   }
   float a, b;
-  piece_reduce<VPL>(s1, s2, P, C, s.rows_per_sweep, lds, a, b);
-  if (threadIdx.x < C) {
-    partial[static_cast<size_t>(blockIdx.x) * 2 * C + threadIdx.x] = a;
-    partial[static_cast<size_t>(blockIdx.x) * 2 * C + C + threadIdx.x] = b;
+  piece_reduce<VPL>(s1, s2, P, blk.Cb, s.rows_per_sweep, lds, a, b);
+  if (threadIdx.x < blk.Cb) {
+    partial[static_cast<size_t>(blockIdx.x) * 2 * C + blk.c0 + threadIdx.x] = a;
+    partial[static_cast<size_t>(blockIdx.x) * 2 * C + C + blk.c0 + threadIdx.x] = b;
   }
 }
 
@@ -468,8 +544,9 @@ bn_bwd_finalize_kernel(const float *__restrict__ partial, int G, int C, float *_
 }
 
 // training: dx = w * invstd * (dy - sum_dy / n - xhat * sum_dy_xhat / n);  inference statistics
-// (use_batch_stats == 0): dx = w * invstd * dy.  Per-channel coefficients staged in LDS.
-template <int DT>
+// (use_batch_stats == 0): dx = w * invstd * dy.  Per-channel coefficients staged in LDS.  WIDE: the walk of
+// bn_apply_kernel<DT, true>.
+template <int DT, bool WIDE>
 __global__ void __launch_bounds__(kT)
 bn_bwd_apply_kernel(const u32x4 *__restrict__ x, const u32x4 *__restrict__ dy, u32x4 *__restrict__ dx,
                     long long pieces, int n, int C, const float *__restrict__ mean,
@@ -480,19 +557,43 @@ bn_bwd_apply_kernel(const u32x4 *__restrict__ x, const u32x4 *__restrict__ dy, u
   // xhat = x * l_a + l_b;  relu mask: xhat * l_w + l_bias <= 0;  dx = l_g * (dy' - l_c1 - xhat * l_c2)
   __shared__ __attribute__((aligned(16))) float l_a[kT], l_b[kT], l_w[kT], l_bias[kT], l_g[kT], l_c1[kT], l_c2[kT];
   const int n_eff = live_rows(n_live, n);
-  if (threadIdx.x < C) {
-    const int c = threadIdx.x;
+  const ColBlock blk = col_block<VPL, WIDE>(C);
+  if (threadIdx.x < blk.Cb) {
+    const int t = threadIdx.x, c = blk.c0 + t;           // (LDS by the channel inside the block)
     const float inv_n = (use_batch_stats && n_eff > 0) ? 1.f / static_cast<float>(n_eff) : 0.f;
     const float w = weight ? ldp(weight, pdt, c) : 1.f;
-    l_a[c] = invstd[c];
-    l_b[c] = -mean[c] * invstd[c];
-    l_w[c] = w;
-    l_bias[c] = bias ? ldp(bias, pdt, c) : 0.f;
-    l_g[c] = w * invstd[c];
-    l_c1[c] = sums[c] * inv_n;
-    l_c2[c] = sums[C + c] * inv_n;
+    l_a[t] = invstd[c];
+    l_b[t] = -mean[c] * invstd[c];
+    l_w[t] = w;
+    l_bias[t] = bias ? ldp(bias, pdt, c) : 0.f;
+    l_g[t] = w * invstd[c];
+    l_c1[t] = sums[c] * inv_n;
+    l_c2[t] = sums[C + c] * inv_n;
   }
   __syncthreads();
+  if (WIDE) {
+    const int rps = kT / blk.P, piece = threadIdx.x % blk.P, lane_row = threadIdx.x / blk.P;
+    if (lane_row >= rps) return;
+    const size_t col = blk.piece0 + piece;
+    const int c0 = piece * VPL;
+    const long long step = static_cast<long long>(gridDim.x) * rps;
+    for (long long r = static_cast<long long>(blockIdx.x) * rps + lane_row; r < n; r += step) {
+      const size_t at = static_cast<size_t>(r) * blk.Prow + col;
+      float f[VPL], g[VPL];
+      Vec<DT>::unpack(x[at], f);
+      Vec<DT>::unpack(dy[at], g);
+#pragma unroll
+      for (int e = 0; e < VPL; ++e) {
+        const int c = c0 + e;
+        const float xh = f[e] * l_a[c] + l_b[c];
+        float gg = g[e];
+        if (relu && xh * l_w[c] + l_bias[c] <= 0.f) gg = 0.f;
+        f[e] = r < n_eff ? l_g[c] * (gg - l_c1[c] - xh * l_c2[c]) : 0.f;
+      }
+      __builtin_nontemporal_store(Vec<DT>::pack(f), &dx[at]);
+    }
+    return;
+  }
   const int P = C / VPL;
   const long long live = static_cast<long long>(n_eff) * P;
   for (long long i = static_cast<long long>(blockIdx.x) * kT + threadIdx.x; i < pieces;
@@ -516,14 +617,26 @@ bn_bwd_apply_kernel(const u32x4 *__restrict__ x, const u32x4 *__restrict__ dy, u
 int bn_blocks(int n) {
   // at most 1024 blocks (~390 rows each at 400 k rows), at least 64 rows per block: a 20 k-row level still puts a block
   // on every CU (53 blocks of 384 rows left four CUs in five idle and took 12 us for 5 MB)
-  int g = div_up(n > 0 ? n : 1, 64);
+  int g = n > 0 ? n / 64 + (n % 64 != 0) : 1;      // (not div_up: n + 63 leaves int at the largest row counts)
   return g < 1 ? 1 : (g > 1024 ? 1024 : g);
 }
 
+// widest matrix: 256 column blocks (far inside the 65535 of a grid's second dimension; the widest layer of any
+// backbone this library was written for is 1024)
+constexpr int kMaxC = 256 * kT;
+
 bool bn_shape_ok(int C, int dtype) {
   const int vpl = dtype == SPX_F32 ? 4 : 8;
-  return (dtype == SPX_F32 || dtype == SPX_F16 || dtype == SPX_BF16) && C > 0 && C % vpl == 0 && C <= kT &&
-         C / vpl <= kT;
+  return (dtype == SPX_F32 || dtype == SPX_F16 || dtype == SPX_BF16) && C > 0 && C % vpl == 0 && C <= kMaxC;
+}
+
+// grid of a row-streaming kernel: the row partition of before, times the column blocks of a wide matrix
+dim3 bn_grid(int G, int C) { return C > kT ? dim3(G, div_up(C, kT)) : dim3(G); }
+
+// workgroups per column block of the wide apply kernels: one sweep of a full block covers 256 / (256 / VPL) = VPL rows
+unsigned wide_stream_grid(int n, int C, int vpl) {
+  const long long want = div_up(n, vpl), cap = 4096 / div_up(C, kT);
+  return static_cast<unsigned>(want < 1 ? 1 : (want > cap ? (cap < 1 ? 1 : cap) : want));
 }
 
 unsigned stream_grid(long long pieces) {
@@ -547,11 +660,18 @@ static int bn_phases() {
 static constexpr int bn_phases() { return 7; }
 #endif
 
-#define SPX_BN_DISPATCH(dtype, CALL)                         \
-  do {                                                       \
-    if ((dtype) == SPX_F16) { CALL(SPX_F16); }               \
-    else if ((dtype) == SPX_BF16) { CALL(SPX_BF16); }        \
-    else { CALL(SPX_F32); }                                  \
+// CALL(D, W): the kernel instance of dtype D; W = the column-blocked form (C > kT)
+#define SPX_BN_DISPATCH(dtype, wide, CALL)                                  \
+  do {                                                                      \
+    if (wide) {                                                             \
+      if ((dtype) == SPX_F16) { CALL(SPX_F16, true); }                      \
+      else if ((dtype) == SPX_BF16) { CALL(SPX_BF16, true); }               \
+      else { CALL(SPX_F32, true); }                                         \
+    } else {                                                                \
+      if ((dtype) == SPX_F16) { CALL(SPX_F16, false); }                     \
+      else if ((dtype) == SPX_BF16) { CALL(SPX_BF16, false); }              \
+      else { CALL(SPX_F32, false); }                                        \
+    }                                                                       \
   } while (0)
 
 extern "C" {
@@ -568,13 +688,15 @@ static int batchnorm_fwd_impl(const void *x, void *y, int n, int C, int dtype, c
                               size_t ws_bytes, const int32_t *n_live, spx_stream_t stream,
                               const float *ext_partial, int ext_G) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  SPX_CHECK(bn_shape_ok(C, dtype), "batchnorm: C = %d must be a multiple of %d (<= 256), dtype f16/bf16/f32", C,
-            dtype == SPX_F32 ? 4 : 8);
+  SPX_CHECK(bn_shape_ok(C, dtype), "batchnorm: C = %d must be a multiple of %d (<= %d), dtype f16/bf16/f32", C,
+            dtype == SPX_F32 ? 4 : 8, kMaxC);
   SPX_CHECK(param_dtype == SPX_F32 || param_dtype == SPX_F16 || param_dtype == SPX_BF16, "bad parameter dtype");
   if (n == 0) return 0;
   SPX_CHECK(x && y, "null tensor pointer");
   const int vpl = dtype == SPX_F32 ? 4 : 8;
   const long long pieces = static_cast<long long>(n) * (C / vpl);
+  const bool wide = C > kT;
+  const dim3 apply_grid = wide ? dim3(wide_stream_grid(n, C, vpl), div_up(C, kT)) : dim3(stream_grid(pieces));
   const u32x4 *xv = static_cast<const u32x4 *>(x);
   u32x4 *yv = static_cast<u32x4 *>(y);
   if (training) {
@@ -585,28 +707,29 @@ static int batchnorm_fwd_impl(const void *x, void *y, int n, int C, int dtype, c
     const int G = ext_partial ? ext_G : bn_blocks(n);
     const float *partial = ext_partial ? ext_partial : static_cast<const float *>(ws);
     if (!ext_partial && (bn_phases() & 1)) {
-#define SPX_BN_PARTIAL(D) \
-  hipLaunchKernelGGL(bn_partial_kernel<D>, dim3(G), dim3(kT), 0, s, xv, n, C, static_cast<float *>(ws), n_live)
-      SPX_BN_DISPATCH(dtype, SPX_BN_PARTIAL);
+#define SPX_BN_PARTIAL(D, W)                                                                                  \
+  hipLaunchKernelGGL((bn_partial_kernel<D, W>), bn_grid(G, C), dim3(kT), 0, s, xv, n, C, static_cast<float *>(ws), \
+                     n_live)
+      SPX_BN_DISPATCH(dtype, wide, SPX_BN_PARTIAL);
 #undef SPX_BN_PARTIAL
     }
     if (bn_phases() & 2)
     hipLaunchKernelGGL(bn_finalize_kernel<kT>, dim3(C), dim3(kT), 0, s, partial, G, C, eps, momentum, save_mean,
                        save_invstd, running_mean, running_var, param_dtype, num_batches_tracked);
     if (!(bn_phases() & 4)) return 0;
-#define SPX_BN_APPLY(D)                                                                                    \
-  hipLaunchKernelGGL(bn_apply_kernel<D>, dim3(stream_grid(pieces)), dim3(kT), 0, s, xv, yv, pieces, C,     \
+#define SPX_BN_APPLY(D, W)                                                                                 \
+  hipLaunchKernelGGL((bn_apply_kernel<D, W>), apply_grid, dim3(kT), 0, s, xv, yv, pieces, C,               \
                      static_cast<const void *>(save_mean), static_cast<const void *>(save_invstd), weight,  \
                      bias, param_dtype, eps, 0, relu, n_live, n)
-    SPX_BN_DISPATCH(dtype, SPX_BN_APPLY);
+    SPX_BN_DISPATCH(dtype, wide, SPX_BN_APPLY);
 #undef SPX_BN_APPLY
   } else {
     SPX_CHECK(running_mean && running_var, "inference needs the running statistics");
-#define SPX_BN_APPLY(D)                                                                                    \
-  hipLaunchKernelGGL(bn_apply_kernel<D>, dim3(stream_grid(pieces)), dim3(kT), 0, s, xv, yv, pieces, C,     \
+#define SPX_BN_APPLY(D, W)                                                                                 \
+  hipLaunchKernelGGL((bn_apply_kernel<D, W>), apply_grid, dim3(kT), 0, s, xv, yv, pieces, C,               \
                      static_cast<const void *>(running_mean), static_cast<const void *>(running_var),      \
                      weight, bias, param_dtype, eps, 1, relu, n_live, n)
-    SPX_BN_DISPATCH(dtype, SPX_BN_APPLY);
+    SPX_BN_DISPATCH(dtype, wide, SPX_BN_APPLY);
 #undef SPX_BN_APPLY
   }
   SPX_LAUNCH_CHECK();
@@ -639,7 +762,8 @@ int spx_batchnorm_bwd(const void *x, const void *dy, void *dx, int n, int C, int
                       const float *invstd, int use_batch_stats, int relu, void *dweight, void *dbias,
                       void *ws, size_t ws_bytes, const int32_t *n_live, spx_stream_t stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  SPX_CHECK(bn_shape_ok(C, dtype), "batchnorm: unsupported C = %d / dtype", C);
+  SPX_CHECK(bn_shape_ok(C, dtype), "batchnorm: unsupported C = %d (a multiple of %d, <= %d) / dtype", C,
+            dtype == SPX_F32 ? 4 : 8, kMaxC);
   SPX_CHECK(param_dtype == SPX_F32 || param_dtype == SPX_F16 || param_dtype == SPX_BF16, "bad parameter dtype");
   SPX_CHECK(mean && invstd, "null pointer");
   const size_t pbytes = param_dtype == SPX_F32 ? 4 : 2;
@@ -652,22 +776,24 @@ int spx_batchnorm_bwd(const void *x, const void *dy, void *dx, int n, int C, int
   const int vpl = dtype == SPX_F32 ? 4 : 8;
   const long long pieces = static_cast<long long>(n) * (C / vpl);
   const int G = bn_blocks(n);
+  const bool wide = C > kT;
+  const dim3 apply_grid = wide ? dim3(wide_stream_grid(n, C, vpl), div_up(C, kT)) : dim3(stream_grid(pieces));
   float *partial = static_cast<float *>(ws);
   float *sums = partial + static_cast<size_t>(G) * 2 * C;      // [2][C] behind the partials
   const u32x4 *xv = static_cast<const u32x4 *>(x), *gv = static_cast<const u32x4 *>(dy);
-#define SPX_BN_BP(D)                                                                                        \
-  hipLaunchKernelGGL(bn_bwd_partial_kernel<D>, dim3(G), dim3(kT), 0, s, xv, gv, n, C, mean, invstd, weight, \
-                     bias, param_dtype, relu, partial, n_live)
-  if (bn_phases() & 1) SPX_BN_DISPATCH(dtype, SPX_BN_BP);
+#define SPX_BN_BP(D, W)                                                                                     \
+  hipLaunchKernelGGL((bn_bwd_partial_kernel<D, W>), bn_grid(G, C), dim3(kT), 0, s, xv, gv, n, C, mean, invstd, \
+                     weight, bias, param_dtype, relu, partial, n_live)
+  if (bn_phases() & 1) SPX_BN_DISPATCH(dtype, wide, SPX_BN_BP);
 #undef SPX_BN_BP
   if (bn_phases() & 2)
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(kT), 0, s, partial, G, C, sums, dweight, dbias,
                      param_dtype);
-#define SPX_BN_BA(D)                                                                                        \
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<D>, dim3(stream_grid(pieces)), dim3(kT), 0, s, xv, gv,             \
+#define SPX_BN_BA(D, W)                                                                                     \
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<D, W>), apply_grid, dim3(kT), 0, s, xv, gv,                       \
                      static_cast<u32x4 *>(dx), pieces, n, C, mean, invstd, weight, bias, param_dtype, sums,  \
                      relu, use_batch_stats, n_live)
-  if (bn_phases() & 4) SPX_BN_DISPATCH(dtype, SPX_BN_BA);
+  if (bn_phases() & 4) SPX_BN_DISPATCH(dtype, wide, SPX_BN_BA);
 #undef SPX_BN_BA
   SPX_LAUNCH_CHECK();
   return 0;

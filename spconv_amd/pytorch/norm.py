@@ -22,6 +22,14 @@ from spconv_amd import _lib
 
 ENABLED = os.environ.get("SPCONV_AMD_FUSED_BN", "1") != "0"
 _DT = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16, torch.float32: _lib.DTYPE_F32}
+MAX_CHANNELS = 65536            # kMaxC of csrc/norm.hip: 256 column blocks of 256 channels
+
+
+def shape_supported(C: int, dtype: torch.dtype) -> bool:
+    """The shape rule of csrc/norm.hip (bn_shape_ok): rows of whole 16-byte pieces -- a multiple of 8 channels
+    in a 16-bit dtype, of 4 in fp32 -- and at most MAX_CHANNELS of them.  Beyond 256 channels the kernels run
+    over column blocks of 256."""
+    return dtype in _DT and 0 < C <= MAX_CHANNELS and C % (4 if dtype == torch.float32 else 8) == 0
 
 
 def supported(features: torch.Tensor, bn: nn.Module) -> bool:
@@ -36,7 +44,7 @@ def supported(features: torch.Tensor, bn: nn.Module) -> bool:
     C = features.shape[1]
     if _param_dtype(bn.weight, bn.bias, bn.running_mean, bn.running_var) not in _DT:
         return False            # parameters and buffers of mixed dtypes: torch's path
-    return C == bn.num_features and C % (4 if features.dtype == torch.float32 else 8) == 0 and C <= 256
+    return C == bn.num_features and shape_supported(C, features.dtype)
 
 
 def _param_dtype(*tensors) -> Optional[torch.dtype]:
