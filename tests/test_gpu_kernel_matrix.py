@@ -135,7 +135,8 @@ def reachable():
 
 # Instances deliberately without a case here, and why
 EXCLUDED = [
-    ("igemm_v4/*/*/i8/*", "int8 paths are out of scope; test_gpu_int8.py holds them bit-exact to oracle.int8_conv_ref"),
+    ("igemm_v4/*/*/i8/*", "int8 instances have a matrix of their own, bit for bit against refint8.py: test_gpu_int8_matrix.py, "
+                          "whose test_cases_claim_every_int8_instance holds every one of these keys to a case"),
     ("gen1/*", "first-generation kernel: only tensors beyond 32-bit buffer offsets (multi-GB) reach it; "
                "test_gpu_conv.py covers that form"),
     ("wgrad_mfma/*", "16-bit wgrad fallback: only pair lists beyond 32-bit offsets (n_in * 4 * (kv + 1) >= 2 GiB) reach it"),
