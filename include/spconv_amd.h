@@ -88,6 +88,8 @@ int spx_set_option(const char *name_h, int value);
  *   wgrad_tr/<dt>/<SL>, wgrad_f32                  weight gradient, first stage (SL: 2 | 4 | 8 live slots per row)
  *   wgrad_mfma/<dt>, wgrad_generic/<dt>            weight gradient, fallback kernels
  *   generic/<dt>, gen1/<COUT>/<dt>                 one-thread-per-output and first-generation gather-GEMM
+ *   dense/map, dense/scatter_cl, dense/scatter_cf, dense/gather_cl, dense/gather_cf, dense/compact
+ *                                                  sparse <-> dense conversion (cl / cf: channels last / first)
  * COUT in {16, 32, 64, 128, 256}, NKS in {1, 2}, PK in {1, 2, 4, 8, 16, 32}.  A well-formed key of an instance that is
  * never built counts 0; anything else is unknown.
  * float64 (SPX_F64) has a family and keys of its own, outside the dt vocabulary above:
@@ -643,6 +645,47 @@ int spx_batchnorm_bwd(const void *x, const void *dy, void *dx, int n, int C, int
                       const void *weight, const void *bias, int param_dtype, const float *mean,
                       const float *invstd, int use_batch_stats, int relu, void *dweight, void *dbias,
                       void *ws, size_t ws_bytes, const int32_t *n_live, spx_stream_t stream);
+
+/* ---- sparse <-> dense conversion (csrc/dense.hip) ---------------------------------------------------
+ * Replace the torch composites of the reference's spconv/pytorch/core.py: `scatter_nd` (:44-57, a zero fill and an
+ * index_put), `SparseConvTensor.dense` (:309-320, scatter_nd + permute().contiguous()) and `from_dense` (:296-307,
+ * Tensor.to_sparse).  The kernels move bytes: elem_bytes is 1, 2, 4 or 8, any dtype of that size.
+ *
+ * The CELL MAP: map [batch * prod(spatial)] int32, map[cell] = the row that owns the cell, -1 = none; cell = the
+ * row-major index over (batch, *spatial).  batch * prod(spatial) must fit int32; spx_dense_ws_bytes() gives the
+ * bytes of the map (0 for an empty grid, and for one that is too large).
+ *   spx_dense_map: skips row r when its batch index is < 0 or >= batch, when a coordinate is outside
+ *   [0, extent), and when r >= *n_live (n_live: NULL or a device int32, see spx_conv_rulebook_static).  Of
+ *   several rows with the same coordinate the HIGHEST row number owns the cell, on every call.
+ *   spx_to_dense: out = [batch, *spatial, C] (channels_first = 0) or [batch, C, *spatial] (1); every element is
+ *   written exactly once: rows[map[cell]] or the fill value (fill_bits: bit pattern of one element in the low
+ *   elem_bytes bytes; 0 = zero, a quantised tensor passes its zero point).  rows [n, C] with a row stride of
+ *   row_stride elements (>= C).  A map entry outside [0, n) counts as -1 here and in spx_dense_gather: the map is
+ *   the caller's memory, a stale one must not turn into an access outside `rows`.
+ *   spx_dense_gather: the inverse, rows [n, C] contiguous: rows[map[cell]] = dense[cell]; a row that owns no
+ *   cell (dead, out of range, or a duplicate that lost) receives zeros.  Backward of spx_to_dense. */
+size_t spx_dense_ws_bytes(int ndim, int batch, const int *spatial_h);
+int spx_dense_map(const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch,
+                  const int *spatial_h, int32_t *map, spx_stream_t stream);
+int spx_to_dense(const void *rows, int n, long long row_stride, const int32_t *map, void *out, int C,
+                 int elem_bytes, int channels_first, long long fill_bits, int ndim, int batch,
+                 const int *spatial_h, spx_stream_t stream);
+int spx_dense_gather(const void *dense, const int32_t *map, void *rows, int n, int C, int elem_bytes,
+                     int channels_first, int ndim, int batch, const int *spatial_h,
+                     spx_stream_t stream);
+/* from_dense: dense = channels-last [batch, *spatial, C], contiguous.  A cell is active when any of its channels
+ * compares unequal to zero (is_float: -0.0 is zero, NaN is not -- Tensor.to_sparse).
+ *   count: flags and counts the active cells into ws (spx_from_dense_ws_bytes) and reads the count back into
+ *   *n_active_h (one D->H read, the data-dependent shape; synchronises the stream).
+ *   fill: with the SAME ws, writes indices [n_active, ndim + 1] (ascending cell order = the order of
+ *   to_sparse(...).indices()), rows [n_active, C] and, unless NULL, the cell map of the result. */
+size_t spx_from_dense_ws_bytes(int ndim, int batch, const int *spatial_h);
+int spx_from_dense_count(const void *dense, int C, int elem_bytes, int is_float, int ndim, int batch,
+                         const int *spatial_h, void *ws, size_t ws_bytes, int *n_active_h,
+                         spx_stream_t stream);
+int spx_from_dense_fill(const void *dense, int C, int elem_bytes, int ndim, int batch,
+                        const int *spatial_h, const void *ws, size_t ws_bytes, int32_t *indices,
+                        void *rows, int32_t *map, spx_stream_t stream);
 
 #ifdef __cplusplus
 }

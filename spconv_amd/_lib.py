@@ -132,6 +132,14 @@ SIGNATURES = {
     "spx_launch_count": (ctypes.c_longlong, [ctypes.c_char_p]),
     "spx_bias_act_inplace": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_float, vp]),
+    "spx_dense_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, c_int_p]),
+    "spx_dense_map": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, c_int_p, vp, vp]),
+    "spx_to_dense": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_longlong, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_int_p, vp]),
+    "spx_dense_gather": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 6 + [c_int_p, vp]),
+    "spx_from_dense_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, c_int_p]),
+    "spx_from_dense_count": (ctypes.c_int, [vp] + [ctypes.c_int] * 5 + [c_int_p, vp, ctypes.c_size_t, c_int_p, vp]),
+    "spx_from_dense_fill": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [c_int_p, vp, ctypes.c_size_t, vp, vp, vp, vp]),
 }
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_I8, DTYPE_F64 = 0, 1, 2, 3, 4

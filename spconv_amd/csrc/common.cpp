@@ -33,6 +33,7 @@ std::mutex g_option_mutex;
 std::atomic<long long> g_launches[kFamCount];
 std::atomic<long long> g_inst_launches[inst::kCount];
 std::atomic<long long> g_f64_launches[kF64Count];
+std::atomic<long long> g_dense_launches[kDenseCount];
 
 namespace {
 // "f16" | "bf16" | "i8" | "f32" -> the kernels' DT code, or -1
@@ -124,6 +125,15 @@ std::atomic<long long> *f64_counter(const char *key) {
   if (strcmp(key, "pool/f64") == 0) return &g_f64_launches[kF64Pool];
   return nullptr;
 }
+
+// counter of a dense-conversion key (spx_launch_count), or null
+std::atomic<long long> *dense_counter(const char *key) {
+  static const char *names[kDenseCount] = {"dense/map", "dense/scatter_cl", "dense/scatter_cf", "dense/gather_cl",
+                                           "dense/gather_cf", "dense/compact"};
+  for (int i = 0; i < kDenseCount; ++i)
+    if (strcmp(key, names[i]) == 0) return &g_dense_launches[i];
+  return nullptr;
+}
 }  // namespace
 
 int option_int(const char *name, int dflt) {
@@ -162,6 +172,7 @@ long long spx_launch_count(const char *family_h) {
   for (int i = 0; i < spx::kFamCount; ++i)
     if (strcmp(names[i], family_h) == 0) return spx::g_launches[i].load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::f64_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::dense_counter(family_h)) return c->load(std::memory_order_relaxed);
   const int slot = spx::instance_slot(family_h);
   return slot < 0 ? -1 : spx::g_inst_launches[slot].load(std::memory_order_relaxed);
 }

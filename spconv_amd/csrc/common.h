@@ -181,6 +181,12 @@ inline void count_inst() {
 enum F64Inst { kF64Fwd = 0, kF64Dgrad, kF64Wgrad, kF64Pool, kF64Count };
 extern std::atomic<long long> g_f64_launches[kF64Count];
 inline void count_f64(F64Inst i) { g_f64_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
+// sparse <-> dense conversion (dense.hip): one counter per entry point and layout.
+// Keys dense/map, dense/scatter_cl, dense/scatter_cf, dense/gather_cl, dense/gather_cf, dense/compact.
+enum DenseInst { kDenseMap = 0, kDenseScatterCl, kDenseScatterCf, kDenseGatherCl, kDenseGatherCf, kDenseCompact, kDenseCount };
+extern std::atomic<long long> g_dense_launches[kDenseCount];
+inline void count_dense(DenseInst i) { g_dense_launches[i].fetch_add(1, std::memory_order_relaxed); }
 }  // namespace spx
 
 // ---- row orders (rowsort.hip) ---------------------------------------------------------------------

@@ -300,7 +300,12 @@ class SparseConvTensor(metaclass=torch.fx.ProxyableClassMeta):
 
     @classmethod
     def from_dense(cls, x: torch.Tensor) -> "SparseConvTensor":
-        """x: channel-last dense tensor [N, *spatial, C]."""
+        """x: channel-last dense tensor [N, *spatial, C].  CUDA tensors: the compaction kernels of csrc/dense.hip
+        (spconv_amd/pytorch/_dense.py), same rows in the same order; CPU tensors: torch's to_sparse."""
+        from spconv_amd.pytorch import _dense
+        if _dense.supported(x) and not x.is_quantized:
+            features, indices = _dense.from_dense(x)
+            return cls(features, indices, list(x.shape[1:-1]), x.shape[0])
         x_sp = x.to_sparse(x.ndim - 1)
         spatial_shape = x_sp.shape[1:-1]
         batch_size = x_sp.shape[0]
@@ -320,10 +325,17 @@ class SparseConvTensor(metaclass=torch.fx.ProxyableClassMeta):
         return self.indice_dict.get(key, None)
 
     def dense(self, channels_first: bool = True) -> torch.Tensor:
+        """[N, C, *spatial] (or [N, *spatial, C]).  CUDA features: the kernels of csrc/dense.hip
+        (spconv_amd/pytorch/_dense.py) -- rows outside the grid and the padding rows of a static-shape tensor are
+        ignored, of rows with equal coordinates the last one wins, qint8 features give a quantised dense tensor.
+        CPU features (host-side checks only): torch indexing."""
+        from spconv_amd.pytorch import _dense
+        if _dense.supported(self.features):
+            return _dense.to_dense(self.features, self.indices, self.batch_size, self.spatial_shape, channels_first,
+                                   self.n_live_dev)
         if self.n_live_dev is not None:
-            # a static-shape tensor: padding rows carry batch index -1, which plain indexing would wrap around
-            from spconv_amd.pytorch.static import dense_static
-            return dense_static(self, channels_first)
+            raise NotImplementedError(f"dense() of a static-shape tensor: no kernel for {self.features.dtype} "
+                                      f"features on {self.features.device}")
         out_shape = [self.batch_size] + list(self.spatial_shape) + [self.features.shape[1]]
         res = scatter_nd(self.indices.to(self.features.device).long(), self.features, out_shape)
         if not channels_first:

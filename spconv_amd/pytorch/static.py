@@ -77,18 +77,11 @@ def freeze_bounds(net: torch.nn.Module, bounds: Optional[Dict[str, int]] = None,
 
 
 def dense_static(t: SparseConvTensor, channels_first: bool = True) -> torch.Tensor:
-    """SparseConvTensor.dense() for a tensor with dead rows (batch index -1): they land in a scratch
-    batch slot that is cut off.  No data-dependent shape: can sit inside the captured graph."""
-    idx = t.indices.long()
-    B, nd = t.batch_size, len(t.spatial_shape)
-    dead = idx[:, 0] < 0
-    b = torch.where(dead, torch.full_like(idx[:, 0], B), idx[:, 0])
-    buf = t.features.new_zeros((B + 1, *t.spatial_shape, t.features.shape[1]))
-    buf[(b,) + tuple(idx[:, 1 + d].clamp(min=0) for d in range(nd))] = t.features
-    res = buf[:B]
-    if not channels_first:
-        return res
-    return res.permute(0, nd + 1, *range(1, nd + 1)).contiguous()
+    """SparseConvTensor.dense() for a tensor with dead rows (batch index -1, rows >= n_live_dev): the cell-map
+    kernel skips them (spconv_amd/pytorch/_dense.py).  No data-dependent shape, nothing read back, scratch from the
+    caching allocator: can sit inside the captured graph."""
+    from spconv_amd.pytorch import _dense
+    return _dense.to_dense(t.features, t.indices, t.batch_size, t.spatial_shape, channels_first, t.n_live_dev)
 
 
 def _declare_key_order(runner) -> None:
