@@ -632,7 +632,9 @@ int spx_batchnorm_fwd(const void *x, void *y, int n, int C, int dtype, const voi
                       size_t ws_bytes, const int32_t *n_live, spx_stream_t stream);
 /* Training-mode forward whose statistics pass has already happened: `stats` = the {rows, mean, M2} records
  * (stats_records of them, laid out [3][C][stats_records] fp32) that spx_igemm_fwd_stats left behind the convolution producing x.  Two
- * launches (merge, apply) instead of three; semantics as spx_batchnorm_fwd with training = 1. */
+ * launches (merge, apply) instead of three; semantics as spx_batchnorm_fwd with training = 1.
+ * n = 0 with records given still runs the merge: running estimates, num_batches_tracked and save_mean / save_invstd
+ * come out as on a caller with rows (a SyncBatchNorm rank without voxels); only the apply launch is skipped. */
 int spx_batchnorm_fwd_stats(const void *x, void *y, int n, int C, int dtype, const void *weight,
                             const void *bias, void *running_mean, void *running_var,
                             long long *num_batches_tracked, int param_dtype, float momentum, float eps,
@@ -645,6 +647,40 @@ int spx_batchnorm_bwd(const void *x, const void *dy, void *dx, int n, int C, int
                       const void *weight, const void *bias, int param_dtype, const float *mean,
                       const float *invstd, int use_batch_stats, int relu, void *dweight, void *dbias,
                       void *ws, size_t ws_bytes, const int32_t *n_live, spx_stream_t stream);
+
+/* ---- SyncBatchNorm: the launches above, cut where the ranks of a process group exchange statistics ------------
+ * The library issues no collective; the caller does (spconv_amd/pytorch/norm.py: one all-gather forward, one
+ * all-reduce backward).  Forward: spx_batchnorm_local_stats -> all-gather of the records -> spx_batchnorm_fwd_stats
+ * with stats = [3][C][world], stats_records = world.  Backward: spx_batchnorm_bwd_sums -> all-reduce of `sums` ->
+ * spx_batchnorm_bwd_apply.  Shapes, dtypes, parameter dtypes, n_live and column blocks as above.
+ *
+ * A record counts rows in fp32, which is exact up to 2^24: spx_batchnorm_local_stats refuses n > 2^24, and the caller
+ * must keep the TOTAL over all ranks at or below 2^24 rows (the total exists only on the device; norm.py refuses
+ * rows x world > 2^24 on the host before any collective).
+ *
+ * spx_batchnorm_local_stats: record_out [3][C] fp32 = {live rows, mean, M2 (sum of squared deviations)} per channel
+ * of this caller's rows.  stats_in = NULL: one pass over x (ws: spx_batchnorm_ws_bytes(n, C)) and a merge.  Otherwise
+ * stats_in = the [3][C][stats_in_records] records spx_igemm_fwd_stats left: the merge alone, x is never read (may be
+ * NULL).  n = 0 or *n_live = 0: a record of zero rows, which every merge skips; not an error.  No running estimate
+ * is touched. */
+int spx_batchnorm_local_stats(const void *x, int n, int C, int dtype, const float *stats_in,
+                              int stats_in_records, float *record_out, void *ws, size_t ws_bytes,
+                              const int32_t *n_live, spx_stream_t stream);
+/* The two reduction launches of spx_batchnorm_bwd (batch statistics): sums [2][C] fp32, caller-owned =
+ * {sum dy, sum dy * xhat} over this caller's live rows (dy masked by the ReLU when relu = 1).  dweight / dbias
+ * ([C] of param_dtype, or NULL) are written from these LOCAL sums: SyncBatchNorm's parameter gradients are local and
+ * the gradient all-reduce of data-parallel training averages them.  n = 0 writes zeros. */
+int spx_batchnorm_bwd_sums(const void *x, const void *dy, int n, int C, int dtype, const void *weight,
+                           const void *bias, int param_dtype, const float *mean, const float *invstd,
+                           int relu, float *sums, void *dweight, void *dbias, void *ws, size_t ws_bytes,
+                           const int32_t *n_live, spx_stream_t stream);
+/* The apply launch of spx_batchnorm_bwd with the sums of ALL ranks: dx = w * invstd * (dy - sums[0] / N - xhat *
+ * sums[1] / N), N = *total_rows, a DEVICE fp32 scalar holding the live rows of all ranks (summed from the gathered
+ * records on the device; 0 gives dx = w * invstd * dy').  ReLU mask and zeroed padding rows as spx_batchnorm_bwd. */
+int spx_batchnorm_bwd_apply(const void *x, const void *dy, void *dx, int n, int C, int dtype,
+                            const void *weight, const void *bias, int param_dtype, const float *mean,
+                            const float *invstd, int relu, const float *sums, const float *total_rows,
+                            const int32_t *n_live, spx_stream_t stream);
 
 /* ---- sparse <-> dense conversion (csrc/dense.hip) ---------------------------------------------------
  * Replace the torch composites of the reference's spconv/pytorch/core.py: `scatter_nd` (:44-57, a zero fill and an

@@ -72,6 +72,12 @@ SIGNATURES = {
                                                vp, ctypes.c_int, vp, vp]),
     "spx_batchnorm_bwd": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int,
                                          vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp, vp]),
+    "spx_batchnorm_local_stats": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp,
+                                                 ctypes.c_size_t, vp, vp]),
+    "spx_batchnorm_bwd_sums": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int,
+                                              vp, vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_size_t, vp, vp]),
+    "spx_batchnorm_bwd_apply": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp,
+                                               ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp]),
     "spx_mask_argsort_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "spx_mask_argsort": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_size_t, vp]),
     "spx_mask_argsort_kv": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_size_t, vp]),

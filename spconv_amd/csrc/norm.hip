@@ -276,6 +276,55 @@ bn_partial_kernel(const u32x4 *__restrict__ x, int n, int C, float *__restrict__
   }
 }
 
+// Chan merge of the G records of channel c by the T threads of a block, as bn_finalize_kernel below does it: on return
+// (behind a barrier) ln[0] / lm[0] / l2[0] hold the rows, the mean and M2 of all of them.  Records of zero rows are
+// skipped.  (bn_finalize_kernel keeps its own copy of these lines: behind a call the compiler contracts its
+// multiply-adds differently, and what the existing entry points compute is pinned bit for bit.)
+template <int T>
+__device__ __forceinline__ void chan_merge(const float *__restrict__ partial, int G, int C, int c, float (&ln)[T],
+                                           float (&lm)[T], float (&l2)[T]) {
+  constexpr int kT = T;
+  float n = 0.f, m = 0.f, M2 = 0.f;
+  constexpr int U = 8;                       // eight records per trip, their loads in flight together
+  for (int b0 = threadIdx.x; b0 < G; b0 += kT * U) {
+    float nb[U], mb[U], Mb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int b = b0 + u * kT;
+      const bool ok = b < G;
+      const size_t at = static_cast<size_t>(c) * G + (ok ? b : 0), fs = static_cast<size_t>(C) * G;      // (field stride)
+      nb[u] = ok ? partial[at] : 0.f;
+      mb[u] = ok ? partial[at + fs] : 0.f;
+      Mb[u] = ok ? partial[at + 2 * fs] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (nb[u] > 0.f) {
+        const float tot = n + nb[u], d = mb[u] - m;
+        m += d * (nb[u] / tot);
+        M2 += Mb[u] + d * d * (n * nb[u] / tot);
+        n = tot;
+      }
+    }
+  }
+  ln[threadIdx.x] = n;
+  lm[threadIdx.x] = m;
+  l2[threadIdx.x] = M2;
+  __syncthreads();
+  for (int stride = kT / 2; stride > 0; stride >>= 1) {
+    if (threadIdx.x < stride) {
+      const float na = ln[threadIdx.x], nb = ln[threadIdx.x + stride];
+      if (nb > 0.f) {
+        const float tot = na + nb, d = lm[threadIdx.x + stride] - lm[threadIdx.x];
+        lm[threadIdx.x] += d * (nb / tot);
+        l2[threadIdx.x] += l2[threadIdx.x + stride] + d * d * (na * nb / tot);
+        ln[threadIdx.x] = tot;
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // one block per channel: Chan merge of the G partials; mean / invstd out, running estimates updated
 template <int T>
 __global__ void __launch_bounds__(T)
@@ -338,6 +387,21 @@ bn_finalize_kernel(const float *__restrict__ partial, int G, int C, float eps, f
       const float unbiased = cnt > 1.f ? l2[0] / (cnt - 1.f) : var;
       stp(running_var, pdt, c, (1.f - momentum) * ldp(running_var, pdt, c) + momentum * unbiased);
     }
+  }
+}
+
+// one block per channel: the same merge, stopped at the record -- record[0][c] = rows, [1][c] = mean, [2][c] = M2 of
+// all G partials (one rank's rows: what SyncBatchNorm exchanges).  No mean / invstd, no running estimate touched.
+template <int T>
+__global__ void __launch_bounds__(T)
+bn_merge_record_kernel(const float *__restrict__ partial, int G, int C, float *__restrict__ record) {
+  __shared__ float ln[T], lm[T], l2[T];
+  const int c = blockIdx.x;
+  chan_merge<T>(partial, G, C, c, ln, lm, l2);
+  if (threadIdx.x == 0) {
+    record[c] = ln[0];
+    record[C + c] = ln[0] > 0.f ? lm[0] : 0.f;
+    record[2 * C + c] = ln[0] > 0.f ? l2[0] : 0.f;
   }
 }
 
@@ -545,14 +609,15 @@ bn_bwd_finalize_kernel(const float *__restrict__ partial, int G, int C, float *_
 
 // training: dx = w * invstd * (dy - sum_dy / n - xhat * sum_dy_xhat / n);  inference statistics
 // (use_batch_stats == 0): dx = w * invstd * dy.  Per-channel coefficients staged in LDS.  WIDE: the walk of
-// bn_apply_kernel<DT, true>.
+// bn_apply_kernel<DT, true>.  total_rows: NULL (n = this matrix's live rows), or a device fp32 scalar -- the rows the
+// sums were taken over when they are not this matrix's alone (SyncBatchNorm: all ranks' live rows).
 template <int DT, bool WIDE>
 __global__ void __launch_bounds__(kT)
 bn_bwd_apply_kernel(const u32x4 *__restrict__ x, const u32x4 *__restrict__ dy, u32x4 *__restrict__ dx,
                     long long pieces, int n, int C, const float *__restrict__ mean,
                     const float *__restrict__ invstd, const void *__restrict__ weight,
                     const void *__restrict__ bias, int pdt, const float *__restrict__ sums, int relu,
-                    int use_batch_stats, const int32_t *__restrict__ n_live) {
+                    int use_batch_stats, const int32_t *__restrict__ n_live, const float *__restrict__ total_rows) {
   constexpr int VPL = Vec<DT>::VPL;
   // xhat = x * l_a + l_b;  relu mask: xhat * l_w + l_bias <= 0;  dx = l_g * (dy' - l_c1 - xhat * l_c2)
   __shared__ __attribute__((aligned(16))) float l_a[kT], l_b[kT], l_w[kT], l_bias[kT], l_g[kT], l_c1[kT], l_c2[kT];
@@ -560,7 +625,8 @@ bn_bwd_apply_kernel(const u32x4 *__restrict__ x, const u32x4 *__restrict__ dy, u
   const ColBlock blk = col_block<VPL, WIDE>(C);
   if (threadIdx.x < blk.Cb) {
     const int t = threadIdx.x, c = blk.c0 + t;           // (LDS by the channel inside the block)
-    const float inv_n = (use_batch_stats && n_eff > 0) ? 1.f / static_cast<float>(n_eff) : 0.f;
+    const float rows = total_rows ? *total_rows : static_cast<float>(n_eff);
+    const float inv_n = (use_batch_stats && rows > 0.f) ? 1.f / rows : 0.f;
     const float w = weight ? ldp(weight, pdt, c) : 1.f;
     l_a[t] = invstd[c];
     l_b[t] = -mean[c] * invstd[c];
@@ -624,6 +690,9 @@ int bn_blocks(int n) {
 // widest matrix: 256 column blocks (far inside the 65535 of a grid's second dimension; the widest layer of any
 // backbone this library was written for is 1024)
 constexpr int kMaxC = 256 * kT;
+
+// a statistics record counts its rows in fp32: exact up to 2^24 rows, beyond that a count would round silently
+constexpr int kMaxSyncRows = 1 << 24;
 
 bool bn_shape_ok(int C, int dtype) {
   const int vpl = dtype == SPX_F32 ? 4 : 8;
@@ -691,7 +760,17 @@ static int batchnorm_fwd_impl(const void *x, void *y, int n, int C, int dtype, c
   SPX_CHECK(bn_shape_ok(C, dtype), "batchnorm: C = %d must be a multiple of %d (<= %d), dtype f16/bf16/f32", C,
             dtype == SPX_F32 ? 4 : 8, kMaxC);
   SPX_CHECK(param_dtype == SPX_F32 || param_dtype == SPX_F16 || param_dtype == SPX_BF16, "bad parameter dtype");
-  if (n == 0) return 0;
+  if (n == 0) {
+    // no rows here, but records given (SyncBatchNorm: the other ranks' rows): the merge still runs, so that the running
+    // estimates, the step counter and save_mean / save_invstd are what every other rank holds; nothing to apply
+    if (training && ext_partial) {
+      SPX_CHECK(save_mean && save_invstd, "training needs save_mean / save_invstd");
+      hipLaunchKernelGGL(bn_finalize_kernel<kT>, dim3(C), dim3(kT), 0, s, ext_partial, ext_G, C, eps, momentum,
+                         save_mean, save_invstd, running_mean, running_var, param_dtype, num_batches_tracked);
+      SPX_LAUNCH_CHECK();
+    }
+    return 0;
+  }
   SPX_CHECK(x && y, "null tensor pointer");
   const int vpl = dtype == SPX_F32 ? 4 : 8;
   const long long pieces = static_cast<long long>(n) * (C / vpl);
@@ -757,10 +836,13 @@ int spx_batchnorm_fwd_stats(const void *x, void *y, int n, int C, int dtype, con
                             stats, stats_records);
 }
 
-int spx_batchnorm_bwd(const void *x, const void *dy, void *dx, int n, int C, int dtype,
-                      const void *weight, const void *bias, int param_dtype, const float *mean,
-                      const float *invstd, int use_batch_stats, int relu, void *dweight, void *dbias,
-                      void *ws, size_t ws_bytes, const int32_t *n_live, spx_stream_t stream) {
+// phases: bit 0 = partial sums, 1 = their merge (sums, dweight, dbias), 2 = apply.  sums_ext: caller-owned [2][C] (NULL:
+// behind the partials in ws).  total_rows: see bn_bwd_apply_kernel.
+static int batchnorm_bwd_impl(const void *x, const void *dy, void *dx, int n, int C, int dtype, const void *weight,
+                              const void *bias, int param_dtype, const float *mean, const float *invstd,
+                              int use_batch_stats, int relu, void *dweight, void *dbias, void *ws, size_t ws_bytes,
+                              const int32_t *n_live, spx_stream_t stream, int phases, float *sums_ext,
+                              const float *total_rows) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   SPX_CHECK(bn_shape_ok(C, dtype), "batchnorm: unsupported C = %d (a multiple of %d, <= %d) / dtype", C,
             dtype == SPX_F32 ? 4 : 8, kMaxC);
@@ -768,35 +850,101 @@ int spx_batchnorm_bwd(const void *x, const void *dy, void *dx, int n, int C, int
   SPX_CHECK(mean && invstd, "null pointer");
   const size_t pbytes = param_dtype == SPX_F32 ? 4 : 2;
   if (n == 0) {
-    if (dweight) SPX_HIP(hipMemsetAsync(dweight, 0, pbytes * C, s));
-    if (dbias) SPX_HIP(hipMemsetAsync(dbias, 0, pbytes * C, s));
+    if (phases & 2) {
+      if (dweight) SPX_HIP(hipMemsetAsync(dweight, 0, pbytes * C, s));
+      if (dbias) SPX_HIP(hipMemsetAsync(dbias, 0, pbytes * C, s));
+      if (sums_ext) SPX_HIP(hipMemsetAsync(sums_ext, 0, sizeof(float) * 2 * C, s));
+    }
     return 0;
   }
-  SPX_CHECK(x && dy && dx && ws && ws_bytes >= spx_batchnorm_ws_bytes(n, C), "null pointer / workspace too small");
+  SPX_CHECK(x && dy && ((phases & 4) == 0 || dx), "null pointer");
+  SPX_CHECK((phases & 3) == 0 || (ws && ws_bytes >= spx_batchnorm_ws_bytes(n, C)), "null pointer / workspace too small");
   const int vpl = dtype == SPX_F32 ? 4 : 8;
   const long long pieces = static_cast<long long>(n) * (C / vpl);
   const int G = bn_blocks(n);
   const bool wide = C > kT;
   const dim3 apply_grid = wide ? dim3(wide_stream_grid(n, C, vpl), div_up(C, kT)) : dim3(stream_grid(pieces));
   float *partial = static_cast<float *>(ws);
-  float *sums = partial + static_cast<size_t>(G) * 2 * C;      // [2][C] behind the partials
+  float *sums = sums_ext ? sums_ext : partial + static_cast<size_t>(G) * 2 * C;      // [2][C] behind the partials
   const u32x4 *xv = static_cast<const u32x4 *>(x), *gv = static_cast<const u32x4 *>(dy);
 #define SPX_BN_BP(D, W)                                                                                     \
   hipLaunchKernelGGL((bn_bwd_partial_kernel<D, W>), bn_grid(G, C), dim3(kT), 0, s, xv, gv, n, C, mean, invstd, \
                      weight, bias, param_dtype, relu, partial, n_live)
-  if (bn_phases() & 1) SPX_BN_DISPATCH(dtype, wide, SPX_BN_BP);
+  if (phases & 1) SPX_BN_DISPATCH(dtype, wide, SPX_BN_BP);
 #undef SPX_BN_BP
-  if (bn_phases() & 2)
+  if (phases & 2)
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(kT), 0, s, partial, G, C, sums, dweight, dbias,
                      param_dtype);
 #define SPX_BN_BA(D, W)                                                                                     \
   hipLaunchKernelGGL((bn_bwd_apply_kernel<D, W>), apply_grid, dim3(kT), 0, s, xv, gv,                       \
                      static_cast<u32x4 *>(dx), pieces, n, C, mean, invstd, weight, bias, param_dtype, sums,  \
-                     relu, use_batch_stats, n_live)
-  if (bn_phases() & 4) SPX_BN_DISPATCH(dtype, wide, SPX_BN_BA);
+                     relu, use_batch_stats, n_live, total_rows)
+  if (phases & 4) SPX_BN_DISPATCH(dtype, wide, SPX_BN_BA);
 #undef SPX_BN_BA
   SPX_LAUNCH_CHECK();
   return 0;
+}
+
+int spx_batchnorm_bwd(const void *x, const void *dy, void *dx, int n, int C, int dtype,
+                      const void *weight, const void *bias, int param_dtype, const float *mean,
+                      const float *invstd, int use_batch_stats, int relu, void *dweight, void *dbias,
+                      void *ws, size_t ws_bytes, const int32_t *n_live, spx_stream_t stream) {
+  return batchnorm_bwd_impl(x, dy, dx, n, C, dtype, weight, bias, param_dtype, mean, invstd, use_batch_stats, relu,
+                            dweight, dbias, ws, ws_bytes, n_live, stream, bn_phases(), nullptr, nullptr);
+}
+
+// ---- SyncBatchNorm: the same launches, cut where the ranks exchange one record per channel ----------------------
+
+int spx_batchnorm_local_stats(const void *x, int n, int C, int dtype, const float *stats_in, int stats_in_records,
+                              float *record_out, void *ws, size_t ws_bytes, const int32_t *n_live,
+                              spx_stream_t stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SPX_CHECK(bn_shape_ok(C, dtype), "batchnorm: C = %d must be a multiple of %d (<= %d), dtype f16/bf16/f32", C,
+            dtype == SPX_F32 ? 4 : 8, kMaxC);
+  SPX_CHECK(record_out, "null record pointer");
+  SPX_CHECK(n >= 0 && n <= kMaxSyncRows, "batchnorm: %d rows; a record counts rows in fp32, exact up to 2^24 = %d", n,
+            kMaxSyncRows);
+  if (n == 0) {                                     // a rank without rows: a record of zero rows, which every merge skips
+    SPX_HIP(hipMemsetAsync(record_out, 0, sizeof(float) * 3 * C, s));
+    return 0;
+  }
+  const float *partial = stats_in;
+  int G = stats_in_records;
+  if (!stats_in) {
+    SPX_CHECK(x && ws && ws_bytes >= spx_batchnorm_ws_bytes(n, C), "null pointer / workspace too small");
+    G = bn_blocks(n);
+    partial = static_cast<const float *>(ws);
+    const bool wide = C > kT;
+    const u32x4 *xv = static_cast<const u32x4 *>(x);
+#define SPX_BN_PARTIAL(D, W)                                                                                  \
+  hipLaunchKernelGGL((bn_partial_kernel<D, W>), bn_grid(G, C), dim3(kT), 0, s, xv, n, C, static_cast<float *>(ws), \
+                     n_live)
+    SPX_BN_DISPATCH(dtype, wide, SPX_BN_PARTIAL);
+#undef SPX_BN_PARTIAL
+  } else {
+    SPX_CHECK(stats_in_records > 0, "statistics records required (spx_igemm_fwd_stats)");
+  }
+  hipLaunchKernelGGL(bn_merge_record_kernel<kT>, dim3(C), dim3(kT), 0, s, partial, G, C, record_out);
+  SPX_LAUNCH_CHECK();
+  return 0;
+}
+
+int spx_batchnorm_bwd_sums(const void *x, const void *dy, int n, int C, int dtype, const void *weight,
+                           const void *bias, int param_dtype, const float *mean, const float *invstd, int relu,
+                           float *sums, void *dweight, void *dbias, void *ws, size_t ws_bytes,
+                           const int32_t *n_live, spx_stream_t stream) {
+  SPX_CHECK(sums, "null sums pointer");
+  return batchnorm_bwd_impl(x, dy, nullptr, n, C, dtype, weight, bias, param_dtype, mean, invstd, 1, relu, dweight,
+                            dbias, ws, ws_bytes, n_live, stream, 3, sums, nullptr);
+}
+
+int spx_batchnorm_bwd_apply(const void *x, const void *dy, void *dx, int n, int C, int dtype, const void *weight,
+                            const void *bias, int param_dtype, const float *mean, const float *invstd, int relu,
+                            const float *sums, const float *total_rows, const int32_t *n_live,
+                            spx_stream_t stream) {
+  SPX_CHECK(sums && total_rows, "null sums / total_rows pointer");
+  return batchnorm_bwd_impl(x, dy, dx, n, C, dtype, weight, bias, param_dtype, mean, invstd, 1, relu, nullptr, nullptr,
+                            nullptr, 0, n_live, stream, 4, const_cast<float *>(sums), total_rows);
 }
 
 }  // extern "C"

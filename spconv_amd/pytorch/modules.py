@@ -95,9 +95,9 @@ class SparseSequential(SparseModule):
                 nxt = mods[i] if i < len(mods) else None
                 conv_stats = None
                 if isinstance(nxt, nn.modules.batchnorm._BatchNorm):
-                    # a training-mode BatchNorm1d on the fused path behind a bias-free convolution: its statistics
-                    # come out of the convolution's epilogue (ops.collect_bn_stats), it starts at the merge step
-                    fuse_stats = (ops.BN_EPILOGUE and norm.ENABLED and type(nxt) is nn.BatchNorm1d
+                    # a training-mode BatchNorm1d / SyncBatchNorm on the fused path behind a bias-free convolution: its
+                    # statistics come out of the convolution's epilogue (ops.collect_bn_stats), it starts at the merge step
+                    fuse_stats = (ops.BN_EPILOGUE and norm.ENABLED and type(nxt) in norm.fused_types()
                                   and (nxt.training or nxt.running_mean is None) and is_sparse_conv(module)
                                   and getattr(module, "bias", None) is None and module.training
                                   and not module._forward_hooks and not nxt._forward_hooks
@@ -111,10 +111,11 @@ class SparseSequential(SparseModule):
                 else:
                     input = module(input)
             elif isinstance(input, SparseConvTensor):
-                # dense layers see the [N, C] feature matrix; skipped for empty tensors
-                if input.indices.shape[0] != 0:
+                # dense layers see the [N, C] feature matrix; skipped for empty tensors -- but a layer that owns a
+                # collective (a synchronising SyncBatchNorm) runs on every rank: the others wait for this one
+                if input.indices.shape[0] != 0 or norm.sync_group(module) is not None:
                     if norm.supported(input.features, module):
-                        # BatchNorm1d (+ the ReLU right behind it) in the streaming kernels of csrc/norm.hip
+                        # BatchNorm1d / SyncBatchNorm (+ the ReLU right behind it) in the streaming kernels of csrc/norm.hip
                         # (a ReLU with user hooks -- feature extractors, CAM tools, observers -- is called as a
                         # module so that they fire)
                         fuse = (i < len(mods) and type(mods[i]) is nn.ReLU and not mods[i]._forward_hooks
@@ -156,7 +157,20 @@ class SparseBatchNorm(nn.BatchNorm1d):
 
 
 class SparseSyncBatchNorm(nn.SyncBatchNorm):
-    forward = _on_features(nn.SyncBatchNorm)
+    def forward(self, input):
+        """On a SparseConvTensor: the kernels of csrc/norm.hip where norm.supported (statistics over the live rows of a
+        static-shape tensor, the collectives of a synchronising layer issued from there), else torch's layer."""
+        if not isinstance(input, SparseConvTensor):
+            return nn.SyncBatchNorm.forward(self, input)
+        from spconv_amd.pytorch import norm
+        n_live = getattr(input, "n_live_dev", None)
+        if norm.supported(input.features, self):
+            return input.replace_feature(norm.batch_norm(input.features, self, n_live=n_live))
+        if n_live is not None and self.training:
+            raise RuntimeError("a static-shape tensor (padding rows) needs the batch statistics of csrc/norm.hip; "
+                               "this SparseSyncBatchNorm takes torch's path (norm.supported: dtype / channel count / "
+                               "hooks)")
+        return input.replace_feature(nn.SyncBatchNorm.forward(self, input.features))
 
 
 class SparseReLU(nn.ReLU):

@@ -332,7 +332,12 @@ class StaticTrainingStep:
     (`step.features.grad`).  `example=(features, indices)`: the scene the warm-up passes run on (an empty scene
     without it).  The warm-up passes are real training-mode passes; the buffers they would move -- BatchNorm
     running estimates and batch counters, recorded voxel counts -- are put back before the capture, so building
-    a runner leaves a (pretrained) model's state as it found it."""
+    a runner leaves a (pretrained) model's state as it found it.
+
+    A captured graph must never contain a collective: a network that holds a SyncBatchNorm which would synchronise in
+    training mode (norm.sync_group: a process group of more than one rank is initialised) is refused with a
+    RuntimeError at construction, before anything is frozen, warmed up or captured.  Train such a network eagerly, or
+    capture it with plain BatchNorm layers."""
 
     def __init__(self, net: torch.nn.Module, max_voxels: int, in_channels: int, spatial_shape: Sequence[int],
                  batch_size: int, dtype: torch.dtype = torch.float16, bounds: Optional[Dict[str, int]] = None,
@@ -347,6 +352,13 @@ class StaticTrainingStep:
         self.order = None
         if (backward is None) == (out_grad is None):
             raise ValueError("give exactly one of `backward` (callable on the output tensor) and `out_grad`")
+        from spconv_amd.pytorch import norm
+        syncing = [name for name, m in net.named_modules() if norm.sync_group(m, training=True) is not None]
+        if syncing:
+            raise RuntimeError(f"StaticTrainingStep cannot capture a collective: {len(syncing)} SyncBatchNorm layer(s) "
+                               f"of this network (first: {syncing[0]!r}) would synchronise their statistics across the "
+                               "process group inside the graph. Train it eagerly, or use plain BatchNorm layers in "
+                               "the captured step")
         self.net = net.train()
         self.device = torch.device(device if device is not None else "cuda")
         self.max_voxels, self.spatial_shape, self.batch_size = int(max_voxels), list(spatial_shape), int(batch_size)
