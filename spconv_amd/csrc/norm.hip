@@ -10,7 +10,12 @@
 //   forward (inference) bn_apply with the running statistics
 //   backward            bn_bwd_partial -> bn_bwd_finalize -> bn_bwd_apply
 // Statistics are accumulated in fp32 per block around a per-block shift (the block's first row) and
-// merged with Chan's parallel update, so cancellation is bounded by the spread inside ~400 rows.
+// merged with Chan's parallel update, so cancellation is bounded by the spread inside ~400 rows.  The records of a pass
+// over the rows hold their means relative to an "origin" kept behind the records: an fp32 mean of a channel at -1e4 is
+// good to 5e-4 only, more than the means of two blocks of spread 0.1 differ by, and the merge squares such differences.
+// The origin is row 0 of the matrix where |row 0| is more than 16 times what the first four rows differ by, and 0 --
+// plain means, the arithmetic of before -- for every channel that is not far from zero.  It is added once, to the
+// merged mean.  Records from outside (a convolution's epilogue, the other ranks of SyncBatchNorm) hold plain means.
 // Semantics are torch.nn.BatchNorm1d's: biased variance for normalisation, unbiased for the running
 // estimate, `momentum`, `eps`, affine weight / bias (may be NULL).
 //
@@ -210,7 +215,10 @@ __device__ __forceinline__ void piece_reduce(float (&a)[VPL], float (&b)[VPL], i
 }
 
 // partial[0][c][b] = rows of block b, [1][c][b] = mean, [2][c][b] = M2 (sum of squared deviations): field-major, then
-// channel, then block -- the merge reads each field of a channel as one contiguous run (igemm_defs.h bn_record_store)
+// channel, then block -- the merge reads each field of a channel as one contiguous run (igemm_defs.h bn_record_store).
+// The mean is relative to origin[c] (row 0 of the matrix or 0, see below), which block 0 writes to partial[3][c]
+// (behind the records: the workspace keeps [2][C] more for the backward pass).
+constexpr int kOriginRows = 4;
 template <int DT, bool WIDE>
 __global__ void __launch_bounds__(kT)
 bn_partial_kernel(const u32x4 *__restrict__ x, int n, int C, float *__restrict__ partial,
@@ -221,7 +229,8 @@ bn_partial_kernel(const u32x4 *__restrict__ x, int n, int C, float *__restrict__
   const int P = blk.P;
   const size_t pitch = blk.Prow;
   x += blk.piece0;                                        // (the block's first piece of row 0)
-  const RowSplit s = row_split(live_rows(n_live, n), P, gridDim.x);
+  const int live = live_rows(n_live, n);
+  const RowSplit s = row_split(live, P, gridDim.x);
   float shift[VPL], sum[VPL], sq[VPL];
 #pragma unroll
   for (int i = 0; i < VPL; ++i) shift[i] = sum[i] = sq[i] = 0.f;
@@ -269,9 +278,28 @@ bn_partial_kernel(const u32x4 *__restrict__ x, int n, int C, float *__restrict__
       Vec<DT>::unpack(x[static_cast<size_t>(s.r0) * pitch + piece], f);
       sh = f[e];
     }
+    // origin: row 0, if the channel sits far from zero next to what its first kOriginRows rows differ by; else 0, and the
+    // record is the plain mean (every block decides alike: the same rows)
+    float origin = 0.f;
+    if (live > 0) {
+      u32x4 v[kOriginRows];
+#pragma unroll
+      for (int i = 0; i < kOriginRows; ++i) v[i] = x[static_cast<size_t>(i < live ? i : 0) * pitch + piece];
+      float f[VPL];
+      Vec<DT>::unpack(v[0], f);
+      const float x0 = f[e];
+      float spread = 0.f;
+#pragma unroll
+      for (int i = 1; i < kOriginRows; ++i) {
+        Vec<DT>::unpack(v[i], f);
+        spread = fmaxf(spread, fabsf(f[e] - x0));
+      }
+      if (fabsf(x0) > 16.f * spread) origin = x0;
+    }
     const size_t G = gridDim.x, c = blk.c0 + threadIdx.x;
+    if (blockIdx.x == 0) partial[3 * static_cast<size_t>(C) * G + c] = origin;
     partial[c * G + blockIdx.x] = cnt;
-    partial[(C + c) * G + blockIdx.x] = cnt > 0.f ? sh + a / cnt : 0.f;
+    partial[(C + c) * G + blockIdx.x] = cnt > 0.f ? (sh - origin) + a / cnt : 0.f;
     partial[(2 * static_cast<size_t>(C) + c) * G + blockIdx.x] = cnt > 0.f ? b - a * a / cnt : 0.f;
   }
 }
@@ -331,7 +359,7 @@ __global__ void __launch_bounds__(T)
 bn_finalize_kernel(const float *__restrict__ partial, int G, int C, float eps, float momentum,
                    float *__restrict__ mean_out, float *__restrict__ invstd_out,
                    void *__restrict__ running_mean, void *__restrict__ running_var, int pdt,
-                   long long *__restrict__ num_batches_tracked) {
+                   long long *__restrict__ num_batches_tracked, const float *__restrict__ origin) {
   constexpr int kT = T;
   __shared__ float ln[kT], lm[kT], l2[kT];
   const int c = blockIdx.x;
@@ -378,7 +406,7 @@ bn_finalize_kernel(const float *__restrict__ partial, int G, int C, float eps, f
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    const float cnt = ln[0], mean = lm[0];
+    const float cnt = ln[0], mean = origin ? lm[0] + origin[c] : lm[0];       // (origin: see bn_partial_kernel)
     const float var = cnt > 0.f ? l2[0] / cnt : 0.f;
     mean_out[c] = mean;
     invstd_out[c] = rsqrtf(var + eps);
@@ -394,13 +422,14 @@ bn_finalize_kernel(const float *__restrict__ partial, int G, int C, float eps, f
 // all G partials (one rank's rows: what SyncBatchNorm exchanges).  No mean / invstd, no running estimate touched.
 template <int T>
 __global__ void __launch_bounds__(T)
-bn_merge_record_kernel(const float *__restrict__ partial, int G, int C, float *__restrict__ record) {
+bn_merge_record_kernel(const float *__restrict__ partial, int G, int C, float *__restrict__ record,
+                       const float *__restrict__ origin) {
   __shared__ float ln[T], lm[T], l2[T];
   const int c = blockIdx.x;
   chan_merge<T>(partial, G, C, c, ln, lm, l2);
   if (threadIdx.x == 0) {
     record[c] = ln[0];
-    record[C + c] = ln[0] > 0.f ? lm[0] : 0.f;
+    record[C + c] = ln[0] > 0.f ? (origin ? lm[0] + origin[c] : lm[0]) : 0.f;
     record[2 * C + c] = ln[0] > 0.f ? l2[0] : 0.f;
   }
 }
@@ -766,7 +795,8 @@ static int batchnorm_fwd_impl(const void *x, void *y, int n, int C, int dtype, c
     if (training && ext_partial) {
       SPX_CHECK(save_mean && save_invstd, "training needs save_mean / save_invstd");
       hipLaunchKernelGGL(bn_finalize_kernel<kT>, dim3(C), dim3(kT), 0, s, ext_partial, ext_G, C, eps, momentum,
-                         save_mean, save_invstd, running_mean, running_var, param_dtype, num_batches_tracked);
+                         save_mean, save_invstd, running_mean, running_var, param_dtype, num_batches_tracked,
+                         static_cast<const float *>(nullptr));
       SPX_LAUNCH_CHECK();
     }
     return 0;
@@ -785,6 +815,7 @@ static int batchnorm_fwd_impl(const void *x, void *y, int n, int C, int dtype, c
     // one per workgroup of that launch), or from a pass over the rows here
     const int G = ext_partial ? ext_G : bn_blocks(n);
     const float *partial = ext_partial ? ext_partial : static_cast<const float *>(ws);
+    const float *origin = ext_partial ? nullptr : partial + 3 * static_cast<size_t>(C) * G;
     if (!ext_partial && (bn_phases() & 1)) {
 #define SPX_BN_PARTIAL(D, W)                                                                                  \
   hipLaunchKernelGGL((bn_partial_kernel<D, W>), bn_grid(G, C), dim3(kT), 0, s, xv, n, C, static_cast<float *>(ws), \
@@ -794,7 +825,7 @@ static int batchnorm_fwd_impl(const void *x, void *y, int n, int C, int dtype, c
     }
     if (bn_phases() & 2)
     hipLaunchKernelGGL(bn_finalize_kernel<kT>, dim3(C), dim3(kT), 0, s, partial, G, C, eps, momentum, save_mean,
-                       save_invstd, running_mean, running_var, param_dtype, num_batches_tracked);
+                       save_invstd, running_mean, running_var, param_dtype, num_batches_tracked, origin);
     if (!(bn_phases() & 4)) return 0;
 #define SPX_BN_APPLY(D, W)                                                                                 \
   hipLaunchKernelGGL((bn_apply_kernel<D, W>), apply_grid, dim3(kT), 0, s, xv, yv, pieces, C,               \
@@ -908,12 +939,13 @@ int spx_batchnorm_local_stats(const void *x, int n, int C, int dtype, const floa
     SPX_HIP(hipMemsetAsync(record_out, 0, sizeof(float) * 3 * C, s));
     return 0;
   }
-  const float *partial = stats_in;
+  const float *partial = stats_in, *origin = nullptr;
   int G = stats_in_records;
   if (!stats_in) {
     SPX_CHECK(x && ws && ws_bytes >= spx_batchnorm_ws_bytes(n, C), "null pointer / workspace too small");
     G = bn_blocks(n);
     partial = static_cast<const float *>(ws);
+    origin = partial + 3 * static_cast<size_t>(C) * G;
     const bool wide = C > kT;
     const u32x4 *xv = static_cast<const u32x4 *>(x);
 #define SPX_BN_PARTIAL(D, W)                                                                                  \
@@ -924,7 +956,7 @@ int spx_batchnorm_local_stats(const void *x, int n, int C, int dtype, const floa
   } else {
     SPX_CHECK(stats_in_records > 0, "statistics records required (spx_igemm_fwd_stats)");
   }
-  hipLaunchKernelGGL(bn_merge_record_kernel<kT>, dim3(C), dim3(kT), 0, s, partial, G, C, record_out);
+  hipLaunchKernelGGL(bn_merge_record_kernel<kT>, dim3(C), dim3(kT), 0, s, partial, G, C, record_out, origin);
   SPX_LAUNCH_CHECK();
   return 0;
 }
