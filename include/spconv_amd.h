@@ -37,6 +37,7 @@ extern "C" {
 #endif
 
 #define SPX_MAX_NDIM 4
+#define SPX_UNION_MAX_OPERANDS 8   /* operands of one misaligned add (spx_union_*) */
 
 typedef void *spx_stream_t; /* hipStream_t */
 
@@ -90,6 +91,9 @@ int spx_set_option(const char *name_h, int value);
  *   generic/<dt>, gen1/<COUT>/<dt>                 one-thread-per-output and first-generation gather-GEMM
  *   dense/map, dense/scatter_cl, dense/scatter_cf, dense/gather_cl, dense/gather_cf, dense/compact
  *                                                  sparse <-> dense conversion (cl / cf: channels last / first)
+ *   union/mark, union/prefix, union/claim, union/fill, union/add_fwd, union/add_bwd
+ *                                                  misaligned add: the stages of the union build (prefix: the prefix
+ *                                                  pass and its block scan, counted once) and the two merge launches
  * COUT in {16, 32, 64, 128, 256}, NKS in {1, 2}, PK in {1, 2, 4, 8, 16, 32}.  A well-formed key of an instance that is
  * never built counts 0; anything else is unknown.
  * float64 (SPX_F64) has a family and keys of its own, outside the dt vocabulary above:
@@ -722,6 +726,67 @@ int spx_from_dense_count(const void *dense, int C, int elem_bytes, int is_float,
 int spx_from_dense_fill(const void *dense, int C, int elem_bytes, int ndim, int batch,
                         const int *spatial_h, const void *ws, size_t ws_bytes, int32_t *indices,
                         void *rows, int32_t *map, spx_stream_t stream);
+
+/* ---- misaligned add (csrc/union.hip) -----------------------------------------------------------------
+ * Replace the torch composite behind the reference's spconv/pytorch/functional.py:439-545 (sparse_add_hash_based,
+ * sparse_add) and tables.py AddTableMisaligned: T hash inserts + an arange whose count is read back, T queries, T
+ * index_add_ (float atomics: non-deterministic from three operands on), T indexed index writes and a zero fill.
+ *
+ * UNION of T coordinate sets, 1 <= T <= SPX_UNION_MAX_OPERANDS.  The operands arrive as HOST arrays of length T:
+ * indices_h[t] = device int32 [n_h[t], ndim + 1], n_live_h (or NULL) with n_live_h[t] = NULL or a device int32 (see
+ * spx_conv_rulebook_static).  A row is DEAD -- contributes nothing -- when it lies at or beyond *n_live_h[t], when its
+ * batch index is outside [0, batch) or a coordinate outside [0, extent).  The union is numbered through the level's
+ * RANK MAP (sorted-order levels above; the caller's buffer of spx_rankmap_bytes): byte marks, the prefix pass, one
+ * 8-byte load per row -- no hash table, no atomic on the path that numbers the rows.
+ *   spx_union_ws_bytes: scratch of a build over n_total = sum n_h[t] rows; 0 when the key space does not fit (as
+ *   spx_rankmap_bytes: keep the hash path), for an empty grid and for T outside its range.
+ *   spx_union_count: marks, prefix pass, ownership pass, and the call's ONE D->H read (synchronises the stream):
+ *   result_h [2 + T] = {union size, duplicate flag, live rows of operand 0 .. T-1}.  The duplicate flag is 1 when a
+ *   coordinate occurs twice within one operand: the composite sums such rows, a src table cannot say that -- the
+ *   caller falls back.
+ *   spx_union_fill: with the SAME rankmap and ws, unchanged since the count, writes
+ *     rows_h[t]  device int32 [n_h[t]]: the output row of each input row, -1 for a dead or dropped row
+ *     src        device int32 [T][n_out]: the row of operand t that sits at that output row, or -1
+ *     out_indices [n_out, ndim + 1] (base = -1 only; may be NULL otherwise)
+ *   base = -1: rows in ascending linear key order (batch-major, last axis fastest: the numbering of the sorted-order
+ *   levels); n_out = the union size (a smaller n_out keeps the first n_out keys) and the rank map left behind
+ *   describes the result, so spx_subm_rulebook_ranked applies to it.
+ *   base = b: operand b's own numbering -- n_out = n_h[b], rows_h[b] = identity on its live rows, src of its dead rows
+ *   = -1, the result's indices ARE operand b's.  Legal only when the host has seen live rows of b == union size and the
+ *   duplicate flag 0 (b holds every coordinate of the union exactly once).
+ *   spx_union_static: the static-shape form, always in key order: room for n_out_cap rows, nothing read back
+ *   (hipGraph-safe; five launches).  n_out_dev [3] (device) = {union size found -- may exceed the cap --, duplicate
+ *   flag, live rows = min(found, cap)}; out_indices rows past the live count are -1 (as spx_conv_rulebook_static
+ *   writes them), their src entries -1; outputs beyond the cap are dropped in key order (rows_h entry -1).
+ * With duplicates present every call still finishes with every index in range: of the rows of one operand with one
+ * coordinate the HIGHEST row owns the cell (as spx_dense_map), on every call.
+ *
+ * ROW MERGE.
+ *   spx_union_add_fwd: out[r, :] = sum over the operands t with src[t][r] >= 0, in operand order, of
+ *   feat_h[t][src[t][r], :] ([n_h[t], C] contiguous), accumulated in fp32 (fp64 for SPX_F64) and rounded once to
+ *   `dtype` (SPX_F16 / SPX_BF16 / SPX_F32 / SPX_F64).  An absent operand is skipped, not added as zero: a row held by
+ *   one operand keeps its bits (-0.0 stays -0.0); a row held by none, and every row >= *n_live (NULL or a device
+ *   int32), is zero.  Every output element is written exactly once: no zero fill, no atomics, one launch for all
+ *   operands.  Any C >= 1: rows whose byte size is a multiple of 16 (and 16-byte aligned pointers) move as 16-byte
+ *   pieces per lane, other widths element by element.  A src entry outside [0, n_h[t]) counts as -1.
+ *   spx_union_add_bwd: din_h[t][i, :] = dout[rows_h[t][i], :], zeros where the entry is outside [0, n_out): a
+ *   byte-moving gather for elem_bytes 2, 4 or 8, one launch for all operands. */
+size_t spx_union_ws_bytes(int ndim, int batch, const int *spatial_h, int T, long long n_total);
+int spx_union_count(const int32_t *const *indices_h, const int *n_h, const int32_t *const *n_live_h, int T,
+                    int ndim, int batch, const int *spatial_h, void *rankmap, size_t rankmap_bytes, void *ws,
+                    size_t ws_bytes, int *result_h, spx_stream_t stream);
+int spx_union_fill(const int32_t *const *indices_h, const int *n_h, const int32_t *const *n_live_h, int T,
+                   int ndim, int batch, const int *spatial_h, int n_out, int base, int32_t *out_indices,
+                   int32_t *const *rows_h, int32_t *src, const void *rankmap, size_t rankmap_bytes,
+                   const void *ws, size_t ws_bytes, spx_stream_t stream);
+int spx_union_static(const int32_t *const *indices_h, const int *n_h, const int32_t *const *n_live_h, int T,
+                     int ndim, int batch, const int *spatial_h, int n_out_cap, int32_t *out_indices,
+                     int32_t *const *rows_h, int32_t *src, int32_t *n_out_dev, void *rankmap,
+                     size_t rankmap_bytes, void *ws, size_t ws_bytes, spx_stream_t stream);
+int spx_union_add_fwd(const void *const *feat_h, const int *n_h, int T, const int32_t *src, int n_out, int C,
+                      int dtype, void *out, const int32_t *n_live, spx_stream_t stream);
+int spx_union_add_bwd(const void *dout, int n_out, void *const *din_h, const int32_t *const *rows_h,
+                      const int *n_h, int T, int C, int elem_bytes, spx_stream_t stream);
 
 #ifdef __cplusplus
 }

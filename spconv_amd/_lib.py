@@ -146,6 +146,17 @@ SIGNATURES = {
     "spx_from_dense_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, c_int_p]),
     "spx_from_dense_count": (ctypes.c_int, [vp] + [ctypes.c_int] * 5 + [c_int_p, vp, ctypes.c_size_t, c_int_p, vp]),
     "spx_from_dense_fill": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [c_int_p, vp, ctypes.c_size_t, vp, vp, vp, vp]),
+    "spx_union_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int, ctypes.c_longlong]),
+    "spx_union_count": (ctypes.c_int, [vp, c_int_p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, vp,
+                                       ctypes.c_size_t, vp, ctypes.c_size_t, c_int_p, vp]),
+    "spx_union_fill": (ctypes.c_int, [vp, c_int_p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
+                                      ctypes.c_int, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
+    "spx_union_static": (ctypes.c_int, [vp, c_int_p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
+                                        vp, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
+    "spx_union_add_fwd": (ctypes.c_int, [vp, c_int_p, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp,
+                                         vp]),
+    "spx_union_add_bwd": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         vp]),
 }
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_I8, DTYPE_F64 = 0, 1, 2, 3, 4
@@ -199,3 +210,8 @@ def check(status: int) -> None:
 
 def ints(values):
     return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def ptrs(values):
+    """Host array of device pointers (None = NULL) for the C calls that take a list of operands."""
+    return (ctypes.c_void_p * len(values))(*[None if v is None else int(v) for v in values])

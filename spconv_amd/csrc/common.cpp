@@ -34,6 +34,7 @@ std::atomic<long long> g_launches[kFamCount];
 std::atomic<long long> g_inst_launches[inst::kCount];
 std::atomic<long long> g_f64_launches[kF64Count];
 std::atomic<long long> g_dense_launches[kDenseCount];
+std::atomic<long long> g_union_launches[kUnionCount];
 
 namespace {
 // "f16" | "bf16" | "i8" | "f32" -> the kernels' DT code, or -1
@@ -134,6 +135,15 @@ std::atomic<long long> *dense_counter(const char *key) {
     if (strcmp(key, names[i]) == 0) return &g_dense_launches[i];
   return nullptr;
 }
+
+// counter of a misaligned-add key (spx_launch_count), or null
+std::atomic<long long> *union_counter(const char *key) {
+  static const char *names[kUnionCount] = {"union/mark", "union/prefix", "union/claim", "union/fill", "union/add_fwd",
+                                           "union/add_bwd"};
+  for (int i = 0; i < kUnionCount; ++i)
+    if (strcmp(key, names[i]) == 0) return &g_union_launches[i];
+  return nullptr;
+}
 }  // namespace
 
 int option_int(const char *name, int dflt) {
@@ -173,6 +183,7 @@ long long spx_launch_count(const char *family_h) {
     if (strcmp(names[i], family_h) == 0) return spx::g_launches[i].load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::f64_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::dense_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::union_counter(family_h)) return c->load(std::memory_order_relaxed);
   const int slot = spx::instance_slot(family_h);
   return slot < 0 ? -1 : spx::g_inst_launches[slot].load(std::memory_order_relaxed);
 }

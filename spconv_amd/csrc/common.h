@@ -187,6 +187,12 @@ inline void count_f64(F64Inst i) { g_f64_launches[i].fetch_add(1, std::memory_or
 enum DenseInst { kDenseMap = 0, kDenseScatterCl, kDenseScatterCf, kDenseGatherCl, kDenseGatherCf, kDenseCompact, kDenseCount };
 extern std::atomic<long long> g_dense_launches[kDenseCount];
 inline void count_dense(DenseInst i) { g_dense_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
+// misaligned add (union.hip): one counter per stage.
+// Keys union/mark, union/prefix, union/claim, union/fill, union/add_fwd, union/add_bwd.
+enum UnionInst { kUnionMark = 0, kUnionPrefix, kUnionClaim, kUnionFill, kUnionAddFwd, kUnionAddBwd, kUnionCount };
+extern std::atomic<long long> g_union_launches[kUnionCount];
+inline void count_union(UnionInst i) { g_union_launches[i].fetch_add(1, std::memory_order_relaxed); }
 }  // namespace spx
 
 // ---- row orders (rowsort.hip) ---------------------------------------------------------------------

@@ -18,6 +18,8 @@
 //  * kernel boundaries are the only inter-workgroup synchronisation (XCD L2s
 //    are not coherent inside a launch).
 #include "common.h"
+#include "fill.h"
+#include "rankmap.h"
 
 #include <algorithm>
 #include <mutex>
@@ -200,67 +202,7 @@ __device__ __forceinline__ bool in_range(const int (&c)[4], const int (&dims)[4]
   return ok;
 }
 
-// ------------------------------------------------------------ range fills
-// Every "memset" of a rulebook build in ONE launch: on a host-bound pipeline (a single scene per
-// step) a rulebook is a dozen launches of ~6 us of host time each, and hipMemsetAsync costs a
-// launch like any kernel.  Ranges are 4-byte aligned multiples of 4 bytes; the 16-byte aligned
-// middle of each goes out as dwordx4 stores.
-constexpr int kMaxFills = 8;
-struct FillJobs {
-  uint32_t *ptr[kMaxFills];
-  unsigned long long words[kMaxFills];
-  uint32_t value[kMaxFills];
-  int n;
-};
-
-__global__ void __launch_bounds__(kBlock)
-fill_ranges_kernel(FillJobs jobs) {
-  const unsigned long long t = static_cast<unsigned long long>(blockIdx.x) * kBlock + threadIdx.x;
-  const unsigned long long T = static_cast<unsigned long long>(gridDim.x) * kBlock;
-  for (int j = 0; j < jobs.n; ++j) {
-    uint32_t *p = jobs.ptr[j];
-    const unsigned long long w = jobs.words[j];
-    const uint32_t v = jobs.value[j];
-    unsigned long long head = (4 - ((reinterpret_cast<uintptr_t>(p) >> 2) & 3)) & 3;
-    if (head > w) head = w;
-    const unsigned long long body = (w - head) >> 2, tail = (w - head) & 3;
-    if (t < head) p[t] = v;
-    uint4 *q = reinterpret_cast<uint4 *>(p + head);
-    const uint4 vv = make_uint4(v, v, v, v);
-    for (unsigned long long i = t; i < body; i += T) q[i] = vv;
-    if (t < tail) p[head + 4 * body + t] = v;
-  }
-}
-
-struct FillList {
-  FillJobs jobs;
-  FillList() { jobs.n = 0; }
-  // adjacent ranges with the same value merge (tables carved from one buffer: one range)
-  void add(void *ptr, size_t bytes, uint32_t value) {
-    if (!ptr || bytes == 0) return;
-    uint32_t *p = static_cast<uint32_t *>(ptr);
-    for (int j = 0; j < jobs.n; ++j) {
-      if (jobs.value[j] != value) continue;
-      if (jobs.ptr[j] + jobs.words[j] == p) { jobs.words[j] += bytes / 4; return; }
-      if (p + bytes / 4 == jobs.ptr[j]) { jobs.ptr[j] = p; jobs.words[j] += bytes / 4; return; }
-    }
-    jobs.ptr[jobs.n] = p;
-    jobs.words[jobs.n] = bytes / 4;
-    jobs.value[jobs.n] = value;
-    ++jobs.n;
-  }
-  hipError_t launch(hipStream_t s) const {
-    if (jobs.n == 0) return hipSuccess;
-    unsigned long long most = 0;
-    for (int j = 0; j < jobs.n; ++j) most = jobs.words[j] > most ? jobs.words[j] : most;
-    // 16 words (four dwordx4) per thread of the longest range, at most 2048 workgroups
-    unsigned long long blocks = (most + 16ull * kBlock - 1) / (16ull * kBlock);
-    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-    hipLaunchKernelGGL(fill_ranges_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, jobs);
-    return hipGetLastError();
-  }
-};
-
+// (FillList, every "memset" of a build in one launch: fill.h)
 void table_fill(FillList &f, const Table &t);
 
 // ---------------------------------------------------------------- SubM
@@ -1237,8 +1179,7 @@ conv3_pairs_kernel(const int32_t *__restrict__ indices, int n, Geom g,
 //     tools/order_probe.py).
 // Memory: the map (batch x grid cells) / 4 bytes (47 M cells of a 21 x 800 x 704 x 4 level: 11.8 MB) + one byte per
 // cell of scratch during the build; key spaces beyond 2^31 cells keep the hash builder.
-constexpr int kRankWords = 2048;      // words (65536 cells) per prefix block
-constexpr int kRankPer = kRankWords / kBlock;
+// (kRankWords, conv4_prefix_kernel, rank_of and the size helpers of the map: rankmap.h)
 
 template <int MJ>
 __global__ void __launch_bounds__(kBlock)
@@ -1260,83 +1201,6 @@ conv4_mark_kernel(const int32_t *__restrict__ indices, int n, Geom g, uint8_t *_
     occupied[static_cast<unsigned long long>(layout_key(b, q, g.out_dims))] = 1;
     it.next();
   }
-}
-
-// the byte map packed into the words of the rank map (cells[w].x), block-local exclusive prefix of their popcounts
-// (cells[w].y), block total -> blockcount.  32 bytes (two 16-byte loads) per word; a byte is 0 or 1, so four of them
-// become a nibble with one multiply: ((v * 0x01020408) >> 24) & 15.
-__device__ __forceinline__ uint32_t pack_flags16(const uint4 &v) {
-  auto nib = [](uint32_t d) __attribute__((always_inline)) { return ((d * 0x01020408u) >> 24) & 15u; };
-  return nib(v.x) | (nib(v.y) << 4) | (nib(v.z) << 8) | (nib(v.w) << 12);
-}
-
-__global__ void __launch_bounds__(kBlock)
-conv4_prefix_kernel(const uint4 *__restrict__ occupied, uint2 *__restrict__ cells, unsigned W,
-                    int32_t *__restrict__ blockcount) {
-  __shared__ int lds_wave[kBlock / 64];
-  __shared__ __attribute__((aligned(16))) uint16_t lds_half[2 * kRankWords];
-  const unsigned base = blockIdx.x * kRankWords + threadIdx.x * kRankPer;
-  // The block's 64 KB of flag bytes in 16-byte pieces, lane-consecutive (a thread reading ITS eight words' 256 bytes put
-  // every load instruction on 64 different lines: 27 us for the 59 MB of a 47 M-cell level); a piece becomes 16 bits,
-  // the halves of a word meet in LDS
-  {
-    const size_t piece0 = static_cast<size_t>(blockIdx.x) * (2 * kRankWords);
-    const size_t pieces = 2 * static_cast<size_t>(W);
-    uint4 v[2 * kRankPer];
-#pragma unroll
-    for (int j = 0; j < 2 * kRankPer; ++j) {
-      const size_t pc = piece0 + static_cast<size_t>(j) * kBlock + threadIdx.x;
-      v[j] = pc < pieces ? occupied[pc] : make_uint4(0u, 0u, 0u, 0u);
-    }
-#pragma unroll
-    for (int j = 0; j < 2 * kRankPer; ++j) lds_half[j * kBlock + threadIdx.x] = static_cast<uint16_t>(pack_flags16(v[j]));
-  }
-  __syncthreads();
-  uint32_t bits[kRankPer];
-  int cnt[kRankPer], sum = 0;
-  {
-    const uint4 *w4 = reinterpret_cast<const uint4 *>(lds_half) + threadIdx.x * (kRankPer / 4);
-    static_assert(kRankPer == 8, "two 16-byte reads per thread");
-    const uint4 a = w4[0], b = w4[1];
-    const uint32_t w[kRankPer] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int e = 0; e < kRankPer; ++e) {
-      bits[e] = base + e < W ? w[e] : 0u;
-      cnt[e] = __popc(bits[e]);
-      sum += cnt[e];
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += u;
-  }
-  if (lane == 63) lds_wave[wave] = incl;
-  __syncthreads();
-  int prefix = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kBlock / 64; ++w) {
-    const int x = lds_wave[w];
-    if (w < wave) prefix += x;
-    total += x;
-  }
-  int run = prefix + incl - sum;
-#pragma unroll
-  for (int e = 0; e < kRankPer; ++e) {
-    if (base + e < W) cells[base + e] = make_uint2(bits[e], static_cast<uint32_t>(run));
-    run += cnt[e];
-  }
-  if (threadIdx.x == 0) blockcount[blockIdx.x] = total;
-}
-
-// row of a key: occupied cells before its 65536-cell block + before its word inside the block + below it in the word
-__device__ __forceinline__ int rank_of(const uint2 *__restrict__ cells, const int32_t *__restrict__ blockoff,
-                                       unsigned long long key) {
-  const uint2 cell = cells[key >> 5];
-  const uint32_t bit = 1u << (key & 31);
-  return (cell.x & bit) ? blockoff[key >> 16] + static_cast<int>(cell.y) + __popc(cell.x & (bit - 1u)) : -1;
 }
 
 // The rank map of a level whose rows ALREADY are in ascending, unique key order (level 1 of a backbone when the data
@@ -2827,25 +2691,6 @@ int spx_conv_rulebook_static(const int32_t *indices, int n_in, int ndim, int bat
 // the call, the SubM layers of the level read it.
 namespace spx {
 namespace {
-// words of a level's rank map (0: the key space does not fit)
-size_t rank_words(int ndim, int batch_size, const int *shape) {
-  if (ndim < 1 || ndim > kMaxNdim || batch_size < 1) return 0;
-  unsigned long long cells = static_cast<unsigned long long>(batch_size);
-  for (int i = 0; i < ndim; ++i) {
-    if (shape[i] < 1) return 0;
-    cells *= static_cast<unsigned long long>(shape[i]);
-    if (cells > 0x7fffffe0ull) return 0;
-  }
-  return static_cast<size_t>((cells + 31) / 32);
-}
-
-// the caller's rank-map buffer: W {bits, prefix} words, then the occupied cells before each 2048-word block
-size_t rank_cells_bytes(size_t W) { return align_up(W * sizeof(uint2), 256); }
-size_t rank_blocks(size_t W) { return (W + kRankWords - 1) / kRankWords; }
-size_t rank_bytes(size_t W) { return W ? rank_cells_bytes(W) + align_up(rank_blocks(W) * sizeof(int32_t), 256) : 0; }
-int32_t *rank_blockoff(void *rankmap, size_t W) {
-  return reinterpret_cast<int32_t *>(static_cast<char *>(rankmap) + rank_cells_bytes(W));
-}
 
 struct Conv4Ws {
   int32_t *blockcount, *d_nout, *groupcount;

@@ -278,16 +278,91 @@ def _like_first(first, features, indices, indice_dict=None):
     return res
 
 
-def sparse_add_hash_based(*tens):
-    """Sum of sparse tensors with different coordinate sets (reference functional.py:439-499):
-    the union of the coordinates is numbered through a hash table.  indice_dict is dropped unless
-    one operand already holds every output coordinate."""
-    from spconv_amd.pytorch.hash import HashTable
+class SparseUnionAddFunction(Function):
+    """Row merge of a misaligned add over the kernels of csrc/union.hip: out[r] = sum of feats[t][src[t, r]] over the
+    operands present at r, in operand order, fp32 (fp64) accumulation, one rounding, one launch; rows_t is saved and
+    the backward is one gather launch, din_t[i] = dout[rows_t[i]] (zeros for dead and dropped rows)."""
+
+    @staticmethod
+    def forward(ctx, src, rows, n_out, n_live, *feats):
+        from spconv_amd.pytorch import _union
+        ctx.rows = tuple(rows)
+        return _union.add_fwd([f.detach() for f in feats], src, int(n_out), n_live)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        from spconv_amd.pytorch import _union
+        return (None, None, None, None) + tuple(_union.add_bwd(grad_output, ctx.rows, ctx.needs_input_grad[4:]))
+
+
+_UNION_DTYPES = (torch.float16, torch.bfloat16, torch.float32, torch.float64)
+
+
+def sparse_add_native(tens, static_num_out=None, owner=None):
+    """The misaligned add on the union kernels (spconv_amd/pytorch/_union.py), or None when they do not apply: more
+    than eight operands, features that are not CUDA floating point of one dtype (quantised ones included), indices
+    that are not int32, a key space beyond the rank-map gate, or -- eager form -- a coordinate that occurs twice within
+    one operand (the composite sums such rows).  Static form when an operand carries n_live_dev: key order, room for
+    `static_num_out` rows (default: the rows of all operands), nothing read back; `owner` (the calling module) keeps
+    the device-side counters of its last call in `_static_n_out_dev`."""
+    from spconv_amd.pytorch import _union
+    first = tens[0]
+    feats = [t.features for t in tens]
+    dt = feats[0].dtype
+    if not 1 <= len(tens) <= _union.MAX_OPERANDS or dt not in _UNION_DTYPES:
+        return None
+    for t in tens:
+        f = t.features
+        if not (isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == dt and not f.is_quantized and f.dim() == 2
+                and f.shape[1] >= 1 and t.indices.is_cuda and t.indices.dtype == torch.int32):
+            return None
+    lives = [getattr(t, "n_live_dev", None) for t in tens]
+    static = any(v is not None for v in lives)
+    u = _union.sparse_union([t.indices for t in tens], first.batch_size, first.spatial_shape,
+                            n_live=lives if static else None,
+                            static_num_out=(static_num_out or sum(f.shape[0] for f in feats) or 1) if static else None)
+    if u is None:
+        return None
+    n_live = u.n_out_dev[2:3] if static else None
+    out_features = SparseUnionAddFunction.apply(u.src, u.rows, u.n_out, n_live, *feats)
+    if u.base >= 0:
+        # one operand holds every coordinate: the result lives on ITS rows, its cached rulebooks stay valid
+        res = _like_first(first, out_features, tens[u.base].indices, tens[u.base].indice_dict)
+        res.n_live_dev = tens[u.base].n_live_dev
+    else:
+        res = _like_first(first, out_features, u.out_indices)
+        res.n_live_dev = n_live
+    if static and owner is not None:
+        owner._static_n_out_dev = u.n_out_dev
+    return res
+
+
+def misaligned_add(tens, composite, static_num_out=None, owner=None):
+    """The one body of sparse_add_hash_based, sparse_add and tables.AddTableMisaligned: the union kernels where they
+    apply (sparse_add_native), else `composite`."""
     first = tens[0]
     for ten in tens:
         assert ten.spatial_shape == first.spatial_shape
         assert ten.batch_size == first.batch_size
         assert ten.features.shape[1] == first.features.shape[1]
+    res = sparse_add_native(tens, static_num_out, owner)
+    return res if res is not None else composite(*tens)
+
+
+def sparse_add_hash_based(*tens):
+    """Sum of sparse tensors with different coordinate sets (reference functional.py:439-499).  On the union kernels
+    where they apply (sparse_add_native): rows in ascending key order with the level's rank map attached, or -- when
+    one operand already holds every output coordinate -- in that operand's own numbering, with its index tensor and
+    indice_dict.  Otherwise through the hash-table composite below."""
+    return misaligned_add(tens, _sparse_add_hash_composite)
+
+
+def _sparse_add_hash_composite(*tens):
+    """The union of the coordinates numbered through a hash table (torch composite).  indice_dict is dropped unless
+    one operand already holds every output coordinate."""
+    from spconv_amd.pytorch.hash import HashTable
+    first = tens[0]
     sizes = [t.features.shape[0] for t in tens]
     biggest = max(range(len(tens)), key=lambda i: sizes[i])
     shape = [first.batch_size, *first.spatial_shape]
@@ -313,13 +388,14 @@ def sparse_add_hash_based(*tens):
 
 
 def sparse_add(*tens):
-    """Same sum through sort + unique (reference functional.py:502-545 goes through torch.sparse):
-    output rows are ordered by coordinate."""
+    """Same sum (reference functional.py:502-545 goes through torch.sparse).  On the union kernels where they apply
+    (as sparse_add_hash_based); otherwise through the sort + unique composite below."""
+    return misaligned_add(tens, _sparse_add_sorted_composite)
+
+
+def _sparse_add_sorted_composite(*tens):
+    """Sort + unique of the linear keys (torch composite): output rows are ordered by coordinate."""
     first = tens[0]
-    for ten in tens:
-        assert ten.spatial_shape == first.spatial_shape
-        assert ten.batch_size == first.batch_size
-        assert ten.features.shape[1] == first.features.shape[1]
     sizes = [t.features.shape[0] for t in tens]
     biggest = max(range(len(tens)), key=lambda i: sizes[i])
     shape = [first.batch_size, *first.spatial_shape]

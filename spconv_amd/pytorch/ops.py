@@ -43,6 +43,7 @@ from spconv_amd.pytorch._gemm import (  # noqa: F401
     _STAGE2_JOB_BYTES, _WGRAD_MAX_KV, StatsSink, _check_feat, _defer_lock, _defer_passes, _defer_state, _lane_mult,
     bias_act_inplace, collect_bn_stats, current_stats_sink, deferred_wgrad, igemm_dgrad, igemm_fwd, igemm_fwd_int8,
     igemm_wgrad, output_stays_cached, wgrad_plan)
+from spconv_amd.pytorch._union import sparse_union  # noqa: F401  (misaligned add: the union build of csrc/union.hip)
 
 # ---- the switches that tests and tools set through this module -----------------------------------------------------
 BN_EPILOGUE = os.environ.get("SPCONV_AMD_BN_EPILOGUE", "1") != "0"      # see _gemm.collect_bn_stats

@@ -76,6 +76,25 @@ def freeze_bounds(net: torch.nn.Module, bounds: Optional[Dict[str, int]] = None,
     return used
 
 
+def _bounded_unions(net: torch.nn.Module) -> Dict[str, torch.nn.Module]:
+    """AddTableMisaligned modules that were given an explicit `static_num_out`: their union can overflow it."""
+    from spconv_amd.pytorch.tables import AddTableMisaligned
+    return {name: m for name, m in net.named_modules()
+            if isinstance(m, AddTableMisaligned) and m.static_num_out is not None}
+
+
+def _static_counters(runner) -> Dict[str, torch.Tensor]:
+    """The device-side {found, flag} counters of a captured pass: the strided layers' and the bounded unions' (whose
+    flag says that a coordinate occurred twice within one operand); the unions' bounds join runner.bounds."""
+    out = {name: m._static_n_out_dev for name, m in runner._layers.items()
+           if getattr(m, "_static_n_out_dev", None) is not None}
+    for name, m in _bounded_unions(runner.net).items():
+        if m._static_n_out_dev is not None:
+            out[name] = m._static_n_out_dev[:2]
+            runner.bounds[name] = m.static_num_out
+    return out
+
+
 def dense_static(t: SparseConvTensor, channels_first: bool = True) -> torch.Tensor:
     """SparseConvTensor.dense() for a tensor with dead rows (batch index -1, rows >= n_live_dev): the cell-map
     kernel skips them (spconv_amd/pytorch/_dense.py).  No data-dependent shape, nothing read back, scratch from the
@@ -266,8 +285,7 @@ class StaticInference:
                 self.out = self._forward()
         self.graph = g
         # the device-side counters of the captured pass (static tensors of the graph's pool)
-        self._counters = {name: m._static_n_out_dev for name, m in self._layers.items()
-                          if getattr(m, "_static_n_out_dev", None) is not None}
+        self._counters = _static_counters(self)
 
     def _forward(self):
         feats, idx = _entry(self)
@@ -393,8 +411,7 @@ class StaticTrainingStep:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, capture_error_mode=capture_error_mode):      # (see StaticInference)
                 self._compute()             # gradients land in tensors of the graph's pool: static from here on
-        self._counters = {name: m._static_n_out_dev for name, m in self._layers.items()
-                          if getattr(m, "_static_n_out_dev", None) is not None}
+        self._counters = _static_counters(self)
 
     def _compute(self):
         self.net.zero_grad(set_to_none=True)

@@ -1,11 +1,11 @@
 """Container modules that combine several sparse tensors (reference ``spconv/pytorch/tables.py:25-92``).
 
 ``JoinTable`` concatenates channels, ``AddTable`` sums features of tensors that share one
-coordinate set, ``AddTableMisaligned`` unions the coordinate sets first (hash based,
-``functional.sparse_add_hash_based``), ``ConcatTable`` applies every child to the same input."""
+coordinate set, ``AddTableMisaligned`` unions the coordinate sets first
+(``functional.sparse_add_hash_based``: the union kernels of csrc/union.hip, else hash based), ``ConcatTable`` applies every child to the same input."""
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import torch
 
@@ -56,11 +56,22 @@ class AddTable(SparseModule):
 
 
 class AddTableMisaligned(SparseModule):
-    """Adds tensors of one shape but different coordinate sets.  The result carries a fresh
-    coordinate set, so cached downsample rulebooks (SparseInverseConv) no longer apply."""
+    """Adds tensors of one shape but different coordinate sets.  The result carries a fresh coordinate set (rows in
+    key order), so cached downsample rulebooks (SparseInverseConv) no longer apply -- unless one operand already holds
+    every coordinate: the result then keeps that operand's rows, index tensor and rulebooks.
+
+    Static shapes (operands with ``n_live_dev``: inside StaticInference / StaticTrainingStep) take the sync-free build;
+    ``static_num_out`` bounds its rows (None: the rows of all operands, which always suffices).  The counters of the
+    last call {coordinates found, duplicate flag, live rows} stay on the device in ``_static_n_out_dev``; a module
+    with an explicit bound is part of the runners' ``overflowed()``."""
+
+    def __init__(self, static_num_out: Optional[int] = None):
+        super().__init__()
+        self.static_num_out = None if static_num_out is None else int(static_num_out)
+        self._static_n_out_dev = None
 
     def forward(self, input: List[SparseConvTensor]):
-        return F.sparse_add_hash_based(*input)
+        return F.misaligned_add(input, F._sparse_add_hash_composite, self.static_num_out, self)
 
     def input_spatial_size(self, out_size):
         return out_size
