@@ -101,6 +101,10 @@ int spx_set_option(const char *name_h, int value);
  *   igemm_f64/fwd, igemm_f64/dgrad                 the same, by role
  *   wgrad_f64                                      float64 weight gradient, first stage
  *   pool/f64                                       float64 pooling (max / avg, forward / backward)
+ * Pooling (pool.hip) counts every kernel instance, float64 included:
+ *   pool/<op>/<dt>/<piece>                         op: max_fwd | max_bwd | avg_fwd | avg_bwd; dt: f16 | bf16 | f32 | f64 |
+ *                                                  i8; piece: v (16-byte pieces, C a multiple of 16 / sizeof(dt)) | s (one
+ *                                                  element per thread).  int8 exists for max_fwd only: 34 instances.
  * Host only. */
 long long spx_launch_count(const char *family_h);
 

@@ -35,6 +35,7 @@ std::atomic<long long> g_inst_launches[inst::kCount];
 std::atomic<long long> g_f64_launches[kF64Count];
 std::atomic<long long> g_dense_launches[kDenseCount];
 std::atomic<long long> g_union_launches[kUnionCount];
+std::atomic<long long> g_pool_launches[kPoolCount];
 
 namespace {
 // "f16" | "bf16" | "i8" | "f32" -> the kernels' DT code, or -1
@@ -144,6 +145,27 @@ std::atomic<long long> *union_counter(const char *key) {
     if (strcmp(key, names[i]) == 0) return &g_union_launches[i];
   return nullptr;
 }
+
+// counter of a pooling key pool/<op>/<dt>/<piece> (spx_launch_count), or null
+std::atomic<long long> *pool_counter(const char *key) {
+  static const char *ops[kPoolOps] = {"max_fwd", "max_bwd", "avg_fwd", "avg_bwd"};
+  static const char *dts[kPoolDts] = {"f16", "bf16", "f32", "f64", "i8"};
+  if (strncmp(key, "pool/", 5) != 0) return nullptr;
+  key += 5;
+  for (int op = 0; op < kPoolOps; ++op) {
+    const size_t n = strlen(ops[op]);
+    if (strncmp(key, ops[op], n) != 0 || key[n] != '/') continue;
+    const char *rest = key + n + 1;
+    for (int dt = 0; dt < kPoolDts; ++dt) {
+      const size_t m = strlen(dts[dt]);
+      if (strncmp(rest, dts[dt], m) != 0 || rest[m] != '/') continue;
+      const char *piece = rest + m + 1;
+      if (strcmp(piece, "v") == 0) return &g_pool_launches[pool_slot(op, dt, false)];
+      if (strcmp(piece, "s") == 0) return &g_pool_launches[pool_slot(op, dt, true)];
+    }
+  }
+  return nullptr;
+}
 }  // namespace
 
 int option_int(const char *name, int dflt) {
@@ -184,6 +206,7 @@ long long spx_launch_count(const char *family_h) {
   if (std::atomic<long long> *c = spx::f64_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::dense_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::union_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::pool_counter(family_h)) return c->load(std::memory_order_relaxed);
   const int slot = spx::instance_slot(family_h);
   return slot < 0 ? -1 : spx::g_inst_launches[slot].load(std::memory_order_relaxed);
 }

@@ -193,6 +193,17 @@ inline void count_dense(DenseInst i) { g_dense_launches[i].fetch_add(1, std::mem
 enum UnionInst { kUnionMark = 0, kUnionPrefix, kUnionClaim, kUnionFill, kUnionAddFwd, kUnionAddBwd, kUnionCount };
 extern std::atomic<long long> g_union_launches[kUnionCount];
 inline void count_union(UnionInst i) { g_union_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
+// pooling (pool.hip): one counter per kernel instance, op x dtype x piece.
+// Keys pool/<op>/<dt>/<piece>: op max_fwd | max_bwd | avg_fwd | avg_bwd (PoolOp order), dt f16 | bf16 | f32 | f64 | i8,
+// piece v (16-byte pieces) | s (one element).  int8 is built for max_fwd only; its other keys count 0.
+enum PoolDt { kPoolF16 = 0, kPoolBf16, kPoolF32, kPoolF64, kPoolI8, kPoolDts };
+constexpr int kPoolOps = 4, kPoolCount = kPoolOps * kPoolDts * 2;
+extern std::atomic<long long> g_pool_launches[kPoolCount];
+constexpr int pool_slot(int op, int dt, bool scalar) { return (op * kPoolDts + dt) * 2 + (scalar ? 1 : 0); }
+inline void count_pool(int op, int dt, bool scalar) {
+  g_pool_launches[pool_slot(op, dt, scalar)].fetch_add(1, std::memory_order_relaxed);
+}
 }  // namespace spx
 
 // ---- row orders (rowsort.hip) ---------------------------------------------------------------------

@@ -33,24 +33,28 @@ struct PoolParams {
 template <typename T> struct Elem;
 template <> struct Elem<double> {
   typedef double Acc;
+  static constexpr int kDt = kPoolF64;
   static __device__ __forceinline__ double to_f(double v) { return v; }
   static __device__ __forceinline__ double from_f(double v) { return v; }
   static __device__ __forceinline__ double lowest() { return -1.7976931348623157e+308; }
 };
 template <> struct Elem<float> {
   typedef float Acc;
+  static constexpr int kDt = kPoolF32;
   static __device__ __forceinline__ float to_f(float v) { return v; }
   static __device__ __forceinline__ float from_f(float v) { return v; }
   static __device__ __forceinline__ float lowest() { return -3.402823466e+38f; }
 };
 template <> struct Elem<_Float16> {
   typedef float Acc;
+  static constexpr int kDt = kPoolF16;
   static __device__ __forceinline__ float to_f(_Float16 v) { return static_cast<float>(v); }
   static __device__ __forceinline__ _Float16 from_f(float v) { return static_cast<_Float16>(v); }
   static __device__ __forceinline__ _Float16 lowest() { return static_cast<_Float16>(-65504.f); }
 };
 template <> struct Elem<__bf16> {
   typedef float Acc;
+  static constexpr int kDt = kPoolBf16;
   static __device__ __forceinline__ float to_f(__bf16 v) { return static_cast<float>(v); }
   static __device__ __forceinline__ __bf16 from_f(float v) { return static_cast<__bf16>(v); }
   static __device__ __forceinline__ __bf16 lowest() {
@@ -59,6 +63,7 @@ template <> struct Elem<__bf16> {
 };
 template <> struct Elem<int8_t> {
   typedef float Acc;
+  static constexpr int kDt = kPoolI8;
   static __device__ __forceinline__ float to_f(int8_t v) { return static_cast<float>(v); }
   static __device__ __forceinline__ int8_t from_f(float v) { return static_cast<int8_t>(v); }
   static __device__ __forceinline__ int8_t lowest() { return -128; }
@@ -179,10 +184,12 @@ int launch_pool(const PoolParams &p, hipStream_t s) {
   if (p.n_dst == 0) return 0;
   if (std::is_same<T, double>::value) count_f64(kF64Pool);     // (counted where the launch happens, like the others)
   if (p.C % V == 0) {
+    count_pool(OP, Elem<T>::kDt, false);
     const long long total = static_cast<long long>(p.n_dst) * (p.C / V);
     hipLaunchKernelGGL((pool_kernel<T, V, OP>), dim3(static_cast<unsigned>((total + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, s, p);
   } else {
+    count_pool(OP, Elem<T>::kDt, true);
     const long long total = static_cast<long long>(p.n_dst) * p.C;
     hipLaunchKernelGGL((pool_kernel<T, 1, OP>), dim3(static_cast<unsigned>((total + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, s, p);

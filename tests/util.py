@@ -84,7 +84,7 @@ def rel_err(a, ref):
     return float(np.abs(a - ref).max() / max(np.abs(ref).max(), 1e-12))
 
 
-HALF_ULP = {"float16": 2.0 ** -11, "bfloat16": 2.0 ** -8, "float32": 2.0 ** -24}
+HALF_ULP = {"float16": 2.0 ** -11, "bfloat16": 2.0 ** -8, "float32": 2.0 ** -24, "float64": 2.0 ** -53}
 
 
 def assert_close_abs_sum(a, ref, abs_sum, dtype, c=1e-6, name=""):
