@@ -27,15 +27,17 @@
 //   gather   the same tile walk backwards (dense -> rows): tiles without a live cell are skipped after a ballot on the
 //            map and read nothing; the rows are cleared first, so rows that own no cell come out as zeros.
 //   compact  from_dense: pass 1 flags the cells with a non-zero channel (to_sparse semantics: -0.0 is zero, NaN is
-//            not) and counts them per 256-cell block (ballot + mbcnt ranks, as rulebook.hip), one block scans the
-//            counts; the total is read back once; pass 2 writes the coordinates in ascending cell order, the rows,
+//            not) and counts them per 256-cell block (block_rank of scan.h), one block scans the
+//            counts (scan_kernel of scan.h); the total is read back once; pass 2 writes the coordinates in ascending cell order, the rows,
 //            and the cell map of the result.
 #include "common.h"
+#include "scan.h"
 
 namespace spx {
 namespace {
 
 constexpr int kBlock = 256;
+static_assert(kBlock == kScanThreads, "scan.h's primitives are written for this unit's workgroup size");
 constexpr int kTS = 256;          // cells of a channels-first tile
 constexpr int kChunkBytes = 64;   // bytes of channels of a channels-first tile
 
@@ -301,26 +303,6 @@ gather_cf_kernel(const typename UInt<E>::type *__restrict__ dense, const int32_t
 
 // -------------------------------------------------------------------------------------------- compaction
 
-// Exclusive rank of this thread among the threads of the block with pred set + the block total
-// (wave64 ballot + mbcnt; wave totals through LDS -- the block_rank of rulebook.hip)
-__device__ __forceinline__ int block_rank(bool pred, int &total, int *lds_wave /*[kBlock / 64]*/) {
-  const unsigned long long bal = __ballot(pred);
-  const int lane_rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(bal >> 32),
-                            __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bal), 0u));
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) lds_wave[wave] = __popcll(bal);
-  __syncthreads();
-  int prefix = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kBlock / 64; ++w) {
-    const int c = lds_wave[w];
-    if (w < wave) prefix += c;
-    total += c;
-  }
-  return prefix + lane_rank;
-}
-
 template <typename T> __device__ __forceinline__ bool piece_nonzero(T v, unsigned long long mask8) {
   return (v & static_cast<T>(mask8)) != 0;
 }
@@ -352,37 +334,6 @@ compact_flag_kernel(const T *__restrict__ dense, int pieces, long long cells, un
   int count;
   block_rank(on, count, lds_wave);
   if (threadIdx.x == 0) blockcount[blockIdx.x] = count;
-}
-
-// Exclusive scan of cnt[0 .. len) by one block; *total receives the sum.
-__global__ void __launch_bounds__(kBlock)
-compact_scan_kernel(const int32_t *__restrict__ cnt, int32_t *__restrict__ off, int len, int32_t *__restrict__ total) {
-  __shared__ int lds_wave[kBlock / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int carry = 0;
-  for (int base = 0; base < len; base += kBlock) {
-    const int idx = base + threadIdx.x;
-    const int v = idx < len ? cnt[idx] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += u;
-    }
-    __syncthreads();                      // (lds_wave of the previous round has been read)
-    if (lane == 63) lds_wave[wave] = incl;
-    __syncthreads();
-    int prefix = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-      const int s = lds_wave[w];
-      if (w < wave) prefix += s;
-      sum += s;
-    }
-    if (idx < len) off[idx] = carry + prefix + incl - v;
-    carry += sum;
-  }
-  if (threadIdx.x == 0) *total = carry;
 }
 
 // Pass 2: coordinates (ascending cell order), rows, and the cell map of the result.
@@ -653,7 +604,7 @@ int spx_from_dense_count(const void *dense, int C, int elem_bytes, int is_float,
                                      static_cast<const P *>(dense), row_bytes / static_cast<int>(sizeof(P)), g.cells,
                                      mask8, w.flags, w.blockcount));
   SPX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(spx::compact_scan_kernel, dim3(1), dim3(spx::kBlock), 0, s, w.blockcount, w.blockoff, w.nblk,
+  hipLaunchKernelGGL(spx::scan_kernel, dim3(1), dim3(spx::kBlock), 0, s, w.blockcount, w.blockoff, w.nblk,
                      w.total);
   SPX_LAUNCH_CHECK();
   SPX_HIP(hipMemcpyAsync(n_active_h, w.total, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -83,7 +83,7 @@ struct GemmParams {
 // rule: ops._LAYOUT_MIN_ROWS)
 constexpr int kAppBudget = 64;
 constexpr int kLayoutMinRows = 32768;
-// appendix geometry (the same arithmetic in spx_subm_layout_mcap, rulebook.hip)
+// appendix geometry (the same arithmetic in spx_subm_layout_mcap, rowsort.hip)
 __host__ __device__ inline int layout_mcap(int n) { return ((n / 4 + 63) & ~63) + 256; }
 // appendix workgroups that lead a launch of TM-row tiles: the class rule (4 M < n) bounds M by n / 4
 __host__ __device__ inline int layout_app_tiles(int n, int tm) { return (n / 4 + tm - 1) / tm; }

@@ -1,13 +1,17 @@
 // Row orders of a rulebook: stable LSD radix argsort (spx_mask_argsort: the reference's
-// sort_1d_by_key_allocator, all.py:935-991) and the copies of a pair table / its mask words in
-// that order (spx_permute_tables) which let a sorted tile read its tables as contiguous runs.
-// Nothing here influences results: a row order only changes which workgroup computes a row.
+// sort_1d_by_key_allocator, all.py:935-991), the copies of a pair table / its mask words in
+// that order (spx_permute_tables) which let a sorted tile read its tables as contiguous runs,
+// the rows of a level in coordinate-key order (spx_key_argsort) and the SubM rows layout
+// (spx_subm_layout).  A mask order or a rows layout never influences results: it only changes
+// which workgroup computes a row.
 #include "common.h"
+#include "scan.h"
 
 namespace spx {
 namespace {
 
 constexpr int kBlock = 256;
+static_assert(kBlock == kScanThreads, "scan.h's primitives are written for this unit's workgroup size");
 constexpr int kSortItems = 512;               // entries per block of a radix pass (>= 256 blocks at 128 k rows)
 
 // Digits of BITS = 8 or 9 bits, R = 2^BITS bins, R threads per workgroup.  Round 6: 9-bit digits where they save a
@@ -35,39 +39,7 @@ radix_count_kernel(const uint32_t *__restrict__ keys, int n, int shift, int nblk
   hist[static_cast<size_t>(threadIdx.x) * nblk + blockIdx.x] = lds_hist[threadIdx.x];
 }
 
-// one block per digit: exclusive scan of the digit's per-block counts, digit total to totals[digit]
-__global__ void __launch_bounds__(kBlock)
-radix_scan_kernel(const int32_t *__restrict__ hist, int32_t *__restrict__ off, int nblk,
-                       int32_t *__restrict__ totals) {
-  __shared__ int lds_wave[kBlock / 64];
-  const int32_t *c = hist + static_cast<size_t>(blockIdx.x) * nblk;
-  int32_t *o = off + static_cast<size_t>(blockIdx.x) * nblk;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int carry = 0;
-  for (int base = 0; base < nblk; base += kBlock) {
-    const int idx = base + threadIdx.x;
-    const int v = idx < nblk ? c[idx] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += u;
-    }
-    __syncthreads();
-    if (lane == 63) lds_wave[wave] = incl;
-    __syncthreads();
-    int prefix = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-      const int s = lds_wave[w];
-      if (w < wave) prefix += s;
-      total += s;
-    }
-    if (idx < nblk) o[idx] = carry + prefix + incl - v;
-    carry += total;
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
-}
+// (the per-digit exclusive scan of the counts between the two passes: scan_kernel of scan.h, one block per digit)
 
 // stable scatter of one pass; the base of a digit = (entries of smaller digits) + (entries of this
 // digit in earlier blocks); inside a T-entry group the rank among equal digits comes from a
@@ -466,6 +438,94 @@ permute_tables_kernel(const int32_t *__restrict__ pair, const uint32_t *__restri
   }
 }
 
+// ---------------------------------------------------------------- SubM row layout
+// The default row order of a SubM rulebook (include/spconv_amd.h, spx_subm_layout): the reference sorts the rows of
+// every rulebook by mask (SPCONV_DO_SORT, constants.py:121; ops.py:763-785 -> all.py:935-991); here the finished
+// masks are classified and, for a sparse rulebook, the rows WITH a neighbour move into a compact appendix -- bucket
+// 1 + j = rows whose lowest neighbour offset is j, a stable counting partition -- while the row-order walk keeps the
+// rows that only have their centre pair.  count -> scan (one block per bucket) -> scatter; ranks inside a block
+// come from wave ballots, every position is a function of the masks alone (no order-dependent atomics).  Nothing is
+// read back: class and count land in the blob, the gather-GEMM's appendix workgroups read them.
+constexpr int kLayBuckets = 33;       // centre-only + lowest neighbour offset 0 .. 31
+constexpr int kLayItems = 256;        // rows per block: one round (a 100 k-row rulebook must fill 256 CUs: 391 blocks)
+
+__device__ __forceinline__ int lay_bucket(uint32_t m, int centre) {
+  m &= ~(1u << centre);
+  return m ? 1 + __builtin_ctz(m) : 0;
+}
+
+__global__ void __launch_bounds__(kBlock)
+layout_count_kernel(const uint32_t *__restrict__ mask, int n, int kv, int nblk, int32_t *__restrict__ cnt) {
+  __shared__ int h[kLayBuckets];
+  if (threadIdx.x < kLayBuckets) h[threadIdx.x] = 0;
+  __syncthreads();
+  const int centre = kv / 2, begin = blockIdx.x * kLayItems;
+#pragma unroll
+  for (int it = 0; it < kLayItems / kBlock; ++it) {
+    const int i = begin + it * kBlock + threadIdx.x;
+    if (i < n) atomicAdd(&h[lay_bucket(mask[i], centre)], 1);      // (counts: the order of the adds is immaterial)
+  }
+  __syncthreads();
+  if (threadIdx.x < kLayBuckets) cnt[static_cast<size_t>(threadIdx.x) * nblk + blockIdx.x] = h[threadIdx.x];
+}
+
+__global__ void __launch_bounds__(kBlock)
+layout_scatter_kernel(const int32_t *__restrict__ pair, const uint32_t *__restrict__ mask, int n, int kv, int nblk,
+                      const int32_t *__restrict__ off, const int32_t *__restrict__ totals,
+                      int32_t *__restrict__ blob, int npad, int mcap) {
+  __shared__ int base[kLayBuckets];              // first appendix position of (bucket, this block); bucket 0 unused
+  __shared__ int wcnt[kBlock / 64][kLayBuckets]; // rows of a bucket per wave
+  const int centre = kv / 2;
+  const int heavy = n - totals[0];
+  const int cls = (heavy > 0 && 4ll * heavy < n) ? 1 : 0;
+  uint32_t *mask_main = reinterpret_cast<uint32_t *>(blob + SPX_LAYOUT_HEADER);
+  int32_t *order = blob + SPX_LAYOUT_HEADER + npad;
+  uint32_t *mask_app = reinterpret_cast<uint32_t *>(order + mcap);
+  int32_t *pair_app = order + 2 * static_cast<size_t>(mcap);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    blob[0] = cls;
+    blob[1] = heavy;
+    blob[2] = n;
+    blob[3] = kv;
+    blob[4] = mcap;
+  }
+  const int i = blockIdx.x * kLayItems + threadIdx.x;
+  const bool ok = i < n;
+  const uint32_t m = ok ? mask[i] : 0u;
+  const int b = ok ? lay_bucket(m, centre) : -1;
+  // the row-order walk keeps every row of a dense rulebook, and the centre-only rows of a sparse one
+  if (ok) mask_main[i] = (cls && b > 0) ? 0u : m;
+  if (!cls) return;
+  if (threadIdx.x < kLayBuckets) {
+    int s = 0;
+    for (int j = 1; j < static_cast<int>(threadIdx.x); ++j) s += totals[j];
+    base[threadIdx.x] = s + off[static_cast<size_t>(threadIdx.x) * nblk + blockIdx.x];
+  }
+  for (int j = threadIdx.x; j < (kBlock / 64) * kLayBuckets; j += kBlock) (&wcnt[0][0])[j] = 0;
+  __syncthreads();
+  // rank of a row with a neighbour among the rows of its bucket in this wave: one ballot per DISTINCT bucket present
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool hv = ok && b > 0;
+  int rank = 0;
+  unsigned long long todo = __ballot(hv);
+  while (todo) {
+    const int leader = __builtin_ctzll(todo);
+    const int lb = __builtin_amdgcn_readlane(b, leader);
+    const unsigned long long same = __ballot(hv && b == lb);
+    if (b == lb) rank = __popcll(same & ((1ull << lane) - 1ull));
+    if (lane == leader) wcnt[wave][lb] = __popcll(same);
+    todo &= ~same;
+  }
+  __syncthreads();
+  if (hv) {
+    int pos = base[b] + rank;
+    for (int w = 0; w < wave; ++w) pos += wcnt[w][b];
+    order[pos] = i;
+    mask_app[pos] = m;
+    for (int k = 0; k < kv; ++k) pair_app[static_cast<size_t>(k) * mcap + pos] = pair[static_cast<size_t>(k) * n + i];
+  }
+}
+
 }  // namespace
 
 size_t radix_argsort_ws_bytes(int n_in) {
@@ -481,7 +541,7 @@ void radix_pass(const uint32_t *kin, const int32_t *vin, int n, int shift, int n
                 int32_t *totals, uint32_t *kout, int32_t *vout, hipStream_t s) {
   constexpr int R = 1 << BITS;
   hipLaunchKernelGGL(radix_count_kernel<BITS>, dim3(nblk), dim3(R), 0, s, kin, n, shift, nblk, hist);
-  hipLaunchKernelGGL(radix_scan_kernel, dim3(R), dim3(kBlock), 0, s, hist, hist_off, nblk, totals);
+  hipLaunchKernelGGL(scan_kernel, dim3(R), dim3(kBlock), 0, s, hist, hist_off, nblk, totals);
   hipLaunchKernelGGL(radix_scatter_kernel<BITS>, dim3(nblk), dim3(R), 0, s, kin, vin, n, shift, nblk, hist_off, totals,
                      kout, vout);
 }
@@ -572,7 +632,7 @@ int key_argsort(const int32_t *indices, int n, int ndim, int batch_size, const i
   // pass 0 makes the keys while it counts (and clears the flag)
   hipLaunchKernelGGL(key_count_kernel, dim3(nblk), dim3(512), 0, s, indices, n, g, sh, nblk, k0, hist, violation,
                      static_cast<uint4 *>(rankmap), zero_units);
-  hipLaunchKernelGGL(radix_scan_kernel, dim3(512), dim3(kBlock), 0, s, hist, hist_off, nblk, totals);
+  hipLaunchKernelGGL(scan_kernel, dim3(512), dim3(kBlock), 0, s, hist, hist_off, nblk, totals);
   hipLaunchKernelGGL(radix_scatter_kernel<9>, dim3(nblk), dim3(512), 0, s, k0, static_cast<const int32_t *>(nullptr), n,
                      sh, nblk, hist_off, totals, kA, vA);
   const uint32_t *kin = kA;
@@ -611,6 +671,62 @@ int spx_permute_tables(const int32_t *pair, const uint32_t *mask, const int32_t 
   if (n == 0) return 0;
   hipLaunchKernelGGL(permute_tables_kernel, dim3(div_up(n, kBlock), kv + 1), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), pair, mask, order, kv, n, words, pair_t, mask_t);
+  SPX_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t spx_mask_argsort_ws_bytes(int n) { return radix_argsort_ws_bytes(n) + 256; }
+
+int spx_mask_argsort(const uint32_t *mask, int n, int words, int32_t *argsort, void *ws,
+                     size_t ws_bytes, spx_stream_t stream) {
+  SPX_CHECK(words == 1, "mask_argsort supports kernel volume <= 32 (words == 1), got %d", words);
+  SPX_CHECK(ws_bytes >= spx_mask_argsort_ws_bytes(n), "workspace too small");
+  if (n == 0) return 0;
+  // stable argsort of the mask words (all.py:935-991 sorts the same keys with thrust)
+  return radix_argsort(mask, n, 32, argsort, ws, static_cast<hipStream_t>(stream));
+}
+
+int spx_mask_argsort_kv(const uint32_t *mask, int n, int kv, int32_t *argsort, void *ws, size_t ws_bytes,
+                        spx_stream_t stream) {
+  SPX_CHECK(kv >= 1 && kv <= 32, "mask_argsort supports kernel volume <= 32, got %d", kv);
+  SPX_CHECK(ws_bytes >= spx_mask_argsort_ws_bytes(n), "workspace too small");
+  if (n == 0) return 0;
+  // the mask words of a kernel volume kv carry kv bits: 27 bits are three 9-bit passes instead of four 8-bit ones
+  return radix_argsort(mask, n, kv, argsort, ws, static_cast<hipStream_t>(stream));
+}
+
+size_t spx_subm_layout_mcap(int n) {
+  const size_t nn = n > 0 ? n : 1;
+  return ((nn / 4 + 63) & ~static_cast<size_t>(63)) + 256;
+}
+
+size_t spx_subm_layout_bytes(int n, int kv) {
+  const size_t nn = n > 0 ? n : 1, npad = (nn + 63) & ~static_cast<size_t>(63), mcap = spx_subm_layout_mcap(n);
+  return (SPX_LAYOUT_HEADER + npad + (2 + static_cast<size_t>(kv)) * mcap) * sizeof(int32_t);
+}
+
+size_t spx_subm_layout_ws_bytes(int n) {
+  const size_t nblk = div_up(n > 0 ? n : 1, kLayItems);
+  return 2 * align_up(static_cast<size_t>(kLayBuckets) * nblk * sizeof(int32_t), 256) + 256;
+}
+
+int spx_subm_layout(const int32_t *pair_fwd, const uint32_t *mask, int n, int kv, int32_t *layout, void *ws,
+                    size_t ws_bytes, spx_stream_t stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SPX_CHECK(kv >= 1 && kv <= 32, "a rows layout needs a kernel volume <= 32 (one mask word), got %d", kv);
+  if (n <= 0) return 0;
+  SPX_CHECK(pair_fwd && mask && layout && ws, "null pointer");
+  SPX_CHECK(ws_bytes >= spx_subm_layout_ws_bytes(n), "workspace too small");
+  const int nblk = div_up(n, kLayItems);
+  const int npad = (n + 63) & ~63;
+  Carver cv(ws);
+  int32_t *cnt = cv.take<int32_t>(static_cast<size_t>(kLayBuckets) * nblk);
+  int32_t *off = cv.take<int32_t>(static_cast<size_t>(kLayBuckets) * nblk);
+  int32_t *totals = cv.take<int32_t>(64);
+  hipLaunchKernelGGL(layout_count_kernel, dim3(nblk), dim3(kBlock), 0, s, mask, n, kv, nblk, cnt);
+  hipLaunchKernelGGL(scan_kernel, dim3(kLayBuckets), dim3(kBlock), 0, s, cnt, off, nblk, totals);
+  hipLaunchKernelGGL(layout_scatter_kernel, dim3(nblk), dim3(kBlock), 0, s, pair_fwd, mask, n, kv, nblk, off,
+                     totals, layout, npad, static_cast<int>(spx_subm_layout_mcap(n)));
   SPX_LAUNCH_CHECK();
   return 0;
 }

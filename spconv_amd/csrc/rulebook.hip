@@ -1,12 +1,15 @@
-// Rulebook ("indice pair") builder for gfx950.
+// Rulebook ("indice pair") builders for gfx950, and the conversions between their two list forms:
+//   SubM        spx_subm_rulebook (hash table), spx_subm_rulebook_ranked (over a level's rank map)
+//   first-seen  spx_conv_rulebook_count / _fill / _static: regular and transposed convolution, outputs numbered in
+//               the reference's first-seen order (conv_*, the compact-candidate passes conv3_*, the ratio cache)
+//   sorted      spx_conv_rulebook_*_sorted, spx_rankmap_from_sorted: outputs numbered by key rank (conv4_*)
+//   lists       Native-list compaction, spx_native_to_table / spx_table_to_native
+// What used to live here besides them: the voxeliser is voxelize.hip, the user hash table hash.hip, the rows layout
+// and the mask argsort's entry points rowsort.hip; the hash table the builders share is table.h, the block scan and
+// rank scan.h, the range fills fill.h, the rank map rankmap.h.
 //
 // Design (MI355X-first, not a translation of the reference kernels):
-//  * one open-addressing hash table in global memory.  Whenever the key space (batch x grid
-//    volume) fits 32 bits -- every configuration in BASELINE.json does -- a slot is ONE 64-bit
-//    word {key32 : value32}: an insert is a single atomicCAS (plus an atomicMin only when a
-//    duplicate key has to lower the value) and a probe is a single 8-byte load.  Larger key
-//    spaces use separate int64 key / int32 value arrays.  At 2x load headroom the packed table
-//    is 2 MB per 100k voxels and stays in the 4 MiB XCD-local L2;
+//  * one open-addressing hash table in global memory (table.h);
 //  * NO order-dependent atomics anywhere: duplicate keys are resolved with
 //    atomicMin (smallest index wins == the CPU path's unordered_map::insert),
 //    the dense tables are written by the thread that owns the row (coalesced
@@ -20,6 +23,8 @@
 #include "common.h"
 #include "fill.h"
 #include "rankmap.h"
+#include "scan.h"
+#include "table.h"
 
 #include <algorithm>
 #include <mutex>
@@ -30,180 +35,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kItems = 2048;  // entries per block in count/scatter passes (8 x 256)
-typedef long long hkey_t;      // EMPTY == -1
-
-struct Table {
-  hkey_t *keys;    // wide: keys[cap].  packed: slots[cap], slot = (key32 << 32) | value32
-  int32_t *vals;   // wide: vals[cap].  packed: the low halves of the slots (stride 2)
-  uint32_t mask;   // capacity - 1 (capacity is a power of two)
-  int packed;      // 1 when every key fits 32 bits
-  int gbits;       // low key bits that pick the slot inside a group of 2^gbits slots (see hash_key)
-  uint32_t max_probe;  // longest probe walk (slots - 1).  A table sized for the guaranteed bound is never more than
-                       // half full and walks a handful of slots; a table sized for the outputs EXPECTED
-                       // (table_shrink: static bound / last ratio) can fill up, and without a cap every insert and
-                       // lookup of a key that no longer fits would walk all of it -- O(capacity) per candidate.
-                       // Inserts and lookups share the cap, so a key that went in is found; one that did not fit
-                       // raises the overflow flag of its pass (the count's read-back / the static form's counter).
-};
-constexpr uint32_t kMaxProbeShrunk = 2047;
-
-constexpr unsigned long long kEmptySlot = ~0ull;
-
-// Home slot of a key: the murmur3 finaliser of key >> gbits picks a group of 2^gbits slots, the low key
-// bits the slot inside it (gbits = 3: 8 consecutive cells along the last spatial dimension share one
-// 64-byte line of the table).  Measured and left at gbits = 0 everywhere: on the half-full SubM tables
-// groups that are either empty or full turn every collision into a walk across a full group (fixture
-// rulebook 78 -> 139 us); on the 4-8 % full regular-conv tables the lookups get 5-12 % faster
-// (conv_count_first 8.5 -> 7.5, conv_assign 19.6 -> 18.0 us) but the inserts of neighbouring threads
-// now contend for the same lines (conv_stage1 22.6 -> 30.6 us).  Results never depend on the slot.
-__device__ __forceinline__ uint32_t hash_key(hkey_t k, int gbits) {
-  // murmur3 fmix64
-  unsigned long long x = static_cast<unsigned long long>(k) >> gbits;
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdULL;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ULL;
-  x ^= x >> 33;
-  return (static_cast<uint32_t>(x) << gbits) | (static_cast<uint32_t>(k) & ((1u << gbits) - 1u));
-}
-
-__device__ __forceinline__ uint32_t hash_key32(uint32_t k, int gbits) {
-  // murmur3 fmix32
-  uint32_t x = k >> gbits;
-  x ^= x >> 16;
-  x *= 0x85ebca6bu;
-  x ^= x >> 13;
-  x *= 0xc2b2ae35u;
-  x ^= x >> 16;
-  return (x << gbits) | (k & ((1u << gbits) - 1u));
-}
-
-// Value stored in a slot returned by table_insert_min.
-__device__ __forceinline__ int32_t table_val(const Table &t, int slot) {
-  return t.vals[static_cast<size_t>(slot) << t.packed];
-}
-
-// Inserts key (if absent) and lowers its value to min(value, val). Returns the slot.
-template <bool LOOK = false>
-__device__ __forceinline__ int table_insert_min(const Table &t, hkey_t key, int32_t val) {
-  if (t.packed) {
-    unsigned long long *slots = reinterpret_cast<unsigned long long *>(t.keys);
-    const uint32_t k32 = static_cast<uint32_t>(key);
-    const unsigned long long want =
-        (static_cast<unsigned long long>(k32) << 32) | static_cast<uint32_t>(val);
-    uint32_t slot = hash_key32(k32, t.gbits) & t.mask;
-    for (uint32_t probe = 0; probe <= t.max_probe; ++probe) {  // bounded: the table is never full (or capped)
-      // look before the atomic: a slot only ever goes empty -> key, and its value only decreases, so a
-      // (possibly stale) plain read that shows our key with a value <= ours, or another key, is final --
-      // several inputs reach the same output on dense scenes, and all but the winner leave here
-      // (LOOK: regular-conv builders; SubM keys are distinct, there the read would only add latency)
-      unsigned long long cur = LOOK ? slots[slot] : kEmptySlot;
-      if (cur == kEmptySlot) {
-        cur = atomicCAS(&slots[slot], kEmptySlot, want);
-        if (cur == kEmptySlot) return static_cast<int>(slot);
-      }
-      if (static_cast<uint32_t>(cur >> 32) == k32) {
-        if (static_cast<uint32_t>(cur) > static_cast<uint32_t>(val)) atomicMin(&slots[slot], want);
-        return static_cast<int>(slot);
-      }
-      slot = (slot + (1u << t.gbits)) & t.mask;      // (stays in its in-line position, see hash_key)
-    }
-    return -1;
-  }
-  uint32_t slot = hash_key(key, t.gbits) & t.mask;
-  for (uint32_t probe = 0; probe <= t.max_probe; ++probe) {
-    unsigned long long prev = LOOK ? static_cast<unsigned long long>(t.keys[slot])     // (as above)
-                                   : static_cast<unsigned long long>(-1LL);
-    if (prev == static_cast<unsigned long long>(-1LL))
-      prev = atomicCAS(reinterpret_cast<unsigned long long *>(&t.keys[slot]),
-                       static_cast<unsigned long long>(-1LL), static_cast<unsigned long long>(key));
-    if (prev == static_cast<unsigned long long>(-1LL) ||
-        prev == static_cast<unsigned long long>(key)) {
-      // values start as 0xFFFFFFFF (one memset with the keys): unsigned min
-      if (!LOOK || static_cast<unsigned int>(t.vals[slot]) > static_cast<unsigned int>(val))
-        atomicMin(reinterpret_cast<unsigned int *>(&t.vals[slot]), static_cast<unsigned int>(val));
-      return static_cast<int>(slot);
-    }
-    slot = (slot + (1u << t.gbits)) & t.mask;
-  }
-  return -1;
-}
-
-// Home slot of a key.
-__device__ __forceinline__ uint32_t table_home(const Table &t, hkey_t key) {
-  return (t.packed ? hash_key32(static_cast<uint32_t>(key), t.gbits) : hash_key(key, t.gbits)) & t.mask;
-}
-
-// Value of key, or -1 when absent (values are row indices / positions, never negative): the walk from `slot`,
-// `probe` slots into it.
-__device__ __forceinline__ int32_t table_find_from(const Table &t, hkey_t key, uint32_t slot, uint32_t probe) {
-  if (t.packed) {
-    const unsigned long long *slots = reinterpret_cast<const unsigned long long *>(t.keys);
-    const uint32_t k32 = static_cast<uint32_t>(key);
-    for (; probe <= t.max_probe; ++probe) {
-      const unsigned long long v = slots[slot];
-      if (static_cast<uint32_t>(v >> 32) == k32 && v != kEmptySlot) return static_cast<int32_t>(v);
-      if (v == kEmptySlot) return -1;
-      slot = (slot + (1u << t.gbits)) & t.mask;
-    }
-    return -1;
-  }
-  for (; probe <= t.max_probe; ++probe) {
-    const hkey_t k = t.keys[slot];
-    if (k == key) return t.vals[slot];
-    if (k == -1LL) return -1;
-    slot = (slot + (1u << t.gbits)) & t.mask;
-  }
-  return -1;
-}
-
-__device__ __forceinline__ int32_t table_find(const Table &t, hkey_t key) {
-  return table_find_from(t, key, table_home(t, key), 0u);
-}
-
-// Reads one index row (batch, coords...) into canonical 4-d form.
-__device__ __forceinline__ void read_row(const int32_t *indices, int i, int ndim, int &b,
-                                         int (&c)[4]) {
-  if (ndim == 3) {
-    const int4 v = reinterpret_cast<const int4 *>(indices)[i];
-    b = v.x;
-    c[0] = 0;
-    c[1] = v.y;
-    c[2] = v.z;
-    c[3] = v.w;
-  } else {
-    const int32_t *row = indices + static_cast<size_t>(i) * (ndim + 1);
-    b = row[0];
-    const int lead = 4 - ndim;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) c[d] = (d < lead) ? 0 : row[1 + d - lead];
-  }
-}
-
-__device__ __forceinline__ hkey_t layout_key(int b, const int (&c)[4], const int (&dims)[4]) {
-  hkey_t v = b;
-#pragma unroll
-  for (int d = 0; d < 4; ++d) v = v * dims[d] + c[d];
-  return v;
-}
-
-__device__ __forceinline__ void decode_offset(int k, const int (&ksize)[4], int (&r)[4]) {
-#pragma unroll
-  for (int d = 3; d >= 0; --d) {
-    r[d] = k % ksize[d];
-    k /= ksize[d];
-  }
-}
-
-__device__ __forceinline__ bool in_range(const int (&c)[4], const int (&dims)[4]) {
-  bool ok = true;
-#pragma unroll
-  for (int d = 0; d < 4; ++d) ok = ok && c[d] >= 0 && c[d] < dims[d];
-  return ok;
-}
-
-// (FillList, every "memset" of a build in one launch: fill.h)
-void table_fill(FillList &f, const Table &t);
+static_assert(kBlock == kScanThreads, "scan.h's primitives are written for this unit's workgroup size");
 
 // ---------------------------------------------------------------- SubM
 
@@ -460,101 +292,6 @@ subm_probe5_kernel(const int32_t *__restrict__ indices, int n, Geom g, Table t,
       groupcount[static_cast<size_t>(l) * ngroups + blockIdx.x] =
           lds_cnt[l * 4] + lds_cnt[l * 4 + 1] + lds_cnt[l * 4 + 2] + lds_cnt[l * 4 + 3];
   }
-}
-
-// ------------------------------------------------- block-level primitives
-
-// Exclusive rank of this thread among the threads of the block with pred set,
-// plus the block total.  wave64 ballot + mbcnt; wave totals through LDS.
-__device__ __forceinline__ int block_rank(bool pred, int &total, int *lds_wave /*[4]*/) {
-  const unsigned long long bal = __ballot(pred);
-  const int lane_rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(bal >> 32),
-                            __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bal), 0u));
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();  // protect lds_wave reuse across calls
-  if ((threadIdx.x & 63) == 0) lds_wave[wave] = __popcll(bal);
-  __syncthreads();
-  int prefix = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kBlock / 64; ++w) {
-    const int c = lds_wave[w];
-    if (w < wave) prefix += c;
-    total += c;
-  }
-  return prefix + lane_rank;
-}
-
-// seq-wise exclusive scan of `cnt` (length len per sequence), one block per
-// sequence; totals[seq] receives the sequence sum.
-constexpr int kScanPer = 32;          // items per thread of the one-pass form
-__global__ void __launch_bounds__(kBlock)
-scan_kernel(const int32_t *__restrict__ cnt, int32_t *__restrict__ off, int len,
-            int32_t *__restrict__ totals) {
-  __shared__ int lds_wave[kBlock / 64];
-  const int seq = blockIdx.x;
-  const int32_t *c = cnt + static_cast<size_t>(seq) * len;
-  int32_t *o = off + static_cast<size_t>(seq) * len;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (len <= kBlock * kScanPer) {
-    // one pass: every thread owns `per` consecutive items (all loads in flight together), one block
-    // scan of the thread sums -- the loop below pays a load -> barrier -> store round per 256 items
-    const int per = (len + kBlock - 1) / kBlock, base = threadIdx.x * per;
-    int v[kScanPer];
-    int sum = 0;
-#pragma unroll
-    for (int e = 0; e < kScanPer; ++e) {
-      v[e] = (e < per && base + e < len) ? c[base + e] : 0;
-      sum += v[e];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += u;
-    }
-    if (lane == 63) lds_wave[wave] = incl;
-    __syncthreads();
-    int prefix = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-      const int x = lds_wave[w];
-      if (w < wave) prefix += x;
-      total += x;
-    }
-    int run = prefix + incl - sum;
-#pragma unroll
-    for (int e = 0; e < kScanPer; ++e) {
-      if (e < per && base + e < len) o[base + e] = run;
-      run += v[e];
-    }
-    if (threadIdx.x == 0 && totals) totals[seq] = total;
-    return;
-  }
-  int carry = 0;
-  for (int base = 0; base < len; base += kBlock) {
-    const int idx = base + threadIdx.x;
-    const int v = idx < len ? c[idx] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += u;
-    }
-    __syncthreads();
-    if (lane == 63) lds_wave[wave] = incl;
-    __syncthreads();
-    int prefix = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-      const int s = lds_wave[w];
-      if (w < wave) prefix += s;
-      total += s;
-    }
-    if (idx < len) o[idx] = carry + prefix + incl - v;
-    carry += total;
-  }
-  if (threadIdx.x == 0 && totals) totals[seq] = carry;
 }
 
 // ------------------------------------------- Native-list compaction (a4/a5)
@@ -1511,81 +1248,6 @@ mask_from_tables_kernel(const int32_t *__restrict__ ta, int n_a, uint32_t *__res
   }
 }
 
-// ------------------------------------------------------- mask argsort (a9)
-// Stable LSD radix sort of (mask word, row) with 8-bit digits built from the
-// same count -> scan -> scatter primitives.  words == 1 only (kv <= 32).
-constexpr int kRadixBits = 8;
-constexpr int kRadix = 1 << kRadixBits;
-
-__global__ void __launch_bounds__(kBlock)
-radix_count_kernel(const uint32_t *__restrict__ keys, int n, int shift, int nblk,
-                   int32_t *__restrict__ hist /*[kRadix][nblk]*/) {
-  __shared__ int lds_hist[kRadix];
-  for (int d = threadIdx.x; d < kRadix; d += kBlock) lds_hist[d] = 0;
-  __syncthreads();
-  const int begin = blockIdx.x * kItems;
-  for (int it = 0; it < kItems / kBlock; ++it) {
-    const int e = begin + it * kBlock + threadIdx.x;
-    if (e < n) atomicAdd(&lds_hist[(keys[e] >> shift) & (kRadix - 1)], 1);
-  }
-  __syncthreads();
-  for (int d = threadIdx.x; d < kRadix; d += kBlock)
-    hist[static_cast<size_t>(d) * nblk + blockIdx.x] = lds_hist[d];
-}
-
-// Stable scatter: processes the block's entries in order, 256 at a time; the
-// rank of an entry among equal digits inside the 256-entry tile comes from a
-// per-digit match over wave ballots.
-__global__ void __launch_bounds__(kBlock)
-radix_scatter_kernel(const uint32_t *__restrict__ keys_in, const int32_t *__restrict__ vals_in,
-                     int n, int shift, int nblk, const int32_t *__restrict__ hist_off,
-                     uint32_t *__restrict__ keys_out, int32_t *__restrict__ vals_out) {
-  __shared__ int lds_base[kRadix];                 // running output offset per digit
-  __shared__ int lds_cnt[kBlock / 64][kRadix];     // per-wave digit counts of this tile
-  for (int d = threadIdx.x; d < kRadix; d += kBlock)
-    lds_base[d] = hist_off[static_cast<size_t>(d) * nblk + blockIdx.x];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int begin = blockIdx.x * kItems;
-  for (int it = 0; it < kItems / kBlock; ++it) {
-    for (int d = threadIdx.x; d < kRadix; d += kBlock)
-#pragma unroll
-      for (int w = 0; w < kBlock / 64; ++w) lds_cnt[w][d] = 0;
-    __syncthreads();
-    const int e = begin + it * kBlock + threadIdx.x;
-    const bool valid = e < n;
-    const uint32_t key = valid ? keys_in[e] : 0u;
-    const int val = (valid && vals_in) ? vals_in[e] : e;
-    const int digit = valid ? static_cast<int>((key >> shift) & (kRadix - 1)) : -1;
-    // lanes of this wave holding the same digit (bitwise match over 8 ballots)
-    unsigned long long same = __ballot(valid);
-#pragma unroll
-    for (int bit = 0; bit < kRadixBits; ++bit) {
-      const unsigned long long bal = __ballot((digit >> bit) & 1);
-      same &= ((digit >> bit) & 1) ? bal : ~bal;
-    }
-    const int rank_in_wave = __popcll(same & ((1ull << lane) - 1ull));
-    if (valid && rank_in_wave == 0) lds_cnt[wave][digit] = __popcll(same);
-    __syncthreads();
-    if (valid) {
-      int prior = 0;
-#pragma unroll
-      for (int w = 0; w < kBlock / 64; ++w)
-        if (w < wave) prior += lds_cnt[w][digit];
-      const int dst = lds_base[digit] + prior + rank_in_wave;
-      keys_out[dst] = key;
-      vals_out[dst] = val;
-    }
-    __syncthreads();
-    for (int d = threadIdx.x; d < kRadix; d += kBlock) {
-      int s = 0;
-#pragma unroll
-      for (int w = 0; w < kBlock / 64; ++w) s += lds_cnt[w][d];
-      lds_base[d] += s;
-    }
-    __syncthreads();
-  }
-}
-
 // Dense table from ConvAlgo.Native lists (for callers that only hold the lists):
 // table[k][dst_j] = src_j for j < count(k).  count(): SubM mirror rule (ops.py:962-968).
 __global__ void __launch_bounds__(kBlock)
@@ -1605,59 +1267,6 @@ native_to_table_kernel(const int32_t *__restrict__ native, const int32_t *__rest
   const int in_idx = native[e], out_idx = native[plane + e];
   const int src = inverse ? out_idx : in_idx, dst = inverse ? in_idx : out_idx;
   table[static_cast<size_t>(k) * n_dst + dst] = src;
-}
-
-uint32_t table_capacity(size_t entries) {
-  size_t cap = 256;
-  while (cap < 2 * entries) cap <<= 1;
-  return static_cast<uint32_t>(cap);
-}
-
-// True when every key of a (batch, dims[0..3]) layout is below 0xFFFFFFFF: the table then keeps
-// key and value in one 64-bit slot.
-bool keys_fit_u32(long long batch, const int *dims, int ndims) {
-  unsigned long long v = batch > 0 ? static_cast<unsigned long long>(batch) : 1ull;
-  for (int d = 0; d < ndims; ++d) {
-    const unsigned long long e = dims[d] > 0 ? static_cast<unsigned long long>(dims[d]) : 1ull;
-    if (v > 0xFFFFFFFFull / e) return false;
-    v *= e;
-  }
-  return v <= 0xFFFFFFFFull;   // largest key is v - 1 <= 0xFFFFFFFE
-}
-
-// Places a table of `cap` slots at `mem` (room for the wide form: 12 bytes per slot).
-void table_place(Table &t, hkey_t *keys, int32_t *vals, uint32_t cap, bool packed, int gbits = 0) {
-  t.keys = keys;
-  t.vals = packed ? reinterpret_cast<int32_t *>(keys) : vals;
-  t.mask = cap - 1;
-  t.packed = packed ? 1 : 0;
-  t.gbits = gbits;
-  t.max_probe = t.mask;
-}
-
-// The same storage as a smaller table (capacity a power of two below the placed one).
-void table_shrink(Table &t, uint32_t cap) {
-  if (!t.packed) t.vals = reinterpret_cast<int32_t *>(t.keys + cap);
-  t.mask = cap - 1;
-  t.max_probe = t.mask < kMaxProbeShrunk ? t.mask : kMaxProbeShrunk;
-}
-
-// The table's bytes as a 0xFF range of a FillList (see table_clear).
-void table_fill(FillList &f, const Table &t) {
-  const size_t cap = static_cast<size_t>(t.mask) + 1;
-  const size_t bytes = t.packed ? cap * sizeof(unsigned long long)
-                                : static_cast<size_t>(reinterpret_cast<char *>(t.vals + cap) -
-                                                      reinterpret_cast<char *>(t.keys));
-  f.add(t.keys, bytes, 0xFFFFFFFFu);
-}
-
-// Empties the table: every byte 0xFF (keys -1, values 0xFFFFFFFF, packed slots ~0).
-hipError_t table_clear(const Table &t, hipStream_t s) {
-  const size_t cap = static_cast<size_t>(t.mask) + 1;
-  const size_t bytes = t.packed ? cap * sizeof(unsigned long long)
-                                : static_cast<size_t>(reinterpret_cast<char *>(t.vals + cap) -
-                                                      reinterpret_cast<char *>(t.keys));
-  return hipMemsetAsync(t.keys, 0xFF, bytes, s);
 }
 
 int gcd_int(int a, int b) {
@@ -1783,482 +1392,12 @@ int launch_native_lists(const int32_t *table, int mode, int kv, int n, int nlist
   return 0;
 }
 
-// ------------------------------------------------------------- point -> voxel
-// Voxeliser.  Deterministic and identical to the reference's CPU loop
-// (csrc/sparse/pointops.py Point2VoxelCPU::point_to_voxel, lines 135-172 of the class): voxels
-// are numbered in first-seen point order, a voxel keeps its first max_points points in point
-// order, voxels past max_voxels are dropped.  Same building blocks as the rulebook: hash with
-// atomicMin (first point of a voxel), count -> scan -> assign (numbering), stable radix sort by
-// voxel id (slot of a point inside its voxel), no order-dependent atomics.
-struct P2VGeom {
-  int ndim;
-  float vsize[4], lo[4];
-  int grid[4];
-};
-
-__device__ __forceinline__ bool p2v_coor(const float *__restrict__ pt, const P2VGeom &g, int (&c)[4]) {
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (j < g.ndim) {
-      // zyx order: coordinate j comes from point column ndim-1-j (pointops.py:107,138)
-      const float v = floorf((pt[g.ndim - 1 - j] - g.lo[j]) / g.vsize[j]);
-      const int ci = static_cast<int>(v);
-      ok = ok && !(v < 0.f) && v < static_cast<float>(g.grid[j]);
-      c[j] = ci;
-    } else {
-      c[j] = 0;
-    }
-  }
-  return ok;
-}
-
-__global__ void __launch_bounds__(kBlock)
-p2v_insert_kernel(const float *__restrict__ pts, int n, int nfeat, P2VGeom g, Table t,
-                  int32_t *__restrict__ slot_of) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  int c[4];
-  int slot = -1;
-  if (p2v_coor(pts + static_cast<size_t>(i) * nfeat, g, c)) {
-    hkey_t key = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < g.ndim) key = key * g.grid[j] + c[j];
-    slot = table_insert_min(t, key, i);
-  }
-  slot_of[i] = slot;
-}
-
-__global__ void __launch_bounds__(kBlock)
-p2v_count_first_kernel(const int32_t *__restrict__ slot_of, Table t, int n,
-                       int32_t *__restrict__ blockcount) {
-  __shared__ int lds_wave[kBlock / 64];
-  const int begin = blockIdx.x * kItems;
-  int cnt = 0;
-#pragma unroll
-  for (int it = 0; it < kItems / kBlock; ++it) {
-    const int e = begin + it * kBlock + threadIdx.x;
-    const int slot = e < n ? slot_of[e] : -1;
-    cnt += __popcll(__ballot(slot >= 0 && table_val(t, slot) == e));
-  }
-  if ((threadIdx.x & 63) == 0) lds_wave[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int sum = 0;
-    for (int w = 0; w < kBlock / 64; ++w) sum += lds_wave[w];
-    blockcount[blockIdx.x] = sum;
-  }
-}
-
-__global__ void __launch_bounds__(kBlock)
-p2v_assign_kernel(const float *__restrict__ pts, int n, int nfeat, P2VGeom g,
-                  const int32_t *__restrict__ slot_of, Table t,
-                  const int32_t *__restrict__ blockoff, int max_voxels,
-                  int32_t *__restrict__ slot_vid, int32_t *__restrict__ indices) {
-  __shared__ int lds_wave[kBlock / 64];
-  const int begin = blockIdx.x * kItems;
-  int running = blockoff[blockIdx.x];
-  for (int it = 0; it < kItems / kBlock; ++it) {
-    const int e = begin + it * kBlock + threadIdx.x;
-    const int slot = e < n ? slot_of[e] : -1;
-    const bool first = slot >= 0 && table_val(t, slot) == e;
-    int total;
-    const int rank = block_rank(first, total, lds_wave);
-    if (first) {
-      const int vid = running + rank;
-      if (vid < max_voxels) {
-        slot_vid[slot] = vid;
-        int c[4];
-        p2v_coor(pts + static_cast<size_t>(e) * nfeat, g, c);
-        for (int j = 0; j < g.ndim; ++j) indices[static_cast<size_t>(vid) * g.ndim + j] = c[j];
-      }
-    }
-    running += total;
-  }
-}
-
-__global__ void __launch_bounds__(kBlock)
-p2v_point_vid_kernel(const int32_t *__restrict__ slot_of, const int32_t *__restrict__ slot_vid, int n,
-                     long long *__restrict__ pc_voxel_id, uint32_t *__restrict__ key32) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const int slot = slot_of[i];
-  const int vid = slot >= 0 ? slot_vid[slot] : -1;
-  pc_voxel_id[i] = vid;
-  key32[i] = vid < 0 ? 0xffffffffu : static_cast<uint32_t>(vid);
-}
-
-// sorted (voxel id, point) pairs -> slot of the point inside its voxel
-__global__ void __launch_bounds__(kBlock)
-p2v_segment_kernel(const uint32_t *__restrict__ keys, int n, int32_t *__restrict__ seg_start) {
-  const int q = blockIdx.x * kBlock + threadIdx.x;
-  if (q >= n) return;
-  const uint32_t v = keys[q];
-  if (v != 0xffffffffu && (q == 0 || keys[q - 1] != v)) seg_start[v] = q;
-}
-
-__global__ void __launch_bounds__(kBlock)
-p2v_scatter_kernel(const float *__restrict__ pts, int nfeat, const uint32_t *__restrict__ keys,
-                   const int32_t *__restrict__ order, int n, const int32_t *__restrict__ seg_start,
-                   int max_points, float *__restrict__ voxels, int32_t *__restrict__ num_per_voxel) {
-  const int q = blockIdx.x * kBlock + threadIdx.x;
-  if (q >= n) return;
-  const uint32_t v = keys[q];
-  if (v == 0xffffffffu) return;
-  const int rank = q - seg_start[v];
-  if (rank < max_points) {
-    const float *src = pts + static_cast<size_t>(order[q]) * nfeat;
-    float *dst = voxels + (static_cast<size_t>(v) * max_points + rank) * nfeat;
-    for (int k = 0; k < nfeat; ++k) dst[k] = src[k];
-  }
-  if (q == n - 1 || keys[q + 1] != v) num_per_voxel[v] = min(rank + 1, max_points);
-}
-
-// empty_mean: slots num..max_points-1 of a voxel receive the mean of its points
-__global__ void __launch_bounds__(kBlock)
-p2v_mean_kernel(float *__restrict__ voxels, const int32_t *__restrict__ num_per_voxel,
-                const int32_t *__restrict__ n_voxels, int max_points, int nfeat) {
-  const long long gid = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
-  const int v = static_cast<int>(gid / nfeat), k = static_cast<int>(gid % nfeat);
-  if (v >= *n_voxels) return;
-  const int num = num_per_voxel[v];
-  if (num <= 0 || num >= max_points) return;
-  float *base = voxels + static_cast<size_t>(v) * max_points * nfeat + k;
-  float sum = 0.f;
-  for (int j = 0; j < num; ++j) sum += base[static_cast<size_t>(j) * nfeat];
-  const float mean = sum / static_cast<float>(num);
-  for (int j = num; j < max_points; ++j) base[static_cast<size_t>(j) * nfeat] = mean;
-}
-
-// The reference's CPU loop AS IT BEHAVES (pointops.py:663-686): `mean_value.clear()` leaves the accumulator's
-// contents in place, so voxel v starts from the mean of voxel v - 1:  m_v = (m_{v-1} + sum_j x_j) / num_v, point by
-// point in fp32.  A sequential recurrence over the voxels in their (first-seen) order: one thread per feature
-// walks all of them.  Opt-in (empty_mean = 2: SPCONV_AMD_REFERENCE_QUIRKS=1), bit-identical to the reference's code
-// executed (tests/golden/p2v_ref.npz); milliseconds, not microseconds.
-__global__ void p2v_mean_carry_kernel(float *__restrict__ voxels, const int32_t *__restrict__ num_per_voxel,
-                                      const int32_t *__restrict__ n_voxels, int max_points, int nfeat) {
-  const int k = threadIdx.x;
-  if (k >= nfeat) return;
-  const int nv = *n_voxels;
-  float carry = 0.f;
-  for (int v = 0; v < nv; ++v) {
-    const int num = num_per_voxel[v];
-    if (num <= 0) continue;
-    float *base = voxels + static_cast<size_t>(v) * max_points * nfeat + k;
-    for (int j = 0; j < num; ++j) carry += base[static_cast<size_t>(j) * nfeat];
-    carry /= static_cast<float>(num);
-    for (int j = num; j < max_points; ++j) base[static_cast<size_t>(j) * nfeat] = carry;
-  }
-}
-
-__global__ void p2v_clamp_count_kernel(const int32_t *total, int max_voxels, int32_t *n_voxels) {
-  *n_voxels = *total < max_voxels ? *total : max_voxels;
-}
-
-struct P2VWs {
-  Table t;
-  int32_t *slot_of, *slot_vid, *blockcount, *blockoff, *total, *n_voxels, *seg_start, *order, *hist, *hist_off;
-  uint32_t *key32, *kA, *kB;
-  int32_t *vB;
-  int nblk;
-  size_t bytes;
-};
-
-P2VWs carve_p2v_ws(void *ws, int n, int max_voxels, bool packed = false) {
-  const uint32_t cap = table_capacity(n > 0 ? n : 1);
-  const size_t np = n > 0 ? n : 1;
-  P2VWs w;
-  w.nblk = div_up(static_cast<int>(np), kItems);
-  Carver cv(ws);
-  {
-    hkey_t *keys = cv.take<hkey_t>(cap);
-    table_place(w.t, keys, cv.take<int32_t>(cap), cap, packed);
-  }
-  w.slot_vid = cv.take<int32_t>(cap);
-  w.slot_of = cv.take<int32_t>(np);
-  w.blockcount = cv.take<int32_t>(w.nblk);
-  w.blockoff = cv.take<int32_t>(w.nblk);
-  w.total = cv.take<int32_t>(1);
-  w.n_voxels = cv.take<int32_t>(1);
-  w.seg_start = cv.take<int32_t>(max_voxels > 0 ? max_voxels : 1);
-  w.order = cv.take<int32_t>(np);
-  w.key32 = cv.take<uint32_t>(np);
-  w.kA = cv.take<uint32_t>(np);
-  w.kB = cv.take<uint32_t>(np);
-  w.vB = cv.take<int32_t>(np);
-  w.hist = cv.take<int32_t>(static_cast<size_t>(kRadix) * w.nblk);
-  w.hist_off = cv.take<int32_t>(static_cast<size_t>(kRadix) * w.nblk);
-  w.bytes = cv.off;
-  return w;
-}
-
-// ------------------------------------------------------------- user hash table
-// Fixed-size open-addressing table over caller-owned key / value arrays (SURVEY.md section 8f
-// row 4; replaces spconv/csrc/hash/core.py HashTable as used by spconv/pytorch/hash.py).  Keys
-// are 32- or 64-bit integers (all-ones = empty), values are opaque 4- or 8-byte items.
-// assign_arange / items walk the table in SLOT order (count -> scan -> assign), so their result
-// is a pure function of the set of keys -- the reference's GPU table numbers entries in atomic
-// arrival order.
-template <typename K> struct UKey;
-template <> struct UKey<uint32_t> { static __device__ __forceinline__ uint32_t empty() { return 0xffffffffu; } };
-template <> struct UKey<unsigned long long> {
-  static __device__ __forceinline__ unsigned long long empty() { return ~0ull; }
-};
-
-template <typename K>
-__device__ __forceinline__ uint32_t user_hash(K k) {
-  return hash_key(static_cast<hkey_t>(k), 0);
-}
-
-template <typename K>
-__device__ __forceinline__ int user_find(const K *keys, int cap, K key, bool insert) {
-  uint32_t slot = user_hash(key) % static_cast<uint32_t>(cap);
-  for (int probe = 0; probe < cap; ++probe) {
-    if (insert) {
-      const K prev = atomicCAS(const_cast<K *>(&keys[slot]), UKey<K>::empty(), key);
-      if (prev == UKey<K>::empty() || prev == key) return static_cast<int>(slot);
-    } else {
-      const K cur = keys[slot];
-      if (cur == key) return static_cast<int>(slot);
-      if (cur == UKey<K>::empty()) return -1;
-    }
-    slot = slot + 1 == static_cast<uint32_t>(cap) ? 0u : slot + 1;
-  }
-  return -1;
-}
-
-// op 0: insert (values optional), 1: query, 2: insert only where the key exists
-template <typename K, typename V>
-__global__ void __launch_bounds__(kBlock)
-user_hash_kernel(K *__restrict__ tkeys, V *__restrict__ tvals, int cap, const K *__restrict__ keys,
-                 V *__restrict__ values, unsigned char *__restrict__ is_empty, int n, int op) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const K key = keys[i];
-  if (op == 0) {
-    const int slot = user_find(tkeys, cap, key, true);
-    if (slot >= 0 && values) tvals[slot] = values[i];
-  } else {
-    const int slot = user_find(tkeys, cap, key, false);
-    if (is_empty) is_empty[i] = slot < 0 ? 1 : 0;
-    if (slot >= 0) {
-      if (op == 1) values[i] = tvals[slot];
-      else tvals[slot] = values[i];
-    }
-  }
-}
-
-template <typename K>
-__global__ void __launch_bounds__(kBlock)
-user_count_kernel(const K *__restrict__ tkeys, int cap, int32_t *__restrict__ blockcount) {
-  __shared__ int lds_wave[kBlock / 64];
-  const int begin = blockIdx.x * kItems;
-  int cnt = 0;
-#pragma unroll
-  for (int it = 0; it < kItems / kBlock; ++it) {
-    const int e = begin + it * kBlock + threadIdx.x;
-    cnt += __popcll(__ballot(e < cap && tkeys[e] != UKey<K>::empty()));
-  }
-  if ((threadIdx.x & 63) == 0) lds_wave[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int sum = 0;
-    for (int w = 0; w < kBlock / 64; ++w) sum += lds_wave[w];
-    blockcount[blockIdx.x] = sum;
-  }
-}
-
-// mode 0: tvals[slot] = rank (assign_arange); mode 1: (keys_out, vals_out)[rank] = entry (items)
-template <typename K, typename V>
-__global__ void __launch_bounds__(kBlock)
-user_walk_kernel(const K *__restrict__ tkeys, V *__restrict__ tvals, int cap,
-                 const int32_t *__restrict__ blockoff, int mode, K *__restrict__ keys_out,
-                 V *__restrict__ vals_out, int max_out) {
-  __shared__ int lds_wave[kBlock / 64];
-  const int begin = blockIdx.x * kItems;
-  int running = blockoff[blockIdx.x];
-  for (int it = 0; it < kItems / kBlock; ++it) {
-    const int e = begin + it * kBlock + threadIdx.x;
-    const bool used = e < cap && tkeys[e] != UKey<K>::empty();
-    int total;
-    const int rank = block_rank(used, total, lds_wave);
-    if (used) {
-      const int r = running + rank;
-      if (mode == 0) {
-        tvals[e] = static_cast<V>(r);
-      } else if (r < max_out) {
-        keys_out[r] = tkeys[e];
-        vals_out[r] = tvals[e];
-      }
-    }
-    running += total;
-  }
-}
-
-template <typename T>
-__global__ void user_store_count_kernel(const int32_t *total, T *count_out) { *count_out = static_cast<T>(*total); }
-
-template <typename K, typename V>
-int user_hash_dispatch2(int what, void *tkeys, void *tvals, int cap, const void *keys, void *values,
-                        unsigned char *is_empty, int n, void *keys_out, void *vals_out, int max_out,
-                        void *count_out, void *ws, hipStream_t s) {
-  K *tk = static_cast<K *>(tkeys);
-  V *tv = static_cast<V *>(tvals);
-  if (what <= 2) {
-    if (n > 0)
-      hipLaunchKernelGGL((user_hash_kernel<K, V>), dim3(div_up(n, kBlock)), dim3(kBlock), 0, s, tk, tv, cap,
-                         static_cast<const K *>(keys), static_cast<V *>(values), is_empty, n, what);
-  } else {
-    const int nblk = div_up(cap, kItems);
-    Carver cv(ws);
-    int32_t *blockcount = cv.take<int32_t>(nblk);
-    int32_t *blockoff = cv.take<int32_t>(nblk);
-    int32_t *total = cv.take<int32_t>(1);
-    hipLaunchKernelGGL((user_count_kernel<K>), dim3(nblk), dim3(kBlock), 0, s, tk, cap, blockcount);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kBlock), 0, s, blockcount, blockoff, nblk, total);
-    hipLaunchKernelGGL((user_walk_kernel<K, V>), dim3(nblk), dim3(kBlock), 0, s, tk, tv, cap, blockoff,
-                       what == 3 ? 0 : 1, static_cast<K *>(keys_out), static_cast<V *>(vals_out), max_out);
-    if (count_out) hipLaunchKernelGGL((user_store_count_kernel<K>), dim3(1), dim3(1), 0, s, total, static_cast<K *>(count_out));
-  }
-  SPX_LAUNCH_CHECK();
-  return 0;
-}
-
 }  // namespace
 }  // namespace spx
 
 using namespace spx;
 
-namespace spx {
-namespace {
-// ---------------------------------------------------------------- SubM row layout
-// The default row order of a SubM rulebook (include/spconv_amd.h, spx_subm_layout): the reference sorts the rows of
-// every rulebook by mask (SPCONV_DO_SORT, constants.py:121; ops.py:763-785 -> all.py:935-991); here the finished
-// masks are classified and, for a sparse rulebook, the rows WITH a neighbour move into a compact appendix -- bucket
-// 1 + j = rows whose lowest neighbour offset is j, a stable counting partition -- while the row-order walk keeps the
-// rows that only have their centre pair.  count -> scan (one block per bucket) -> scatter; ranks inside a block
-// come from wave ballots, every position is a function of the masks alone (no order-dependent atomics).  Nothing is
-// read back: class and count land in the blob, the gather-GEMM's appendix workgroups read them.
-constexpr int kLayBuckets = 33;       // centre-only + lowest neighbour offset 0 .. 31
-constexpr int kLayItems = 256;        // rows per block: one round (a 100 k-row rulebook must fill 256 CUs: 391 blocks)
-
-__device__ __forceinline__ int lay_bucket(uint32_t m, int centre) {
-  m &= ~(1u << centre);
-  return m ? 1 + __builtin_ctz(m) : 0;
-}
-
-__global__ void __launch_bounds__(kBlock)
-layout_count_kernel(const uint32_t *__restrict__ mask, int n, int kv, int nblk, int32_t *__restrict__ cnt) {
-  __shared__ int h[kLayBuckets];
-  if (threadIdx.x < kLayBuckets) h[threadIdx.x] = 0;
-  __syncthreads();
-  const int centre = kv / 2, begin = blockIdx.x * kLayItems;
-#pragma unroll
-  for (int it = 0; it < kLayItems / kBlock; ++it) {
-    const int i = begin + it * kBlock + threadIdx.x;
-    if (i < n) atomicAdd(&h[lay_bucket(mask[i], centre)], 1);      // (counts: the order of the adds is immaterial)
-  }
-  __syncthreads();
-  if (threadIdx.x < kLayBuckets) cnt[static_cast<size_t>(threadIdx.x) * nblk + blockIdx.x] = h[threadIdx.x];
-}
-
-__global__ void __launch_bounds__(kBlock)
-layout_scatter_kernel(const int32_t *__restrict__ pair, const uint32_t *__restrict__ mask, int n, int kv, int nblk,
-                      const int32_t *__restrict__ off, const int32_t *__restrict__ totals,
-                      int32_t *__restrict__ blob, int npad, int mcap) {
-  __shared__ int base[kLayBuckets];              // first appendix position of (bucket, this block); bucket 0 unused
-  __shared__ int wcnt[kBlock / 64][kLayBuckets]; // rows of a bucket per wave
-  const int centre = kv / 2;
-  const int heavy = n - totals[0];
-  const int cls = (heavy > 0 && 4ll * heavy < n) ? 1 : 0;
-  uint32_t *mask_main = reinterpret_cast<uint32_t *>(blob + SPX_LAYOUT_HEADER);
-  int32_t *order = blob + SPX_LAYOUT_HEADER + npad;
-  uint32_t *mask_app = reinterpret_cast<uint32_t *>(order + mcap);
-  int32_t *pair_app = order + 2 * static_cast<size_t>(mcap);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    blob[0] = cls;
-    blob[1] = heavy;
-    blob[2] = n;
-    blob[3] = kv;
-    blob[4] = mcap;
-  }
-  const int i = blockIdx.x * kLayItems + threadIdx.x;
-  const bool ok = i < n;
-  const uint32_t m = ok ? mask[i] : 0u;
-  const int b = ok ? lay_bucket(m, centre) : -1;
-  // the row-order walk keeps every row of a dense rulebook, and the centre-only rows of a sparse one
-  if (ok) mask_main[i] = (cls && b > 0) ? 0u : m;
-  if (!cls) return;
-  if (threadIdx.x < kLayBuckets) {
-    int s = 0;
-    for (int j = 1; j < static_cast<int>(threadIdx.x); ++j) s += totals[j];
-    base[threadIdx.x] = s + off[static_cast<size_t>(threadIdx.x) * nblk + blockIdx.x];
-  }
-  for (int j = threadIdx.x; j < (kBlock / 64) * kLayBuckets; j += kBlock) (&wcnt[0][0])[j] = 0;
-  __syncthreads();
-  // rank of a row with a neighbour among the rows of its bucket in this wave: one ballot per DISTINCT bucket present
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool hv = ok && b > 0;
-  int rank = 0;
-  unsigned long long todo = __ballot(hv);
-  while (todo) {
-    const int leader = __builtin_ctzll(todo);
-    const int lb = __builtin_amdgcn_readlane(b, leader);
-    const unsigned long long same = __ballot(hv && b == lb);
-    if (b == lb) rank = __popcll(same & ((1ull << lane) - 1ull));
-    if (lane == leader) wcnt[wave][lb] = __popcll(same);
-    todo &= ~same;
-  }
-  __syncthreads();
-  if (hv) {
-    int pos = base[b] + rank;
-    for (int w = 0; w < wave; ++w) pos += wcnt[w][b];
-    order[pos] = i;
-    mask_app[pos] = m;
-    for (int k = 0; k < kv; ++k) pair_app[static_cast<size_t>(k) * mcap + pos] = pair[static_cast<size_t>(k) * n + i];
-  }
-}
-}  // namespace
-}  // namespace spx
-
 extern "C" {
-
-size_t spx_subm_layout_mcap(int n) {
-  const size_t nn = n > 0 ? n : 1;
-  return ((nn / 4 + 63) & ~static_cast<size_t>(63)) + 256;
-}
-
-size_t spx_subm_layout_bytes(int n, int kv) {
-  const size_t nn = n > 0 ? n : 1, npad = (nn + 63) & ~static_cast<size_t>(63), mcap = spx_subm_layout_mcap(n);
-  return (SPX_LAYOUT_HEADER + npad + (2 + static_cast<size_t>(kv)) * mcap) * sizeof(int32_t);
-}
-
-size_t spx_subm_layout_ws_bytes(int n) {
-  const size_t nblk = div_up(n > 0 ? n : 1, kLayItems);
-  return 2 * align_up(static_cast<size_t>(kLayBuckets) * nblk * sizeof(int32_t), 256) + 256;
-}
-
-int spx_subm_layout(const int32_t *pair_fwd, const uint32_t *mask, int n, int kv, int32_t *layout, void *ws,
-                    size_t ws_bytes, spx_stream_t stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  SPX_CHECK(kv >= 1 && kv <= 32, "a rows layout needs a kernel volume <= 32 (one mask word), got %d", kv);
-  if (n <= 0) return 0;
-  SPX_CHECK(pair_fwd && mask && layout && ws, "null pointer");
-  SPX_CHECK(ws_bytes >= spx_subm_layout_ws_bytes(n), "workspace too small");
-  const int nblk = div_up(n, kLayItems);
-  const int npad = (n + 63) & ~63;
-  Carver cv(ws);
-  int32_t *cnt = cv.take<int32_t>(static_cast<size_t>(kLayBuckets) * nblk);
-  int32_t *off = cv.take<int32_t>(static_cast<size_t>(kLayBuckets) * nblk);
-  int32_t *totals = cv.take<int32_t>(64);
-  hipLaunchKernelGGL(layout_count_kernel, dim3(nblk), dim3(kBlock), 0, s, mask, n, kv, nblk, cnt);
-  hipLaunchKernelGGL(scan_kernel, dim3(kLayBuckets), dim3(kBlock), 0, s, cnt, off, nblk, totals);
-  hipLaunchKernelGGL(layout_scatter_kernel, dim3(nblk), dim3(kBlock), 0, s, pair_fwd, mask, n, kv, nblk, off,
-                     totals, layout, npad, static_cast<int>(spx_subm_layout_mcap(n)));
-  SPX_LAUNCH_CHECK();
-  return 0;
-}
 
 size_t spx_subm_rulebook_ws_bytes(int n, int kv) {
   const uint32_t cap = table_capacity(n > 0 ? n : 1) << 1;      // (room for the larger of the two table sizes, below)
@@ -2298,7 +1437,6 @@ int spx_subm_rulebook(const int32_t *indices, int n, int ndim, int batch_size,
   const Geom g = make_geom(ndim, batch_size, spatial_shape, spatial_shape, ksize, stride,
                            padding, dilation);
   const int words = div_up(kv, 32);
-  if (n == 0) return 0;
 
   // 4 N slots instead of 2 N while the table stays within 8 MB (two XCD L2s): at load 0.1-0.19 a lookup resolves in
   // ~1.2 probes instead of ~2 -- SubM tables 40.8 -> 36.9 us at 100 k uniform voxels, 67.1 -> 54.6 on the 125 k fixture;
@@ -2572,10 +1710,9 @@ int conv_fill_impl(const int32_t *indices, int n_in, int ndim, int batch_size,
   SPX_CHECK(pair_fwd && pair_bwd && out_indices, "out_indices, pair_fwd and pair_bwd are required");
   const int kv = g.kv, words = div_up(kv, 32);
   const int ngroups = div_up(n_in > 0 ? n_in : 1, kBlock);
-  const int version = 2;
   // second form: the Native lists come from subm_lists_kernel (conv mode) over the 256-row pair counts
   // stage 2 leaves behind -- no count / scan launches, no -1 pre-fill of the lists
-  const bool v2 = version >= 2 && (pair_native || num_per_loc) && ngroups <= 16384 && kv <= 128;
+  const bool v2 = (pair_native || num_per_loc) && ngroups <= 16384 && kv <= 128;
   FillList fills;                                           // every fill of this call: one launch
   if (!v2) {
     if (num_per_loc) fills.add(num_per_loc, sizeof(int32_t) * kv, 0u);
@@ -2658,7 +1795,6 @@ int spx_conv_rulebook_static(const int32_t *indices, int n_in, int ndim, int bat
                              int32_t *pair_bwd, uint32_t *mask_fwd, uint32_t *mask_bwd,
                              int32_t *pair_native, int32_t *num_per_loc, int32_t *n_out_dev, void *ws,
                              size_t ws_bytes, spx_stream_t stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
   SPX_CHECK(n_out_cap > 0 && n_out_dev && out_indices, "n_out_cap > 0, n_out_dev and out_indices are required");
   SPX_CHECK(n_in > 0, "static-shape rulebook needs n_in > 0 (pad the input with batch = -1 rows)");
   // every launch below is stream-ordered and nothing is read back: the whole call can sit in a
@@ -2668,7 +1804,6 @@ int spx_conv_rulebook_static(const int32_t *indices, int n_in, int ndim, int bat
   // and {distinct outputs found (may exceed the cap: the first n_out_cap survive), hash-table overflow
   // flag} are written straight into n_out_dev: two launches and a copy fewer than the two-call form.
   SPX_CHECK(pair_fwd && pair_bwd, "pair_fwd and pair_bwd are required");
-  (void)s;
   int kv = 1;
   for (int i = 0; i < ndim; ++i) kv *= ksize[i];
   spx::FillList pre;
@@ -2967,30 +2102,6 @@ int spx_subm_rulebook_ranked(const int32_t *indices, int n, int ndim, int batch_
   return 0;
 }
 
-}  // extern "C"
-
-extern "C" {
-
-size_t spx_mask_argsort_ws_bytes(int n) { return radix_argsort_ws_bytes(n) + 256; }
-
-int spx_mask_argsort(const uint32_t *mask, int n, int words, int32_t *argsort, void *ws,
-                     size_t ws_bytes, spx_stream_t stream) {
-  SPX_CHECK(words == 1, "mask_argsort supports kernel volume <= 32 (words == 1), got %d", words);
-  SPX_CHECK(ws_bytes >= spx_mask_argsort_ws_bytes(n), "workspace too small");
-  if (n == 0) return 0;
-  // stable argsort of the mask words (all.py:935-991 sorts the same keys with thrust)
-  return radix_argsort(mask, n, 32, argsort, ws, static_cast<hipStream_t>(stream));
-}
-
-int spx_mask_argsort_kv(const uint32_t *mask, int n, int kv, int32_t *argsort, void *ws, size_t ws_bytes,
-                        spx_stream_t stream) {
-  SPX_CHECK(kv >= 1 && kv <= 32, "mask_argsort supports kernel volume <= 32, got %d", kv);
-  SPX_CHECK(ws_bytes >= spx_mask_argsort_ws_bytes(n), "workspace too small");
-  if (n == 0) return 0;
-  // the mask words of a kernel volume kv carry kv bits: 27 bits are three 9-bit passes instead of four 8-bit ones
-  return radix_argsort(mask, n, kv, argsort, ws, static_cast<hipStream_t>(stream));
-}
-
 int spx_native_to_table(const int32_t *pair_native, const int32_t *num_per_loc, int n_in,
                         int n_dst, int kv, int subm, int inverse, int32_t *table,
                         uint32_t *mask, spx_stream_t stream) {
@@ -3030,147 +2141,6 @@ int spx_table_to_native(const int32_t *table, int subm, int kv, int n, int32_t *
                        pair_native, kv, n);
   return launch_native_lists(table, subm ? 0 : 1, kv, n, subm ? kv / 2 : kv, nblk, blockcount,
                              blockoff, pair_native, num_per_loc, s);
-}
-
-size_t spx_point2voxel_ws_bytes(int n_points, int max_voxels) {
-  return carve_p2v_ws(nullptr, n_points, max_voxels).bytes + 256;
-}
-
-int spx_point2voxel(const float *points, int n, int nfeat, int ndim, const float *vsize,
-                    const float *coors_range, const int *grid_size, int max_voxels, int max_points,
-                    int empty_mean, int clear_voxels, float *voxels, int32_t *indices,
-                    int32_t *num_per_voxel, long long *pc_voxel_id, int *n_voxels_h, void *ws,
-                    size_t ws_bytes, spx_stream_t stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  SPX_CHECK(ndim >= 1 && ndim <= kMaxNdim, "ndim must be in [1,4], got %d", ndim);
-  SPX_CHECK(nfeat >= ndim, "points need at least %d columns, got %d", ndim, nfeat);
-  SPX_CHECK(max_voxels > 0 && max_points > 0 && n >= 0, "bad sizes");
-  SPX_CHECK(voxels && indices && num_per_voxel && (pc_voxel_id || n == 0) && n_voxels_h, "null pointer");
-  SPX_CHECK(ws_bytes >= spx_point2voxel_ws_bytes(n, max_voxels), "workspace too small");
-  *n_voxels_h = 0;
-  SPX_HIP(hipMemsetAsync(num_per_voxel, 0, sizeof(int32_t) * max_voxels, s));
-  if (clear_voxels)
-    SPX_HIP(hipMemsetAsync(voxels, 0, sizeof(float) * static_cast<size_t>(max_voxels) * max_points * nfeat, s));
-  if (n == 0) return 0;
-  SPX_CHECK(points, "null pointer");
-  P2VGeom g;
-  g.ndim = ndim;
-  for (int j = 0; j < 4; ++j) {
-    g.vsize[j] = j < ndim ? vsize[j] : 1.f;
-    g.lo[j] = j < ndim ? coors_range[j] : 0.f;
-    g.grid[j] = j < ndim ? grid_size[j] : 1;
-  }
-  P2VWs w = carve_p2v_ws(ws, n, max_voxels, keys_fit_u32(1, g.grid, 4));
-  const size_t cap = static_cast<size_t>(w.t.mask) + 1;
-  SPX_HIP(table_clear(w.t, s));
-  SPX_HIP(hipMemsetAsync(w.slot_vid, 0xFF, sizeof(int32_t) * cap, s));
-  const dim3 gp(div_up(n, kBlock));
-  hipLaunchKernelGGL(p2v_insert_kernel, gp, dim3(kBlock), 0, s, points, n, nfeat, g, w.t, w.slot_of);
-  hipLaunchKernelGGL(p2v_count_first_kernel, dim3(w.nblk), dim3(kBlock), 0, s, w.slot_of, w.t, n,
-                     w.blockcount);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kBlock), 0, s, w.blockcount, w.blockoff, w.nblk, w.total);
-  hipLaunchKernelGGL(p2v_clamp_count_kernel, dim3(1), dim3(1), 0, s, w.total, max_voxels, w.n_voxels);
-  hipLaunchKernelGGL(p2v_assign_kernel, dim3(w.nblk), dim3(kBlock), 0, s, points, n, nfeat, g, w.slot_of,
-                     w.t, w.blockoff, max_voxels, w.slot_vid, indices);
-  hipLaunchKernelGGL(p2v_point_vid_kernel, gp, dim3(kBlock), 0, s, w.slot_of, w.slot_vid, n, pc_voxel_id,
-                     w.key32);
-  // stable sort of the points by voxel id (4 x 8-bit LSD passes, as mask_argsort)
-  const uint32_t *kin = w.key32;
-  const int32_t *vin = nullptr;
-  uint32_t *kout[4] = {w.kB, w.kA, w.kB, w.kA};
-  int32_t *vout[4] = {w.vB, w.order, w.vB, w.order};
-  for (int pass = 0; pass < 4; ++pass) {
-    hipLaunchKernelGGL(radix_count_kernel, dim3(w.nblk), dim3(kBlock), 0, s, kin, n, pass * kRadixBits,
-                       w.nblk, w.hist);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kBlock), 0, s, w.hist, w.hist_off, kRadix * w.nblk,
-                       static_cast<int32_t *>(nullptr));
-    hipLaunchKernelGGL(radix_scatter_kernel, dim3(w.nblk), dim3(kBlock), 0, s, kin, vin, n,
-                       pass * kRadixBits, w.nblk, w.hist_off, kout[pass], vout[pass]);
-    kin = kout[pass];
-    vin = vout[pass];
-  }
-  hipLaunchKernelGGL(p2v_segment_kernel, gp, dim3(kBlock), 0, s, w.kA, n, w.seg_start);
-  hipLaunchKernelGGL(p2v_scatter_kernel, gp, dim3(kBlock), 0, s, points, nfeat, w.kA, w.order, n,
-                     w.seg_start, max_points, voxels, num_per_voxel);
-  if (empty_mean == 2) {
-    SPX_CHECK(nfeat <= 1024, "reference-quirk mean fill: at most 1024 point features");
-    hipLaunchKernelGGL(p2v_mean_carry_kernel, dim3(1), dim3(((nfeat + 63) / 64) * 64), 0, s, voxels, num_per_voxel,
-                       w.n_voxels, max_points, nfeat);
-  } else if (empty_mean) {
-    const long long total = static_cast<long long>(max_voxels) * nfeat;
-    hipLaunchKernelGGL(p2v_mean_kernel, dim3(static_cast<unsigned>((total + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, voxels, num_per_voxel, w.n_voxels, max_points, nfeat);
-  }
-  SPX_LAUNCH_CHECK();
-  int32_t host_n = 0;
-  SPX_HIP(hipMemcpyAsync(&host_n, w.n_voxels, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  SPX_HIP(hipStreamSynchronize(s));
-  *n_voxels_h = host_n;
-  return 0;
-}
-
-/* what: 0 insert, 1 query, 2 insert_exist_keys, 3 assign_arange, 4 items */
-static int user_hash_call(int what, void *tkeys, void *tvals, int cap, int key_bytes, int val_bytes,
-                          const void *keys, void *values, unsigned char *is_empty, int n, void *keys_out,
-                          void *vals_out, int max_out, void *count_out, void *ws, size_t ws_bytes,
-                          spx_stream_t stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  SPX_CHECK(tkeys && tvals && cap > 0, "hash table storage required");
-  SPX_CHECK((key_bytes == 4 || key_bytes == 8) && (val_bytes == 4 || val_bytes == 8),
-            "keys and values must be 4 or 8 bytes wide");
-  if (what >= 3) SPX_CHECK(ws && ws_bytes >= spx_hash_ws_bytes(cap), "workspace too small");
-#define SPX_UH(KT, VT) \
-  return user_hash_dispatch2<KT, VT>(what, tkeys, tvals, cap, keys, values, is_empty, n, keys_out, vals_out, \
-                                     max_out, count_out, ws, s)
-  if (key_bytes == 4 && val_bytes == 4) SPX_UH(uint32_t, uint32_t);
-  if (key_bytes == 4 && val_bytes == 8) SPX_UH(uint32_t, unsigned long long);
-  if (key_bytes == 8 && val_bytes == 4) SPX_UH(unsigned long long, uint32_t);
-  SPX_UH(unsigned long long, unsigned long long);
-#undef SPX_UH
-}
-
-size_t spx_hash_ws_bytes(int capacity) {
-  const int nblk = div_up(capacity > 0 ? capacity : 1, kItems);
-  return 2 * align_up(static_cast<size_t>(nblk) * sizeof(int32_t), 256) + 512;
-}
-
-int spx_hash_clear(void *table_keys, int capacity, int key_bytes, spx_stream_t stream) {
-  SPX_CHECK(table_keys && capacity > 0 && (key_bytes == 4 || key_bytes == 8), "bad hash table");
-  SPX_HIP(hipMemsetAsync(table_keys, 0xFF, static_cast<size_t>(capacity) * key_bytes,
-                         static_cast<hipStream_t>(stream)));
-  return 0;
-}
-
-int spx_hash_insert(void *table_keys, void *table_vals, int capacity, int key_bytes, int val_bytes,
-                    const void *keys, const void *values, int n, spx_stream_t stream) {
-  return user_hash_call(0, table_keys, table_vals, capacity, key_bytes, val_bytes, keys,
-                        const_cast<void *>(values), nullptr, n, nullptr, nullptr, 0, nullptr, nullptr, 0, stream);
-}
-
-int spx_hash_query(void *table_keys, void *table_vals, int capacity, int key_bytes, int val_bytes,
-                   const void *keys, void *values_out, unsigned char *is_empty, int n, spx_stream_t stream) {
-  return user_hash_call(1, table_keys, table_vals, capacity, key_bytes, val_bytes, keys, values_out, is_empty,
-                        n, nullptr, nullptr, 0, nullptr, nullptr, 0, stream);
-}
-
-int spx_hash_insert_exist(void *table_keys, void *table_vals, int capacity, int key_bytes, int val_bytes,
-                          const void *keys, const void *values, unsigned char *is_empty, int n,
-                          spx_stream_t stream) {
-  return user_hash_call(2, table_keys, table_vals, capacity, key_bytes, val_bytes, keys,
-                        const_cast<void *>(values), is_empty, n, nullptr, nullptr, 0, nullptr, nullptr, 0, stream);
-}
-
-int spx_hash_assign_arange(void *table_keys, void *table_vals, int capacity, int key_bytes, int val_bytes,
-                           void *count_out, void *ws, size_t ws_bytes, spx_stream_t stream) {
-  return user_hash_call(3, table_keys, table_vals, capacity, key_bytes, val_bytes, nullptr, nullptr, nullptr, 0,
-                        nullptr, nullptr, 0, count_out, ws, ws_bytes, stream);
-}
-
-int spx_hash_items(void *table_keys, void *table_vals, int capacity, int key_bytes, int val_bytes,
-                   void *keys_out, void *vals_out, int max_out, void *count_out, void *ws, size_t ws_bytes,
-                   spx_stream_t stream) {
-  return user_hash_call(4, table_keys, table_vals, capacity, key_bytes, val_bytes, nullptr, nullptr, nullptr, 0,
-                        keys_out, vals_out, max_out, count_out, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

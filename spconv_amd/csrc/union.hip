@@ -28,11 +28,13 @@
 #include "common.h"
 #include "fill.h"
 #include "rankmap.h"
+#include "scan.h"
 
 namespace spx {
 namespace {
 
 constexpr int kBlock = 256;
+static_assert(kBlock == kScanThreads, "scan.h's primitives are written for this unit's workgroup size");
 constexpr int kMaxOps = SPX_UNION_MAX_OPERANDS;
 constexpr int kCounters = 4 + kMaxOps;       // {union size, duplicate flag, live output rows, -, live rows of operand t}
 
@@ -84,36 +86,13 @@ union_mark_kernel(UnionOps ops, UnionGeom g, uint8_t *__restrict__ occupied) {
   if (key >= 0) occupied[key] = 1;
 }
 
-// Exclusive scan of the prefix pass's block totals by one block (as compact_scan_kernel of dense.hip); counters[0] =
+// Exclusive scan of the prefix pass's block totals by one block (block_scan_loop of scan.h); counters[0] =
 // the union's size, counters[2] = the live output rows = min(size, cap) (cap < 0: no bound).
 __global__ void __launch_bounds__(kBlock)
 union_scan_kernel(const int32_t *__restrict__ cnt, int32_t *__restrict__ off, int len, int cap,
                   int32_t *__restrict__ counters) {
   __shared__ int lds_wave[kBlock / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int carry = 0;
-  for (int base = 0; base < len; base += kBlock) {
-    const int idx = base + threadIdx.x;
-    const int v = idx < len ? cnt[idx] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += u;
-    }
-    __syncthreads();                      // (lds_wave of the previous round has been read)
-    if (lane == 63) lds_wave[wave] = incl;
-    __syncthreads();
-    int prefix = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-      const int s = lds_wave[w];
-      if (w < wave) prefix += s;
-      sum += s;
-    }
-    if (idx < len) off[idx] = carry + prefix + incl - v;
-    carry += sum;
-  }
+  const int carry = block_scan_loop(cnt, off, len, lds_wave);
   if (threadIdx.x == 0) {
     counters[0] = carry;
     counters[2] = cap >= 0 && carry > cap ? cap : carry;

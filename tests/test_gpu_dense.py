@@ -222,6 +222,38 @@ def test_from_dense_equals_to_sparse(cuda, dtype):
             assert bool(torch.isnan(x.features.float()).any()) and x.features.shape[0] == n + 1
 
 
+@pytest.mark.parametrize("dtype", [torch.int8, torch.float16], ids=lambda d: str(d).replace("torch.", ""))
+@pytest.mark.parametrize("spatial", [[257, 16, 16], [128, 128, 128], [129, 128, 128]], ids=lambda s: "x".join(map(str, s)))
+def test_from_dense_across_scan_boundary(cuda, spatial, dtype):
+    """from_dense counts per 256-cell block and one workgroup scans the counts (scan_kernel of csrc/scan.h), len =
+    cells / 256 of them: 257 (one pass, two items per thread, the last threads hold none), 8192 (the last one-pass
+    length, every thread holds 32 items) and 8256 (the loop form, 256 items per round).  Occupied with 1 .. 5 cells each:
+    the first and the last block and the two blocks either side of every 32nd block boundary -- the ends of a thread's
+    run in the one-pass form at each of these lengths, and the ends of a round of the loop form; a few thousand cells
+    anywhere besides.  One channel; coordinates, row order and features exactly as torch's to_sparse."""
+    import spconv_amd.pytorch as spconv
+    cells = int(np.prod(spatial))
+    nblk = cells // 256
+    assert cells % 256 == 0 and nblk in (257, 8192, 8256)
+    rng = np.random.default_rng(91)
+    edge = np.arange(0, nblk, 2 if nblk == 257 else 32)
+    blocks = np.unique(np.concatenate([[0, nblk - 1], edge, edge[1:] - 1]))
+    pick = [rng.integers(0, cells, 3000)]
+    for b in blocks:
+        pick.append(b * 256 + rng.choice(256, size=1 + int(b) % 5, replace=False))
+    pick = np.unique(np.concatenate(pick))
+    flat = torch.zeros((cells, 1), dtype=dtype, device=cuda)
+    vals = _rows(pick.size, 1, dtype, cuda, 92)
+    vals[vals == 0] = 1
+    flat[torch.from_numpy(pick).to(cuda)] = vals
+    d = flat.view([1] + list(spatial) + [1])
+    sp = d.to_sparse(d.dim() - 1)
+    x = spconv.SparseConvTensor.from_dense(d)
+    assert x.features.shape[0] == pick.size
+    assert torch.equal(x.indices, sp.indices().T.int())
+    assert torch.equal(_bits(x.features), _bits(sp.values()))
+
+
 def test_from_dense_round_trip_and_gradient(cuda):
     import spconv_amd.pytorch as spconv
     B, spatial, C = 2, [3, 5, 7], 5

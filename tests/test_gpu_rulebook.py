@@ -167,6 +167,23 @@ def test_mask_argsort_is_stable_sort(cuda):
     np.testing.assert_array_equal(to_np(a).astype(np.int64), np.argsort(m[:, 0], kind="stable"))
 
 
+@pytest.mark.parametrize("n", [512 * 257, 512 * 8192, 512 * 8192 + 1])
+def test_mask_argsort_across_scan_boundary(cuda, n):
+    """A radix pass counts per 512 keys and one workgroup per digit scans the counts (scan_kernel of csrc/scan.h), len =
+    ceil(n / 512) of them: 257 (one pass, two items per thread, the last threads hold none), 8192 (the last one-pass
+    length) and 8193 (the loop form).  Random 27-bit keys, most of them equal; the order is that of a stable torch.sort of
+    the same keys, exactly.  kv = 27 runs the 9-bit digits; the smallest size also the 8-bit digits of the 32-bit path."""
+    from spconv_amd.pytorch import ops
+    g = torch.Generator(device=cuda).manual_seed(n)
+    keys = torch.randint(0, 1 << 27, (n,), generator=g, device=cuda)
+    keys[torch.rand((n,), generator=g, device=cuda) < 0.6] = 1 << 13
+    expect = torch.sort(keys, stable=True).indices
+    mask = keys.int().view(n, 1)
+    assert torch.equal(ops.mask_argsort(mask, 27).long(), expect)
+    if n == 512 * 257:
+        assert torch.equal(ops.mask_argsort(mask, 0).long(), expect)
+
+
 def test_layout_conversions_round_trip(cuda):
     """spx_native_to_table / spx_table_to_native reproduce the builder's own artefacts."""
     from spconv_amd.pytorch import ops
