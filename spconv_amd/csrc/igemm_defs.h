@@ -1,5 +1,5 @@
-// Shared definitions of the gather-GEMM translation units (igemm.hip: the 128-row direct-fragment
-// kernels, wgrad, dispatch and the C ABI; igemm_gen1.hip; igemm_bwdn.hip).
+// Shared definitions of the gather-GEMM translation units: igemm.hip (dispatch and the C ABI of forward, dgrad and
+// the fused backward), igemm_wgrad.hip (the weight gradient), one unit per operand type, igemm_gen1.hip, igemm_bwdn.hip.
 #pragma once
 #include "common.h"
 
@@ -249,7 +249,8 @@ __device__ __forceinline__ void wg_bn_stats_empty(float *__restrict__ stats, int
   if (threadIdx.x < COUT) bn_record_store<COUT>(stats, rec, nrec, threadIdx.x, 0.f, 0.f, 0.f);
 }
 
-// balanced-segment weight gradient (igemm_bwd.h: wgrad_tr_body / wgrad_f32_body; plan: wgrad_plan2_kernel in igemm.hip)
+// balanced-segment weight gradient (igemm_bwd.h: wgrad_tr_body / wgrad_f32_body; plan: wgrad_plan2_kernel in
+// igemm_wgrad.hip)
 struct Wgrad2Params {
   const void *feat;        // [n_in, C]
   const void *dout;        // [n_out, K]
@@ -262,7 +263,7 @@ struct Wgrad2Params {
 };
 
 // One translation unit per operand type (the template bodies live in igemm_v4.h / igemm_bwd.h; igemm.hip holds the f16
-// instantiations, the generic kernels, the plans and the C ABI): a full rebuild compiles them side by side.
+// instantiations, the generic gather-GEMM and the C ABI): a full rebuild compiles them side by side.
 int dispatch_gather_gemm_bf16(const GemmParams &p, hipStream_t s);                                   // igemm_bf16.hip
 int dispatch_bwd_bf16(const GemmParams &p, const Wgrad2Params &q, int n_wgrad_blocks, hipStream_t s);
 int dispatch_gather_gemm_f32(const GemmParams &p, hipStream_t s);                                    // igemm_f32.hip
@@ -285,6 +286,35 @@ size_t wgrad_f64_ws_bytes(int n_in, int C, int K, int kv);
 int wgrad_f64(const void *feat, const void *dout, void *dw, const int32_t *pair_native, const int32_t *num_per_loc,
               int n_in, int C, int K, int kv, int subm, void *ws, size_t ws_bytes, hipStream_t s);
 int bias_act_f64(void *out, const void *bias, int n, int K, int act, float act_alpha, hipStream_t s);
+// igemm_wgrad.hip: what the fused backward (igemm.hip) takes from the weight gradient's unit
+// the caller's plan, or one built at ws + ws_bytes - spx_wgrad_plan_bytes (behind the partials); null = the build failed
+const int32_t *wgrad_plan_or_build(const int32_t *plan, const int32_t *num_per_loc, int n_in, int kv, int subm, void *ws,
+                                   size_t ws_bytes, spx_stream_t stream);
+Wgrad2Params wgrad2_params(const void *feat, const void *dout, void *ws, const int32_t *pair_native,
+                           const int32_t *num_per_loc, const int32_t *plan, int n_in, int n_out, int C, int K, int kv,
+                           int subm);
+int launch_reduce2(const Wgrad2Params &q, void *dw, int dtype, int ntile, hipStream_t s, void *defer);
+int igemm_wgrad_impl(const void *feat, const void *dout, void *dw, const int32_t *pair_native,
+                     const int32_t *num_per_loc, const int32_t *plan, int n_in, int n_out, int C, int K, int kv,
+                     int dtype, int subm, void *ws, size_t ws_bytes, spx_stream_t stream, void *stage2_job);
+
+inline int elem_bytes(int dtype) { return dtype == SPX_F64 ? 8 : (dtype == SPX_F32 ? 4 : (dtype == SPX_I8 ? 1 : 2)); }
+
+// ---- 32-bit buffer offsets ------------------------------------------------------------------------------------------
+// The MFMA kernels address a tensor through one raw buffer resource with 32-bit byte offsets: a [rows, width] array of
+// elem_bytes-sized elements qualifies below 0x7fff0000 bytes (kOob and beyond mark out-of-range lanes).
+inline bool fits32(long long rows, long long width, int elem_bytes) {
+  return static_cast<unsigned long long>(rows) * width * elem_bytes < 0x7fff0000ull;
+}
+// the resources of the gathered operands of a weight gradient: dout [n_out, K] and feat [n_in, C]
+inline bool wgrad_rows_fit(int n_in, int n_out, int C, int K, int es) { return fits32(n_out, K, es) && fits32(n_in, C, es); }
+// the pair lists [2, kv, n_in] of the 16-bit weight gradient and of the fused backward of every dtype: the in list (row
+// k) and the out list (row kv + k) of an offset are read through ONE resource that starts at the in list
+inline bool wgrad_lists_fit(int n_in, int kv) { return fits32(n_in, kv + 1, 4); }
+// the stand-alone f32 weight gradient asks for less: one list below the bound.  The two rules differ, and nobody has
+// established which of them wgrad_f32_body needs; each launch path keeps the one it has always had.
+inline bool wgrad_f32_list_fits(int n_in) { return fits32(n_in, 1, 4); }
+
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -346,6 +376,30 @@ template <bool BF16> __device__ __forceinline__ uint32_t pack2(float a, float b)
     typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, f16x2));
   }
+}
+
+// element types of the kernels that are templated on one (generic gather-GEMM and weight gradient, the second stages,
+// bias_act): fp32 accumulate whatever the storage
+template <typename T> __device__ __forceinline__ float load_f(const T *p);
+template <> __device__ __forceinline__ float load_f<float>(const float *p) { return *p; }
+struct h16 { uint16_t v; };
+struct b16 { uint16_t v; };
+template <> __device__ __forceinline__ float load_f<h16>(const h16 *p) { return to_float<false>(p->v); }
+template <> __device__ __forceinline__ float load_f<b16>(const b16 *p) { return to_float<true>(p->v); }
+template <typename T> __device__ __forceinline__ void store_f(T *p, float f);
+template <> __device__ __forceinline__ void store_f<float>(float *p, float f) { *p = f; }
+template <> __device__ __forceinline__ void store_f<h16>(h16 *p, float f) { p->v = from_float<false>(f); }
+template <> __device__ __forceinline__ void store_f<b16>(b16 *p, float f) { p->v = from_float<true>(f); }
+
+// The one dtype switch of those kernels: calls f(T{}, slot) with T = float, h16 or b16 and slot = the type's instance
+// counter slot as a std::integral_constant (f16 0, bf16 1, f32 3: the kernels' DT codes).  Any other dtype is an error.
+template <typename F>
+int with_elem_type(int dtype, F &&f) {
+  if (dtype == SPX_F32) f(float{}, std::integral_constant<int, 3>{});
+  else if (dtype == SPX_F16) f(h16{}, std::integral_constant<int, 0>{});
+  else if (dtype == SPX_BF16) f(b16{}, std::integral_constant<int, 1>{});
+  else SPX_CHECK(false, "unsupported dtype %d", dtype);
+  return 0;
 }
 
 __device__ __forceinline__ float apply_act(float v, int act, float alpha) {

@@ -78,7 +78,7 @@ def bwd_key(dtype, C, K, pk_mode=1):
 
 
 def wgrad_key(dtype, C, K):
-    """first stage of spx_igemm_wgrad for lane-multiple widths (igemm.hip wgrad dispatch: sl from the padded widths)."""
+    """first stage of spx_igemm_wgrad for lane-multiple widths (igemm_wgrad.hip igemm_wgrad_impl: sl from the padded widths)."""
     if dtype == F32:
         return "wgrad_f32"
     C, K = padw(C, dtype), padw(K, dtype)
@@ -96,8 +96,8 @@ def reachable():
     - igemm_bwd: dispatch_bwd (igemm_bwd.h:400-409) for COUT 16..128, MB 2; launch_bwd's forms (:386-396);
     - igemm_ws: launch_gather_gemm_ws (igemm_ws.hip:413-445), f16 / bf16;
     - igemm_bwd_rows: spx_igemm_bwd_rows (igemm_bwdn.hip:431-435): eight waves at C = K = 16 only;
-    - wgrad_tr / wgrad_f32 / wgrad_mfma / wgrad_generic: igemm_wgrad_impl (igemm.hip:1104-1175);
-    - generic: run_gather_gemm_single (igemm.hip:708-743); gen1: launch_gen1_cout (igemm_gen1.hip:284-293)."""
+    - wgrad_tr / wgrad_f32 / wgrad_mfma / wgrad_generic: igemm_wgrad_impl (igemm_wgrad.hip:749-828);
+    - generic: run_gather_gemm_single (igemm.hip:105-134); gen1: launch_gen1_cout (igemm_gen1.hip:284-293)."""
     keys = set()
     for dt in ("f16", "bf16"):
         for cout, mb in ((16, 1), (16, 2), (32, 1), (32, 2), (64, 1), (64, 2), (128, 1), (256, 1)):

@@ -261,7 +261,7 @@ def test_remove_duplicate_keeps_first_row_of_a_coordinate():
 
 
 def test_xcd_aware_mappings_are_bijective():
-    """The block -> tile map of the fused backward (csrc/igemm.hip: xcd_tile_rot) and the block -> range
+    """The block -> tile map of the fused backward (csrc/igemm_defs.h: xcd_tile_rot) and the block -> range
     hand-out of the wgrad plan (wgrad_plan2_kernel, rec[5]) restated in Python: every tile / range is
     taken exactly once, and a workgroup that runs on XCD x gets work of row eighth x."""
     def xcd_tile_rot(bid, ntiles, rot):
@@ -322,7 +322,7 @@ def test_global_avg_pool_accumulates_in_fp32(dtype):
 
 
 def test_wgrad_plan_cost_space_cut_covers_every_pair_once():
-    """wgrad_plan2_kernel (csrc/igemm.hip) restated: the pair lists are laid end to end in COST units
+    """wgrad_plan2_kernel (csrc/igemm_wgrad.hip) restated: the pair lists are laid end to end in COST units
     (pairs + a fixed pad per non-empty list) and cut into G equal ranges; a segment is the part of a
     list's PAIRS inside a range.  Every pair belongs to exactly one segment, the closed form the second
     stage uses for the segments of a list equals their enumerated count, and the short lists of a sparse

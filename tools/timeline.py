@@ -123,12 +123,12 @@ def main():
                             tile_order=to) if i8 else ops.igemm_fwd(f, w, pair, mask, order, n, 13, tile_order=to))
     buf = np.zeros((8192, 8), dtype=np.uint64)
     _lib.check(getter(buf.ctypes.data))
-    mb = 2 if n > 32 * 1024 else 1                 # the library's tile-height rule (csrc/igemm.hip dispatch_gather_gemm)
+    mb = 2 if n > 32 * 1024 else 1                 # the library's tile-height rule (csrc/igemm_v4.h dispatch_gather_gemm)
     ntiles = (n + 64 * mb - 1) // (64 * mb)
     if i8:
         ntiles = (n + 127) // 128
     napp = 0
-    if srt:                       # rows layout: the appendix workgroups lead the grid (csrc/igemm.hip)
+    if srt:                       # rows layout: the appendix workgroups lead the grid (csrc/igemm_v4.h)
         napp = (n // 4 + 64 * mb - 1) // (64 * mb)
     allt = buf[:napp + ntiles].astype(np.int64)
     app = allt[:napp]
