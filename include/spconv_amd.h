@@ -583,6 +583,45 @@ int spx_point2voxel(const float *points, int n, int nfeat, int ndim, const float
                     int32_t *num_per_voxel, long long *pc_voxel_id, int *n_voxels_h, void *ws,
                     size_t ws_bytes, spx_stream_t stream);
 
+/* The voxeliser with static shapes: nothing is read back -- no copy to the host, no stream synchronisation, every
+ * grid a function of host-known sizes, one stream -- so the call can be recorded in a stream capture in front of a
+ * captured backbone pass (spconv_amd/pytorch/static.py).
+ *   points [n_cap, nfeat] fp32; *n_points_dev (device int32): only rows below it are points, the rows behind it may
+ *   hold anything (NaN included), get pc_voxel_id -1 and touch nothing else
+ *   point_batch [n_cap] device int32 or NULL (every point in scene 0): the batch index is the leading digit of the
+ *   voxel key; a point whose batch index is outside [0, batch_size) is dropped like a point outside the range
+ *   vsize / coors_range / grid_size: host arrays in ZYX order, as spx_point2voxel
+ *   indices [max_voxels, ndim + 1]: batch index, then zyx (the layout of a SparseConvTensor)
+ *   num_per_voxel [max_voxels], pc_voxel_id [n_cap] int64
+ *   voxels [max_voxels, max_points, nfeat] fp32, or NULL (only the mean is wanted): neither cleared nor written
+ *   n_voxels_dev (device int32 [2]) = {voxels kept, voxels found}; found > kept: the scene hit max_voxels
+ *   DEAD ROWS: every row >= kept comes out dead on every call, whatever the call before left there: -1 in every
+ *   column of indices, count 0, zeros in voxels and mean_out (the padding contract of the static runners).
+ * key_order = 0: voxels numbered first-seen by point index over the whole array, the first max_points points of a
+ *   voxel kept in point order, voxels past max_voxels dropped.  With batch_size 1 and point_batch NULL the live rows
+ *   of the zyx columns, of num_per_voxel, voxels and pc_voxel_id equal spx_point2voxel's bit for bit.  Grids beyond
+ *   2^32 cells take the 64-bit-key form of the hash table.
+ * key_order = 1: the same kept set (at the cap: the first max_voxels voxels in first-seen order), numbered by
+ *   ascending linear key (batch-major, last axis fastest); pc_voxel_id, the stored points and the counts follow.
+ *   With rankmap (>= spx_rankmap_bytes(ndim, batch_size, grid_size) bytes) the call leaves the level's rank map of
+ *   `indices` behind: every key answers with its row, as in the map spx_rankmap_from_sorted builds from the same
+ *   rows; keys are unique by construction, there is no violation flag.  Needs batch x grid <= 0xffe00000 cells and a
+ *   rank map of at most 1 GiB: beyond that the call (and the workspace query: 0) fails -- number first-seen and sort.
+ * mean_out [max_voxels, nfeat] of mean_dtype SPX_F32 / SPX_F16 / SPX_BF16, or NULL: row v = the stored points
+ *   j = 0 .. num - 1 of voxel v added in that order in fp32, divided by num in fp32, rounded to nearest-even; computed
+ *   from the points, never from the empty-slot fill.
+ * empty_mean: 0 or 1 (1 needs voxels); 2, the sequential reference-quirk recurrence, stays with spx_point2voxel.
+ * ws >= spx_point2voxel_static_ws_bytes(...) bytes (key_order = 1: + a rank map of the call's own for a caller that
+ * passes none). */
+size_t spx_point2voxel_static_ws_bytes(int n_cap, int max_voxels, int ndim, int batch_size, const int *grid_size,
+                                       int key_order);
+int spx_point2voxel_static(const float *points, const int32_t *point_batch, int n_cap, const int32_t *n_points_dev,
+                           int nfeat, int ndim, const float *vsize, const float *coors_range, const int *grid_size,
+                           int batch_size, int max_voxels, int max_points, int empty_mean, int key_order,
+                           float *voxels, int32_t *indices, int32_t *num_per_voxel, long long *pc_voxel_id,
+                           int32_t *n_voxels_dev, void *mean_out, int mean_dtype, void *rankmap, size_t rankmap_bytes,
+                           void *ws, size_t ws_bytes, spx_stream_t stream);
+
 /* ---------------------------------------------------------------- hash table */
 
 /* Fixed-size hash table over caller-owned storage.  Replaces

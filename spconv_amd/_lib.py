@@ -119,6 +119,11 @@ SIGNATURES = {
                                        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                        c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        vp, vp, vp, vp, c_int_p, vp, ctypes.c_size_t, vp]),
+    "spx_point2voxel_static_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4 + [c_int_p, ctypes.c_int]),
+    "spx_point2voxel_static": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_int_p]
+                               + [ctypes.c_int] * 5 + [vp] * 6 + [ctypes.c_int, vp, ctypes.c_size_t, vp,
+                                                                  ctypes.c_size_t, vp]),
     "spx_hash_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "spx_hash_clear": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp]),
     "spx_hash_insert": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp]),

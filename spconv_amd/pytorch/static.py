@@ -180,7 +180,14 @@ def _entry(runner):
     a result that lives on the input's rows goes back into the caller's order before the runner returns it (_exit), levels
     behind a strided layer are in key order with or without the sort; `runner.order[t]` = the input row behind sorted
     row t, for code that looks at tensors INSIDE the network.  The coordinates of a scene must be unique (a voxeliser's
-    are): `runner.input_order_violation()` reads the device-side verdict."""
+    are): `runner.input_order_violation()` reads the device-side verdict.
+    A runner built on a voxeliser (`voxelizer=`) starts the pass with its one call; a key-ordered voxeliser's index
+    buffer already carries the level's rank map, written by that call: true by construction, nothing to sort or declare."""
+    vox = getattr(runner, "voxelizer", None)
+    if vox is not None:
+        vox.run()
+        if vox.key_order:
+            return runner.features, runner.indices
     if runner.key_ordered_input or not runner.entry_sort:
         _declare_key_order(runner)
         return runner.features, runner.indices
@@ -230,6 +237,25 @@ def _input_order_violation(runner) -> bool:
     return bool(int(runner._order_flag.item()) != 0)
 
 
+def _check_voxelizer(vox, max_voxels, in_channels, spatial_shape, batch_size, dtype, device) -> None:
+    """A voxeliser at the head of a captured pass must describe the level the runner was asked for."""
+    from spconv_amd.pytorch.utils import StaticPointToVoxel
+    if not isinstance(vox, StaticPointToVoxel):
+        raise TypeError(f"voxelizer must be a StaticPointToVoxel, got {type(vox).__name__}")
+    want = {"max_voxels": (int(max_voxels), vox.max_num_voxels),
+            "spatial_shape": ([int(v) for v in spatial_shape], list(vox.grid_size)),
+            "batch_size": (int(batch_size), vox.batch_size),
+            "in_channels": (int(in_channels), vox.num_point_features),
+            "dtype": (dtype, vox.mean_dtype)}
+    for name, (asked, has) in want.items():
+        if asked != has:
+            raise ValueError(f"voxelizer does not fit the runner: {name} is {asked}, the voxeliser has {has}")
+    if device is not None:
+        d = torch.device(device)
+        if d.type != vox.device.type or (d.index is not None and d.index != vox.device.index):
+            raise ValueError(f"voxelizer lives on {vox.device}, the runner was asked for {d}")
+
+
 class StaticInference:
     """`net` (eval mode, SparseConvTensor -> SparseConvTensor or tensor) captured for scenes of at
     most `max_voxels` voxels.
@@ -243,15 +269,28 @@ class StaticInference:
 
     Constructing the runner freezes `static_num_out` on the network's strided layers: until `release_bounds()`
     every pass of `net` -- also an eager one outside the runner -- stays bounded and padded with dead rows.
+
+    From points: `voxelizer=StaticPointToVoxel(...)` (spconv_amd.pytorch.utils; same max_voxels, grid, batch size,
+    `num_point_features == in_channels`, `mean_dtype == dtype`) puts the voxeliser's one call at the head of the captured
+    pass: the network reads its mean feature rows, its index buffer and its device-side voxel count, nothing is read back
+    between the points and the result.
+
+        out = runner.run_points(pc, batch_ids=None)      # load the points, replay
+        runner.voxelizer.pc_voxel_id                     # voxel row of every point, to carry results back
     """
 
     def __init__(self, net: torch.nn.Module, max_voxels: int, in_channels: int,
                  spatial_shape: Sequence[int], batch_size: int, dtype: torch.dtype = torch.float16,
                  bounds: Optional[Dict[str, int]] = None, margin: float = 1.25,
                  device: Optional[torch.device] = None, warmup: int = 2, capture_error_mode: str = "global",
-                 key_ordered_input: bool = False, entry_sort: Optional[bool] = None):
+                 key_ordered_input: bool = False, entry_sort: Optional[bool] = None, voxelizer=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StaticInference needs the GPU (there is no CPU path)")
+        self.voxelizer = voxelizer
+        if voxelizer is not None:
+            _check_voxelizer(voxelizer, max_voxels, in_channels, spatial_shape, batch_size, dtype, device)
+            device = voxelizer.device
+            key_ordered_input = voxelizer.key_order
         self.key_ordered_input = bool(key_ordered_input)
         self.entry_sort = _entry_sort_default(net) if entry_sort is None else bool(entry_sort)
         self.order = None
@@ -263,9 +302,12 @@ class StaticInference:
         self.bounds = freeze_bounds(net, bounds, margin)
         self._layers = strided_layers(net)
         nd = len(self.spatial_shape)
-        self.features = torch.zeros((self.max_voxels, in_channels), dtype=dtype, device=self.device)
-        self.indices = torch.full((self.max_voxels, nd + 1), -1, dtype=torch.int32, device=self.device)
-        self.n_live = torch.zeros((1,), dtype=torch.int32, device=self.device)   # rows of the current scene
+        if voxelizer is not None:           # the network reads the voxeliser's static buffers
+            self.features, self.indices, self.n_live = voxelizer.mean, voxelizer.indices, voxelizer.n_voxels[0:1]
+        else:
+            self.features = torch.zeros((self.max_voxels, in_channels), dtype=dtype, device=self.device)
+            self.indices = torch.full((self.max_voxels, nd + 1), -1, dtype=torch.int32, device=self.device)
+            self.n_live = torch.zeros((1,), dtype=torch.int32, device=self.device)   # rows of the current scene
         self._order_flag = torch.zeros((1,), dtype=torch.int32, device=self.device)
         self._live = 0
         self.graph = None
@@ -295,6 +337,8 @@ class StaticInference:
 
     def load(self, features: torch.Tensor, indices: torch.Tensor) -> None:
         """Copies one scene into the static input buffers (stream-ordered, no synchronisation)."""
+        if self.voxelizer is not None:
+            raise ValueError("this runner starts from points (voxelizer=...): use run_points(pc, batch_ids)")
         n = features.shape[0]
         if n > self.max_voxels:
             raise ValueError(f"scene has {n} voxels, the graph was captured for at most {self.max_voxels}")
@@ -313,6 +357,16 @@ class StaticInference:
             self.graph.replay()
         return self.out
 
+    def run_points(self, pc: torch.Tensor, batch_ids: Optional[torch.Tensor] = None):
+        """Points in, result out, in one replay (a runner built with `voxelizer=`): the points (and the scene index of
+        each) are copied into the voxeliser's buffers, the graph does the rest.  Nothing is read back."""
+        if self.voxelizer is None:
+            raise ValueError("run_points needs a runner built with voxelizer=StaticPointToVoxel(...)")
+        with torch.cuda.device(self.device):
+            self.voxelizer.load(pc, batch_ids)
+            self.graph.replay()
+        return self.out
+
     def counts(self) -> Dict[str, List[int]]:
         """{layer: [outputs found, hash-table overflow flag]} of the last replay (synchronises)."""
         if not self._counters:
@@ -323,8 +377,15 @@ class StaticInference:
 
     def overflowed(self) -> Dict[str, int]:
         """Layers whose last replay found more outputs than their bound (or filled their hash table):
-        {layer: outputs found}.  Empty = every live row is exact."""
-        return {k: c for k, (c, ovf) in self.counts().items() if c > self.bounds[k] or ovf}
+        {layer: outputs found}.  Empty = every live row is exact.  A voxeliser at the head of the pass that found more
+        voxels than it keeps is listed as "voxelizer"."""
+        over = {k: c for k, (c, ovf) in self.counts().items() if c > self.bounds[k] or ovf}
+        vox = getattr(self, "voxelizer", None)
+        if vox is not None:
+            kept, found = vox.n_voxels.tolist()
+            if found > kept:
+                over["voxelizer"] = found
+        return over
 
     input_order_violation = _input_order_violation
 

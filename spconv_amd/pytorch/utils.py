@@ -8,7 +8,7 @@ voxels are numbered in first-seen point order and keep their first
 from __future__ import annotations
 
 import ctypes
-from typing import List, Union
+from typing import List, Optional, Union
 
 import numpy as np
 import torch
@@ -107,6 +107,144 @@ class PointToVoxel(object):
                         self.num_per_voxel[:num_voxels][order].contiguous(), pc_voxel_id)
             return (self.voxels[:num_voxels].clone(), self.indices[:num_voxels].clone(),
                     self.num_per_voxel[:num_voxels].clone(), pc_voxel_id)
+
+
+class StaticPointToVoxel(object):
+    """The voxeliser with static shapes (``spx_point2voxel_static``; not in the reference): points in, key-ordered
+    voxels and their mean feature rows out, nothing read back -- so it can be recorded in a stream capture, in front of a
+    captured backbone pass (``StaticInference(net, ..., voxelizer=...)``).
+
+        gen = StaticPointToVoxel([0.1, 0.1, 0.2], [0, -40, -3, 70.4, 40, 1], 4, max_num_voxels=120_000,
+                                 max_num_points_per_voxel=5, max_num_points=300_000, mean_dtype=torch.float16)
+        voxels, indices, num_per_voxel, pc_voxel_id = gen(pc)      # the static buffers, full length
+        gen.mean, gen.n_voxels                                      # [max_num_voxels, F]; device {kept, found}
+
+    The object owns every buffer -- points, batch ids, the point count, all outputs, the scratch -- and allocates nothing
+    per call.  ``load(pc, batch_ids=None)`` copies one batch of points in (stream-ordered; more than ``max_num_points``
+    raises ValueError), ``run(empty_mean=False)`` is the one C call, ``__call__`` does both.  Rows behind the voxels
+    kept come out DEAD on every call: -1 in every column of ``indices`` ([max_num_voxels, ndim + 1]: batch index, then
+    zyx -- what a SparseConvTensor takes), count 0, zeros in ``voxels`` and ``mean``: the padding contract of
+    ``spconv_amd.pytorch.static``.  ``n_voxels`` stays on the device; ``overflowed()`` reads it (one synchronisation).
+
+    ``key_order=True`` (default): voxels numbered by ascending coordinate key (batch-major, last axis fastest) -- the set
+    kept at the cap is still the first ``max_num_voxels`` in first-seen order -- and ``indices`` carries the level's rank
+    map as its tag, the way ``ops.key_argsort(..., rank_map=True)`` attaches it: the SubM layers of the first level build
+    their rulebooks without a hash table.  A grid whose key space has no rank map (``batch_size`` x grid beyond 0xffe00000
+    cells, or beyond the size gates of ``ops.attach_rank_map``) raises ValueError: construct with ``key_order=False``
+    (first-seen numbering, as ``PointToVoxel``) and let the runner sort.
+    ``mean_dtype`` (float32 / float16 / bfloat16, None = no mean): ``mean[v]`` = the stored points of voxel v added in
+    point order in fp32, divided by their number in fp32, rounded to nearest-even.  ``keep_voxels=False`` drops the
+    ``[max_num_voxels, max_num_points_per_voxel, F]`` tensor (``voxels`` is None) when only the mean is wanted."""
+
+    def __init__(self, vsize_xyz: List[float], coors_range_xyz: List[float], num_point_features: int,
+                 max_num_voxels: int, max_num_points_per_voxel: int, max_num_points: int, batch_size: int = 1,
+                 key_order: bool = True, mean_dtype: Optional[torch.dtype] = None, keep_voxels: bool = True,
+                 device: torch.device = torch.device("cuda:0")):
+        from spconv_amd.pytorch import _rulebook
+        self.ndim = len(vsize_xyz)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise NotImplementedError("spconv_amd runs on MI355X only: construct StaticPointToVoxel with a "
+                                      "cuda device (there is no CPU path)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if min(int(max_num_voxels), int(max_num_points_per_voxel), int(max_num_points), int(batch_size)) < 1:
+            raise ValueError("max_num_voxels, max_num_points_per_voxel, max_num_points and batch_size must be positive")
+        if mean_dtype is not None and mean_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"mean_dtype must be float32, float16 or bfloat16, got {mean_dtype}")
+        vsize, grid_size, grid_stride, coors_range = calc_point2voxel_meta_data(vsize_xyz, coors_range_xyz)
+        self.num_point_features = int(num_point_features)
+        self.max_num_voxels = int(max_num_voxels)
+        self.max_num_points_per_voxel = int(max_num_points_per_voxel)
+        self.max_num_points = int(max_num_points)
+        self.batch_size = int(batch_size)
+        self.key_order = bool(key_order)
+        self.mean_dtype = mean_dtype
+        self.vsize, self.grid_size, self.grid_stride, self.coors_range = vsize, grid_size, grid_stride, coors_range
+        L = _lib.load()
+        grid_c = _lib.ints(grid_size)
+        rank_bytes = 0
+        if self.key_order:
+            cells = _rulebook._cells(self.batch_size, grid_size)
+            rank_bytes = int(L.spx_rankmap_bytes(self.ndim, self.batch_size, grid_c)) if cells <= 0xffe00000 else 0
+            if not _rulebook._rankmap_fits(rank_bytes, cells, self.max_num_voxels):
+                raise ValueError(f"key_order=True numbers voxels through the level's rank map, and {self.batch_size} x "
+                                 f"{grid_size} ({cells} cells for {self.max_num_voxels} voxels) has none: construct "
+                                 f"with key_order=False")
+        ws_bytes = int(L.spx_point2voxel_static_ws_bytes(self.max_num_points, self.max_num_voxels, self.ndim,
+                                                         self.batch_size, grid_c, int(self.key_order)))
+        if ws_bytes == 0:
+            raise ValueError(f"no static voxeliser for {self.batch_size} x {grid_size} with key_order={self.key_order}")
+        with torch.cuda.device(self.device):
+            new = dict(device=self.device)
+            self.points = torch.zeros([self.max_num_points, self.num_point_features], dtype=torch.float32, **new)
+            self.batch_ids = torch.zeros([self.max_num_points], dtype=torch.int32, **new)
+            self.n_points = torch.zeros([1], dtype=torch.int32, **new)
+            self.voxels = (torch.zeros([self.max_num_voxels, self.max_num_points_per_voxel, self.num_point_features],
+                                       dtype=torch.float32, **new) if keep_voxels else None)
+            self.indices = torch.full([self.max_num_voxels, self.ndim + 1], -1, dtype=torch.int32, **new)
+            self.num_per_voxel = torch.zeros([self.max_num_voxels], dtype=torch.int32, **new)
+            self.pc_voxel_id = torch.full([self.max_num_points], -1, dtype=torch.int64, **new)
+            self.n_voxels = torch.zeros([2], dtype=torch.int32, **new)          # {kept, found}
+            self.mean = (None if mean_dtype is None else
+                         torch.zeros([self.max_num_voxels, self.num_point_features], dtype=mean_dtype, **new))
+            self._ws = torch.empty([ws_bytes], dtype=torch.uint8, **new)
+            self._rankmap = torch.zeros([rank_bytes // 4], dtype=torch.int32, **new) if self.key_order else None
+        if self._rankmap is not None:       # (behind the last in-place write of `indices`: the tag records its version)
+            _rulebook._tag_rank_map(self.indices, self._rankmap, self.batch_size, grid_size, self.max_num_voxels)
+        self._ids_loaded = False
+        f = lambda v: (ctypes.c_float * len(v))(*v)
+        self._host = (f(vsize), f(coors_range), grid_c)        # host arrays of the call, made once
+        self._L = L
+
+    def load(self, pc: torch.Tensor, batch_ids: Optional[torch.Tensor] = None) -> None:
+        """Copies one batch of points (and the scene index of each, default scene 0) into the static buffers:
+        stream-ordered, no synchronisation."""
+        assert pc.ndim == 2 and pc.shape[1] == self.num_point_features, \
+            "your points num features doesn't equal to voxel."
+        n = pc.shape[0]
+        if n > self.max_num_points:
+            raise ValueError(f"{n} points, the buffers were sized for at most {self.max_num_points}")
+        with torch.cuda.device(self.device), torch.no_grad():
+            self.points[:n].copy_(pc, non_blocking=True)
+            if batch_ids is not None:
+                assert batch_ids.shape == (n,), "one batch index per point"
+                self.batch_ids[:n].copy_(batch_ids, non_blocking=True)
+                self._ids_loaded = True
+            elif self._ids_loaded:
+                self.batch_ids.zero_()
+                self._ids_loaded = False
+            self.n_points.fill_(n)
+
+    def run(self, empty_mean: bool = False) -> None:
+        """The one C call over whatever `load` left in the buffers: no allocation, nothing read back."""
+        if empty_mean and self.voxels is None:
+            raise ValueError("empty_mean fills the unused slots of `voxels`: construct with keep_voxels=True")
+        p = lambda t: None if t is None else t.data_ptr()
+        vsize, coors_range, grid = self._host
+        _lib.check(self._L.spx_point2voxel_static(
+            self.points.data_ptr(), self.batch_ids.data_ptr(), self.max_num_points, self.n_points.data_ptr(),
+            self.num_point_features, self.ndim, vsize, coors_range, grid, self.batch_size, self.max_num_voxels,
+            self.max_num_points_per_voxel, int(bool(empty_mean)), int(self.key_order), p(self.voxels),
+            self.indices.data_ptr(), self.num_per_voxel.data_ptr(), self.pc_voxel_id.data_ptr(),
+            self.n_voxels.data_ptr(), p(self.mean),
+            0 if self.mean is None else {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16,
+                                         torch.bfloat16: _lib.DTYPE_BF16}[self.mean.dtype],
+            p(self._rankmap), 0 if self._rankmap is None else self._rankmap.numel() * 4,
+            self._ws.data_ptr(), self._ws.numel(), torch._C._cuda_getCurrentRawStream(self.device.index)))
+
+    def __call__(self, pc: torch.Tensor, batch_ids: Optional[torch.Tensor] = None, empty_mean: bool = False):
+        """pc [N, F] -> (voxels, indices, num_per_voxel, pc_voxel_id): the static buffers, full length (rows behind
+        ``n_voxels[0]`` dead, ``pc_voxel_id`` -1 behind the N points)."""
+        self.load(pc, batch_ids)
+        with torch.cuda.device(self.device):
+            self.run(empty_mean)
+        return self.voxels, self.indices, self.num_per_voxel, self.pc_voxel_id
+
+    def overflowed(self) -> bool:
+        """True when the last run found more voxels than ``max_num_voxels`` (one synchronisation)."""
+        kept, found = self.n_voxels.tolist()
+        return found > kept
 
 
 def gather_features_by_pc_voxel_id(seg_res_features: torch.Tensor, pc_voxel_id: torch.Tensor,
