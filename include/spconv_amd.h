@@ -105,6 +105,24 @@ int spx_set_option(const char *name_h, int value);
  *   pool/<op>/<dt>/<piece>                         op: max_fwd | max_bwd | avg_fwd | avg_bwd; dt: f16 | bf16 | f32 | f64 |
  *                                                  i8; piece: v (16-byte pieces, C a multiple of 16 / sizeof(dt)) | s (one
  *                                                  element per thread).  int8 exists for max_fwd only: 34 instances.
+ * The rulebook builders over the hash table (spx_subm_rulebook, spx_conv_rulebook_count / _fill / _static) count every
+ * dispatch decision of a build, where the launch is issued:
+ *   rulebook/subm_probe3 | subm_probe4 | subm_probe5  form of the SubM probe pass (probe3: kernel volume 1, beyond 128,
+ *                                                  or more than 4 M voxels; probe5: tables of 2^10 .. 2^19 slots)
+ *   rulebook/subm_mask_pass                        SubM masks from a pass over the finished table (SPX_SUBM_MASK_PASS)
+ *   rulebook/subm_lists, rulebook/native_lists_v1  SubM Native lists from the probe's group counts / by count -> scan ->
+ *                                                  scatter (behind subm_probe3)
+ *   rulebook/conv3/<MJ>, rulebook/conv_generic     strided convolution: compact-candidate passes (MJ in {1, 2, 4, 8}
+ *                                                  candidates per input) / one thread per (offset, input) (SPX_CONV_V = 2,
+ *                                                  transposed, stride 1, ...); once per count pass and once per fill pass
+ *   rulebook/conv_lists_v1                         strided-convolution lists by count -> scan -> scatter (kernel volume
+ *                                                  beyond 128)
+ *   rulebook/conv_shrunk, rulebook/conv_retry      count pass over a table sized for the outputs expected (last ratio /
+ *                                                  static bound); count pass run again at the guaranteed size after that
+ *                                                  table overflowed
+ *   rulebook/conv3_shares/<S>                      grid.y of the compact-candidate passes (S in {1, 2, 4, 8} shares per
+ *                                                  input row; SPX_TEST_CONV3_SHARES), once per count pass and once per
+ *                                                  fill pass
  * Host only. */
 long long spx_launch_count(const char *family_h);
 

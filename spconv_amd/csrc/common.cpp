@@ -36,6 +36,7 @@ std::atomic<long long> g_f64_launches[kF64Count];
 std::atomic<long long> g_dense_launches[kDenseCount];
 std::atomic<long long> g_union_launches[kUnionCount];
 std::atomic<long long> g_pool_launches[kPoolCount];
+std::atomic<long long> g_rulebook_launches[kRbCount];
 
 namespace {
 // "f16" | "bf16" | "i8" | "f32" -> the kernels' DT code, or -1
@@ -146,6 +147,18 @@ std::atomic<long long> *union_counter(const char *key) {
   return nullptr;
 }
 
+// counter of a rulebook-builder key rulebook/<pass> (spx_launch_count), or null
+std::atomic<long long> *rulebook_counter(const char *key) {
+  static const char *names[kRbCount] = {"subm_probe3", "subm_probe4", "subm_probe5", "subm_mask_pass", "subm_lists",
+                                        "native_lists_v1", "conv3/1", "conv3/2", "conv3/4", "conv3/8", "conv_generic",
+                                        "conv_lists_v1", "conv_shrunk", "conv_retry", "conv3_shares/1", "conv3_shares/2",
+                                        "conv3_shares/4", "conv3_shares/8"};
+  if (strncmp(key, "rulebook/", 9) != 0) return nullptr;
+  for (int i = 0; i < kRbCount; ++i)
+    if (strcmp(key + 9, names[i]) == 0) return &g_rulebook_launches[i];
+  return nullptr;
+}
+
 // counter of a pooling key pool/<op>/<dt>/<piece> (spx_launch_count), or null
 std::atomic<long long> *pool_counter(const char *key) {
   static const char *ops[kPoolOps] = {"max_fwd", "max_bwd", "avg_fwd", "avg_bwd"};
@@ -207,6 +220,7 @@ long long spx_launch_count(const char *family_h) {
   if (std::atomic<long long> *c = spx::dense_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::union_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pool_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::rulebook_counter(family_h)) return c->load(std::memory_order_relaxed);
   const int slot = spx::instance_slot(family_h);
   return slot < 0 ? -1 : spx::g_inst_launches[slot].load(std::memory_order_relaxed);
 }

@@ -204,6 +204,21 @@ constexpr int pool_slot(int op, int dt, bool scalar) { return (op * kPoolDts + d
 inline void count_pool(int op, int dt, bool scalar) {
   g_pool_launches[pool_slot(op, dt, scalar)].fetch_add(1, std::memory_order_relaxed);
 }
+
+// rulebook builders over the hash table (rulebook.hip: spx_subm_rulebook, spx_conv_rulebook_count / _fill / _static):
+// one counter per dispatch decision, counted on the host where the launch is issued.
+// Keys rulebook/<pass>: subm_probe3 | subm_probe4 | subm_probe5 (form of the SubM probe pass), subm_mask_pass (masks
+// from a pass over the finished table), subm_lists (lists from the probe's group counts), native_lists_v1 (SubM lists by
+// count -> scan -> scatter), conv3/1 | conv3/2 | conv3/4 | conv3/8 (compact-candidate passes, by candidates per input)
+// and conv_generic (thread per (offset, input)) -- both once in the count pass and once in the fill pass --,
+// conv_lists_v1 (conv lists by count -> scan -> scatter), conv_shrunk (table sized for an expectation), conv_retry
+// (count pass run again at the guaranteed size after an overflow), conv3_shares/1 | 2 | 4 | 8 (grid.y of the compact
+// passes, once per count pass and once per fill pass: the two must agree).
+enum RulebookPass { kRbSubmProbe3 = 0, kRbSubmProbe4, kRbSubmProbe5, kRbSubmMaskPass, kRbSubmLists, kRbNativeListsV1,
+                    kRbConv3_1, kRbConv3_2, kRbConv3_4, kRbConv3_8, kRbConvGeneric, kRbConvListsV1, kRbConvShrunk,
+                    kRbConvRetry, kRbShares1, kRbShares2, kRbShares4, kRbShares8, kRbCount };
+extern std::atomic<long long> g_rulebook_launches[kRbCount];
+inline void count_rulebook(RulebookPass p) { g_rulebook_launches[p].fetch_add(1, std::memory_order_relaxed); }
 }  // namespace spx
 
 // ---- row orders (rowsort.hip) ---------------------------------------------------------------------

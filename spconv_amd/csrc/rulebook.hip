@@ -607,7 +607,12 @@ conv_stage2_kernel(const int32_t *__restrict__ slot_of, const int32_t *__restric
     const int slot = slot_of[pos];
     if (slot >= 0) {
       oid = slot_out[slot];                          // -1: an output beyond the caller's bound
-      if (oid >= 0) pair_fwd[static_cast<size_t>(k) * n_out + oid] = i;
+      // rows that repeat a coordinate reach the same output through the same offset: the FIRST of them owns the
+      // entry (as in the SubM tables and the CPU lists' first entry), whatever order the workgroups run in --
+      // the table starts as 0xFFFFFFFF, an unsigned minimum
+      if (oid >= 0)
+        atomicMin(reinterpret_cast<unsigned int *>(&pair_fwd[static_cast<size_t>(k) * n_out + oid]),
+                  static_cast<unsigned int>(i));
     }
     pair_bwd[pos] = oid;
   }
@@ -874,7 +879,9 @@ conv3_pairs_kernel(const int32_t *__restrict__ indices, int n, Geom g,
       if (slot[j] >= 0) oid[j] = slot_out[slot[j]];    // -1: an output beyond the caller's bound
 #pragma unroll
     for (int j = 0; j < MJ; ++j)
-      if (oid[j] >= 0) pair_fwd[static_cast<size_t>(kk[j]) * n_out + oid[j]] = i;
+      if (oid[j] >= 0)      // (smallest row wins among rows that repeat a coordinate, as conv_stage2_kernel)
+        atomicMin(reinterpret_cast<unsigned int *>(&pair_fwd[static_cast<size_t>(kk[j]) * n_out + oid[j]]),
+                  static_cast<unsigned int>(i));
   }
   uint32_t mword = 0;
   for (int k = 0; k < kv; ++k) {
@@ -1327,9 +1334,23 @@ int conv3_cands(int ndim, const int *in_shape, const int *ksize, const int *stri
 // Shares per input row of the compact passes that are bound by dependent memory round trips (grid.y): a
 // power of two <= the candidate count, enough for ~1.5 M threads.
 int conv3_shares(int n_in, int mj) {
+  // tests only (spx_set_option): 1, 2 or 4 shares whatever the size, at most mj (0 = by size) -- a share count below
+  // mj otherwise takes 187 500 inputs and more
+  const int forced = option_int("SPX_TEST_CONV3_SHARES", 0);
+  if (forced == 1 || forced == 2 || forced == 4) return forced < mj ? forced : mj;
   int s = 1;
   while (s < mj && static_cast<long long>(n_in) * s < 1500000) s <<= 1;
   return s;
+}
+
+// Launch counter (rulebook/conv3/<mj> | rulebook/conv_generic) of the passes conv3_cands picked.
+RulebookPass conv_pass_counter(int mj) {
+  return mj == 0 ? kRbConvGeneric : (mj == 1 ? kRbConv3_1 : (mj == 2 ? kRbConv3_2 : (mj == 4 ? kRbConv3_4 : kRbConv3_8)));
+}
+
+// Launch counter (rulebook/conv3_shares/<s>) of the grid.y a compact pass is launched with.
+RulebookPass conv_shares_counter(int shares) {
+  return shares <= 1 ? kRbShares1 : (shares == 2 ? kRbShares2 : (shares == 4 ? kRbShares4 : kRbShares8));
 }
 
 #define SPX_CONV3_LAUNCH(kernel, mj, ...)                                     \
@@ -1482,6 +1503,7 @@ int spx_subm_rulebook(const int32_t *indices, int n, int ndim, int batch_size,
                        mask_pass ? static_cast<uint32_t *>(nullptr) : mask, words, pair_fwd, pair_bwd,
                        occ_bits ? occupied : static_cast<uint32_t *>(nullptr));
     const bool lists = pair_native || num_per_loc;
+    count_rulebook(probe5 ? kRbSubmProbe5 : kRbSubmProbe4);
     if (probe5) {
       const int fwords = occ_bits ? static_cast<int>(cap / 32) : 0;
       const size_t lds = static_cast<size_t>(fwords) * 4 + static_cast<size_t>(kv / 2) * (16 + 8 + 16);
@@ -1493,10 +1515,13 @@ int spx_subm_rulebook(const int32_t *indices, int n, int ndim, int batch_size,
       hipLaunchKernelGGL(subm_probe4_kernel, dim3(div_up(n, kBlock), kv / 2 + 1), dim3(kBlock), 0, s, indices, n,
                          g, t, slot_of, pair_fwd, pair_bwd, mask, words, lists ? groupcount : nullptr, nblk256, mask_pass);
     }
-    if (mask_pass)
+    if (mask_pass) {
+      count_rulebook(kRbSubmMaskPass);
       hipLaunchKernelGGL(mask_from_table_kernel, dim3(div_up(n, kBlock)), dim3(kBlock), 0, s, pair_fwd, kv, n, words, mask);
+    }
     if (lists) {
       SPX_CHECK(!pair_native || num_per_loc || kv / 2 <= 64, "num_per_loc required for kv > 128");
+      count_rulebook(kRbSubmLists);
       hipLaunchKernelGGL(subm_lists_kernel, dim3(nblk, kv / 2 + 1), dim3(kBlock), 0, s, pair_fwd, kv, n,
                          nblk256, groupcount, pair_native, num_per_loc ? num_per_loc : scratch_totals,
                          num_per_loc ? kv : 0);
@@ -1518,6 +1543,7 @@ int spx_subm_rulebook(const int32_t *indices, int n, int ndim, int batch_size,
   }
   SPX_HIP(fills.launch(s));
   hipLaunchKernelGGL(subm_insert_kernel, grid, dim3(kBlock), 0, s, indices, n, g, t, slot_of);
+  count_rulebook(kRbSubmProbe3);
   hipLaunchKernelGGL(subm_probe3_kernel, dim3(div_up(n, kBlock), kv / 2 + 1), dim3(kBlock), 0, s, indices,
                      n, g, t, slot_of, pair_fwd, pair_bwd, mask, words, pair_native);
   SPX_LAUNCH_CHECK();
@@ -1525,6 +1551,7 @@ int spx_subm_rulebook(const int32_t *indices, int n, int ndim, int batch_size,
     // num_per_loc: counts only for k < kv/2 (indices.py:1685,1692)
     int32_t *totals = num_per_loc ? num_per_loc : scratch_totals;
     SPX_CHECK(num_per_loc || kv / 2 <= 64, "num_per_loc required for kv > 128");
+    if (kv / 2 > 0) count_rulebook(kRbNativeListsV1);
     if (launch_native_lists(pair_fwd, 0, kv, n, kv / 2, nblk, blockcount, blockoff, pair_native,
                             totals, s))
       return -2;
@@ -1616,7 +1643,10 @@ int conv_count_impl(const int32_t *indices, int n_in, int ndim, int batch_size,
   const int mj = conv3_cands(ndim, in_shape, ksize, stride, padding, dilation, transposed);
   if (mj && expect_out > 0) {            // (the later passes of this form never touch the table)
     const uint32_t cap = table_capacity(expect_out);
-    if (cap < w.t.mask + 1u) table_shrink(w.t, cap);
+    if (cap < w.t.mask + 1u) {
+      count_rulebook(kRbConvShrunk);
+      table_shrink(w.t, cap);
+    }
   }
   {
     FillList fills;                      // table and flags in one launch
@@ -1629,8 +1659,10 @@ int conv_count_impl(const int32_t *indices, int n_in, int ndim, int batch_size,
     if (mj) fills.add(w.firstbits, sizeof(uint32_t) * static_cast<size_t>(g.kv) * w.nblk * (kItems / 32), 0u);
     SPX_HIP(fills.launch(s));
   }
+  count_rulebook(conv_pass_counter(mj));
   if (mj) {
     const int shares = conv3_shares(n_in, mj);
+    count_rulebook(conv_shares_counter(shares));
     SPX_CONV3_LAUNCH(conv3_insert_kernel, mj, dim3(div_up(n_in, kBlock), shares), dim3(kBlock), 0, s, indices, n_in, g,
                      w.t, w.slot_of, w.d_nout + 1);
     SPX_CONV3_LAUNCH(conv3_first_kernel, mj, dim3(div_up(n_in, kBlock), shares), dim3(kBlock), 0, s, indices, n_in, g, w.t,
@@ -1678,6 +1710,7 @@ int spx_conv_rulebook_count(const int32_t *indices, int n_in, int ndim, int batc
                            dilation, transposed, ws, ws_bytes, n_out_h, &overflow, expect, stream);
   if (rc) return rc;
   if (overflow && expect > 0) {          // the expectation was too small: once more, at the bound
+    count_rulebook(kRbConvRetry);
     rc = conv_count_impl(indices, n_in, ndim, batch_size, in_shape, out_shape, ksize, stride, padding,
                          dilation, transposed, ws, ws_bytes, n_out_h, &overflow, 0, stream);
     if (rc) return rc;
@@ -1728,8 +1761,11 @@ int conv_fill_impl(const int32_t *indices, int n_in, int ndim, int batch_size,
                            keys_fit_u32(g.batch, g.out_dims, 4));   // as spx_conv_rulebook_count
   const dim3 grid2(w.nblk, kv);
   const int mj = conv3_cands(ndim, in_shape, ksize, stride, padding, dilation, transposed);
+  count_rulebook(conv_pass_counter(mj));
   if (mj) {
-    SPX_CONV3_LAUNCH(conv3_assign_kernel, mj, dim3(div_up(n_in, kBlock), conv3_shares(n_in, mj)), dim3(kBlock), 0, s, indices, n_in, g,
+    const int shares = conv3_shares(n_in, mj);                 // (as the count pass: it wrote one flag plane per share)
+    count_rulebook(conv_shares_counter(shares));
+    SPX_CONV3_LAUNCH(conv3_assign_kernel, mj, dim3(div_up(n_in, kBlock), shares), dim3(kBlock), 0, s, indices, n_in, g,
                      static_cast<const int32_t *>(w.slot_of), w.nblk, static_cast<const uint32_t *>(w.firstbits),
                      static_cast<const uint8_t *>(w.firstflags), static_cast<const int32_t *>(w.wordpre),
                      static_cast<const int32_t *>(w.blockoff), w.slot_out, out_indices, n_out);
@@ -1759,6 +1795,7 @@ int conv_fill_impl(const int32_t *indices, int n_in, int ndim, int batch_size,
   }
   if (pair_native) {
     SPX_CHECK(num_per_loc, "num_per_loc is required with pair_native");
+    count_rulebook(kRbConvListsV1);
     if (launch_native_lists(pair_bwd, 1, kv, n_in, kv, w.nblk, w.blockcount, w.blockoff,
                             pair_native, num_per_loc, s))
       return -2;

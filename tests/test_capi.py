@@ -80,6 +80,19 @@ def test_workspace_size_queries(lib):
     assert lib.spx_table_to_native_ws_bytes(100_000, 27) > 0
 
 
+def test_rulebook_launch_counter_keys(lib):
+    """spx_launch_count knows every rulebook/<pass> key of include/spconv_amd.h and rejects malformed ones (nothing
+    launches)."""
+    for key in ("subm_probe3", "subm_probe4", "subm_probe5", "subm_mask_pass", "subm_lists", "native_lists_v1", "conv3/1",
+                "conv3/2", "conv3/4", "conv3/8", "conv_generic", "conv_lists_v1", "conv_shrunk", "conv_retry",
+                "conv3_shares/1", "conv3_shares/2", "conv3_shares/4", "conv3_shares/8"):
+        assert lib.spx_launch_count(f"rulebook/{key}".encode()) >= 0, key
+    for bad in ("rulebook", "rulebook/", "rulebook/subm_probe", "rulebook/subm_probe5/", "rulebook/conv3", "rulebook/conv3/",
+                "rulebook/conv3/3", "rulebook/conv3/16", "rulebook/conv3_shares/3", "subm_probe5", "rulebook/conv_v2",
+                "rulebook//conv_retry"):
+        assert lib.spx_launch_count(bad.encode()) == -1, bad
+
+
 def test_sorted_order_host_queries(lib):
     """Rank-map sizing and the geometries that take the sorted-order builder (host-only entry points)."""
     I = _lib.ints
