@@ -38,6 +38,10 @@ extern "C" {
 
 #define SPX_MAX_NDIM 4
 #define SPX_UNION_MAX_OPERANDS 8   /* operands of one misaligned add (spx_union_*) */
+/* reduction of an axis collapse (spx_collapse_fwd / _bwd) */
+#define SPX_COLLAPSE_SUM 0
+#define SPX_COLLAPSE_MEAN 1
+#define SPX_COLLAPSE_MAX 2
 
 typedef void *spx_stream_t; /* hipStream_t */
 
@@ -94,6 +98,10 @@ int spx_set_option(const char *name_h, int value);
  *   union/mark, union/prefix, union/claim, union/fill, union/add_fwd, union/add_bwd
  *                                                  misaligned add: the stages of the union build (prefix: the prefix
  *                                                  pass and its block scan, counted once) and the two merge launches
+ *   collapse/mark, collapse/prefix, collapse/rank, collapse/list, collapse/fwd, collapse/bwd
+ *                                                  axis collapse: the passes of the build (prefix: the prefix pass and
+ *                                                  its block scan; list: the radix argsort and the boundary launch
+ *                                                  behind it, counted once) and the two reduction launches
  * COUT in {16, 32, 64, 128, 256}, NKS in {1, 2}, PK in {1, 2, 4, 8, 16, 32}.  A well-formed key of an instance that is
  * never built counts 0; anything else is unknown.
  * float64 (SPX_F64) has a family and keys of its own, outside the dt vocabulary above:
@@ -848,6 +856,77 @@ int spx_union_add_fwd(const void *const *feat_h, const int *n_h, int T, const in
                       int dtype, void *out, const int32_t *n_live, spx_stream_t stream);
 int spx_union_add_bwd(const void *dout, int n_out, void *const *din_h, const int32_t *const *rows_h,
                       const int *n_h, int T, int C, int elem_bytes, spx_stream_t stream);
+
+/* ---- axis collapse (csrc/collapse.hip) -----------------------------------------------------------------
+ * Drops spatial axes of a sparse tensor and merges the rows that land on one cell of the PROJECTED grid: the height
+ * compression of the fully sparse detectors ((batch, z, y, x) rows -> (batch, y, x) rows, a SubMConv2d / SparseConv2d
+ * head behind).  Stands where a torch composite would: unique of the projected keys (a count read back), index_add_
+ * (float atomics: not reproducible), rows in `unique` order without a rank map, no notion of dead rows.
+ *
+ * indices = device int32 [n, ndim + 1], n_live = NULL or a device int32 (see spx_conv_rulebook_static).  axes_mask: bit
+ * d set = spatial axis d (0 = the first, z of a zyx tensor) is removed; at least one axis stays; 0 is legal and merges
+ * duplicate coordinates.  A row is DEAD -- contributes nothing -- when it lies at or beyond *n_live, when its batch index
+ * is outside [0, batch) or ANY coordinate, a removed one included, outside [0, extent).  Live rows are grouped by their
+ * projected coordinate (batch index + the kept axes in their order); a coordinate that occurs twice is two rows of its
+ * group.  OUTPUT ROWS are the groups in ascending linear key of the projected grid (batch-major, last kept axis
+ * fastest: the numbering of the sorted-order levels), numbered through the projected level's RANK MAP (the caller's
+ * buffer of spx_rankmap_bytes(kept axes); left behind, it describes the result, so spx_subm_rulebook_ranked applies):
+ * byte marks, the prefix pass, one 8-byte load per row -- no hash table, no atomic on the path that numbers the rows.
+ * THE ROWS OF A GROUP ARE LISTED IN ASCENDING INPUT ROW: the list is a stable radix argsort of the rows by their rank
+ * (dead rows take a key behind every rank), so the order is a property of the sort, not of any scheduling.
+ *   spx_collapse_ws_bytes: scratch of a build over n rows; 0 when the projected key space does not fit (the rule of
+ *   spx_rankmap_bytes on the projected grid), for an empty grid (any extent < 1), when no axis is kept, and for a mask
+ *   that names an axis >= ndim.
+ *   spx_collapse_count: marks, prefix pass, and the call's ONE D->H read (synchronises the stream):
+ *   result_h [2] = {n_out = cells found, live input rows}.
+ *   spx_collapse_fill: with the SAME rankmap and ws, unchanged since the count, writes
+ *     out_indices [n_out, kept + 1]
+ *     rows        [n]: the output row of each input row, -1 for a dead or dropped row
+ *     offsets     [n_out + 1]: group r is list[offsets[r] .. offsets[r + 1])
+ *     list        [n]: the input rows group after group, ascending inside a group; entries from offsets[n_out] on are
+ *                 unspecified
+ *   (a smaller n_out keeps the first n_out keys).  Launches: a one-word fill, rank, the sort (three per radix pass of
+ *   8 or 9 bits over ceil(log2(n_out + 1)) bits), boundaries.
+ *   spx_collapse_static: the static-shape form: room for n_out_cap rows (offsets [n_out_cap + 1]), nothing read back
+ *   (hipGraph-safe).  n_out_dev [3] (device) = {cells found -- may exceed the cap --, 0, live = min(found, cap)}; groups
+ *   beyond the cap are dropped in key order (rows entry -1); out_indices rows past the live count are -1, offsets
+ *   entries past it equal offsets[live].
+ *
+ * REDUCTION.  op: SPX_COLLAPSE_SUM / _MEAN / _MAX; dtype SPX_F16 / SPX_BF16 / SPX_F32 / SPX_F64; any C >= 1: rows whose
+ * byte size is a multiple of 16 (and 16-byte aligned pointers) move as 16-byte pieces per lane, other widths element by
+ * element.  The argument checks (mask, dtype, C, op) come before any pointer is looked at.
+ *   spx_collapse_fwd: out [n_out, C] from feat [n, C].  An output row belongs to a group of lanes that covers its
+ *   pieces (a power of two, at most a wave; wider rows take several passes) and walks its list entries in order.
+ *     sum:  the accumulator (fp32; fp64 for SPX_F64) starts from the first row's value and adds the others one by one
+ *           in list order; one rounding to `dtype`.  A group of one row is copied bit for bit (-0.0 stays -0.0).  No
+ *           atomics, no zero fill, every output element written exactly once: identical run to run, and reproducible
+ *           on the host with a sequential loop.
+ *     mean: that sum divided by the group's row count in fp32 (fp64), rounded once.
+ *     max:  the maximum of the stored values (the first of equals): a copy of an input element.  NaN: unspecified.
+ *   Rows at or beyond *n_live_out (NULL or a device int32) are written as zeros.  A list entry outside [0, n) is
+ *   skipped.
+ *   spx_collapse_bwd (mean and max; the gradient of a sum is spx_union_add_bwd with one operand): with r = rows[i],
+ *     mean: din[i] = dout[r] / (offsets[r + 1] - offsets[r]), divided in fp32 (fp64), rounded once (feat / out unused)
+ *     max:  din[i, c] = dout[r, c] where feat[i, c] == out[r, c], else 0: ties all receive, as spx_maxpool_bwd
+ *           (offsets unused)
+ *   zeros where rows[i] is outside [0, n_out). */
+size_t spx_collapse_ws_bytes(int ndim, int batch, const int *spatial_h, int axes_mask, long long n);
+int spx_collapse_count(const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch,
+                       const int *spatial_h, int axes_mask, void *rankmap, size_t rankmap_bytes, void *ws,
+                       size_t ws_bytes, int *result_h, spx_stream_t stream);
+int spx_collapse_fill(const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch,
+                      const int *spatial_h, int axes_mask, int n_out, int32_t *out_indices, int32_t *rows,
+                      int32_t *offsets, int32_t *list, const void *rankmap, size_t rankmap_bytes, void *ws,
+                      size_t ws_bytes, spx_stream_t stream);
+int spx_collapse_static(const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch,
+                        const int *spatial_h, int axes_mask, int n_out_cap, int32_t *out_indices, int32_t *rows,
+                        int32_t *offsets, int32_t *list, int32_t *n_out_dev, void *rankmap, size_t rankmap_bytes,
+                        void *ws, size_t ws_bytes, spx_stream_t stream);
+int spx_collapse_fwd(const void *feat, int n, const int32_t *offsets, const int32_t *list, int n_out, int C,
+                     int dtype, int op, void *out, const int32_t *n_live_out, spx_stream_t stream);
+int spx_collapse_bwd(const void *feat, const void *out, const void *dout, const int32_t *rows,
+                     const int32_t *offsets, int n, int n_out, int C, int dtype, int op, void *din,
+                     spx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -162,10 +162,23 @@ SIGNATURES = {
                                          vp]),
     "spx_union_add_bwd": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          vp]),
+    "spx_collapse_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int, ctypes.c_longlong]),
+    "spx_collapse_count": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int, vp,
+                                          ctypes.c_size_t, vp, ctypes.c_size_t, c_int_p, vp]),
+    "spx_collapse_fill": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
+                                         ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
+    "spx_collapse_static": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
+                                           ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t,
+                                           vp]),
+    "spx_collapse_fwd": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        vp, vp, vp]),
+    "spx_collapse_bwd": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, vp, vp]),
 }
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_I8, DTYPE_F64 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_LEAKY_RELU = 0, 1, 2, 3
+COLLAPSE_SUM, COLLAPSE_MEAN, COLLAPSE_MAX = 0, 1, 2
 
 _lib: Optional[ctypes.CDLL] = None
 

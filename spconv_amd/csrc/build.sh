@@ -6,7 +6,7 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../lib
-HIP_UNITS="rulebook igemm igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_gen1 igemm_ws igemm_bwdn pool rowsort norm dense union voxelize hash"
+HIP_UNITS="rulebook igemm igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_gen1 igemm_ws igemm_bwdn pool rowsort norm dense union collapse voxelize hash"
 CPP_UNITS="common"
 OBJS=""
 for f in $HIP_UNITS $CPP_UNITS; do OBJS="$OBJS $OUT/$f.o"; done
@@ -22,7 +22,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -mllvm -amdgpu-kernarg-preload-count=16"
 pids=()
 for f in $HIP_UNITS; do
-  if [ ! -f $OUT/$f.o ] || [ $f.hip -nt $OUT/$f.o ] || [ common.h -nt $OUT/$f.o ] || [ igemm_defs.h -nt $OUT/$f.o ] || [ igemm_v4.h -nt $OUT/$f.o ] || [ igemm_bwd.h -nt $OUT/$f.o ] || [ rankmap.h -nt $OUT/$f.o ] || [ fill.h -nt $OUT/$f.o ] || [ scan.h -nt $OUT/$f.o ] || [ table.h -nt $OUT/$f.o ] || [ ../../include/spconv_amd.h -nt $OUT/$f.o ]; then
+  if [ ! -f $OUT/$f.o ] || [ $f.hip -nt $OUT/$f.o ] || [ common.h -nt $OUT/$f.o ] || [ igemm_defs.h -nt $OUT/$f.o ] || [ igemm_v4.h -nt $OUT/$f.o ] || [ igemm_bwd.h -nt $OUT/$f.o ] || [ rankmap.h -nt $OUT/$f.o ] || [ fill.h -nt $OUT/$f.o ] || [ piece.h -nt $OUT/$f.o ] || [ scan.h -nt $OUT/$f.o ] || [ table.h -nt $OUT/$f.o ] || [ ../../include/spconv_amd.h -nt $OUT/$f.o ]; then
     rm -f $OUT/$f.o
     $HIPCC $FLAGS -c $f.hip -o $OUT/$f.o &
     pids+=($!)

@@ -35,6 +35,7 @@ std::atomic<long long> g_inst_launches[inst::kCount];
 std::atomic<long long> g_f64_launches[kF64Count];
 std::atomic<long long> g_dense_launches[kDenseCount];
 std::atomic<long long> g_union_launches[kUnionCount];
+std::atomic<long long> g_collapse_launches[kCollapseCount];
 std::atomic<long long> g_pool_launches[kPoolCount];
 std::atomic<long long> g_rulebook_launches[kRbCount];
 
@@ -147,6 +148,15 @@ std::atomic<long long> *union_counter(const char *key) {
   return nullptr;
 }
 
+// counter of an axis-collapse key (spx_launch_count), or null
+std::atomic<long long> *collapse_counter(const char *key) {
+  static const char *names[kCollapseCount] = {"collapse/mark", "collapse/prefix", "collapse/rank", "collapse/list",
+                                              "collapse/fwd", "collapse/bwd"};
+  for (int i = 0; i < kCollapseCount; ++i)
+    if (strcmp(key, names[i]) == 0) return &g_collapse_launches[i];
+  return nullptr;
+}
+
 // counter of a rulebook-builder key rulebook/<pass> (spx_launch_count), or null
 std::atomic<long long> *rulebook_counter(const char *key) {
   static const char *names[kRbCount] = {"subm_probe3", "subm_probe4", "subm_probe5", "subm_mask_pass", "subm_lists",
@@ -219,6 +229,7 @@ long long spx_launch_count(const char *family_h) {
   if (std::atomic<long long> *c = spx::f64_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::dense_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::union_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::collapse_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pool_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::rulebook_counter(family_h)) return c->load(std::memory_order_relaxed);
   const int slot = spx::instance_slot(family_h);

@@ -194,6 +194,13 @@ enum UnionInst { kUnionMark = 0, kUnionPrefix, kUnionClaim, kUnionFill, kUnionAd
 extern std::atomic<long long> g_union_launches[kUnionCount];
 inline void count_union(UnionInst i) { g_union_launches[i].fetch_add(1, std::memory_order_relaxed); }
 
+// axis collapse (collapse.hip): one counter per pass.
+// Keys collapse/mark, collapse/prefix, collapse/rank, collapse/list, collapse/fwd, collapse/bwd.
+enum CollapseInst { kCollapseMark = 0, kCollapsePrefix, kCollapseRank, kCollapseList, kCollapseFwd, kCollapseBwd,
+                    kCollapseCount };
+extern std::atomic<long long> g_collapse_launches[kCollapseCount];
+inline void count_collapse(CollapseInst i) { g_collapse_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
 // pooling (pool.hip): one counter per kernel instance, op x dtype x piece.
 // Keys pool/<op>/<dt>/<piece>: op max_fwd | max_bwd | avg_fwd | avg_bwd (PoolOp order), dt f16 | bf16 | f32 | f64 | i8,
 // piece v (16-byte pieces) | s (one element).  int8 is built for max_fwd only; its other keys count 0.

@@ -27,6 +27,7 @@
 // kernel's argument block.  The backward is a byte-moving gather, din_t[i] = dout[rows_t[i]], one launch as well.
 #include "common.h"
 #include "fill.h"
+#include "piece.h"
 #include "rankmap.h"
 #include "scan.h"
 
@@ -176,47 +177,10 @@ union_fill_kernel(UnionOps ops, UnionGeom g, const uint2 *__restrict__ cells, co
 
 // -------------------------------------------------------------------------------------------- row merge
 
-template <int DT> struct Elem;
-template <> struct Elem<SPX_F32> {
-  using S = float;
-  using A = float;
-  static __device__ __forceinline__ A up(S v) { return v; }
-  static __device__ __forceinline__ S down(A v) { return v; }
-};
-template <> struct Elem<SPX_F64> {
-  using S = double;
-  using A = double;
-  static __device__ __forceinline__ A up(S v) { return v; }
-  static __device__ __forceinline__ S down(A v) { return v; }
-};
-template <> struct Elem<SPX_F16> {
-  using S = uint16_t;
-  using A = float;
-  static __device__ __forceinline__ A up(S v) { return static_cast<float>(__builtin_bit_cast(_Float16, v)); }
-  static __device__ __forceinline__ S down(A v) { return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v)); }
-};
-template <> struct Elem<SPX_BF16> {
-  using S = uint16_t;
-  using A = float;
-  static __device__ __forceinline__ A up(S v) { return __builtin_bit_cast(float, static_cast<unsigned>(v) << 16); }
-  static __device__ __forceinline__ S down(A x) {            // round to nearest even; NaN stays NaN
-    unsigned u = __builtin_bit_cast(unsigned, x);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40u);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return static_cast<uint16_t>(u >> 16);
-  }
-};
-
 struct AddOps {
   const void *feat[kMaxOps];
   int n[kMaxOps];
   int T;
-};
-
-// A piece of a row: V elements, 16 bytes (V = 16 / sizeof(S)) or one element (V = 1: the scalar tail form for rows
-// whose byte size is no multiple of 16).
-template <typename S, int V> struct alignas(V * sizeof(S)) Piece {
-  S e[V];
 };
 
 template <int DT, int V>
@@ -280,9 +244,6 @@ struct BwdOps {
   int T;
 };
 
-template <typename P> __device__ __forceinline__ P zero_piece() { return P(0); }
-template <> __device__ __forceinline__ uint4 zero_piece<uint4>() { return make_uint4(0u, 0u, 0u, 0u); }
-
 // din_t[i] = dout[rows_t[i]] or zeros, in pieces of sizeof(P) bytes
 template <typename P>
 __global__ void __launch_bounds__(kBlock)
@@ -301,13 +262,6 @@ union_add_bwd_kernel(BwdOps ops, const P *__restrict__ dout, int n_out, int piec
 }
 
 // -------------------------------------------------------------------------------------------- host side
-
-inline bool aligned_to(const void *p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
-inline unsigned stream_blocks(long long total) {
-  const long long b = (total + kBlock - 1) / kBlock;
-  return static_cast<unsigned>(b < 2048 ? (b < 1 ? 1 : b) : 2048);       // (grid-stride loops beyond)
-}
 
 // scratch of a build: the byte map, the prefix pass's block totals, the counters, the owner tables [T][n_total]
 struct UnionWs {
@@ -391,34 +345,23 @@ int number_union(const Build &b, void *rankmap, const UnionWs &w, int32_t *count
   return 0;
 }
 
-// widest piece (16 bytes down to one element) that divides the row's byte count and the alignment of every pointer
-int piece_bytes(int elem_bytes, long long row_bytes, std::initializer_list<const void *> ptrs) {
-  int v = 16;
-  for (; v > elem_bytes; v >>= 1) {
-    bool ok = row_bytes % v == 0;
-    for (const void *p : ptrs) ok = ok && (p == nullptr || aligned_to(p, v));
-    if (ok) break;
-  }
-  return v;
-}
-
 template <int DT>
 void launch_add_fwd(const AddOps &ops, const int32_t *src, int n_out, int C, bool vec, void *out, const int32_t *n_live,
                     hipStream_t s) {
   constexpr int V = 16 / static_cast<int>(sizeof(typename Elem<DT>::S));
   if (vec) {
     const int pieces = C / V;
-    hipLaunchKernelGGL((union_add_fwd_kernel<DT, V>), dim3(stream_blocks(static_cast<long long>(n_out) * pieces)),
+    hipLaunchKernelGGL((union_add_fwd_kernel<DT, V>), dim3(stream_blocks(static_cast<long long>(n_out) * pieces, kBlock)),
                        dim3(kBlock), 0, s, ops, src, n_out, pieces, out, n_live);
   } else {
-    hipLaunchKernelGGL((union_add_fwd_kernel<DT, 1>), dim3(stream_blocks(static_cast<long long>(n_out) * C)), dim3(kBlock),
+    hipLaunchKernelGGL((union_add_fwd_kernel<DT, 1>), dim3(stream_blocks(static_cast<long long>(n_out) * C, kBlock)), dim3(kBlock),
                        0, s, ops, src, n_out, C, out, n_live);
   }
 }
 
 template <typename P>
 void launch_add_bwd(const BwdOps &ops, const void *dout, int n_out, int pieces, hipStream_t s) {
-  hipLaunchKernelGGL(union_add_bwd_kernel<P>, dim3(stream_blocks(static_cast<long long>(ops.off[ops.T]) * pieces)),
+  hipLaunchKernelGGL(union_add_bwd_kernel<P>, dim3(stream_blocks(static_cast<long long>(ops.off[ops.T]) * pieces, kBlock)),
                      dim3(kBlock), 0, s, ops, static_cast<const P *>(dout), n_out, pieces);
 }
 

@@ -10,6 +10,7 @@ from spconv_amd.pytorch.conv import (SparseConv1d, SparseConv2d, SparseConv3d, S
                                      SubMConv4d)
 from spconv_amd.pytorch.core import ConvAlgo, SparseConvTensor
 from spconv_amd.pytorch.identity import Identity
+from spconv_amd.pytorch.spatial import SparseCollapse
 from spconv_amd.pytorch.tables import AddTable, AddTableMisaligned, ConcatTable, JoinTable
 from spconv_amd.pytorch.pool import (SparseAvgPool1d, SparseAvgPool2d, SparseAvgPool3d,
                                      SparseGlobalAvgPool, SparseGlobalMaxPool, SparseMaxPool1d,

@@ -350,6 +350,65 @@ def misaligned_add(tens, composite, static_num_out=None, owner=None):
     return res if res is not None else composite(*tens)
 
 
+class SparseCollapseFunction(Function):
+    """Reduction of an axis collapse over the kernels of csrc/collapse.hip: out[r] = sum / mean / max of the rows of
+    group r in ascending input row, fp32 (fp64) accumulation, one rounding, one launch, no atomics.  The backward is one
+    launch as well: a gather for sum (spx_union_add_bwd), spx_collapse_bwd for mean and max; dead and dropped rows
+    receive zeros."""
+
+    @staticmethod
+    def forward(ctx, feat, build, reduce, n_live):
+        from spconv_amd.pytorch import _collapse
+        out = _collapse.fwd(feat.detach(), build, reduce, n_live)
+        ctx.build, ctx.reduce = build, reduce
+        if reduce == "max":
+            ctx.save_for_backward(feat, out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        from spconv_amd.pytorch import _collapse
+        feat, out = ctx.saved_tensors if ctx.reduce == "max" else (None, None)
+        return _collapse.bwd(grad_output, ctx.build, ctx.reduce, feat, out), None, None, None
+
+
+def sparse_collapse(x, axes, reduce="sum", static_num_out=None, owner=None):
+    """Drops the spatial axes `axes` of x (0 = the first: z of a zyx tensor) and merges the rows that land on one
+    (batch, kept axes) cell by `reduce` = "sum" | "mean" | "max" -- the height compression of the fully sparse
+    detectors, on the kernels of csrc/collapse.hip.  `axes = ()` merges duplicate coordinates.  The result is a fresh
+    SparseConvTensor over the kept extents: rows in ascending key order with the level's rank map attached (the SubM
+    layers behind build their rulebooks from it), an empty indice_dict, no grid.  Static form when x carries
+    n_live_dev or `static_num_out` is given: room for `static_num_out` rows (default: x's rows, which always
+    suffices), nothing read back, n_live_dev = the live rows found; `owner` (the calling module) keeps the
+    device-side counters {found, 0, live} of its last call in `_static_n_out_dev`."""
+    from spconv_amd.pytorch import _collapse
+    from spconv_amd.pytorch._rulebook import _require_gpu
+    from spconv_amd.pytorch.core import SparseConvTensor
+    feat = x.features
+    _require_gpu(feat, "features")
+    if feat.is_quantized or feat.dtype not in _UNION_DTYPES:
+        raise NotImplementedError(f"sparse_collapse: features must be float16, bfloat16, float32 or float64, "
+                                  f"got {feat.dtype}")
+    if reduce not in _collapse.OPS:
+        raise ValueError(f"sparse_collapse: reduce must be 'sum', 'mean' or 'max', got {reduce!r}")
+    n_live_in = getattr(x, "n_live_dev", None)
+    static = n_live_in is not None or static_num_out is not None
+    build = _collapse.sparse_collapse_build(x.indices, x.batch_size, x.spatial_shape, axes, n_live=n_live_in,
+                                            static_num_out=(static_num_out or feat.shape[0] or 1) if static else None)
+    n_live = build.n_out_dev[2:3] if static else None
+    out_features = SparseCollapseFunction.apply(feat, build, reduce, n_live)
+    res = SparseConvTensor(out_features, build.out_indices, build.spatial_shape, x.batch_size, benchmark=x.benchmark)
+    res.benchmark_record = x.benchmark_record
+    res._timer = x._timer
+    res.thrust_allocator = x.thrust_allocator
+    res.force_algo = x.force_algo
+    res.n_live_dev = n_live
+    if static and owner is not None:
+        owner._static_n_out_dev = build.n_out_dev
+    return res
+
+
 def sparse_add_hash_based(*tens):
     """Sum of sparse tensors with different coordinate sets (reference functional.py:439-499).  On the union kernels
     where they apply (sparse_add_native): rows in ascending key order with the level's rank map attached, or -- when

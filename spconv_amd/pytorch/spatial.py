@@ -1,4 +1,7 @@
-"""``spconv.pytorch.spatial`` (reference ``spconv/pytorch/spatial.py:28-45``)."""
+"""``spconv.pytorch.spatial`` (reference ``spconv/pytorch/spatial.py:28-45``), and ``SparseCollapse``: the hand-over
+from a 3-D backbone to a sparse 2-D head on the kernels of csrc/collapse.hip."""
+from typing import Optional, Sequence
+
 import torch
 
 from spconv_amd.pytorch.core import SparseConvTensor
@@ -23,3 +26,36 @@ class RemoveDuplicate(SparseModule):
         first = first.sort().values                      # keep the surviving rows in their order
         return SparseConvTensor(x.features[first], inds[first].contiguous(), x.spatial_shape,
                                 x.batch_size, x.grid)
+
+
+class SparseCollapse(SparseModule):
+    """Drops the spatial axes ``axes`` (0 = the first: z of a zyx tensor) and merges the rows that land on one
+    (batch, kept axes) cell by ``reduce`` = "sum" | "mean" | "max": the height compression of the fully sparse
+    detectors (``functional.sparse_collapse``).  ``axes = ()`` merges duplicate coordinates.  The result is a fresh
+    tensor over the kept extents with rows in key order and the level's rank map attached, so ``SubMConv2d`` /
+    ``SparseConv2d`` carry on in key order; the rows of a cell are reduced in ascending input row, without atomics:
+    results are identical run to run.
+
+    Static shapes (an input with ``n_live_dev``: inside StaticInference / StaticTrainingStep) take the sync-free
+    build; ``static_num_out`` bounds its rows (None: the input's rows, which always suffices).  The counters of the last
+    call {cells found, 0, live rows} stay on the device in ``_static_n_out_dev``; a module with an explicit bound is
+    part of the runners' ``overflowed()``."""
+
+    def __init__(self, axes: Sequence[int], reduce: str = "sum", static_num_out: Optional[int] = None,
+                 name: Optional[str] = None):
+        super().__init__(name=name)
+        self.axes = tuple(int(a) for a in axes)
+        if len(set(self.axes)) != len(self.axes) or any(a < 0 for a in self.axes):
+            raise ValueError(f"SparseCollapse: axes {self.axes} must be distinct and >= 0")
+        if reduce not in ("sum", "mean", "max"):
+            raise ValueError(f"SparseCollapse: reduce must be 'sum', 'mean' or 'max', got {reduce!r}")
+        self.reduce = reduce
+        self.static_num_out = None if static_num_out is None else int(static_num_out)
+        self._static_n_out_dev = None
+
+    def forward(self, x: SparseConvTensor) -> SparseConvTensor:
+        from spconv_amd.pytorch import functional as F
+        return F.sparse_collapse(x, self.axes, self.reduce, self.static_num_out, self)
+
+    def extra_repr(self) -> str:
+        return f"axes={self.axes}, reduce={self.reduce!r}, static_num_out={self.static_num_out}"

@@ -83,12 +83,20 @@ def _bounded_unions(net: torch.nn.Module) -> Dict[str, torch.nn.Module]:
             if isinstance(m, AddTableMisaligned) and m.static_num_out is not None}
 
 
+def _bounded_collapses(net: torch.nn.Module) -> Dict[str, torch.nn.Module]:
+    """SparseCollapse modules that were given an explicit `static_num_out`: their cells can overflow it."""
+    from spconv_amd.pytorch.spatial import SparseCollapse
+    return {name: m for name, m in net.named_modules()
+            if isinstance(m, SparseCollapse) and m.static_num_out is not None}
+
+
 def _static_counters(runner) -> Dict[str, torch.Tensor]:
-    """The device-side {found, flag} counters of a captured pass: the strided layers' and the bounded unions' (whose
-    flag says that a coordinate occurred twice within one operand); the unions' bounds join runner.bounds."""
+    """The device-side {found, flag} counters of a captured pass: the strided layers', the bounded unions' (whose
+    flag says that a coordinate occurred twice within one operand) and the bounded collapses'; the unions' and the
+    collapses' bounds join runner.bounds."""
     out = {name: m._static_n_out_dev for name, m in runner._layers.items()
            if getattr(m, "_static_n_out_dev", None) is not None}
-    for name, m in _bounded_unions(runner.net).items():
+    for name, m in {**_bounded_unions(runner.net), **_bounded_collapses(runner.net)}.items():
         if m._static_n_out_dev is not None:
             out[name] = m._static_n_out_dev[:2]
             runner.bounds[name] = m.static_num_out
