@@ -102,6 +102,10 @@ int spx_set_option(const char *name_h, int value);
  *                                                  axis collapse: the passes of the build (prefix: the prefix pass and
  *                                                  its block scan; list: the radix argsort and the boundary launch
  *                                                  behind it, counted once) and the two reduction launches
+ *   pointvoxel/groups, pointvoxel/gather, pointvoxel/decorate
+ *                                                  point <-> voxel features: calls of spx_point_groups (the key pass, the
+ *                                                  radix argsort and the boundary launch, counted once),
+ *                                                  spx_voxel_to_point and spx_point_decorate
  * COUT in {16, 32, 64, 128, 256}, NKS in {1, 2}, PK in {1, 2, 4, 8, 16, 32}.  A well-formed key of an instance that is
  * never built counts 0; anything else is unknown.
  * float64 (SPX_F64) has a family and keys of its own, outside the dt vocabulary above:
@@ -927,6 +931,62 @@ int spx_collapse_fwd(const void *feat, int n, const int32_t *offsets, const int3
 int spx_collapse_bwd(const void *feat, const void *out, const void *dout, const int32_t *rows,
                      const int32_t *offsets, int n, int n_out, int C, int dtype, int op, void *din,
                      spx_stream_t stream);
+
+/* ---- point <-> voxel features (csrc/pointvoxel.hip) ------------------------------------------------------
+ * The three operations of a learned voxel feature encoder (the DynamicVFE / DynamicPillarVFE of the fully sparse
+ * detectors) between a voxeliser and the first sparse layer: the points of every voxel as GROUPS, voxel rows carried
+ * back to their points, and the decorated input row of the per-point MLP.  They stand where torch_scatter composites
+ * would: argsort + bincount + cumsum, index_select + where, index_add_ (float atomics: not reproducible).  The
+ * reductions over the groups (sum, mean, max over ALL points of a voxel) are spx_collapse_fwd / _bwd with the rows,
+ * offsets and list made here; the gradient of spx_voxel_to_point is spx_collapse_fwd(dout, op = SPX_COLLAPSE_SUM) over
+ * the same groups -- added in ascending point index in fp32 (fp64 for SPX_F64), rounded once, identical run to run.
+ * Every call: the caller allocates, nothing is read back, nothing synchronises, every grid depends on host-known sizes
+ * only (hipGraph-safe).  The argument checks that need no pointer come before any pointer is looked at.
+ *
+ *   spx_point_groups: ids = device [n_cap], int64 (id_bytes 8: the pc_voxel_id of spx_point2voxel / _static) or int32
+ *   (id_bytes 4).  n_points_dev = NULL or a device int32: rows at or beyond it are no points, whatever they hold.  A
+ *   point belongs to voxel v = ids[i] when 0 <= v < num_voxels (num_voxels >= 1); every other point, negative ids
+ *   included, belongs to no voxel.  Outputs (device int32):
+ *     rows    [n_cap]: v, or -1
+ *     offsets [num_voxels + 1]: group v is list[offsets[v] .. offsets[v + 1]); an empty voxel is an empty range
+ *     list    [n_cap]: the points group after group IN ASCENDING POINT INDEX; entries from offsets[num_voxels] on are
+ *             unspecified
+ *   The list is a stable radix argsort of the points by voxel id (the LSD radix of rowsort.hip over
+ *   ceil(log2(num_voxels + 1)) bits; a point without a voxel takes the key num_voxels, behind every id), so the order
+ *   inside a group is a property of the sort, not of any scheduling; offsets[v] is the first sorted position whose key
+ *   is >= v (a bisection per voxel: runs of empty voxels cost nothing extra).  n_cap = 0 is legal (offsets all 0).
+ *   Launches: the key pass, three per radix pass of 8 or 9 bits, the boundary pass.
+ *   spx_point_groups_ws_bytes: its scratch; 0 for n_cap < 0 or num_voxels < 1.  Monotone in both arguments.
+ *
+ *   spx_voxel_to_point: out[i, :] = vfeat[rows[i], :] ([num_voxels, C] -> [n_cap, C], contiguous), or C copies of the
+ *   fill element (the low elem_bytes bytes of fill_bits) where rows[i] is outside [0, num_voxels).  A byte-moving
+ *   gather: elem_bytes 1, 2, 4 or 8, any C >= 1; rows whose byte size is a multiple of 16 (and 16-byte aligned
+ *   pointers) move as 16-byte pieces per lane, other widths element by element.  One launch, no temporaries, every
+ *   output element written exactly once.
+ *
+ *   spx_point_decorate: the input row of a dynamic VFE.  points = fp32 [n_cap, nfeat], the first ndim columns x, y, z
+ *   (as spx_point2voxel); rows = spx_point_groups' (entries >= 0 are trusted to be voxel rows of `indices` and
+ *   `cluster_mean`); indices = the voxel index rows [*, ndim + 1] (batch index, then zyx); vsize [ndim] and
+ *   coors_range [2 * ndim] = HOST arrays in zyx order, as spx_point2voxel takes them; cluster_mean = fp32
+ *   [num_voxels, nfeat] (spx_collapse_fwd(points, op = SPX_COLLAPSE_MEAN) over the groups; may be NULL without flag
+ *   bit 0).  Row i of out [n_cap, C_out], with r = rows[i] and j = 0 .. ndim - 1 the columns x, y, z:
+ *     the point's nfeat columns;
+ *     flags & 1: points[i, j] - cluster_mean[r, j];
+ *     flags & 2: points[i, j] - centre_j, centre_j = (float(c_j) + 0.5f) * vsize_j + lo_j with c_j the voxel's
+ *                coordinate along that axis (indices[r, ndim - j]);
+ *     zeros up to C_out (C_out >= nfeat + ndim * popcount(flags & 3)).
+ *   A point without a voxel (r < 0) gets a row of zeros.  All arithmetic is fp32, every multiply, add and subtract
+ *   rounded on its own (no contraction into an FMA: float32 arithmetic on the host reproduces every element bit for
+ *   bit), then one round-to-nearest-even into out_dtype (SPX_F32 / SPX_F16 / SPX_BF16).  One launch. */
+size_t spx_point_groups_ws_bytes(int n_cap, int num_voxels);
+int spx_point_groups(const void *ids, int id_bytes, int n_cap, const int32_t *n_points_dev, int num_voxels,
+                     int32_t *rows, int32_t *offsets, int32_t *list, void *ws, size_t ws_bytes,
+                     spx_stream_t stream);
+int spx_voxel_to_point(const void *vfeat, int num_voxels, const int32_t *rows, int n_cap, int C, int elem_bytes,
+                       long long fill_bits, void *out, spx_stream_t stream);
+int spx_point_decorate(const float *points, int nfeat, int n_cap, const int32_t *rows, const int32_t *indices,
+                       int ndim, const float *vsize, const float *coors_range, const float *cluster_mean,
+                       int flags, void *out, int out_dtype, int C_out, spx_stream_t stream);
 
 #ifdef __cplusplus
 }

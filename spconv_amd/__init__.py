@@ -18,7 +18,7 @@ def install_as_spconv() -> None:
     sys.modules.setdefault("spconv", spconv_amd)
     sys.modules.setdefault("spconv.pytorch", sp)
     for name in ("core", "conv", "functional", "ops", "modules", "pool", "hash", "utils", "tables",
-                 "identity"):
+                 "identity", "vfe"):
         sys.modules.setdefault(f"spconv.pytorch.{name}", getattr(sp, name))
     # the quantization package tree (spconv.pytorch.quantization.intrinsic.qat, ...)
     import importlib

@@ -20,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPX_LIB") or os.path.join(_HERE, "lib", "libspconv_amd.so")
 
 c_int_p = ctypes.POINTER(ctypes.c_int)
+c_float_p = ctypes.POINTER(ctypes.c_float)
 vp = ctypes.c_void_p
 
 # Every exported symbol of include/spconv_amd.h with (restype, argtypes).
@@ -174,6 +175,13 @@ SIGNATURES = {
                                         vp, vp, vp]),
     "spx_collapse_bwd": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, vp, vp]),
+    "spx_point_groups_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "spx_point_groups": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp,
+                                        ctypes.c_size_t, vp]),
+    "spx_voxel_to_point": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_longlong, vp, vp]),
+    "spx_point_decorate": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, c_float_p, c_float_p,
+                                          vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp]),
 }
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_I8, DTYPE_F64 = 0, 1, 2, 3, 4

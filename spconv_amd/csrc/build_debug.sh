@@ -17,9 +17,10 @@ $HIPCC $FLAGS -c norm.hip -o $OUT/dbg/norm.o &
 $HIPCC $FLAGS -c dense.hip -o $OUT/dbg/dense.o &
 $HIPCC $FLAGS -c union.hip -o $OUT/dbg/union.o &
 $HIPCC $FLAGS -c collapse.hip -o $OUT/dbg/collapse.o &
+$HIPCC $FLAGS -c pointvoxel.hip -o $OUT/dbg/pointvoxel.o &
 $HIPCC $FLAGS -c voxelize.hip -o $OUT/dbg/voxelize.o &
 $HIPCC $FLAGS -c hash.hip -o $OUT/dbg/hash.o &
 $HIPCC $FLAGS -x hip -c common.cpp -o $OUT/dbg/common.o &
 wait
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT/libspconv_amd_dbg.so $OUT/dbg/rulebook.o $OUT/dbg/igemm.o $OUT/dbg/igemm_wgrad.o $OUT/dbg/pool.o $OUT/dbg/igemm_gen1.o $OUT/dbg/igemm_bf16.o $OUT/dbg/igemm_f32.o $OUT/dbg/igemm_f64.o $OUT/dbg/igemm_i8.o $OUT/dbg/igemm_wide.o $OUT/dbg/igemm_ws.o $OUT/dbg/igemm_bwdn.o $OUT/dbg/rowsort.o $OUT/dbg/norm.o $OUT/dbg/dense.o $OUT/dbg/union.o $OUT/dbg/collapse.o $OUT/dbg/voxelize.o $OUT/dbg/hash.o $OUT/dbg/common.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT/libspconv_amd_dbg.so $OUT/dbg/rulebook.o $OUT/dbg/igemm.o $OUT/dbg/igemm_wgrad.o $OUT/dbg/pool.o $OUT/dbg/igemm_gen1.o $OUT/dbg/igemm_bf16.o $OUT/dbg/igemm_f32.o $OUT/dbg/igemm_f64.o $OUT/dbg/igemm_i8.o $OUT/dbg/igemm_wide.o $OUT/dbg/igemm_ws.o $OUT/dbg/igemm_bwdn.o $OUT/dbg/rowsort.o $OUT/dbg/norm.o $OUT/dbg/dense.o $OUT/dbg/union.o $OUT/dbg/collapse.o $OUT/dbg/pointvoxel.o $OUT/dbg/voxelize.o $OUT/dbg/hash.o $OUT/dbg/common.o
 echo built $OUT/libspconv_amd_dbg.so

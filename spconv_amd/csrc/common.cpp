@@ -36,6 +36,7 @@ std::atomic<long long> g_f64_launches[kF64Count];
 std::atomic<long long> g_dense_launches[kDenseCount];
 std::atomic<long long> g_union_launches[kUnionCount];
 std::atomic<long long> g_collapse_launches[kCollapseCount];
+std::atomic<long long> g_pointvoxel_launches[kPvCount];
 std::atomic<long long> g_pool_launches[kPoolCount];
 std::atomic<long long> g_rulebook_launches[kRbCount];
 
@@ -157,6 +158,14 @@ std::atomic<long long> *collapse_counter(const char *key) {
   return nullptr;
 }
 
+// counter of a point <-> voxel key (spx_launch_count), or null
+std::atomic<long long> *pointvoxel_counter(const char *key) {
+  static const char *names[kPvCount] = {"pointvoxel/groups", "pointvoxel/gather", "pointvoxel/decorate"};
+  for (int i = 0; i < kPvCount; ++i)
+    if (strcmp(key, names[i]) == 0) return &g_pointvoxel_launches[i];
+  return nullptr;
+}
+
 // counter of a rulebook-builder key rulebook/<pass> (spx_launch_count), or null
 std::atomic<long long> *rulebook_counter(const char *key) {
   static const char *names[kRbCount] = {"subm_probe3", "subm_probe4", "subm_probe5", "subm_mask_pass", "subm_lists",
@@ -230,6 +239,7 @@ long long spx_launch_count(const char *family_h) {
   if (std::atomic<long long> *c = spx::dense_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::union_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::collapse_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::pointvoxel_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pool_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::rulebook_counter(family_h)) return c->load(std::memory_order_relaxed);
   const int slot = spx::instance_slot(family_h);

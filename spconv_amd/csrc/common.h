@@ -201,6 +201,12 @@ enum CollapseInst { kCollapseMark = 0, kCollapsePrefix, kCollapseRank, kCollapse
 extern std::atomic<long long> g_collapse_launches[kCollapseCount];
 inline void count_collapse(CollapseInst i) { g_collapse_launches[i].fetch_add(1, std::memory_order_relaxed); }
 
+// point <-> voxel features (pointvoxel.hip): one counter per entry point.
+// Keys pointvoxel/groups, pointvoxel/gather, pointvoxel/decorate.
+enum PointVoxelInst { kPvGroups = 0, kPvGather, kPvDecorate, kPvCount };
+extern std::atomic<long long> g_pointvoxel_launches[kPvCount];
+inline void count_pointvoxel(PointVoxelInst i) { g_pointvoxel_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
 // pooling (pool.hip): one counter per kernel instance, op x dtype x piece.
 // Keys pool/<op>/<dt>/<piece>: op max_fwd | max_bwd | avg_fwd | avg_bwd (PoolOp order), dt f16 | bf16 | f32 | f64 | i8,
 // piece v (16-byte pieces) | s (one element).  int8 is built for max_fwd only; its other keys count 0.

@@ -472,3 +472,8 @@ def _sparse_add_sorted_composite(*tens):
     keep = tens[biggest].indice_dict if uniq.shape[0] == sizes[biggest] else None
     return _like_first(first, out_features, out_indices, keep)
 
+
+# point <-> voxel features (csrc/pointvoxel.hip; not part of the reference): the groups of a point cloud, the reductions
+# over them and the way back, for learned voxel feature encoders (vfe.DynamicVFE)
+from spconv_amd.pytorch._pointvoxel import (PointGroups, decorate_points, point_groups,  # noqa: E402,F401
+                                            points_to_voxels, voxels_to_points)

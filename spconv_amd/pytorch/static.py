@@ -190,10 +190,14 @@ def _entry(runner):
     row t, for code that looks at tensors INSIDE the network.  The coordinates of a scene must be unique (a voxeliser's
     are): `runner.input_order_violation()` reads the device-side verdict.
     A runner built on a voxeliser (`voxelizer=`) starts the pass with its one call; a key-ordered voxeliser's index
-    buffer already carries the level's rank map, written by that call: true by construction, nothing to sort or declare."""
+    buffer already carries the level's rank map, written by that call: true by construction, nothing to sort or declare.
+    With a `point_encoder` the voxel features are its output over the voxeliser's points and groups instead of the mean."""
     vox = getattr(runner, "voxelizer", None)
     if vox is not None:
         vox.run()
+        enc = getattr(runner, "point_encoder", None)
+        if enc is not None:             # a learned encoder between the points and the network: groups, then its pass
+            runner.features = enc(vox.points, vox.point_groups(), vox.indices, vox.vsize_xyz, vox.coors_range_xyz)
         if vox.key_order:
             return runner.features, runner.indices
     if runner.key_ordered_input or not runner.entry_sort:
@@ -245,8 +249,10 @@ def _input_order_violation(runner) -> bool:
     return bool(int(runner._order_flag.item()) != 0)
 
 
-def _check_voxelizer(vox, max_voxels, in_channels, spatial_shape, batch_size, dtype, device) -> None:
-    """A voxeliser at the head of a captured pass must describe the level the runner was asked for."""
+def _check_voxelizer(vox, max_voxels, in_channels, spatial_shape, batch_size, dtype, device, point_encoder=None) -> None:
+    """A voxeliser at the head of a captured pass must describe the level the runner was asked for.  With a point
+    encoder behind it the feature rows are the encoder's: `in_channels` is its output width, it reads the voxeliser's
+    points, and it runs in the runner's dtype (the mean and its dtype are not looked at)."""
     from spconv_amd.pytorch.utils import StaticPointToVoxel
     if not isinstance(vox, StaticPointToVoxel):
         raise TypeError(f"voxelizer must be a StaticPointToVoxel, got {type(vox).__name__}")
@@ -255,6 +261,15 @@ def _check_voxelizer(vox, max_voxels, in_channels, spatial_shape, batch_size, dt
             "batch_size": (int(batch_size), vox.batch_size),
             "in_channels": (int(in_channels), vox.num_point_features),
             "dtype": (dtype, vox.mean_dtype)}
+    if point_encoder is not None:
+        enc_out = getattr(point_encoder, "out_channels", None)
+        enc_in = getattr(point_encoder, "num_point_features", vox.num_point_features)
+        enc_dtype = next((p.dtype for p in point_encoder.parameters()), dtype)
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"a point encoder runs in float32, float16 or bfloat16, the runner was asked for {dtype}")
+        want["in_channels"] = (int(in_channels), enc_out)
+        want["dtype"] = (dtype, enc_dtype)
+        want["num_point_features"] = (enc_in, vox.num_point_features)
     for name, (asked, has) in want.items():
         if asked != has:
             raise ValueError(f"voxelizer does not fit the runner: {name} is {asked}, the voxeliser has {has}")
@@ -285,18 +300,30 @@ class StaticInference:
 
         out = runner.run_points(pc, batch_ids=None)      # load the points, replay
         runner.voxelizer.pc_voxel_id                     # voxel row of every point, to carry results back
+
+    With `point_encoder=` (a module like `vfe.DynamicVFE`; put in eval mode and into the runner's dtype) the head of the
+    captured pass is the voxeliser's call, its `point_groups()`, then `point_encoder(points, groups, indices, vsize_xyz,
+    coors_range_xyz)`; the network reads the encoder's rows, so `in_channels` is the encoder's `out_channels` and the
+    voxeliser needs no mean.
     """
 
     def __init__(self, net: torch.nn.Module, max_voxels: int, in_channels: int,
                  spatial_shape: Sequence[int], batch_size: int, dtype: torch.dtype = torch.float16,
                  bounds: Optional[Dict[str, int]] = None, margin: float = 1.25,
                  device: Optional[torch.device] = None, warmup: int = 2, capture_error_mode: str = "global",
-                 key_ordered_input: bool = False, entry_sort: Optional[bool] = None, voxelizer=None):
+                 key_ordered_input: bool = False, entry_sort: Optional[bool] = None, voxelizer=None,
+                 point_encoder: Optional[torch.nn.Module] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("StaticInference needs the GPU (there is no CPU path)")
         self.voxelizer = voxelizer
+        self.point_encoder = None
+        if point_encoder is not None:
+            if voxelizer is None:
+                raise ValueError("point_encoder needs the points: pass voxelizer=StaticPointToVoxel(...) as well")
+            self.point_encoder = point_encoder.to(device=voxelizer.device, dtype=dtype).eval()
         if voxelizer is not None:
-            _check_voxelizer(voxelizer, max_voxels, in_channels, spatial_shape, batch_size, dtype, device)
+            _check_voxelizer(voxelizer, max_voxels, in_channels, spatial_shape, batch_size, dtype, device,
+                             self.point_encoder)
             device = voxelizer.device
             key_ordered_input = voxelizer.key_order
         self.key_ordered_input = bool(key_ordered_input)

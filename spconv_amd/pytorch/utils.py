@@ -161,6 +161,8 @@ class StaticPointToVoxel(object):
         self.key_order = bool(key_order)
         self.mean_dtype = mean_dtype
         self.vsize, self.grid_size, self.grid_stride, self.coors_range = vsize, grid_size, grid_stride, coors_range
+        self.vsize_xyz, self.coors_range_xyz = [float(v) for v in vsize_xyz], [float(v) for v in coors_range_xyz]
+        self._groups = None
         L = _lib.load()
         grid_c = _lib.ints(grid_size)
         rank_bytes = 0
@@ -241,6 +243,25 @@ class StaticPointToVoxel(object):
             self.run(empty_mean)
         return self.voxels, self.indices, self.num_per_voxel, self.pc_voxel_id
 
+    def point_groups(self):
+        """The points of every voxel of the last ``run()`` as ``functional.PointGroups`` (``spx_point_groups`` over the
+        object's own ``pc_voxel_id``, ``n_points`` and ``n_voxels[0:1]``): what ``points_to_voxels``, ``voxels_to_points``
+        and ``vfe.DynamicVFE`` take.  Its outputs and scratch are allocated once, at first use, so the call can be
+        recorded in a stream capture behind ``run()``.  (The points are sorted a second time: the voxeliser's own
+        sorted list stays private in its scratch.)"""
+        from spconv_amd.pytorch import _pointvoxel
+        with torch.cuda.device(self.device):
+            if self._groups is None:
+                i32 = dict(dtype=torch.int32, device=self.device)
+                ws = torch.empty([max(int(self._L.spx_point_groups_ws_bytes(self.max_num_points, self.max_num_voxels)), 16)],
+                                 dtype=torch.uint8, device=self.device)
+                self._groups = (_pointvoxel.PointGroups(
+                    torch.full([self.max_num_points], -1, **i32), torch.zeros([self.max_num_voxels + 1], **i32),
+                    torch.zeros([self.max_num_points], **i32), self.max_num_voxels, self.n_points, self.n_voxels[0:1]), ws)
+            g, ws = self._groups
+            _pointvoxel.point_groups_into(self.pc_voxel_id, self.max_num_voxels, self.n_points, g.rows, g.offsets, g.list, ws)
+        return g
+
     def overflowed(self) -> bool:
         """True when the last run found more voxels than ``max_num_voxels`` (one synchronisation)."""
         kept, found = self.n_voxels.tolist()
@@ -251,8 +272,23 @@ def gather_features_by_pc_voxel_id(seg_res_features: torch.Tensor, pc_voxel_id: 
                                    invalid_value: Union[int, float] = 0):
     """Per-voxel results back to the points: row i of the result is the row of point i's voxel,
     `invalid_value` for points that fell outside the grid (pc_voxel_id == -1).  Same contract as
-    the reference helper (spconv/pytorch/utils.py:163-176)."""
+    the reference helper (spconv/pytorch/utils.py:163-176).
+
+    CUDA rows [num_voxels, C] of 1, 2, 4 or 8 bytes per element go through ``functional.voxels_to_points``: one launch
+    (spx_voxel_to_point) instead of four and three [N, C] temporaries, and a gradient that is a segment sum in ascending
+    point index instead of ``index_add_``'s float atomics.  Other inputs take the composite below."""
     ids = pc_voxel_id.to(seg_res_features.device)
+    if (seg_res_features.is_cuda and seg_res_features.ndim == 2 and ids.ndim == 1
+            and ids.dtype in (torch.int64, torch.int32) and not seg_res_features.is_quantized
+            and not seg_res_features.is_complex() and seg_res_features.element_size() in (1, 2, 4, 8)
+            and seg_res_features.shape[0] > 0 and seg_res_features.shape[1] > 0):
+        from spconv_amd.pytorch import _pointvoxel
+        num_voxels = int(seg_res_features.shape[0])
+        if seg_res_features.requires_grad and torch.is_grad_enabled() and seg_res_features.is_floating_point():
+            groups = _pointvoxel.point_groups(ids, num_voxels)      # (the gradient walks the groups)
+        else:
+            groups = _pointvoxel.PointGroups(ids.to(torch.int32), None, None, num_voxels)
+        return _pointvoxel.voxels_to_points(seg_res_features, groups, invalid_value)
     inside = ids >= 0
     rows = seg_res_features.index_select(0, ids.clamp_min(0))
     shape = [-1] + [1] * (seg_res_features.ndim - 1)
