@@ -6,7 +6,7 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../lib
-HIP_UNITS="rulebook igemm igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_gen1 igemm_ws igemm_bwdn pool rowsort norm dense union collapse pointvoxel voxelize hash"
+HIP_UNITS="rulebook_subm rulebook_conv rulebook_sorted rulebook_lists igemm igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_gen1 igemm_ws igemm_bwdn pool rowsort norm dense union collapse pointvoxel voxelize hash"
 CPP_UNITS="common"
 OBJS=""
 for f in $HIP_UNITS $CPP_UNITS; do OBJS="$OBJS $OUT/$f.o"; done
@@ -20,16 +20,22 @@ if [ "$1" = "--force" ]; then
 fi
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -mllvm -amdgpu-kernarg-preload-count=16"
+# an object is stale when it is missing or older than its source or than any header (every *.h here + the public one)
+stale() {
+  [ -f $1 ] || return 0
+  for d in $2 *.h ../../include/spconv_amd.h; do [ $d -nt $1 ] && return 0; done
+  return 1
+}
 pids=()
 for f in $HIP_UNITS; do
-  if [ ! -f $OUT/$f.o ] || [ $f.hip -nt $OUT/$f.o ] || [ common.h -nt $OUT/$f.o ] || [ igemm_defs.h -nt $OUT/$f.o ] || [ igemm_v4.h -nt $OUT/$f.o ] || [ igemm_bwd.h -nt $OUT/$f.o ] || [ rankmap.h -nt $OUT/$f.o ] || [ fill.h -nt $OUT/$f.o ] || [ piece.h -nt $OUT/$f.o ] || [ scan.h -nt $OUT/$f.o ] || [ table.h -nt $OUT/$f.o ] || [ ../../include/spconv_amd.h -nt $OUT/$f.o ]; then
+  if stale $OUT/$f.o $f.hip; then
     rm -f $OUT/$f.o
     $HIPCC $FLAGS -c $f.hip -o $OUT/$f.o &
     pids+=($!)
   fi
 done
 for f in $CPP_UNITS; do
-  if [ ! -f $OUT/$f.o ] || [ $f.cpp -nt $OUT/$f.o ] || [ common.h -nt $OUT/$f.o ]; then
+  if stale $OUT/$f.o $f.cpp; then
     rm -f $OUT/$f.o
     $HIPCC $FLAGS -x hip -c $f.cpp -o $OUT/$f.o &
     pids+=($!)

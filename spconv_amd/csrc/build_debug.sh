@@ -1,26 +1,25 @@
 #!/bin/bash
-# Debug build with the in-kernel timeline stamps (tools/timeline.py): lib/libspconv_amd_dbg.so
+# Debug build with the in-kernel timeline stamps (tools/timeline.py): lib/libspconv_amd_dbg.so.  Every translation unit
+# of the product build (build.sh --list) compiled with -DSPX_TIMELINE into lib/dbg/.
+#   build_debug.sh --list    print the object files the library is linked from, one per line
 set -e
 cd "$(dirname "$0")"
 OUT=../lib
+OBJS=""
+for o in $(bash build.sh --list); do OBJS="$OBJS $OUT/dbg/$o"; done
+if [ "$1" = "--list" ]; then
+  for o in $OBJS; do echo $o; done
+  exit 0
+fi
 mkdir -p $OUT/dbg
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -mllvm -amdgpu-kernarg-preload-count=16 -DSPX_TIMELINE"
-$HIPCC $FLAGS -c rulebook.hip -o $OUT/dbg/rulebook.o &
-$HIPCC $FLAGS -c igemm.hip -o $OUT/dbg/igemm.o &
-$HIPCC $FLAGS -c pool.hip -o $OUT/dbg/pool.o &
-$HIPCC $FLAGS -c igemm_gen1.hip -o $OUT/dbg/igemm_gen1.o &
-for f in igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_ws; do $HIPCC $FLAGS -c $f.hip -o $OUT/dbg/$f.o & done
-$HIPCC $FLAGS -c igemm_bwdn.hip -o $OUT/dbg/igemm_bwdn.o &
-$HIPCC $FLAGS -c rowsort.hip -o $OUT/dbg/rowsort.o &
-$HIPCC $FLAGS -c norm.hip -o $OUT/dbg/norm.o &
-$HIPCC $FLAGS -c dense.hip -o $OUT/dbg/dense.o &
-$HIPCC $FLAGS -c union.hip -o $OUT/dbg/union.o &
-$HIPCC $FLAGS -c collapse.hip -o $OUT/dbg/collapse.o &
-$HIPCC $FLAGS -c pointvoxel.hip -o $OUT/dbg/pointvoxel.o &
-$HIPCC $FLAGS -c voxelize.hip -o $OUT/dbg/voxelize.o &
-$HIPCC $FLAGS -c hash.hip -o $OUT/dbg/hash.o &
-$HIPCC $FLAGS -x hip -c common.cpp -o $OUT/dbg/common.o &
-wait
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT/libspconv_amd_dbg.so $OUT/dbg/rulebook.o $OUT/dbg/igemm.o $OUT/dbg/igemm_wgrad.o $OUT/dbg/pool.o $OUT/dbg/igemm_gen1.o $OUT/dbg/igemm_bf16.o $OUT/dbg/igemm_f32.o $OUT/dbg/igemm_f64.o $OUT/dbg/igemm_i8.o $OUT/dbg/igemm_wide.o $OUT/dbg/igemm_ws.o $OUT/dbg/igemm_bwdn.o $OUT/dbg/rowsort.o $OUT/dbg/norm.o $OUT/dbg/dense.o $OUT/dbg/union.o $OUT/dbg/collapse.o $OUT/dbg/pointvoxel.o $OUT/dbg/voxelize.o $OUT/dbg/hash.o $OUT/dbg/common.o
+pids=()
+for o in $OBJS; do
+  f=$(basename $o .o)
+  if [ -f $f.hip ]; then $HIPCC $FLAGS -c $f.hip -o $o & else $HIPCC $FLAGS -x hip -c $f.cpp -o $o & fi
+  pids+=($!)
+done
+for p in "${pids[@]}"; do wait $p; done   # a failed compile aborts the build (set -e)
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT/libspconv_amd_dbg.so $OBJS
 echo built $OUT/libspconv_amd_dbg.so

@@ -218,7 +218,8 @@ inline void count_pool(int op, int dt, bool scalar) {
   g_pool_launches[pool_slot(op, dt, scalar)].fetch_add(1, std::memory_order_relaxed);
 }
 
-// rulebook builders over the hash table (rulebook.hip: spx_subm_rulebook, spx_conv_rulebook_count / _fill / _static):
+// rulebook builders over the hash table (rulebook_subm.hip: spx_subm_rulebook; rulebook_conv.hip: spx_conv_rulebook_count /
+// _fill / _static):
 // one counter per dispatch decision, counted on the host where the launch is issued.
 // Keys rulebook/<pass>: subm_probe3 | subm_probe4 | subm_probe5 (form of the SubM probe pass), subm_mask_pass (masks
 // from a pass over the finished table), subm_lists (lists from the probe's group counts), native_lists_v1 (SubM lists by

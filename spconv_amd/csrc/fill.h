@@ -1,4 +1,4 @@
-// Range fills shared by the translation units that build index structures (rulebook.hip, union.hip, collapse.hip, through table.h); every
+// Range fills shared by the translation units that build index structures (rulebook_*.hip, union.hip, collapse.hip, through table.h); every
 // definition has internal linkage.
 #pragma once
 #include "common.h"
@@ -55,6 +55,10 @@ struct FillList {
     jobs.words[jobs.n] = bytes / 4;
     jobs.value[jobs.n] = value;
     ++jobs.n;
+  }
+  // another list's ranges, in its order (a caller's fills riding in a pass's launch)
+  void add(const FillList &more) {
+    for (int j = 0; j < more.jobs.n; ++j) add(more.jobs.ptr[j], more.jobs.words[j] * 4, more.jobs.value[j]);
   }
   hipError_t launch(hipStream_t s) const {
     if (jobs.n == 0) return hipSuccess;

@@ -1,4 +1,5 @@
-// The RANK MAP of a level (rulebook.hip, "outputs numbered by KEY RANK"; union.hip; collapse.hip): its layout in the caller's buffer,
+// The RANK MAP of a level (rulebook_sorted.hip, "outputs numbered by KEY RANK"; rulebook_subm.hip; union.hip;
+// collapse.hip): its layout in the caller's buffer,
 // the prefix pass that builds it from a byte-per-cell occupancy map, and the lookup.  Shared by the translation units
 // that build or read one; every definition has internal linkage.
 #pragma once

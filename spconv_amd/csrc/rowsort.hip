@@ -203,7 +203,7 @@ __device__ __forceinline__ void store_index_row(int32_t *__restrict__ out, int p
   }
 }
 
-struct RankMapOut {        // the level's rank map (csrc/rulebook.hip rank_of: {bits, rows before the word}, block offsets 0)
+struct RankMapOut {        // the level's rank map (csrc/rankmap.h rank_of: {bits, rows before the word}, block offsets 0)
   uint2 *cells;            // null: not wanted.  Zero-filled by key_count_kernel: only occupied words are written
   unsigned long long words;
   int32_t *violation;
@@ -624,7 +624,7 @@ int key_argsort(const int32_t *indices, int n, int ndim, int batch_size, const i
   rm.rows_out = static_cast<char *>(rows_sorted);
   rm.row_bytes = row_bytes;
   unsigned long long zero_units = 0;               // 16-byte units of the rank map (cells, padding, block offsets)
-  if (rankmap) {                                   // layout: csrc/rulebook.hip rank_bytes (cells, then one int per 2048 words)
+  if (rankmap) {                                   // layout: csrc/rankmap.h rank_bytes (cells, then one int per 2048 words)
     rm.words = (cells + 31ull) / 32ull;
     rm.cells = static_cast<uint2 *>(rankmap);
     zero_units = (align_up(rm.words * sizeof(uint2), 256) + align_up(((rm.words + 2047ull) / 2048ull) * sizeof(int32_t), 256)) / 16;

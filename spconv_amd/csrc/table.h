@@ -1,4 +1,4 @@
-// The build-time hash table of the index builders (rulebook.hip, voxelize.hip; hash.hip borrows its hash function) and
+// The build-time hash table of the index builders (rulebook_*.hip, voxelize.hip; hash.hip borrows its hash function) and
 // the coordinate helpers that make its keys.  Every definition has internal linkage.
 //
 // One open-addressing table in global memory.  Whenever the key space (batch x grid volume) fits 32 bits -- every

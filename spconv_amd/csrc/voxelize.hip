@@ -102,7 +102,7 @@ p2v_count_first_kernel(const int32_t *__restrict__ slot_of, Table t, int n,
 // lead = 1: index rows carry the batch index in front of zyx (the static form).  cells (key order): a kept voxel sets
 // its cell's bit in the zeroed rank map instead of writing its row -- one atomicOr per VOXEL, whose result does not
 // depend on the order of arrival (the level builders mark a byte per cell with plain stores: they mark 27 candidates
-// per row, rulebook.hip conv4_mark_kernel; here the byte map would cost 32 x the fill and a pass over it per call);
+// per row, rulebook_sorted.hip conv4_mark_kernel; here the byte map would cost 32 x the fill and a pass over it per call);
 // p2v_renumber_kernel numbers the voxel once p2v_rank_prefix_kernel has turned the bits into ranks.
 __global__ void __launch_bounds__(kBlock)
 p2v_assign_kernel(const float *__restrict__ pts, const int32_t *__restrict__ point_batch, int n, int nfeat, P2VGeom g,

@@ -8,7 +8,7 @@ a forward pass has a static shape, so on this backend the WHOLE pass -- hash-tab
 tables, gather-GEMMs -- can be recorded once and replayed per scene:
 
   * the input is padded to `max_voxels` rows; padding rows carry batch index -1 (dead rows: the
-    rulebook kernels neither hash them nor pair them, csrc/rulebook.hip subm_insert_kernel /
+    rulebook kernels neither hash them nor pair them, csrc/rulebook_subm.hip subm_insert_kernel /
     conv_stage1_kernel)
   * a strided layer builds its rulebook with spx_conv_rulebook_static (include/spconv_amd.h): room
     for `static_num_out` outputs, nothing read back; the rows past the real count come out dead

@@ -80,6 +80,26 @@ def test_workspace_size_queries(lib):
     assert lib.spx_table_to_native_ws_bytes(100_000, 27) > 0
 
 
+def test_rulebook_workspace_sizes_are_pinned(lib):
+    """The five size queries of the rulebook builders return what they returned before each became its build's own carve
+    function run over a null buffer (values recorded from that build): captured runners allocate by these numbers, so
+    their pool layout must not move.  600 000 rows: a SubM table beyond 2^19 slots, which the build does not double
+    but the query still reserves doubled."""
+    I = _lib.ints
+    nk = [(0, 27), (1, 27), (2500, 27), (100_000, 27), (600_000, 27), (2500, 1), (2500, 175)]
+    for fn, want in ((lib.spx_subm_rulebook_ws_bytes, [7680, 7680, 210432, 6790144, 53451008, 209920, 215808]),
+                     (lib.spx_subm_rulebook_ranked_ws_bytes, [768, 768, 1280, 22528, 131840, 768, 4096]),
+                     (lib.spx_table_to_native_ws_bytes, [768, 768, 768, 11008, 63744, 768, 3328])):
+        assert [int(fn(n, kv)) for n, kv in nk] == want
+    geoms = [([3] * 3, [2] * 3, 0), ([2] * 3, [2] * 3, 0), ([3] * 3, [1] * 3, 0), ([3] * 3, [2] * 3, 1)]   # k3 s2, k2 s2, k3 s1, transposed k3 s2
+    want = {0: [19712, 9984, 19712, 19712], 1: [19712, 9984, 19712, 19712],
+            2500: [1368832, 241152, 4514560, 4514560], 100_000: [45885440, 8411648, 146548736, 146548736]}
+    for n_in, sizes in want.items():
+        assert [int(lib.spx_conv_rulebook_ws_bytes(n_in, 3, I(k), I(s), I([1] * 3), t)) for k, s, t in geoms] == sizes
+    assert [int(lib.spx_conv_rulebook_sorted_ws_bytes(n_in, 3, 4, I([21, 800, 704]), I([3] * 3)))
+            for n_in in (2500, 100_000)] == [47313664, 47354624]
+
+
 def test_rulebook_launch_counter_keys(lib):
     """spx_launch_count knows every rulebook/<pass> key of include/spconv_amd.h and rejects malformed ones (nothing
     launches)."""

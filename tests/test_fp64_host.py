@@ -3,6 +3,7 @@ entries that refuse float64 (they return before anything is enqueued)."""
 import ctypes
 import os
 import re
+import subprocess
 
 import torch
 
@@ -72,13 +73,15 @@ def test_empty_float64_pooling_counts_no_launch():
 def test_every_build_script_links_every_unit():
     """The timeline (build_debug.sh) and ablation (build_ablate.sh) libraries link every translation unit of the
     product build (csrc/build.sh --list): a unit missing there leaves symbols undefined, and the library then fails to
-    load although its link succeeded."""
+    load although its link succeeded.  Both scripts take their objects from that list; `--list` prints what they link."""
     csrc = os.path.join(ROOT, "spconv_amd", "csrc")
     units = [os.path.splitext(os.path.basename(o))[0] for o in _lib.linked_objects()]
-    for script, fmt in (("build_debug.sh", "$OUT/dbg/{}.o"), ("build_ablate.sh", "$OUT/{}.o")):
+    assert len(units) > 20 and "igemm" in units and "common" in units
+    for script, arg, fmt in (("build_debug.sh", [], "../lib/dbg/{}.o"), ("build_ablate.sh", ["3"], "../lib/{}.o")):
+        out = subprocess.check_output(["bash", os.path.join(csrc, script), "--list"] + arg, text=True).split()
+        want = ["../lib/abl/igemm3.o" if (script == "build_ablate.sh" and u == "igemm") else fmt.format(u) for u in units]
+        assert out == want, script
         with open(os.path.join(csrc, script)) as fh:
             link = [ln for ln in fh if "-shared" in ln]
-        assert len(link) == 1, script
-        for u in units:
-            obj = "$OUT/abl/igemm$v.o" if (script == "build_ablate.sh" and u == "igemm") else fmt.format(u)
-            assert obj in link[0], f"{script} does not link {u}"
+        assert len(link) == 1, script       # one link line, and it links that list
+        assert ("$OBJS" if script == "build_debug.sh" else "$(objs $v)") in link[0], script

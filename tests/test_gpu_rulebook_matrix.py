@@ -1,4 +1,4 @@
-"""GPU: every path of the hash-table rulebook builders (csrc/rulebook.hip) against pairs derived from the coordinates.
+"""GPU: every path of the hash-table rulebook builders (csrc/rulebook_subm.hip, csrc/rulebook_conv.hip) against pairs derived from the coordinates.
 
 test_gpu_rulebook.py holds the builders to the oracle on whichever path the default dispatch picks for its sizes.  Here
 every dispatch decision of spx_subm_rulebook and spx_conv_rulebook_count / _fill / _static is reached on purpose --

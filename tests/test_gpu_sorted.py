@@ -1,5 +1,5 @@
-"""GPU: sorted-order levels (include/spconv_amd.h "sorted-order levels"; csrc/rulebook.hip conv4_* /
-subm_rank_probe_kernel).
+"""GPU: sorted-order levels (include/spconv_amd.h "sorted-order levels"; csrc/rulebook_sorted.hip conv4_* /
+csrc/rulebook_subm.hip subm_rank_probe_kernel).
 
 The reference's GPU path fixes no order for the outputs of a strided convolution (sort + unique of the coordinate keys,
 spconv/csrc/sparse/all.py:1533-1552, or hash-slot order, csrc/sparse/indices.py:1380-1425); the CPU path numbers them

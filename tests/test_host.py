@@ -417,7 +417,7 @@ def test_device_guard_switches_to_the_tensor_device(monkeypatch):
 
 
 def test_compact_candidates_of_a_strided_convolution():
-    """Python restatement of csrc/rulebook.hip CandIter (third-generation strided-conv rulebook): the valid
+    """Python restatement of csrc/rulebook.h CandIter (third-generation strided-conv rulebook): the valid
     offsets of an axis as a bit set computed WITHOUT integer division (float32 multiply by 1/s + round, exact
     below 2^21), their product walked in ascending offset index.  Against the brute force over all offsets with
     the reference's integer formula (query_npq, indices.py:174-203): same candidates, same order, and never more
