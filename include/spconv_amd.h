@@ -42,6 +42,9 @@ extern "C" {
 #define SPX_COLLAPSE_SUM 0
 #define SPX_COLLAPSE_MEAN 1
 #define SPX_COLLAPSE_MAX 2
+/* row score of a voxel pruning step (spx_row_score) */
+#define SPX_SCORE_ABSMEAN 0
+#define SPX_SCORE_ABSMAX 1
 
 typedef void *spx_stream_t; /* hipStream_t */
 
@@ -106,6 +109,11 @@ int spx_set_option(const char *name_h, int value);
  *                                                  point <-> voxel features: calls of spx_point_groups (the key pass, the
  *                                                  radix argsort and the boundary launch, counted once),
  *                                                  spx_voxel_to_point and spx_point_decorate
+ *   select/score, select/hist, select/pick, select/ties, select/flags, select/count, select/scan, select/scatter,
+ *   select/map                                     voxel pruning, one count per launch: spx_row_score; the passes of
+ *                                                  spx_topk_flags (hist and pick once per 8-bit digit: four each; ties:
+ *                                                  the blocks' tie counts and their scan, counted once); the passes of a
+ *                                                  selection build (map: spx_rankmap_from_sorted over the result)
  * COUT in {16, 32, 64, 128, 256}, NKS in {1, 2}, PK in {1, 2, 4, 8, 16, 32}.  A well-formed key of an instance that is
  * never built counts 0; anything else is unknown.
  * float64 (SPX_F64) has a family and keys of its own, outside the dt vocabulary above:
@@ -987,6 +995,86 @@ int spx_voxel_to_point(const void *vfeat, int num_voxels, const int32_t *rows, i
 int spx_point_decorate(const float *points, int nfeat, int n_cap, const int32_t *rows, const int32_t *indices,
                        int ndim, const float *vsize, const float *coors_range, const float *cluster_mean,
                        int flags, void *out, int out_dtype, int C_out, spx_stream_t stream);
+
+/* ---- voxel pruning (csrc/select.hip) ---------------------------------------------------------------------
+ * Keep the most important rows of a sparse tensor and drop, or process separately, the rest: the pruned down-sampling
+ * blocks of SPS-Conv and VoxelNeXt, and every sparse head that keeps its top-scoring voxels.  Stands where a torch
+ * composite would: abs().mean(1), topk (ties unspecified), boolean indexing (a count read back: not capturable), rows
+ * that know nothing of dead rows and leave without a rank map.  Every call: the caller allocates, every grid depends on
+ * host-known sizes only, nothing is read back except by spx_select_count, and the argument checks that need no pointer
+ * come before any pointer is looked at.
+ *
+ * ROW SCORE.  spx_row_score: score[i] (fp32 [n]) from feat [n, C] (contiguous; SPX_F16 / SPX_BF16 / SPX_F32 / SPX_F64,
+ * any C >= 1); -inf for rows at or beyond *n_live (NULL or a device int32).  One launch, no atomics, every element
+ * written exactly once.
+ *   SPX_SCORE_ABSMAX: the maximum of |feat[i, c]| (exact in any order; NaN: unspecified), rounded to fp32 for SPX_F64.
+ *   SPX_SCORE_ABSMEAN: the sum of |feat[i, c]| in fp32 (fp64 for SPX_F64), divided by C in that type, rounded once to
+ *   fp32.  THE ORDER OF THE SUM is a function of C and the dtype alone.  With e = the element size in bytes:
+ *     V = 16 / e when C * e is a multiple of 16, else 1         (elements of a piece)
+ *     P = C / V                                                 (pieces of a row)
+ *     G = the smallest power of two >= P, at most 64            (lanes of a row)
+ *     acc[s] = 0 for s = 0 .. G - 1
+ *     for s in 0 .. G - 1: for p = s, s + G, s + 2 G, ... < P: for j = 0 .. V - 1: acc[s] = acc[s] + |feat[i, p V + j]|
+ *     for d = G / 2, G / 4, ..., 1: for s in 0 .. d - 1: acc[s] = acc[s] + acc[s + d]
+ *     score[i] = acc[0] / C
+ *   every addition rounded on its own.  A row whose bytes are a multiple of 16 moves as 16-byte pieces per lane when
+ *   feat is 16-byte aligned (the rule of spx_collapse_fwd) and element by element otherwise -- in the same order.
+ *
+ * TOP-K FLAGS.  spx_topk_flags: keep (uint8 [n]) = 1 for exactly k live rows, 0 elsewhere.  A row is LIVE when it lies
+ * below *n_live and, when `indices` (NULL, or int32 [n, ndim + 1]) is given, its batch index is inside [0, batch).
+ * With `live` the number of live rows: k_abs >= 0 gives k = min(k_abs, live); k_abs < 0 gives k = (int)(ratio *
+ * (double)live) with ratio in [0, 1] -- one IEEE fp64 multiply, truncated, computed on the device.  Scores are ordered
+ * by the unsigned KEY = bits ^ (bits >> 31 ? 0xffffffff : 0x80000000): a total order on all fp32 bit patterns (-0.0
+ * below +0.0, a positive NaN above +inf).  Kept: every live row whose key is above the k-th largest key T, and of the
+ * live rows whose key equals T those with the LOWEST ROW INDEX, as many as are needed.  sel_dev (device int32 [4]) =
+ * {live, k, T, ties taken}; k = 0 leaves T = 0xffffffff and ties = 0.  n = 0, k = 0 and k = live are legal.
+ *   Radix select on the key, most significant 8-bit digit first: per digit a histogram pass (per-wave copies in LDS,
+ *   merged with integer atomics, whose result does not depend on order) and a pick by one workgroup; then the tie
+ *   rows are counted per workgroup, the counts scanned, and one flag pass ranks the tie rows by a block scan.
+ *   Launches: a fill, 4 x (hist, pick), ties, its scan, flags (n = 0: the fill and the picks).
+ *   spx_topk_ws_bytes: its scratch; 0 for n < 0.  Monotone in n.
+ *
+ * ROW SELECTION.  indices = int32 [n, ndim + 1], keep = uint8 [n] (nonzero = keep), invert = 0 or 1.  A row is LIVE
+ * when it lies below *n_live, its batch index is inside [0, batch) and every coordinate inside [0, extent): the rule
+ * of the collapse builder.  A row is SELECTED when it is live and (keep[i] != 0) != invert.  The selected rows are
+ * compacted in ascending input row (a stable compaction):
+ *     out_indices [n_out, ndim + 1]
+ *     rows        [n]: the output row of each input row, -1 if the row is not selected or is cut
+ *     src         [n_out]: the input row of each output row
+ *   spx_select_ws_bytes: scratch of a build over n rows; 0 for n < 0 and for ndim outside [1, 4].  Monotone in n.
+ *   spx_select_count: a fill, the blocks' counts, their scan, and the call's ONE D->H read (synchronises the stream):
+ *   result_h [2] = {selected rows, live rows}.
+ *   spx_select_fill: with the SAME arguments and ws, unchanged since the count, the scatter.  n_out = the count's
+ *   result; a smaller n_out keeps the first n_out selected rows, the entries of out_indices and src beyond the selected
+ *   rows are -1.
+ *   spx_select_static: the static-shape form: room for n_out_cap rows, nothing read back (hipGraph-safe): a fill, count,
+ *   scan, scatter.  n_out_dev [3] (device) = {found -- may exceed the cap --, 0, live = min(found, cap)}; selected rows
+ *   beyond the cap are cut in row order (rows entry -1); out_indices and src past the live count are -1: the dead-row
+ *   contract of spx_collapse_static and spx_union_static.
+ *   RANK MAP.  rankmap = NULL, or a buffer of spx_rankmap_bytes(ndim, batch, spatial_h): the caller vouches that the
+ *   live input rows are in ascending, unique key order.  A subset of such rows, taken in row order, is in ascending,
+ *   unique key order itself, so _fill and _static leave the rank map of out_indices behind (spx_rankmap_from_sorted
+ *   over the result: two more launches, no marks, no scan); `violation` (device int32 [1] or NULL) as there.
+ *
+ * FEATURE ROWS use kernels the library already has: out[r] = feat[src[r]] is spx_voxel_to_point with a zero fill, the
+ * gradient din[i] = dout[rows[i]] is spx_union_add_bwd with one operand.  A row keeps its bits. */
+int spx_row_score(const void *feat, int n, int C, int dtype, int op, const int32_t *n_live, float *score,
+                  spx_stream_t stream);
+size_t spx_topk_ws_bytes(long long n);
+int spx_topk_flags(const float *score, const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch,
+                   int k_abs, double ratio, uint8_t *keep, int32_t *sel_dev, void *ws, size_t ws_bytes,
+                   spx_stream_t stream);
+size_t spx_select_ws_bytes(int ndim, long long n);
+int spx_select_count(const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch, const int *spatial_h,
+                     const uint8_t *keep, int invert, void *ws, size_t ws_bytes, int *result_h, spx_stream_t stream);
+int spx_select_fill(const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch, const int *spatial_h,
+                    const uint8_t *keep, int invert, int n_out, int32_t *out_indices, int32_t *rows, int32_t *src,
+                    void *rankmap, size_t rankmap_bytes, int32_t *violation, const void *ws, size_t ws_bytes,
+                    spx_stream_t stream);
+int spx_select_static(const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch, const int *spatial_h,
+                      const uint8_t *keep, int invert, int n_out_cap, int32_t *out_indices, int32_t *rows,
+                      int32_t *src, int32_t *n_out_dev, void *rankmap, size_t rankmap_bytes, int32_t *violation,
+                      void *ws, size_t ws_bytes, spx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -182,11 +182,23 @@ SIGNATURES = {
                                           ctypes.c_longlong, vp, vp]),
     "spx_point_decorate": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, c_float_p, c_float_p,
                                           vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp]),
+    "spx_row_score": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
+    "spx_topk_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "spx_topk_flags": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_double, vp, vp, vp, ctypes.c_size_t, vp]),
+    "spx_select_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_longlong]),
+    "spx_select_count": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, c_int_p, vp, ctypes.c_int, vp,
+                                        ctypes.c_size_t, c_int_p, vp]),
+    "spx_select_fill": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, c_int_p, vp, ctypes.c_int,
+                                       ctypes.c_int, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp]),
+    "spx_select_static": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, c_int_p, vp, ctypes.c_int,
+                                         ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp]),
 }
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_I8, DTYPE_F64 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_LEAKY_RELU = 0, 1, 2, 3
 COLLAPSE_SUM, COLLAPSE_MEAN, COLLAPSE_MAX = 0, 1, 2
+SCORE_ABSMEAN, SCORE_ABSMAX = 0, 1
 
 _lib: Optional[ctypes.CDLL] = None
 

@@ -37,6 +37,7 @@ std::atomic<long long> g_dense_launches[kDenseCount];
 std::atomic<long long> g_union_launches[kUnionCount];
 std::atomic<long long> g_collapse_launches[kCollapseCount];
 std::atomic<long long> g_pointvoxel_launches[kPvCount];
+std::atomic<long long> g_select_launches[kSelInstCount];
 std::atomic<long long> g_pool_launches[kPoolCount];
 std::atomic<long long> g_rulebook_launches[kRbCount];
 
@@ -166,6 +167,15 @@ std::atomic<long long> *pointvoxel_counter(const char *key) {
   return nullptr;
 }
 
+// counter of a voxel-pruning key (spx_launch_count), or null
+std::atomic<long long> *select_counter(const char *key) {
+  static const char *names[kSelInstCount] = {"select/score", "select/hist", "select/pick", "select/ties", "select/flags",
+                                             "select/count", "select/scan", "select/scatter", "select/map"};
+  for (int i = 0; i < kSelInstCount; ++i)
+    if (strcmp(key, names[i]) == 0) return &g_select_launches[i];
+  return nullptr;
+}
+
 // counter of a rulebook-builder key rulebook/<pass> (spx_launch_count), or null
 std::atomic<long long> *rulebook_counter(const char *key) {
   static const char *names[kRbCount] = {"subm_probe3", "subm_probe4", "subm_probe5", "subm_mask_pass", "subm_lists",
@@ -240,6 +250,7 @@ long long spx_launch_count(const char *family_h) {
   if (std::atomic<long long> *c = spx::union_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::collapse_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pointvoxel_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::select_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pool_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::rulebook_counter(family_h)) return c->load(std::memory_order_relaxed);
   const int slot = spx::instance_slot(family_h);

@@ -207,6 +207,15 @@ enum PointVoxelInst { kPvGroups = 0, kPvGather, kPvDecorate, kPvCount };
 extern std::atomic<long long> g_pointvoxel_launches[kPvCount];
 inline void count_pointvoxel(PointVoxelInst i) { g_pointvoxel_launches[i].fetch_add(1, std::memory_order_relaxed); }
 
+// voxel pruning (select.hip): one counter per pass, counted once per launch (a top-k call counts hist and pick four
+// times each: once per digit).
+// Keys select/score, select/hist, select/pick, select/ties, select/flags, select/count, select/scan, select/scatter,
+// select/map.
+enum SelectInst { kSelScore = 0, kSelHist, kSelPick, kSelTies, kSelFlags, kSelCount, kSelScan, kSelScatter, kSelMap,
+                  kSelInstCount };
+extern std::atomic<long long> g_select_launches[kSelInstCount];
+inline void count_select(SelectInst i) { g_select_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
 // pooling (pool.hip): one counter per kernel instance, op x dtype x piece.
 // Keys pool/<op>/<dt>/<piece>: op max_fwd | max_bwd | avg_fwd | avg_bwd (PoolOp order), dt f16 | bf16 | f32 | f64 | i8,
 // piece v (16-byte pieces) | s (one element).  int8 is built for max_fwd only; its other keys count 0.

@@ -1,4 +1,4 @@
-// Range fills shared by the translation units that build index structures (rulebook_*.hip, union.hip, collapse.hip, through table.h); every
+// Range fills shared by the translation units that build index structures (rulebook_*.hip, union.hip, collapse.hip, select.hip, through table.h); every
 // definition has internal linkage.
 #pragma once
 #include "common.h"

@@ -1,6 +1,7 @@
 // Feature rows as PIECES: the storage / accumulator types of the four floating dtypes, the 16-byte (or one-element)
 // piece a lane moves, and the host helpers that pick a piece width and a grid for a streaming launch.  Shared by the
-// translation units that merge or reduce rows (union.hip, collapse.hip); every definition has internal linkage.
+// translation units that merge, reduce or score rows (union.hip, collapse.hip, select.hip); every definition has internal
+// linkage.
 #pragma once
 #include <initializer_list>
 

@@ -409,6 +409,117 @@ def sparse_collapse(x, axes, reduce="sum", static_num_out=None, owner=None):
     return res
 
 
+# ------------------------------------------------------------------ voxel pruning
+def row_score(features, op="absmean", n_live=None):
+    """One fp32 score per row on the kernel of csrc/select.hip: the mean ("absmean") or the maximum ("absmax") of
+    |features[i, :]|, -inf for rows at or beyond *n_live.  The order of the mean's sum depends on the channel count
+    and the dtype only (include/spconv_amd.h, voxel pruning): identical run to run and for any number of rows."""
+    from spconv_amd.pytorch import _select
+    return _select.row_score(features, op, n_live)
+
+
+def topk_mask(score, k=None, ratio=None, indices=None, batch_size=None, n_live=None):
+    """uint8 flags [n] of exactly k live rows: the rows with the largest scores, of equal scores those with the lowest
+    row index.  Exactly one of `k` (a count, capped at the live rows) and `ratio` (in [0, 1]: k = int(ratio * live),
+    computed on the device) is given.  A row is live below *n_live and, with `indices` and `batch_size`, when its
+    batch index is inside [0, batch_size).  Nothing is read back (spx_topk_flags)."""
+    from spconv_amd.pytorch import _select
+    return _select.topk_flags(score, k, ratio, indices, batch_size, n_live)[0]
+
+
+class SparseSelectFunction(Function):
+    """Feature rows of a row selection: out[r] = feat[src[r]] (zeros past the live rows), one gather launch; the
+    backward is one gather launch as well, din[i] = dout[rows[i]] (zeros for rows that were not selected or were cut).
+    Bytes move, nothing is added: a row keeps its bits."""
+
+    @staticmethod
+    def forward(ctx, feat, build):
+        from spconv_amd.pytorch import _select
+        ctx.build = build
+        return _select.fwd(feat.detach(), build)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        from spconv_amd.pytorch import _select
+        return _select.bwd(grad_output, ctx.build), None
+
+
+def _select_checks(x, what):
+    from spconv_amd.pytorch._rulebook import _require_gpu
+    feat = x.features
+    _require_gpu(feat, "features")
+    if feat.is_quantized or feat.dtype not in _UNION_DTYPES:
+        raise NotImplementedError(f"{what}: features must be float16, bfloat16, float32 or float64, got {feat.dtype}")
+    _require_gpu(x.indices, "indices")
+    if x.indices.dtype != torch.int32:
+        raise NotImplementedError(f"{what}: indices must be int32, got {x.indices.dtype}")
+    return feat
+
+
+def sparse_select(x, keep, invert=False, static_num_out=None, owner=None):
+    """The live rows of x whose flag `keep[i]` (bool or uint8 [n]) is set -- `invert`: is not set -- as a fresh
+    SparseConvTensor, rows in x's order, on the kernels of csrc/select.hip.  Spatial shape and batch size are x's; the
+    indice_dict is empty (the coordinate set is new) and there is no grid.  When x's index tensor carries the level's
+    rank map (its rows are in key order) the result's map is built and attached: the SubM layers behind build their
+    rulebooks from it.  Static form when x carries n_live_dev or `static_num_out` is given: room for `static_num_out`
+    rows (default: x's rows, which always suffices), nothing read back, n_live_dev = the live rows found; `owner` (the
+    calling module) keeps the device-side counters {found, 0, live} of its last call in `_static_n_out_dev`.  Only the
+    features carry a gradient."""
+    from spconv_amd.pytorch import _select, ops
+    from spconv_amd.pytorch.core import SparseConvTensor
+    feat = _select_checks(x, "sparse_select")
+    n = int(feat.shape[0])
+    n_live_in = getattr(x, "n_live_dev", None)
+    static = n_live_in is not None or static_num_out is not None
+    ranked = ops._rankmap_of(x.indices, x.batch_size, x.spatial_shape, n, 27) is not None
+    build = _select.select_build(x.indices, x.batch_size, x.spatial_shape, keep, invert, n_live=n_live_in,
+                                 static_num_out=(static_num_out or n or 1) if static else None, rank_map=ranked)
+    out_features = SparseSelectFunction.apply(feat, build)
+    res = SparseConvTensor(out_features, build.out_indices, x.spatial_shape, x.batch_size, benchmark=x.benchmark)
+    res.benchmark_record = x.benchmark_record
+    res._timer = x._timer
+    res.thrust_allocator = x.thrust_allocator
+    res.force_algo = x.force_algo
+    res.n_live_dev = build.n_out_dev[2:3] if static else None
+    if static and owner is not None:
+        owner._static_n_out_dev = build.n_out_dev
+    return res
+
+
+def sparse_prune(x, ratio=None, k=None, score="absmean", return_dropped=False, static_num_out=None, owner=None):
+    """Spatial voxel pruning: keeps the k live rows of x with the largest score -- `k` rows, or int(ratio * live rows)
+    -- and returns them as a fresh SparseConvTensor (sparse_select); of equal scores the lowest rows stay, so the
+    selection is identical run to run.  `score`: "absmean" | "absmax" of the row's features (row_score), or a tensor
+    of one value per row (the predicted importance of a small head: detached and cast to fp32).  return_dropped=True
+    returns (kept, dropped) from the same flags.  Dead rows (at or beyond n_live_dev, batch index -1) never compete.
+    Static form as sparse_select; the kept side's default bound is max(1, int(ratio * rows)) or min(k, rows), which
+    always suffices, the dropped side's is x's rows; an explicit `static_num_out` bounds the kept side and is reported
+    through `owner._static_n_out_dev`."""
+    from spconv_amd.pytorch import _select
+    k_abs, r = _select.check_count(k, ratio, "sparse_prune")
+    feat = _select_checks(x, "sparse_prune")
+    n = int(feat.shape[0])
+    n_live_in = getattr(x, "n_live_dev", None)
+    if isinstance(score, torch.Tensor):
+        if score.numel() != n:
+            raise ValueError(f"sparse_prune: score holds {score.numel()} values for {n} rows")
+        s = score.detach().reshape(n).to(torch.float32)
+    elif score in _select.OPS:
+        s = _select.row_score(feat, score, n_live_in)
+    else:
+        raise ValueError(f"sparse_prune: score must be 'absmean', 'absmax' or a tensor, got {score!r}")
+    keep, _ = _select.topk_flags(s, k, ratio, x.indices, x.batch_size, n_live_in)
+    static = n_live_in is not None or static_num_out is not None
+    bound = None
+    if static:
+        bound = static_num_out or max(1, int(r * n) if k is None else min(k_abs, n))
+    kept = sparse_select(x, keep, False, bound, owner)
+    if not return_dropped:
+        return kept
+    return kept, sparse_select(x, keep, True, (n or 1) if static else None, None)
+
+
 def sparse_add_hash_based(*tens):
     """Sum of sparse tensors with different coordinate sets (reference functional.py:439-499).  On the union kernels
     where they apply (sparse_add_native): rows in ascending key order with the level's rank map attached, or -- when

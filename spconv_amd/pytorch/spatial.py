@@ -59,3 +59,40 @@ class SparseCollapse(SparseModule):
 
     def extra_repr(self) -> str:
         return f"axes={self.axes}, reduce={self.reduce!r}, static_num_out={self.static_num_out}"
+
+
+class SparsePrune(SparseModule):
+    """Spatial voxel pruning (``functional.sparse_prune``): keeps the ``k`` live rows with the largest score, or
+    ``int(ratio * live rows)`` of them -- exactly one of ``ratio`` and ``k`` is given -- on the kernels of
+    csrc/select.hip.  ``score`` = "absmean" | "absmax" of the row's features.  Of equal scores the lowest rows stay:
+    the selection is identical run to run.  The result is a fresh tensor over the same grid, rows in the input's
+    order; when the input's rows are in key order (its index tensor carries the level's rank map) the result's rank map
+    is attached, and the ``SubMConv`` layers behind build their rulebooks from it.  ``return_dropped=True`` returns
+    ``(kept, dropped)``.
+
+    Static shapes (an input with ``n_live_dev``: inside StaticInference / StaticTrainingStep) take the sync-free form;
+    ``static_num_out`` bounds the kept rows (None: the bound that follows from ``ratio`` / ``k`` and the input's rows,
+    which always suffices).  The counters of the last call {rows found, 0, live rows} stay on the device in
+    ``_static_n_out_dev``; a module with an explicit bound is part of the runners' ``overflowed()``."""
+
+    def __init__(self, ratio: Optional[float] = None, k: Optional[int] = None, score: str = "absmean",
+                 return_dropped: bool = False, static_num_out: Optional[int] = None, name: Optional[str] = None):
+        super().__init__(name=name)
+        from spconv_amd.pytorch import _select
+        _select.check_count(k, ratio, "SparsePrune")
+        if score not in _select.OPS:
+            raise ValueError(f"SparsePrune: score must be 'absmean' or 'absmax', got {score!r}")
+        self.ratio = None if ratio is None else float(ratio)
+        self.k = None if k is None else int(k)
+        self.score = score
+        self.return_dropped = bool(return_dropped)
+        self.static_num_out = None if static_num_out is None else int(static_num_out)
+        self._static_n_out_dev = None
+
+    def forward(self, x: SparseConvTensor):
+        from spconv_amd.pytorch import functional as F
+        return F.sparse_prune(x, self.ratio, self.k, self.score, self.return_dropped, self.static_num_out, self)
+
+    def extra_repr(self) -> str:
+        return (f"ratio={self.ratio}, k={self.k}, score={self.score!r}, return_dropped={self.return_dropped}, "
+                f"static_num_out={self.static_num_out}")

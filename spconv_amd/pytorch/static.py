@@ -90,13 +90,21 @@ def _bounded_collapses(net: torch.nn.Module) -> Dict[str, torch.nn.Module]:
             if isinstance(m, SparseCollapse) and m.static_num_out is not None}
 
 
+def _bounded_prunes(net: torch.nn.Module) -> Dict[str, torch.nn.Module]:
+    """SparsePrune modules that were given an explicit `static_num_out`: their kept rows can overflow it."""
+    from spconv_amd.pytorch.spatial import SparsePrune
+    return {name: m for name, m in net.named_modules()
+            if isinstance(m, SparsePrune) and m.static_num_out is not None}
+
+
 def _static_counters(runner) -> Dict[str, torch.Tensor]:
     """The device-side {found, flag} counters of a captured pass: the strided layers', the bounded unions' (whose
-    flag says that a coordinate occurred twice within one operand) and the bounded collapses'; the unions' and the
-    collapses' bounds join runner.bounds."""
+    flag says that a coordinate occurred twice within one operand), the bounded collapses' and the bounded prunes';
+    the unions', the collapses' and the prunes' bounds join runner.bounds."""
     out = {name: m._static_n_out_dev for name, m in runner._layers.items()
            if getattr(m, "_static_n_out_dev", None) is not None}
-    for name, m in {**_bounded_unions(runner.net), **_bounded_collapses(runner.net)}.items():
+    for name, m in {**_bounded_unions(runner.net), **_bounded_collapses(runner.net),
+                    **_bounded_prunes(runner.net)}.items():
         if m._static_n_out_dev is not None:
             out[name] = m._static_n_out_dev[:2]
             runner.bounds[name] = m.static_num_out
