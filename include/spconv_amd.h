@@ -109,6 +109,9 @@ int spx_set_option(const char *name_h, int value);
  *                                                  point <-> voxel features: calls of spx_point_groups (the key pass, the
  *                                                  radix argsort and the boundary launch, counted once),
  *                                                  spx_voxel_to_point and spx_point_decorate
+ *   interp/corners_ranked, interp/corners_hash, interp/fwd, interp/bwd
+ *                                                  trilinear devoxelisation: calls of spx_point_corners by lookup form,
+ *                                                  of spx_interp_fwd and of spx_interp_bwd
  *   select/score, select/hist, select/pick, select/ties, select/flags, select/count, select/scan, select/scatter,
  *   select/map                                     voxel pruning, one count per launch: spx_row_score; the passes of
  *                                                  spx_topk_flags (hist and pick once per 8-bit digit: four each; ties:
@@ -995,6 +998,66 @@ int spx_voxel_to_point(const void *vfeat, int num_voxels, const int32_t *rows, i
 int spx_point_decorate(const float *points, int nfeat, int n_cap, const int32_t *rows, const int32_t *indices,
                        int ndim, const float *vsize, const float *coors_range, const float *cluster_mean,
                        int flags, void *out, int out_dtype, int C_out, spx_stream_t stream);
+
+/* ---- trilinear devoxelisation (csrc/interp.hip) ------------------------------------------------------------
+ * Voxel rows of a sparse level interpolated to points: every point reads the K = 2^ndim voxels whose CENTRES surround
+ * it and blends their rows (the devoxelize of SPVCNN / PVCNN, the point refinement of Cylinder3D, the voxel-to-keypoint
+ * interpolation of the PV-RCNN family).  Stands where a torch composite would: K hash queries per point, index_select
+ * + mul + sum over [N, K, C] temporaries, an index_add_ backward (float atomics: not reproducible), none of it aware of
+ * dead rows or a device-side point count.  Every call: the caller allocates, nothing is read back, nothing
+ * synchronises, every grid depends on host-known sizes only (hipGraph-safe).  The argument checks that need no pointer
+ * come before any pointer is looked at.  There is no gradient with respect to the points or the weights.
+ *
+ *   spx_point_corners: points = fp32 [n_cap, nfeat], the first ndim columns x, y, z (as spx_point2voxel); batch_ids =
+ *   int32 [n_cap] or NULL (all batch 0); n_points_dev = NULL or a device int32: rows at or beyond it are no points;
+ *   ndim = 2 or 3, K = 2^ndim; vsize [ndim] and coors_range [2 * ndim] = HOST arrays in zyx order, as
+ *   spx_point_decorate takes them -- the voxel size is that of the level being read; indices = int32 [n, ndim + 1], the
+ *   level's index rows; n_live = NULL or a device int32; batch, spatial_h [ndim] = batch count and grid extents;
+ *   rankmap = NULL or a buffer of spx_rankmap_bytes(ndim, batch, spatial_h); flags bit 0 = normalise.
+ *   Outputs (device, 16-byte aligned): corner_rows int32 [n_cap, K], corner_w fp32 [n_cap, K].
+ *   Per point column j (x = 0; grid axis ndim - 1 - j), all in fp32:
+ *     t_j = (p_j - lo_j) / vsize_j          (the voxeliser's expression: the point's own voxel is floorf(t_j))
+ *     g_j = t_j - 0.5f, b_j = floorf(g_j), f_j = g_j - b_j
+ *   Corner c steps by bit j of c along axis j: coordinate b_j + bit, weight ((w_x * w_y) * w_z) with
+ *   w_j = bit ? f_j : 1.0f - f_j.  A point is VALID when it lies below *n_points, its batch id is in [0, batch) and
+ *   floorf(t_j) is in [0, extent_j) on every axis (false for NaN); an invalid point gets rows -1 and weights 0.  A
+ *   corner outside the grid, or one that no LIVE row holds, gets row -1 and weight 0; a row is live when it lies below
+ *   *n_live, its batch index is in [0, batch) and its coordinates are in range.  Normalise: s = the sum of the present
+ *   corners' weights added in ascending corner index, every present weight becomes w / s, s == 0 leaves rows -1 and
+ *   weights 0.  Every multiply, add, subtract and divide is rounded on its own (no FMA).
+ *   Lookup: with a rank map the caller vouches that the live rows are in ascending, unique key order and the row is
+ *   the rank of the key (one launch, no hash table, ws may be NULL).  With rankmap = NULL the call builds the hash
+ *   table of the index builders in ws from the live rows' keys -- a duplicate coordinate goes to the lowest row -- and
+ *   probes it: a fill, the insert pass, the corner pass.  Both forms return identical tables for a key-ordered,
+ *   duplicate-free level.  Requires n_cap * K < 2^31.
+ *   At most 2^30 rows (the table holds two slots per row), and batch x grid must fit a 63-bit key.
+ *   spx_point_corners_ws_bytes: scratch of the hash form; monotone in its arguments, 0 for arguments that are refused
+ *   (ndim outside {2, 3}, a negative count, n_cap * K >= 2^31, n > 2^30).
+ *
+ *   spx_interp_fwd: out[i, :] = sum over c = 0 .. K - 1 of corner_w[i, c] * vfeat[corner_rows[i, c], :] ([n, C] ->
+ *   [n_cap, C], contiguous; SPX_F16 / SPX_BF16 / SPX_F32 / SPX_F64).  Corners whose row is outside [0, n) are skipped;
+ *   fp32 accumulation (fp64 for SPX_F64) from zero in ascending c as acc = acc + (w * x), each operation rounded on its
+ *   own, one round-to-nearest-even into the feature type; a point without a corner gets zeros.  Rows whose byte size is
+ *   a multiple of 16 (and 16-byte aligned pointers) move as 16-byte pieces per lane, other widths element by element.
+ *   One launch, no temporaries, every output element written exactly once.
+ *
+ *   spx_interp_bwd: the gradient with respect to the voxel rows over the TRANSPOSED corner list: offsets [n + 1] and
+ *   list [n_cap * K] = spx_point_groups(ids = corner_rows flattened, id_bytes 4, n_cap * K entries, num_voxels = n),
+ *   whose groups hold the entries e = i * K + c in ascending e.  dvfeat[v, :] = sum over e in list[offsets[v] ..
+ *   offsets[v + 1]) of corner_w[e] * dout[e / K, :], in list order, accumulated and rounded as the forward; zeros for
+ *   an empty group and for rows at or beyond *n_live.  No atomics, identical run to run; a voxel's row belongs to a
+ *   group of lanes (the walk of spx_collapse_fwd), so long groups do not serialise on one lane.  One launch. */
+size_t spx_point_corners_ws_bytes(int n_cap, int ndim, int n);
+int spx_point_corners(const float *points, int nfeat, const int32_t *batch_ids, int n_cap,
+                      const int32_t *n_points_dev, int ndim, const float *vsize, const float *coors_range,
+                      const int32_t *indices, int n, const int32_t *n_live, int batch, const int *spatial_h,
+                      const void *rankmap, size_t rankmap_bytes, int flags, int32_t *corner_rows, float *corner_w,
+                      void *ws, size_t ws_bytes, spx_stream_t stream);
+int spx_interp_fwd(const void *vfeat, int n, const int32_t *corner_rows, const float *corner_w, int n_cap, int ndim,
+                   int C, int dtype, void *out, spx_stream_t stream);
+int spx_interp_bwd(const void *dout, int n_cap, int ndim, const float *corner_w, const int32_t *offsets,
+                   const int32_t *list, int n, const int32_t *n_live, int C, int dtype, void *dvfeat,
+                   spx_stream_t stream);
 
 /* ---- voxel pruning (csrc/select.hip) ---------------------------------------------------------------------
  * Keep the most important rows of a sparse tensor and drop, or process separately, the rest: the pruned down-sampling

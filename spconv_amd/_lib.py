@@ -182,6 +182,14 @@ SIGNATURES = {
                                           ctypes.c_longlong, vp, vp]),
     "spx_point_decorate": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, c_float_p, c_float_p,
                                           vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp]),
+    "spx_point_corners_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "spx_point_corners": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, c_float_p, c_float_p, vp,
+                                         ctypes.c_int, vp, ctypes.c_int, c_int_p, vp, ctypes.c_size_t, ctypes.c_int, vp,
+                                         vp, vp, ctypes.c_size_t, vp]),
+    "spx_interp_fwd": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      vp, vp]),
+    "spx_interp_bwd": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int,
+                                      ctypes.c_int, vp, vp]),
     "spx_row_score": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
     "spx_topk_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "spx_topk_flags": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -37,6 +37,7 @@ std::atomic<long long> g_dense_launches[kDenseCount];
 std::atomic<long long> g_union_launches[kUnionCount];
 std::atomic<long long> g_collapse_launches[kCollapseCount];
 std::atomic<long long> g_pointvoxel_launches[kPvCount];
+std::atomic<long long> g_interp_launches[kInterpCount];
 std::atomic<long long> g_select_launches[kSelInstCount];
 std::atomic<long long> g_pool_launches[kPoolCount];
 std::atomic<long long> g_rulebook_launches[kRbCount];
@@ -167,6 +168,14 @@ std::atomic<long long> *pointvoxel_counter(const char *key) {
   return nullptr;
 }
 
+// counter of a trilinear-devoxelisation key (spx_launch_count), or null
+std::atomic<long long> *interp_counter(const char *key) {
+  static const char *names[kInterpCount] = {"interp/corners_ranked", "interp/corners_hash", "interp/fwd", "interp/bwd"};
+  for (int i = 0; i < kInterpCount; ++i)
+    if (strcmp(key, names[i]) == 0) return &g_interp_launches[i];
+  return nullptr;
+}
+
 // counter of a voxel-pruning key (spx_launch_count), or null
 std::atomic<long long> *select_counter(const char *key) {
   static const char *names[kSelInstCount] = {"select/score", "select/hist", "select/pick", "select/ties", "select/flags",
@@ -250,6 +259,7 @@ long long spx_launch_count(const char *family_h) {
   if (std::atomic<long long> *c = spx::union_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::collapse_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pointvoxel_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::interp_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::select_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pool_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::rulebook_counter(family_h)) return c->load(std::memory_order_relaxed);

@@ -207,6 +207,12 @@ enum PointVoxelInst { kPvGroups = 0, kPvGather, kPvDecorate, kPvCount };
 extern std::atomic<long long> g_pointvoxel_launches[kPvCount];
 inline void count_pointvoxel(PointVoxelInst i) { g_pointvoxel_launches[i].fetch_add(1, std::memory_order_relaxed); }
 
+// trilinear devoxelisation (interp.hip): one counter per entry point and lookup form.
+// Keys interp/corners_ranked, interp/corners_hash, interp/fwd, interp/bwd.
+enum InterpInst { kInterpCornersRanked = 0, kInterpCornersHash, kInterpFwd, kInterpBwd, kInterpCount };
+extern std::atomic<long long> g_interp_launches[kInterpCount];
+inline void count_interp(InterpInst i) { g_interp_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
 // voxel pruning (select.hip): one counter per pass, counted once per launch (a top-k call counts hist and pick four
 // times each: once per digit).
 // Keys select/score, select/hist, select/pick, select/ties, select/flags, select/count, select/scan, select/scatter,

@@ -1,0 +1,471 @@
+// Trilinear devoxelisation (spx_point_corners, spx_interp_fwd, spx_interp_bwd): voxel rows of a sparse level
+// interpolated to points, the way the point-voxel networks (SPVCNN, PVCNN, the keypoint interpolation of the PV-RCNN
+// family) read per-point features out of a sparse level.
+//
+//   corners   per point the K = 2^ndim voxels whose centres surround it: corner_rows [n_cap, K] (row of the level, -1:
+//             outside the grid or no live row there) and corner_w [n_cap, K] (the multilinear weight, 0 where the row
+//             is -1).  A coordinate lookup is one load of the level's rank map (rankmap.h) for a key-ordered level, or
+//             a probe of the builders' hash table (table.h), built here from the level's rows, for rows in any order.
+//   forward   out[i] = sum_c corner_w[i, c] * vfeat[corner_rows[i, c]]: one item per (point, piece), the K loads of a
+//             piece in flight together, the sum in ascending c.
+//   backward  dvfeat[v] = sum over the entries e = i * K + c of voxel v's group of corner_w[e] * dout[e / K]: a segment
+//             sum over the TRANSPOSED corner list, which is spx_point_groups over the flattened corner table (a stable
+//             sort: ascending e inside a group).  A voxel's row belongs to a group of G lanes as in collapse.hip, each
+//             lane walks the whole list for its pieces, four entries' loads in flight: no atomics, list order.
+// All arithmetic is fp32 (fp64 accumulation for SPX_F64) with every operation rounded on its own, so a host loop
+// reproduces every element bit for bit.
+#include "common.h"
+#include "fill.h"
+#include "piece.h"
+#include "rankmap.h"
+#include "table.h"
+
+// no multiply-add pair of this unit may be contracted into an FMA (see pointvoxel.hip)
+#pragma clang fp contract(off)
+
+namespace spx {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kAhead = 4;             // list entries whose loads are in flight together (backward)
+constexpr int kDims = 3;              // ndim is 2 or 3
+constexpr int kMaxRows = 1 << 30;     // rows of a level: table_capacity(n) = 2^31 slots still fits its 32-bit mask
+
+struct CornerGeom {
+  int ndim, batch;
+  int dims[kDims];                    // grid extents, index-column (zyx) order
+  float vsize[kDims], lo[kDims];      // by POINT COLUMN (x, y, z): entry j belongs to grid axis ndim - 1 - j
+};
+
+// linear key of index row i (batch-major, last axis fastest), -1 for a dead row
+__device__ __forceinline__ long long row_key(const int32_t *__restrict__ idx, const int32_t *__restrict__ n_live,
+                                             const CornerGeom &g, int i) {
+  if (n_live && i >= *n_live) return -1;
+  const int32_t *r = idx + static_cast<size_t>(i) * (g.ndim + 1);
+  const int b = r[0];
+  if (static_cast<unsigned>(b) >= static_cast<unsigned>(g.batch)) return -1;
+  long long key = b;
+  for (int d = 0; d < g.ndim; ++d) {
+    const int v = r[1 + d];
+    if (static_cast<unsigned>(v) >= static_cast<unsigned>(g.dims[d])) return -1;
+    key = key * g.dims[d] + v;
+  }
+  return key;
+}
+
+__global__ void __launch_bounds__(kBlock)
+corner_insert_kernel(const int32_t *__restrict__ idx, int n, const int32_t *__restrict__ n_live, CornerGeom g, Table t) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const long long key = row_key(idx, n_live, g, i);
+  if (key >= 0) table_insert_min(t, key, i);      // (a duplicate coordinate: the lowest row stays)
+}
+
+// One thread per point.  RANKED: the lookup is rank_of over the level's rank map, else a probe of the table.
+template <int NDIM, bool RANKED>
+__global__ void __launch_bounds__(kBlock)
+corner_kernel(const float *__restrict__ points, int nfeat, const int32_t *__restrict__ batch_ids, int n_cap,
+              const int32_t *__restrict__ n_points, CornerGeom g, int n, const int32_t *__restrict__ n_live,
+              const uint2 *__restrict__ cells, const int32_t *__restrict__ blockoff, Table t, int normalise,
+              int32_t *__restrict__ corner_rows, float *__restrict__ corner_w) {
+  constexpr int K = 1 << NDIM;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_cap) return;
+  const int np = n_points ? *n_points : n_cap;
+  const int live = n_live ? min(*n_live, n) : n;
+  int rows[K];
+  float w[K];
+#pragma unroll
+  for (int c = 0; c < K; ++c) {
+    rows[c] = -1;
+    w[c] = 0.f;
+  }
+  const int b = i < np ? (batch_ids ? batch_ids[i] : 0) : -1;
+  bool valid = b >= 0 && b < g.batch;
+  int base[NDIM] = {};
+  float f[NDIM] = {};
+  if (valid) {
+    const float *pt = points + static_cast<size_t>(i) * nfeat;
+#pragma unroll
+    for (int j = 0; j < NDIM; ++j) {
+      const float tj = (pt[j] - g.lo[j]) / g.vsize[j];        // (the voxeliser's own expression: voxelize.hip)
+      const float cell = floorf(tj);
+      valid = valid && cell >= 0.f && cell < static_cast<float>(g.dims[NDIM - 1 - j]);      // (false for NaN)
+      const float gj = tj - 0.5f;
+      const float bj = floorf(gj);
+      f[j] = gj - bj;
+      base[j] = valid ? static_cast<int>(bj) : 0;             // in [-1, extent - 1] for a valid point
+    }
+  }
+  if (valid) {
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+      long long key = b;
+      bool in = true;
+      float wc = 1.f;
+#pragma unroll
+      for (int d = 0; d < NDIM; ++d) {                        // grid axis d = point column j = NDIM - 1 - d
+        const int j = NDIM - 1 - d;
+        const int v = base[j] + ((c >> j) & 1);
+        in = in && static_cast<unsigned>(v) < static_cast<unsigned>(g.dims[d]);
+        key = key * g.dims[d] + v;
+      }
+#pragma unroll
+      for (int j = 0; j < NDIM; ++j) {                        // ((wx * wy) * wz)
+        const float wj = ((c >> j) & 1) ? f[j] : 1.0f - f[j];
+        wc = j == 0 ? wj : wc * wj;
+      }
+      int r = -1;
+      if (in) r = RANKED ? rank_of(cells, blockoff, static_cast<unsigned long long>(key)) : table_find(t, key);
+      if (static_cast<unsigned>(r) < static_cast<unsigned>(live)) {
+        rows[c] = r;
+        w[c] = wc;
+      }
+    }
+    if (normalise) {
+      float s = 0.f;
+#pragma unroll
+      for (int c = 0; c < K; ++c)
+        if (rows[c] >= 0) s = s + w[c];
+#pragma unroll
+      for (int c = 0; c < K; ++c) {
+        if (s == 0.f) {
+          rows[c] = -1;
+          w[c] = 0.f;
+        } else if (rows[c] >= 0) {
+          w[c] = w[c] / s;
+        }
+      }
+    }
+  }
+  int4 *ro = reinterpret_cast<int4 *>(corner_rows + static_cast<size_t>(i) * K);
+  float4 *wo = reinterpret_cast<float4 *>(corner_w + static_cast<size_t>(i) * K);
+#pragma unroll
+  for (int q = 0; q < K / 4; ++q) {
+    ro[q] = make_int4(rows[4 * q], rows[4 * q + 1], rows[4 * q + 2], rows[4 * q + 3]);
+    wo[q] = make_float4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  }
+}
+
+// -------------------------------------------------------------------------------------------- forward
+
+// One item per (point, piece): the K corner pieces are loaded together, then added in ascending corner index.
+template <int DT, int V, int K>
+__global__ void __launch_bounds__(kBlock)
+interp_fwd_kernel(const void *__restrict__ vfeat_, int n, const int32_t *__restrict__ corner_rows,
+                  const float *__restrict__ corner_w, long long total, int pieces, void *__restrict__ out_) {
+  using E = Elem<DT>;
+  using S = typename E::S;
+  using A = typename E::A;
+  using P = Piece<S, V>;
+  const P *vfeat = static_cast<const P *>(vfeat_);
+  P *out = static_cast<P *>(out_);
+  for (long long item = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; item < total;
+       item += static_cast<long long>(gridDim.x) * kBlock) {
+    const long long i = total <= 0x7fffffffLL
+                            ? static_cast<long long>(static_cast<unsigned>(item) / static_cast<unsigned>(pieces))
+                            : item / pieces;
+    const int p = static_cast<int>(item - i * pieces);
+    int r[K];
+    float w[K];
+    P v[K];
+#pragma unroll
+    for (int q = 0; q < K / 4; ++q) {           // (the point's corner row and weights: 16-byte loads, lanes of a point alike)
+      const int4 rq = reinterpret_cast<const int4 *>(corner_rows)[i * (K / 4) + q];
+      const float4 wq = reinterpret_cast<const float4 *>(corner_w)[i * (K / 4) + q];
+      r[4 * q] = rq.x, r[4 * q + 1] = rq.y, r[4 * q + 2] = rq.z, r[4 * q + 3] = rq.w;
+      w[4 * q] = wq.x, w[4 * q + 1] = wq.y, w[4 * q + 2] = wq.z, w[4 * q + 3] = wq.w;
+    }
+#pragma unroll
+    for (int c = 0; c < K; ++c)
+      if (static_cast<unsigned>(r[c]) >= static_cast<unsigned>(n)) r[c] = -1;      // (checked, not trusted)
+#pragma unroll
+    for (int c = 0; c < K; ++c)
+      if (r[c] >= 0) v[c] = vfeat[static_cast<long long>(r[c]) * pieces + p];
+    A acc[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc[j] = A(0);
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+      if (r[c] < 0) continue;
+      const A wc = static_cast<A>(w[c]);
+#pragma unroll
+      for (int j = 0; j < V; ++j) acc[j] = acc[j] + (wc * E::up(v[c].e[j]));
+    }
+    P o;
+#pragma unroll
+    for (int j = 0; j < V; ++j) o.e[j] = E::down(acc[j]);
+    out[item] = o;
+  }
+}
+
+// -------------------------------------------------------------------------------------------- backward
+
+// Items = (voxel row, lane of its group): G lanes per row, lane `sub` owns the pieces sub, sub + G, ... and walks the
+// whole list of the row for each of them (collapse_fwd_kernel's walk; a group is never split: that would change the
+// order of the sum).
+template <int DT, int V>
+__global__ void __launch_bounds__(kBlock)
+interp_bwd_kernel(const void *__restrict__ dout_, int n_cap, int kshift, const float *__restrict__ corner_w,
+                  const int32_t *__restrict__ offsets, const int32_t *__restrict__ list, int n, int pieces, int gshift,
+                  const int32_t *__restrict__ n_live, void *__restrict__ dvfeat_) {
+  using E = Elem<DT>;
+  using S = typename E::S;
+  using A = typename E::A;
+  using P = Piece<S, V>;
+  const P *dout = static_cast<const P *>(dout_);
+  P *dvfeat = static_cast<P *>(dvfeat_);
+  const long long total = static_cast<long long>(n) << gshift;
+  const int live = n_live ? min(*n_live, n) : n;
+  const int G = 1 << gshift;
+  const int entries = n_cap << kshift;
+  for (long long item = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; item < total;
+       item += static_cast<long long>(gridDim.x) * kBlock) {
+    const int r = static_cast<int>(item >> gshift);
+    const int sub = static_cast<int>(item) & (G - 1);
+    int beg = 0, end = 0;
+    if (r < live) {
+      beg = offsets[r];
+      end = offsets[r + 1];
+      beg = beg < 0 ? 0 : beg;                  // (checked, not trusted)
+      end = end > entries ? entries : end;
+    }
+    for (int p = sub; p < pieces; p += G) {
+      A acc[V];
+#pragma unroll
+      for (int j = 0; j < V; ++j) acc[j] = A(0);
+      for (int j0 = beg; j0 < end; j0 += kAhead) {
+        int e[kAhead];
+        float w[kAhead];
+        P v[kAhead];
+#pragma unroll
+        for (int u = 0; u < kAhead; ++u) {
+          e[u] = j0 + u < end ? list[j0 + u] : -1;
+          if (static_cast<unsigned>(e[u]) >= static_cast<unsigned>(entries)) e[u] = -1;
+        }
+#pragma unroll
+        for (int u = 0; u < kAhead; ++u)        // (the loads of four entries in flight together)
+          if (e[u] >= 0) {
+            w[u] = corner_w[e[u]];
+            v[u] = dout[static_cast<long long>(e[u] >> kshift) * pieces + p];
+          }
+#pragma unroll
+        for (int u = 0; u < kAhead; ++u) {      // (the additions in list order)
+          if (e[u] < 0) continue;
+          const A wu = static_cast<A>(w[u]);
+#pragma unroll
+          for (int j = 0; j < V; ++j) acc[j] = acc[j] + (wu * E::up(v[u].e[j]));
+        }
+      }
+      P o;
+#pragma unroll
+      for (int j = 0; j < V; ++j) o.e[j] = E::down(acc[j]);
+      dvfeat[static_cast<long long>(r) * pieces + p] = o;
+    }
+  }
+}
+
+// -------------------------------------------------------------------------------------------- host side
+
+// scratch of a hash-form corners call: the table (room for the wide form, 12 bytes per slot)
+struct CornerWs {
+  hkey_t *keys;
+  int32_t *vals;
+  uint32_t cap;
+  size_t bytes;
+  CornerWs(void *ws, int n) {
+    Carver c(ws);
+    cap = table_capacity(static_cast<size_t>(n > 0 ? n : 0));
+    keys = c.take<hkey_t>(cap);
+    vals = c.take<int32_t>(cap);
+    bytes = c.off;
+  }
+};
+
+// 0 = ok: the checks of a corners call that need no pointer
+int check_corners(int n_cap, int nfeat, int ndim, int n, int batch, int flags) {
+  SPX_CHECK(ndim == 2 || ndim == 3, "ndim must be 2 or 3, got %d", ndim);
+  SPX_CHECK(n_cap >= 0 && n >= 0, "bad point / row counts %d / %d", n_cap, n);
+  SPX_CHECK((static_cast<long long>(n_cap) << ndim) < 0x80000000LL, "n_cap * 2^ndim must stay below 2^31, got %d points", n_cap);
+  SPX_CHECK(n <= kMaxRows, "at most 2^30 voxel rows (the table holds two slots per row), got %d", n);
+  SPX_CHECK(nfeat >= ndim, "points need at least %d columns, got %d", ndim, nfeat);
+  SPX_CHECK(batch >= 1, "batch must be >= 1, got %d", batch);
+  SPX_CHECK(flags == 0 || flags == 1, "flags must be 0 or 1 (normalise), got %d", flags);
+  return 0;
+}
+
+int elem_bytes_of(int dtype) { return dtype == SPX_F64 ? 8 : dtype == SPX_F32 ? 4 : 2; }
+
+// 0 = ok: the checks of the two interpolation calls that need no pointer
+int check_interp(int n_cap, int ndim, int n, int C, int dtype) {
+  SPX_CHECK(ndim == 2 || ndim == 3, "ndim must be 2 or 3, got %d", ndim);
+  SPX_CHECK(dtype == SPX_F32 || dtype == SPX_F16 || dtype == SPX_BF16 || dtype == SPX_F64,
+            "dtype must be f32, f16, bf16 or f64, got %d", dtype);
+  SPX_CHECK(C >= 1, "channel count must be >= 1, got %d", C);
+  SPX_CHECK(n_cap >= 0 && n >= 0, "bad point / row counts %d / %d", n_cap, n);
+  SPX_CHECK((static_cast<long long>(n_cap) << ndim) < 0x80000000LL, "n_cap * 2^ndim must stay below 2^31, got %d points", n_cap);
+  SPX_CHECK(static_cast<long long>(C) * elem_bytes_of(dtype) <= 0x7fffffffLL, "row too long");
+  return 0;
+}
+
+template <int DT>
+void launch_fwd(const void *vfeat, int n, const int32_t *rows, const float *w, int n_cap, int ndim, int C, bool vec,
+                void *out, hipStream_t s) {
+  constexpr int V = 16 / static_cast<int>(sizeof(typename Elem<DT>::S));
+  const int pieces = vec ? C / V : C;
+  const long long total = static_cast<long long>(n_cap) * pieces;
+  const dim3 grid(stream_blocks(total, kBlock)), block(kBlock);
+  if (vec && ndim == 3)
+    hipLaunchKernelGGL((interp_fwd_kernel<DT, V, 8>), grid, block, 0, s, vfeat, n, rows, w, total, pieces, out);
+  else if (vec)
+    hipLaunchKernelGGL((interp_fwd_kernel<DT, V, 4>), grid, block, 0, s, vfeat, n, rows, w, total, pieces, out);
+  else if (ndim == 3)
+    hipLaunchKernelGGL((interp_fwd_kernel<DT, 1, 8>), grid, block, 0, s, vfeat, n, rows, w, total, pieces, out);
+  else
+    hipLaunchKernelGGL((interp_fwd_kernel<DT, 1, 4>), grid, block, 0, s, vfeat, n, rows, w, total, pieces, out);
+}
+
+template <int DT>
+void launch_bwd(const void *dout, int n_cap, int ndim, const float *w, const int32_t *offsets, const int32_t *list, int n,
+                int C, bool vec, const int32_t *n_live, void *dvfeat, hipStream_t s) {
+  constexpr int V = 16 / static_cast<int>(sizeof(typename Elem<DT>::S));
+  const int pieces = vec ? C / V : C;
+  int gshift = 0;
+  while (gshift < 6 && (1 << gshift) < pieces) ++gshift;
+  const dim3 grid(stream_blocks(static_cast<long long>(n) << gshift, kBlock)), block(kBlock);
+  if (vec)
+    hipLaunchKernelGGL((interp_bwd_kernel<DT, V>), grid, block, 0, s, dout, n_cap, ndim, w, offsets, list, n, pieces,
+                       gshift, n_live, dvfeat);
+  else
+    hipLaunchKernelGGL((interp_bwd_kernel<DT, 1>), grid, block, 0, s, dout, n_cap, ndim, w, offsets, list, n, pieces,
+                       gshift, n_live, dvfeat);
+}
+
+}  // namespace
+}  // namespace spx
+
+extern "C" {
+
+size_t spx_point_corners_ws_bytes(int n_cap, int ndim, int n) {
+  if ((ndim != 2 && ndim != 3) || n_cap < 0 || n < 0) return 0;
+  if ((static_cast<long long>(n_cap) << ndim) >= 0x80000000LL || n > spx::kMaxRows) return 0;
+  return spx::CornerWs(nullptr, n).bytes;
+}
+
+int spx_point_corners(const float *points, int nfeat, const int32_t *batch_ids, int n_cap, const int32_t *n_points_dev,
+                      int ndim, const float *vsize, const float *coors_range, const int32_t *indices, int n,
+                      const int32_t *n_live, int batch, const int *spatial_h, const void *rankmap, size_t rankmap_bytes,
+                      int flags, int32_t *corner_rows, float *corner_w, void *ws, size_t ws_bytes, spx_stream_t stream) {
+  using namespace spx;
+  if (int rc = check_corners(n_cap, nfeat, ndim, n, batch, flags)) return rc;
+  SPX_CHECK(vsize && coors_range && spatial_h, "vsize / coors_range / spatial shape is NULL");
+  unsigned long long cells_total = static_cast<unsigned long long>(batch);
+  for (int d = 0; d < ndim; ++d) {
+    SPX_CHECK(spatial_h[d] >= 1, "empty grid axis %d", d);
+    SPX_CHECK(vsize[d] > 0.f, "voxel size of axis %d must be positive", d);
+    SPX_CHECK(cells_total <= (0x7fffffffffffffffULL / static_cast<unsigned long long>(spatial_h[d])),
+              "the key space of batch x grid does not fit 63 bits");
+    cells_total *= static_cast<unsigned long long>(spatial_h[d]);
+  }
+  const size_t W = rankmap ? rank_words(ndim, batch, spatial_h) : 0;      // (the pointer's value, not its target)
+  SPX_CHECK(!rankmap || (W > 0 && rankmap_bytes >= rank_bytes(W)), "rank map too small for this level (%zu words)", W);
+  if (n_cap == 0) return 0;
+  SPX_CHECK(points && corner_rows && corner_w && (n == 0 || indices), "points / indices / corner_rows / corner_w is NULL");
+  SPX_CHECK(aligned_to(corner_rows, 16) && aligned_to(corner_w, 16), "corner_rows / corner_w not aligned to 16 bytes");
+  CornerGeom g;
+  g.ndim = ndim;
+  g.batch = batch;
+  for (int d = 0; d < kDims; ++d) {              // the host arrays are zyx: point column j is axis ndim - 1 - j
+    g.dims[d] = d < ndim ? spatial_h[d] : 1;
+    g.vsize[d] = d < ndim ? vsize[ndim - 1 - d] : 1.f;
+    g.lo[d] = d < ndim ? coors_range[ndim - 1 - d] : 0.f;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(div_up(n_cap, kBlock)), block(kBlock);
+  const int norm = flags & 1;
+  Table t = {};
+  if (rankmap) {
+    void *rm = const_cast<void *>(rankmap);
+    const uint2 *cells = static_cast<const uint2 *>(rm);
+    const int32_t *blockoff = rank_blockoff(rm, W);
+    if (ndim == 3)
+      hipLaunchKernelGGL((corner_kernel<3, true>), grid, block, 0, s, points, nfeat, batch_ids, n_cap, n_points_dev, g, n,
+                         n_live, cells, blockoff, t, norm, corner_rows, corner_w);
+    else
+      hipLaunchKernelGGL((corner_kernel<2, true>), grid, block, 0, s, points, nfeat, batch_ids, n_cap, n_points_dev, g, n,
+                         n_live, cells, blockoff, t, norm, corner_rows, corner_w);
+    SPX_LAUNCH_CHECK();
+    count_interp(kInterpCornersRanked);
+    return 0;
+  }
+  CornerWs w(ws, n);
+  SPX_CHECK(ws && ws_bytes >= w.bytes, "workspace too small: %zu < %zu", ws_bytes, w.bytes);
+  int dims4[4] = {1, 1, 1, 1};
+  for (int d = 0; d < ndim; ++d) dims4[d] = spatial_h[d];
+  table_place(t, w.keys, w.vals, w.cap, keys_fit_u32(batch, dims4, 4));
+  {
+    FillList fills;
+    table_fill(fills, t);
+    SPX_HIP(fills.launch(s));
+  }
+  if (n > 0) {
+    hipLaunchKernelGGL(corner_insert_kernel, dim3(div_up(n, kBlock)), block, 0, s, indices, n, n_live, g, t);
+    SPX_LAUNCH_CHECK();
+  }
+  if (ndim == 3)
+    hipLaunchKernelGGL((corner_kernel<3, false>), grid, block, 0, s, points, nfeat, batch_ids, n_cap, n_points_dev, g, n,
+                       n_live, nullptr, nullptr, t, norm, corner_rows, corner_w);
+  else
+    hipLaunchKernelGGL((corner_kernel<2, false>), grid, block, 0, s, points, nfeat, batch_ids, n_cap, n_points_dev, g, n,
+                       n_live, nullptr, nullptr, t, norm, corner_rows, corner_w);
+  SPX_LAUNCH_CHECK();
+  count_interp(kInterpCornersHash);
+  return 0;
+}
+
+int spx_interp_fwd(const void *vfeat, int n, const int32_t *corner_rows, const float *corner_w, int n_cap, int ndim, int C,
+                   int dtype, void *out, spx_stream_t stream) {
+  using namespace spx;
+  if (int rc = check_interp(n_cap, ndim, n, C, dtype)) return rc;
+  if (n_cap == 0) return 0;
+  SPX_CHECK(corner_rows && corner_w && out && (n == 0 || vfeat), "vfeat / corner_rows / corner_w / out is NULL");
+  const int eb = elem_bytes_of(dtype);
+  SPX_CHECK(aligned_to(vfeat, eb) && aligned_to(out, eb), "pointer not aligned to its elements");
+  SPX_CHECK(aligned_to(corner_rows, 16) && aligned_to(corner_w, 16), "corner_rows / corner_w not aligned to 16 bytes");
+  const bool vec = (static_cast<long long>(C) * eb) % 16 == 0 && aligned_to(vfeat, 16) && aligned_to(out, 16);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case SPX_F32: launch_fwd<SPX_F32>(vfeat, n, corner_rows, corner_w, n_cap, ndim, C, vec, out, s); break;
+    case SPX_F16: launch_fwd<SPX_F16>(vfeat, n, corner_rows, corner_w, n_cap, ndim, C, vec, out, s); break;
+    case SPX_BF16: launch_fwd<SPX_BF16>(vfeat, n, corner_rows, corner_w, n_cap, ndim, C, vec, out, s); break;
+    default: launch_fwd<SPX_F64>(vfeat, n, corner_rows, corner_w, n_cap, ndim, C, vec, out, s); break;
+  }
+  SPX_LAUNCH_CHECK();
+  count_interp(kInterpFwd);
+  return 0;
+}
+
+int spx_interp_bwd(const void *dout, int n_cap, int ndim, const float *corner_w, const int32_t *offsets,
+                   const int32_t *list, int n, const int32_t *n_live, int C, int dtype, void *dvfeat,
+                   spx_stream_t stream) {
+  using namespace spx;
+  if (int rc = check_interp(n_cap, ndim, n, C, dtype)) return rc;
+  if (n == 0) return 0;
+  SPX_CHECK(offsets && dvfeat && (n_cap == 0 || (dout && corner_w && list)),
+            "dout / corner_w / offsets / list / dvfeat is NULL");
+  const int eb = elem_bytes_of(dtype);
+  SPX_CHECK(aligned_to(dout, eb) && aligned_to(dvfeat, eb), "pointer not aligned to its elements");
+  const bool vec = (static_cast<long long>(C) * eb) % 16 == 0 && aligned_to(dout, 16) && aligned_to(dvfeat, 16);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case SPX_F32: launch_bwd<SPX_F32>(dout, n_cap, ndim, corner_w, offsets, list, n, C, vec, n_live, dvfeat, s); break;
+    case SPX_F16: launch_bwd<SPX_F16>(dout, n_cap, ndim, corner_w, offsets, list, n, C, vec, n_live, dvfeat, s); break;
+    case SPX_BF16: launch_bwd<SPX_BF16>(dout, n_cap, ndim, corner_w, offsets, list, n, C, vec, n_live, dvfeat, s); break;
+    default: launch_bwd<SPX_F64>(dout, n_cap, ndim, corner_w, offsets, list, n, C, vec, n_live, dvfeat, s); break;
+  }
+  SPX_LAUNCH_CHECK();
+  count_interp(kInterpBwd);
+  return 0;
+}
+
+}  // extern "C"

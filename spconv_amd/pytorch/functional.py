@@ -588,3 +588,8 @@ def _sparse_add_sorted_composite(*tens):
 # over them and the way back, for learned voxel feature encoders (vfe.DynamicVFE)
 from spconv_amd.pytorch._pointvoxel import (PointGroups, decorate_points, point_groups,  # noqa: E402,F401
                                             points_to_voxels, voxels_to_points)
+
+# trilinear devoxelisation (csrc/interp.hip; not part of the reference): the corner table of a point cloud over a sparse
+# level and the interpolation of its rows to the points
+from spconv_amd.pytorch._interp import (PointCorners, point_corners, point_corners_into,  # noqa: E402,F401
+                                        voxels_to_points_trilinear)

@@ -1,5 +1,6 @@
 """``spconv.pytorch.spatial`` (reference ``spconv/pytorch/spatial.py:28-45``), and ``SparseCollapse``: the hand-over
-from a 3-D backbone to a sparse 2-D head on the kernels of csrc/collapse.hip."""
+from a 3-D backbone to a sparse 2-D head on the kernels of csrc/collapse.hip; ``SparsePrune`` (csrc/select.hip);
+``TrilinearDevoxelize``: a sparse level read out at points (csrc/interp.hip)."""
 from typing import Optional, Sequence
 
 import torch
@@ -96,3 +97,34 @@ class SparsePrune(SparseModule):
     def extra_repr(self) -> str:
         return (f"ratio={self.ratio}, k={self.k}, score={self.score!r}, return_dropped={self.return_dropped}, "
                 f"static_num_out={self.static_num_out}")
+
+
+class TrilinearDevoxelize(torch.nn.Module):
+    """Per-point features out of a sparse level by trilinear interpolation (``functional.point_corners`` +
+    ``functional.voxels_to_points_trilinear``, the kernels of csrc/interp.hip): every point blends the rows of the
+    2^ndim voxels whose centres surround it -- the devoxelize of SPVCNN / PVCNN.  Not part of the reference.
+
+    ``vsize_xyz`` / ``coors_range_xyz`` as the voxelisers take them; the voxel size is that of the level being read (a
+    level behind strided layers: the voxeliser's size times the stride).  ``normalize=True`` divides a point's weights
+    by the sum of those whose voxel exists.  ``forward(x, points, batch_ids, n_points=None) -> [N, C]``: points fp32
+    [N, >= ndim], batch_ids int32 [N] or None, n_points a device int32 or None.  A point outside the range or without
+    any voxel around it gets zeros.  Key-ordered levels (an index tensor that carries its rank map) are looked up
+    without a hash table.  The gradient goes to x's features only, added in a fixed order without atomics; there is
+    no gradient with respect to the points."""
+
+    def __init__(self, vsize_xyz: Sequence[float], coors_range_xyz: Sequence[float], normalize: bool = True):
+        super().__init__()
+        from spconv_amd.pytorch import _interp
+        _interp._geometry(vsize_xyz, coors_range_xyz)
+        self.vsize_xyz = [float(v) for v in vsize_xyz]
+        self.coors_range_xyz = [float(v) for v in coors_range_xyz]
+        self.normalize = bool(normalize)
+
+    def forward(self, x: SparseConvTensor, points: torch.Tensor, batch_ids: Optional[torch.Tensor] = None,
+                n_points: Optional[torch.Tensor] = None) -> torch.Tensor:
+        from spconv_amd.pytorch import functional as F
+        corners = F.point_corners(points, batch_ids, x, self.vsize_xyz, self.coors_range_xyz, self.normalize, n_points)
+        return F.voxels_to_points_trilinear(x.features, corners)
+
+    def extra_repr(self) -> str:
+        return f"vsize_xyz={self.vsize_xyz}, coors_range_xyz={self.coors_range_xyz}, normalize={self.normalize}"

@@ -163,6 +163,7 @@ class StaticPointToVoxel(object):
         self.vsize, self.grid_size, self.grid_stride, self.coors_range = vsize, grid_size, grid_stride, coors_range
         self.vsize_xyz, self.coors_range_xyz = [float(v) for v in vsize_xyz], [float(v) for v in coors_range_xyz]
         self._groups = None
+        self._corners = {}          # point_corners(): outputs and scratch by (level, options)
         L = _lib.load()
         grid_c = _lib.ints(grid_size)
         rank_bytes = 0
@@ -261,6 +262,56 @@ class StaticPointToVoxel(object):
             g, ws = self._groups
             _pointvoxel.point_groups_into(self.pc_voxel_id, self.max_num_voxels, self.n_points, g.rows, g.offsets, g.list, ws)
         return g
+
+    def point_corners(self, x=None, vsize_xyz=None, normalize: bool = True, with_groups: bool = False):
+        """The trilinear corner table of the last ``run()``'s points as ``functional.PointCorners``
+        (``spx_point_corners`` over the object's own ``points``, ``batch_ids`` and ``n_points``): what
+        ``functional.voxels_to_points_trilinear`` takes.  By default the corners are taken against the voxeliser's own
+        level, through the rank map it leaves behind (``key_order=True``) or a hash table built from ``indices``; `x` (a
+        SparseConvTensor over the same range, e.g. a strided level) with `vsize_xyz` = that level's voxel size reads
+        another one.  ``with_groups=True`` adds the transposed list a gradient in the voxel rows walks.  Outputs and
+        scratch are allocated once per (index tensor, level shape, normalize, with_groups), at first use -- a second call
+        with the same four overwrites the first one's result -- so the call can be recorded in a stream
+        capture behind ``run()``.  No gradient with respect to the points."""
+        from spconv_amd.pytorch import _interp, _pointvoxel
+        if x is None:
+            indices, shape, B, n_live = self.indices, list(self.grid_size), self.batch_size, self.n_voxels[0:1]
+            vsize_xyz = self.vsize_xyz if vsize_xyz is None else vsize_xyz
+        else:
+            if vsize_xyz is None:
+                raise ValueError("point_corners: a level other than the voxeliser's own needs its voxel size (vsize_xyz)")
+            indices, shape, B = x.indices, [int(v) for v in x.spatial_shape], int(x.batch_size)
+            n_live = getattr(x, "n_live_dev", None)
+        ndim, vsize, coors_range = _interp._geometry(vsize_xyz, self.coors_range_xyz)
+        if ndim != self.ndim or len(shape) != ndim or B != self.batch_size:
+            raise ValueError("point_corners: the level does not match the voxeliser's dimensions or batch size")
+        n, K, N = int(indices.shape[0]), 1 << ndim, self.max_num_points
+        with torch.cuda.device(self.device):
+            rankmap = _interp.level_rankmap(indices, B, shape)
+            key = (indices.data_ptr(), tuple(shape), n, rankmap is None, bool(normalize), bool(with_groups))
+            cache = self._corners
+            if key not in cache:
+                i32 = dict(dtype=torch.int32, device=self.device)
+                u8 = lambda nbytes: torch.empty([max(int(nbytes), 16)], dtype=torch.uint8, device=self.device)
+                rows = torch.full([N, K], -1, **i32)
+                weights = torch.zeros([N, K], dtype=torch.float32, device=self.device)
+                ws = u8(_interp.corners_ws_bytes(N, ndim, n)) if rankmap is None else None
+                groups = None
+                if with_groups and n > 0:
+                    groups = (_pointvoxel.PointGroups(torch.full([N * K], -1, **i32), torch.zeros([n + 1], **i32),
+                                                      torch.zeros([N * K], **i32), n, None, n_live),
+                              u8(self._L.spx_point_groups_ws_bytes(N * K, n)))
+                cache[key] = (rows, weights, ws, groups)
+            rows, weights, ws, groups = cache[key]
+            f = lambda v: (ctypes.c_float * len(v))(*v)
+            _interp.point_corners_into(self.points, self.batch_ids, self.n_points, f(vsize), f(coors_range),
+                                       indices, n_live, B, shape, rankmap, normalize, rows, weights, ws)
+            g = None
+            if groups is not None:
+                g, gws = groups
+                g = g._replace(n_live=n_live)
+                _pointvoxel.point_groups_into(rows.view(-1), n, None, g.rows, g.offsets, g.list, gws)
+        return _interp.PointCorners(rows, weights, g, n, self.n_points, n_live)
 
     def overflowed(self) -> bool:
         """True when the last run found more voxels than ``max_num_voxels`` (one synchronisation)."""
