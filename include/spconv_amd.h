@@ -96,6 +96,8 @@ int spx_set_option(const char *name_h, int value);
  *   wgrad_tr/<dt>/<SL>, wgrad_f32                  weight gradient, first stage (SL: 2 | 4 | 8 live slots per row)
  *   wgrad_mfma/<dt>, wgrad_generic/<dt>            weight gradient, fallback kernels
  *   generic/<dt>, gen1/<COUT>/<dt>                 one-thread-per-output and first-generation gather-GEMM
+ *   sparse_hint/v4, sparse_hint/bwd                igemm_v4 (forward, dgrad) / igemm_bwd launches whose appendix part was
+ *                                                  shaped by SPX_SPARSE_ROWS_HINT (counted next to their family)
  *   dense/map, dense/scatter_cl, dense/scatter_cf, dense/gather_cl, dense/gather_cf, dense/compact
  *                                                  sparse <-> dense conversion (cl / cf: channels last / first)
  *   union/mark, union/prefix, union/claim, union/fill, union/add_fwd, union/add_bwd
@@ -461,6 +463,20 @@ size_t spx_subm_layout_mcap(int n);
  * are bit-identical with and without the hint; a wrong hint only costs time.  Stands in for the reference's tuner choice
  * between implicit-GEMM tile shapes (spconv/csrc/sparse/convops.py:1150-1297). */
 #define SPX_DENSE_HINT 0x100
+/* OR-ed into `tile_order` of spx_igemm_fwd / _fwd_stats / _dgrad / _bwd / _bwd_deferred next to SPX_ROWS_LAYOUT: the
+ * HOST has READ the header of THIS blob, its class word is 1, and bits 12..30 carry its word [1], the EXACT M:
+ *   tile_order = SPX_ROWS_LAYOUT | SPX_SPARSE_ROWS_HINT | (M << SPX_SPARSE_ROWS_SHIFT),  0 <= M <= SPX_SPARSE_ROWS_MAX.
+ * f16 / bf16 launches of up to 256 output columns then hold exactly the appendix workgroups that receive rows under
+ * the dealing rule above (instead of the n / 4 rows' worth the class rule allows), and those workgroups take M from
+ * their arguments instead of loading the header -- the same rows in the same tiles, results bit for bit the same; the
+ * workgroup count spx_igemm_fwd_stats reports shrinks with the grid.  The contract: only for a blob whose header the
+ * caller has read (never a prediction or an estimate: rows past a too-small M would not be computed), M exact, class
+ * 1.  An M that does not fit the bits, or that exceeds n / 4, means no hint; without the hint, and for every other
+ * dtype and for wider layers, the launch is what it is without the bits.  spx_launch_count("sparse_hint/v4") and
+ * ("sparse_hint/bwd") count the launches that were shaped by it. */
+#define SPX_SPARSE_ROWS_HINT 0x200
+#define SPX_SPARSE_ROWS_SHIFT 12
+#define SPX_SPARSE_ROWS_MAX 0x7ffff
 #define SPX_ROWS_LAYOUT_ACT 0x400
 /* OR-ed into `act` of spx_igemm_fwd_int8 next to SPX_ROWS_LAYOUT_ACT: the HOST knows the class word is 1 (it may
  * read it once per rulebook, outside any timed or captured region) -- a launch-shape hint only: 64-row instead

@@ -32,6 +32,7 @@ std::mutex g_option_mutex;
 
 std::atomic<long long> g_launches[kFamCount];
 std::atomic<long long> g_inst_launches[inst::kCount];
+std::atomic<long long> g_hint_launches[kHintCount];
 std::atomic<long long> g_f64_launches[kF64Count];
 std::atomic<long long> g_dense_launches[kDenseCount];
 std::atomic<long long> g_union_launches[kUnionCount];
@@ -254,6 +255,8 @@ long long spx_launch_count(const char *family_h) {
   if (!family_h) return -1;
   for (int i = 0; i < spx::kFamCount; ++i)
     if (strcmp(names[i], family_h) == 0) return spx::g_launches[i].load(std::memory_order_relaxed);
+  if (strcmp(family_h, "sparse_hint/v4") == 0) return spx::g_hint_launches[spx::kHintV4].load(std::memory_order_relaxed);
+  if (strcmp(family_h, "sparse_hint/bwd") == 0) return spx::g_hint_launches[spx::kHintBwd].load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::f64_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::dense_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::union_counter(family_h)) return c->load(std::memory_order_relaxed);

@@ -119,6 +119,12 @@ enum LaunchFamily { kFamV4 = 0, kFamWs, kFamBwdFused, kFamBwdRows, kFamI8Stream,
 extern std::atomic<long long> g_launches[kFamCount];
 inline void count_launch(LaunchFamily f) { g_launches[f].fetch_add(1, std::memory_order_relaxed); }
 
+// Launches shaped by the host's exact appendix row count (SPX_SPARSE_ROWS_HINT), counted NEXT TO their family: keys
+// sparse_hint/v4 (forward and dgrad launches of igemm_v4_kernel) and sparse_hint/bwd (fused backward).
+enum HintInst { kHintV4 = 0, kHintBwd, kHintCount };
+extern std::atomic<long long> g_hint_launches[kHintCount];
+inline void count_hint(HintInst i) { g_hint_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
 // Per-INSTANCE counters (the keys with a '/' of spx_launch_count): one flat table, each template instance a slot whose
 // index is a constant expression of its template parameters, so a launch site adds one relaxed increment and formats
 // nothing.  dt codes are the kernels' DT parameter: 0 f16, 1 bf16, 2 i8, 3 f32.  common.cpp parses the keys.

@@ -217,8 +217,10 @@ static int igemm_fwd_impl(const void *feat, const void *weight, void *out, const
   SPX_CHECK((feat || n_in == 0) && weight && out, "null tensor pointer");
   SPX_CHECK(pair || kv == 1, "pair table required");
   GemmParams p = fwd_params(feat, weight, out, pair, mask, argsort, bias, n_in, n_out, C, K, kv, identity_k);
-  p.dense_hint = (tile_order & SPX_DENSE_HINT) ? 1 : 0;
-  apply_rows_layout(p, tile_order & ~SPX_DENSE_HINT);
+  int dense_hint = 0, app_m = -1;
+  apply_rows_layout(p, split_tile_order(tile_order, &dense_hint, &app_m));
+  p.dense_hint = dense_hint;
+  if (p.cls) p.app_m = app_m;
   p.act = act & 0xff;
   if (act & SPX_OUT_CACHED) p.dbg = 0x400;       // plain result stores: the next launch reads the rows
   p.act_alpha = act_alpha;
@@ -305,8 +307,10 @@ int spx_igemm_dgrad(const void *dout, const void *weight, void *din, const int32
   SPX_CHECK((dout || n_out == 0) && weight && din, "null tensor pointer");
   SPX_CHECK(pair || kv == 1, "pair table required");
   GemmParams p = dgrad_params(dout, weight, din, pair, mask, argsort, n_out, n_in, C, K, kv, subm);
-  p.dense_hint = (tile_order & SPX_DENSE_HINT) ? 1 : 0;
-  apply_rows_layout(p, tile_order & ~SPX_DENSE_HINT);
+  int dense_hint = 0, app_m = -1;
+  apply_rows_layout(p, split_tile_order(tile_order, &dense_hint, &app_m));
+  p.dense_hint = dense_hint;
+  if (p.cls) p.app_m = app_m;
   if (dtype == SPX_F64) return run_gather_gemm_f64(p, true, static_cast<hipStream_t>(stream));
   if (ws && ws_bytes >= spx_igemm_acc_bytes(n_in, C, kv) && kv > 32) p.acc = static_cast<float *>(ws);
   return run_gather_gemm(p, dtype, static_cast<hipStream_t>(stream));
@@ -341,8 +345,10 @@ static int igemm_bwd_impl(const void *feat, const void *dout, const void *weight
   }
   SPX_CHECK(ws_bytes >= spx_igemm_wgrad_ws_bytes(n_in, C, K, kv), "workspace too small");
   GemmParams p = dgrad_params(dout, weight, din, pair, mask, argsort, n_out, n_in, C, K, kv, subm);
-  p.dense_hint = (tile_order & SPX_DENSE_HINT) ? 1 : 0;
-  apply_rows_layout(p, tile_order & ~SPX_DENSE_HINT);
+  int dense_hint = 0, app_m = -1;
+  apply_rows_layout(p, split_tile_order(tile_order, &dense_hint, &app_m));
+  p.dense_hint = dense_hint;
+  if (p.cls) p.app_m = app_m;
   // dgrad + wgrad in one launch (settled A/B) where both halves have an MFMA kernel
   const int es = dtype == SPX_F32 ? 4 : 2, lanes = 16 / es;
   const bool fusable = (dtype == SPX_F16 || dtype == SPX_BF16 || dtype == SPX_F32) && C % lanes == 0 &&

@@ -375,10 +375,22 @@ constexpr size_t bwd_smem_bytes() {
 
 template <int COUT, int MB, int DT>
 int launch_bwd(const GemmParams &p, const Wgrad2Params &q, int n_wgrad_blocks, hipStream_t s) {
-  const int napp = p.cls ? layout_app_tiles(p.n_dst, 64 * MB) : 0;
+  int napp = p.cls ? layout_app_tiles(p.n_dst, 64 * MB) : 0;
+  // the host has READ M (app_m, SPX_SPARSE_ROWS_HINT; 16-bit types): only the appendix workgroups that have rows under
+  // the body's dealing rule (kAppBudget groups; more when M exceeds kAppBudget tiles) -- at 100 k sparse rows the wgrad
+  // ranges, the appendix and the dgrad tiles then fit the chip's 1024 workgroup slots: one dispatch round
+  AppShape exact{-1, 0};
+  if constexpr (DT == 0 || DT == 1) {
+    if (p.cls) exact = app_shape_exact(p.n_dst, 64 * MB, p.app_m, kAppBudget);
+  }
+  if (exact.napp >= 0) napp = exact.napp;
   const int n_dgrad = div_up(p.n_dst, 64 * MB) + napp;
   GemmRest rr = rest_of(p);
   rr.napp = p.cls ? napp : -1;
+  if (exact.napp >= 0) {
+    rr.acc_mode = pack_app_shape(p.acc_mode, p.app_m, exact);
+    count_hint(kHintBwd);
+  }
   constexpr int wgrad_first = 1;           // (the longer chains are dispatched first: settled A/B)
   GemmParams pl = p;
   pl.lpt = p.tile_order && n_dgrad + n_wgrad_blocks > 1024;           // (see launch_v4)

@@ -65,6 +65,10 @@ struct GemmParams {
   int app_rows;           // > 0: the HOST knows an upper bound of M (SPX_SPARSE_HINT): only that many appendix rows get
                           // workgroups instead of the n / 4 the class rule allows
   int app_budget;         // (device side) > 0: the appendix' rows are dealt to at most this many workgroups
+  int app_m;              // >= 0: the HOST has read {class 1, M} of this blob and passes the EXACT M (SPX_SPARSE_ROWS_HINT,
+                          // 16-bit launches): only the appendix workgroups that have rows are launched, and they take M
+                          // and their height from the arguments (device side: app_m, app_h) instead of loading the header
+  int app_h;              // (device side) rows per appendix workgroup of a launch shaped by app_m
   int dense_hint;         // the caller knows the neighbourhoods are dense (SPX_DENSE_HINT in tile_order): forward and
                           // dgrad take the weight-stationary kernel (igemm_ws.hip) where its shape limits allow
   // BatchNorm statistics of the rows the launch stores (spx_igemm_fwd_stats): workgroup b leaves {rows, mean, M2} of
@@ -94,6 +98,8 @@ inline void apply_rows_layout(GemmParams &p, int tile_order) {
   p.mask_rows = nullptr;
   p.app_rows = 0;
   p.app_budget = 0;
+  p.app_m = -1;
+  p.app_h = 0;
   if (tile_order == SPX_ROWS_LAYOUT && p.argsort && p.pair && p.mask) {
     const int32_t *blob = p.argsort;
     const size_t npad = (static_cast<size_t>(p.n_dst) + 63) & ~static_cast<size_t>(63);
@@ -107,6 +113,30 @@ inline void apply_rows_layout(GemmParams &p, int tile_order) {
     if (tile_order == SPX_ROWS_LAYOUT) p.argsort = nullptr;       // (a blob without tables: row order)
   }
 }
+
+// The hint bits of a `tile_order` argument: SPX_DENSE_HINT and SPX_SPARSE_ROWS_HINT with its exact M.  Returns the
+// table form (0, 1, SPX_ROWS_LAYOUT) for apply_rows_layout; *app_m = the M the caller has read, or -1.
+inline int split_tile_order(int tile_order, int *dense_hint, int *app_m) {
+  *dense_hint = (tile_order & SPX_DENSE_HINT) ? 1 : 0;
+  *app_m = (tile_order & SPX_SPARSE_ROWS_HINT) ? (tile_order >> SPX_SPARSE_ROWS_SHIFT) & SPX_SPARSE_ROWS_MAX : -1;
+  return tile_order & 0xff;
+}
+
+// The appendix part of a grid shaped from the exact M (GemmParams::app_m): the rows are dealt exactly as the body deals
+// them from the header -- to `groups` workgroups (the n / 4 rule, capped by `budget` in the fused backward) in whole 16-row
+// blocks, h rows each, at most a tile -- and only the workgroups that receive rows are launched.  M beyond the class
+// rule's bound (4 M < n: the blob's appendix holds no more), or a scene too small for the rule: no hint (napp = -1).
+struct AppShape { int napp, h; };
+inline AppShape app_shape_exact(int n, int tm, int m, int budget) {
+  const int full = layout_app_tiles(n, tm);
+  const int groups = budget > 0 && budget < full ? budget : full;
+  if (m < 0 || m > n / 4 || groups <= 0) return AppShape{-1, 0};
+  const int per = (((m + groups - 1) / groups) + 15) & ~15;
+  const int h = per < tm ? per : tm;
+  return AppShape{h > 0 ? (m + h - 1) / h : 0, h};
+}
+
+inline int pack_app_shape(int acc_mode, int m, const AppShape &a) { return (acc_mode & 3) | ((a.h / 16) << 4) | ((m + 1) << 8); }
 
 // back to the row-order tables (paths that do not read tables by tile position)
 inline void drop_rows_layout(GemmParams &p) {
@@ -137,7 +167,11 @@ struct GemmRest {
   int out_dtype;
   int dbg;
   float *acc;
-  int acc_mode;
+  int acc_mode;           // bits 0-1: GemmParams::acc_mode.  A launch shaped by the exact M the host has read
+                          // (GemmParams::app_m) carries it HERE, next to napp -- the dword pair every workgroup fetches
+                          // before anything else; fields of their own behind napp made that fetch a second, dependent
+                          // kernarg trip at the head of every tile: bits 4-7 = rows per appendix workgroup / 16,
+                          // bits 8-27 = M + 1 (0: no hint; M <= SPX_SPARSE_ROWS_MAX = 2^19 - 1)
   int napp;               // rows layout: appendix workgroups at the head of the grid, or -1 = the n / 4 rule
   float *stats;           // per-workgroup BatchNorm statistics (GemmParams::stats), or null
   const int32_t *n_live;
@@ -345,6 +379,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, ui
 }
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // ---- 16-bit <-> float helpers -------------------------------------------

@@ -90,7 +90,7 @@ __device__ __forceinline__ void unpack_gemm_args(GemmParams &p, const void *argA
   p.kbase = (b_reverse >> 4) & 127;
   p.lpt = (b_reverse >> 11) & 1;
   p.acc = rest.acc;
-  p.acc_mode = rest.acc_mode;
+  p.acc_mode = rest.acc_mode & 3;
   p.out = rest.out;
   p.bias = rest.bias;
   p.strideK = rest.strideK;
@@ -109,6 +109,8 @@ __device__ __forceinline__ void unpack_gemm_args(GemmParams &p, const void *argA
   p.n_live = rest.n_live;
   p.app_rows = rest.napp;      // (the body reads it as a workgroup count)
   p.app_budget = 0;
+  p.app_m = ((rest.acc_mode >> 8) & 0xfffff) - 1;      // (pack_app_shape: the exact M of a hinted launch, or -1)
+  p.app_h = ((rest.acc_mode >> 4) & 15) * 16;
   // rows layout (bit 12): `mask` = the blob's main mask words, `argsort` = the appendix' row list (its mask words and
   // pair table lie behind it, the class word and M npad + 64 words ahead of it), `pair` = the row-order table
   p.cls = nullptr;
@@ -276,24 +278,33 @@ __device__ __forceinline__ void igemm_v4_body(const GemmParams &p, int block) {
   int pos[MB];                                                     // position of this lane's rows in the tables the
                                                                    // workgroup walks (-1: no row)
   if (app) {
-    typedef const int32_t __attribute__((address_space(4))) *cptr_t;
-    const int cls = *(cptr_t)(p.cls);
-    app_m = *(cptr_t)(p.cls + 1);
-    if (!cls) {
-      if constexpr (!I8 && !BT && !WIDE) if (p.stats) wg_bn_stats_empty<COUT>(p.stats, block, static_cast<int>(gridDim.x));
-      return;
-    }
-    // The M rows of the appendix are dealt to the launch's napp appendix workgroups in whole 16-row blocks, h rows
-    // each: the appendix tiles are the launch's critical path (a walk over every offset any of their rows has, after
-    // the main tiles have long finished), and the workgroups reserved for it (n / 4 rows' worth) are there anyway --
-    // config 2: 3 165 rows, 25 tiles of 128 rows walk 4.6 offsets on average and 10 at most, 99 tiles of 32 rows
-    // 2.7 and 7 (forward 11.2 -> 9.5 us).  A full appendix (M = n / 4) keeps whole tiles.  The fused backward shares
-    // the chip's 1024 workgroup slots with the wgrad ranges and deals to at most kAppBudget workgroups (app_budget).
-    const int groups = p.app_budget > 0 ? min(napp, p.app_budget) : napp;
-    const int h = min(TM, (((app_m + groups - 1) / groups) + 15) & ~15);
-    if (block * h >= app_m) {
-      if constexpr (!I8 && !BT && !WIDE) if (p.stats) wg_bn_stats_empty<COUT>(p.stats, block, static_cast<int>(gridDim.x));
-      return;
+    // The host has read {class 1, M} of this blob (SPX_SPARSE_ROWS_HINT): M and the height h are ARGUMENTS, the launch
+    // holds exactly the appendix workgroups that have rows, and the row list and mask words are requested at once --
+    // no dependent scalar trip at the head of the launch's longest workgroups.
+    app_m = p.app_m;
+    int h = p.app_h;
+    if (app_m < 0) {
+      typedef const i32x2 __attribute__((address_space(4))) *cptr_t;   // {class, M}: ONE scalar trip
+      const i32x2 head = *(cptr_t)(p.cls);
+      const int cls = head[0];
+      app_m = head[1];
+      if (!cls) {
+        if constexpr (!I8 && !BT && !WIDE) if (p.stats) wg_bn_stats_empty<COUT>(p.stats, block, static_cast<int>(gridDim.x));
+        return;
+      }
+      // The M rows of the appendix are dealt to the launch's napp appendix workgroups in whole 16-row blocks, h rows
+      // each: the appendix tiles are the launch's critical path (a walk over every offset any of their rows has, after
+      // the main tiles have long finished), and the workgroups reserved for it (n / 4 rows' worth) are there anyway --
+      // config 2: 3 165 rows, 25 tiles of 128 rows walk 4.6 offsets on average and 10 at most, 99 tiles of 32 rows
+      // 2.7 and 7 (forward 11.2 -> 9.5 us).  A full appendix (M = n / 4) keeps whole tiles.  The fused backward shares
+      // the chip's 1024 workgroup slots with the wgrad ranges and deals to at most kAppBudget workgroups (app_budget).
+      // (app_shape_exact, igemm_defs.h, is the same arithmetic on the host.)
+      const int groups = p.app_budget > 0 ? min(napp, p.app_budget) : napp;
+      h = min(TM, (((app_m + groups - 1) / groups) + 15) & ~15);
+      if (block * h >= app_m) {
+        if constexpr (!I8 && !BT && !WIDE) if (p.stats) wg_bn_stats_empty<COUT>(p.stats, block, static_cast<int>(gridDim.x));
+        return;
+      }
     }
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
@@ -849,12 +860,23 @@ int launch_v4(const GemmParams &p, hipStream_t s) {
   const int ntiles = div_up(p.n_dst, 64 * MB);
   // rows layout: appendix workgroups lead the grid -- as many as the class rule allows rows (n / 4), or as many as the
   // host says there are (app_rows, SPX_SPARSE_HINT)
-  const int napp = p.cls ? (p.app_rows > 0 ? div_up(p.app_rows, 64 * MB) : layout_app_tiles(p.n_dst, 64 * MB)) : 0;
+  int napp = p.cls ? (p.app_rows > 0 ? div_up(p.app_rows, 64 * MB) : layout_app_tiles(p.n_dst, 64 * MB)) : 0;
+  // ... or, for the 16-bit types, exactly the workgroups that have rows under the dealing rule when the host has READ
+  // M (app_m, SPX_SPARSE_ROWS_HINT -- an exact count, unlike the upper bound above; same rows in the same tiles)
+  AppShape exact{-1, 0};
+  if constexpr (DT == 0 || DT == 1) {
+    if (p.cls && p.app_rows <= 0) exact = app_shape_exact(p.n_dst, 64 * MB, p.app_m, 0);
+  }
+  if (exact.napp >= 0) napp = exact.napp;
   GemmParams q = p;
   // more tiles than workgroups the chip holds at once (4 per CU up to 64 output channels, fewer beyond)
   q.lpt = p.tile_order && ntiles > ((DT == 2 || COUT > 64) ? 512 : 1024);
   GemmRest r = rest_of(p);
   r.napp = p.cls ? napp : -1;
+  if (exact.napp >= 0) {
+    r.acc_mode = pack_app_shape(p.acc_mode, p.app_m, exact);
+    count_hint(kHintV4);
+  }
   constexpr int es = DT == 2 ? 1 : (DT == 3 ? 4 : 2);
   const bool half = p.CIN * es <= 64;        // narrow rows: only the first 64 bytes of a piece exist
   const int pk = v4_pack(p, DT, es);         // ... <= 32 / 16 bytes: 2 / 4 offsets per step (igemm_v4_body, PK)

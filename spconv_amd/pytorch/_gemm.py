@@ -18,7 +18,7 @@ import torch
 
 from spconv_amd import _lib
 from spconv_amd.pytorch._rulebook import (_MFMA_COUT, _ROWS_LAYOUT, Activation, _dtype_code, _int_repr, _on_device, _ptr,
-                                          _require_gpu, _stream, _with_dense_hint, _ws)
+                                          _require_gpu, _stream, _with_hints, _ws)
 
 # SPX_OUT_CACHED (include/spconv_amd.h): inside this context igemm_fwd asks for result rows that stay in
 # the caches -- SparseSequential opens it around a convolution whose output a BatchNorm reads next
@@ -218,7 +218,7 @@ def igemm_fwd(features: torch.Tensor, filters: torch.Tensor, pair: torch.Tensor,
     f64 = features.dtype == torch.float64
     # every entry point shares its arguments up to the bias pointer
     head = (features.data_ptr(), filters.data_ptr(), out.data_ptr(), _ptr(pair), _ptr(mask), _ptr(argsort),
-            int(tile_order) if f64 else _with_dense_hint(int(tile_order), argsort, mask), features.shape[0], n_out, C, K,
+            int(tile_order) if f64 else _with_hints(int(tile_order), argsort, mask), features.shape[0], n_out, C, K,
             kv, _dtype_code(features), identity_k)
     if f64:
         # csrc/igemm_f64.hip: every width and kernel volume as it is -- no hint, no scratch, no BatchNorm statistics out
@@ -263,7 +263,7 @@ def igemm_dgrad(out_bp: torch.Tensor, filters: torch.Tensor, pair: torch.Tensor,
     ws = None if code == _lib.DTYPE_F64 else _ws(max(L.spx_igemm_dgrad_ws_bytes(C, K, kv, code),
                                                      L.spx_igemm_acc_bytes(n_in, C, kv)), out_bp.device)
     _lib.check(L.spx_igemm_dgrad(out_bp.data_ptr(), filters.data_ptr(), din.data_ptr(), _ptr(pair),
-                                 _ptr(mask), _ptr(argsort), _with_dense_hint(int(tile_order), argsort, mask), out_bp.shape[0],
+                                 _ptr(mask), _ptr(argsort), _with_hints(int(tile_order), argsort, mask), out_bp.shape[0],
                                  n_in, C, K, kv, code,
                                  int(subm), _ptr(ws), 0 if ws is None else ws.numel(), _stream(out_bp)))
     return din if C == C0 else din[:, :C0].contiguous()

@@ -354,6 +354,9 @@ def key_argsort(indices: torch.Tensor, batch_size: int, spatial_shape, want_indi
 # (values and bits of a gather-GEMM call's `tile_order`; the bits of its `act` argument are in _gemm)
 _ROWS_LAYOUT = 2              # SPX_ROWS_LAYOUT: `argsort` of a gather-GEMM call is a layout blob
 _DENSE_HINT = 0x100           # SPX_DENSE_HINT (include/spconv_amd.h)
+_SPARSE_ROWS_HINT = 0x200     # SPX_SPARSE_ROWS_HINT: class word 1 and M of this blob have been READ; M rides in the bits above
+_SPARSE_ROWS_SHIFT = 12       # SPX_SPARSE_ROWS_SHIFT
+_SPARSE_ROWS_MAX = 0x7ffff    # SPX_SPARSE_ROWS_MAX: an M beyond it travels as no hint
 _WS_MIN_ROWS = 98304          # one 512-row workgroup per CU: below ~3/4 of 256 x 512 rows the 128-row tiles fill the chip better
 _CLASS_SLOTS = 1024
 _class_ring = {}              # device index -> [pinned int32 [_CLASS_SLOTS, 2], next slot, owner tokens]
@@ -397,6 +400,7 @@ def _set_class(rb: Rulebook, cls=None, heavy: int = 0, predict: bool = True) -> 
         carrier._spx_dense = _pred_get(rb.pred_key)
         return
     carrier._spx_dense, carrier._spx_heavy = _dense_rule(cls, heavy, rb.n_out), heavy
+    carrier._spx_class = int(bool(cls))
     if predict:
         _predict(rb.pred_key, cls, heavy, rb.n_out)
 
@@ -468,12 +472,48 @@ def poll_class(rb: Optional[Rulebook]) -> None:
         rb._class_req = None
 
 
+def sparse_rows_hint(tile_order: int, rows) -> int:
+    """`tile_order` with the sparse-class hint for an appendix of exactly `rows` rows (None, negative or beyond the bits
+    of the word: no hint).  The encoding only -- whether a hint may be given is _with_sparse_hint's business."""
+    if tile_order != _ROWS_LAYOUT or rows is None or not 0 <= int(rows) <= _SPARSE_ROWS_MAX:
+        return tile_order
+    return tile_order | _SPARSE_ROWS_HINT | (int(rows) << _SPARSE_ROWS_SHIFT)
+
+
+def split_tile_order(word: int):
+    """(table form, dense hint, M of the sparse hint or None) of a `tile_order` word as the drivers pass it."""
+    rows = (word >> _SPARSE_ROWS_SHIFT) & _SPARSE_ROWS_MAX if word & _SPARSE_ROWS_HINT else None
+    return word & 0xff, bool(word & _DENSE_HINT), rows
+
+
+def _with_sparse_hint(tile_order: int, argsort) -> int:
+    """The hint sizes the appendix part of the grid from the EXACT row count: it is given when, and only when, class
+    word 1 and M have been READ from this very blob (_set_class leaves both on the tensor; _gemm.igemm_fwd_int8 spells
+    out the discipline) -- never from a prediction or a caller's number.  Inside a capture nothing is polled: what was
+    read before it shapes the captured launch, and a blob built inside it carries nothing."""
+    if tile_order != _ROWS_LAYOUT or getattr(argsort, "_spx_class", None) != 1:
+        return tile_order
+    return sparse_rows_hint(tile_order, getattr(argsort, "_spx_heavy", None))
+
+
 def _with_dense_hint(tile_order: int, argsort, mask=None) -> int:
     if tile_order == _ROWS_LAYOUT and getattr(argsort, "_spx_dense", False):
         return tile_order | _DENSE_HINT
     if tile_order == 0 and argsort is None and getattr(mask, "_spx_dense", False):
         return _DENSE_HINT               # (a rulebook whose layout was left out: ops.build_rulebook)
     return tile_order
+
+
+def _with_hints(tile_order: int, argsort, mask=None) -> int:
+    """What the 16-bit forward and dgrad drivers pass as `tile_order`: the dense hint, or else the sparse one (a blob is
+    of one class).  Runs for every launch: one pass over the attributes."""
+    if tile_order == _ROWS_LAYOUT:
+        if getattr(argsort, "_spx_dense", False):
+            return tile_order | _DENSE_HINT
+        if getattr(argsort, "_spx_class", None) == 1:
+            return sparse_rows_hint(tile_order, getattr(argsort, "_spx_heavy", None))
+        return tile_order
+    return _with_dense_hint(tile_order, argsort, mask)
 
 
 def sparse_neighbourhoods(rb: Rulebook) -> bool:

@@ -36,9 +36,10 @@ from spconv_amd.pytorch.core import ConvAlgo, Rulebook
 from spconv_amd.pytorch._rulebook import (  # noqa: F401  (re-exports: what callers reach through this module)
     _CLS0_ATTR, _DTYPES, _LAYOUT_MIN_ROWS, _MFMA_COUT, _ROWS_LAYOUT, _SORTED_MAX_SCRATCH, Activation, _build_conv,
     _build_subm, _cells, _dtype_code, _int_repr, _kv, _native_from_table, _on_device, _pred_get, _ptr, _rankmap_of,
-    _require_gpu, _set_class, _stream, _table_from_native, _with_dense_hint, _ws, attach_rank_map, attach_rulebook,
+    _require_gpu, _set_class, _stream, _table_from_native, _with_dense_hint, _with_hints, _with_sparse_hint, _ws,
+    attach_rank_map, attach_rulebook,
     get_conv_output_size, get_deconv_output_size, key_argsort, layout_views, mask_argsort, poll_class, rows_layout,
-    rulebook_of, sort_rulebook, sparse_neighbourhoods, tables_of)
+    rulebook_of, sort_rulebook, sparse_neighbourhoods, sparse_rows_hint, split_tile_order, tables_of)
 from spconv_amd.pytorch._gemm import (  # noqa: F401
     _STAGE2_JOB_BYTES, _WGRAD_MAX_KV, StatsSink, _check_feat, _defer_lock, _defer_passes, _defer_state, _lane_mult,
     bias_act_inplace, collect_bn_stats, current_stats_sink, deferred_wgrad, igemm_dgrad, igemm_fwd, igemm_fwd_int8,
@@ -227,7 +228,8 @@ def igemm_bwd(features: torch.Tensor, out_bp: torch.Tensor, filters: torch.Tenso
     dw = torch.empty_like(filters)
     ws = _ws(L.spx_igemm_wgrad_ws_bytes(native.shape[2], C, K, kv), features.device)
     args = (features.data_ptr(), out_bp.data_ptr(), filters.data_ptr(), din.data_ptr(), dw.data_ptr(), _ptr(table),
-            _ptr(mask), _ptr(argsort), int(tile_order), native.data_ptr(), num_per_loc.data_ptr(), _ptr(plan), n_in,
+            _ptr(mask), _ptr(argsort), _with_sparse_hint(int(tile_order), argsort), native.data_ptr(), num_per_loc.data_ptr(),
+            _ptr(plan), n_in,
             out_bp.shape[0], C, K, kv, _dtype_code(out_bp), int(subm), ws.data_ptr(), ws.numel(), _stream(out_bp))
     if st is not None:
         job = ctypes.create_string_buffer(_STAGE2_JOB_BYTES)
