@@ -2,8 +2,8 @@
 // (spx_collapse_count / _fill / _static, spx_collapse_fwd / _bwd).  Height compression of the fully sparse detectors:
 // (batch, z, y, x) rows -> (batch, y, x) rows, reduced by sum, mean or max, the 2-D level behind in key order.
 //
-// The projected cells are numbered as the union numbers its coordinates (union.hip), through the RANK MAP of the
-// projected grid (rankmap.h) -- no hash table, and no atomic on the path that numbers the rows:
+// The projected cells are numbered through the RANK MAP of the projected grid (rankmap.h: level_key over the kept axes,
+// number_level), as the union numbers its coordinates -- no hash table, and no atomic on the path that numbers the rows:
 //   mark    a plain byte store per live row into the byte-per-cell map of the PROJECTED grid (every writer stores 1),
 //           and the live rows counted (a ballot per wave).  A row is dead when it lies at or beyond *n_live, when its
 //           batch index is outside [0, batch) or any coordinate -- a removed one included -- outside its extent.
@@ -19,10 +19,10 @@
 //           keys differ by at most one) and sets the entries from `live` on to the kept rows' count.
 // The reduction gives an output row to a group of G lanes (G = a power of two covering the row's pieces, at most a
 // wave: a full wave covers 64 x 16 bytes, narrow rows put 64 / G output rows in a wave; a wider row takes several
-// passes).  A lane walks list[offsets[r] .. offsets[r + 1]) for its piece, four entries' loads in flight, the additions
-// in list order in fp32 (fp64 for SPX_F64): the accumulator starts from the first row's value, one rounding at the end,
-// a group of one row is copied bit for bit, every output element is written exactly once.  A group is never split
-// across lanes or waves: that would change the summation order.
+// passes).  A lane walks list[offsets[r] .. offsets[r + 1]) for its piece (the segment walk of piece.h: four entries'
+// loads in flight, a group never split), the additions in list order in fp32 (fp64 for SPX_F64): the accumulator starts
+// from the first row's value, one rounding at the end, a group of one row is copied bit for bit, every output element
+// is written exactly once.
 #include "common.h"
 #include "fill.h"
 #include "piece.h"
@@ -35,28 +35,19 @@ namespace {
 constexpr int kBlock = 256;
 static_assert(kBlock == kScanThreads, "scan.h's primitives are written for this unit's workgroup size");
 constexpr int kCounters = 4;          // {cells found, live input rows, live output rows, kept input rows}
-constexpr int kAhead = 4;             // list entries whose loads are in flight together
 
 struct CollapseGeom {
-  int ndim, batch, kdim;              // kdim: kept axes
-  int dims[kMaxNdim];
-  int keep[kMaxNdim];                 // 1: the axis stays
+  LevelGeom level;                    // the INPUT level
+  int kdim;                           // kept axes
+  unsigned keep;                      // bit d: axis d stays
 };
 
-// linear key of row i on the PROJECTED grid (batch-major, last kept axis fastest), -1 for a dead row
+// linear key of row i on the PROJECTED grid (level_key of rankmap.h over the kept axes; a removed axis is still
+// range-checked), -1 for a dead row
 __device__ __forceinline__ long long key_of(const int32_t *__restrict__ idx, const int32_t *__restrict__ n_live,
                                             const CollapseGeom &g, int i) {
   if (n_live && i >= *n_live) return -1;
-  const int32_t *r = idx + static_cast<size_t>(i) * (g.ndim + 1);
-  const int b = r[0];
-  if (static_cast<unsigned>(b) >= static_cast<unsigned>(g.batch)) return -1;
-  long long key = b;
-  for (int d = 0; d < g.ndim; ++d) {
-    const int v = r[1 + d];
-    if (static_cast<unsigned>(v) >= static_cast<unsigned>(g.dims[d])) return -1;
-    if (g.keep[d]) key = key * g.dims[d] + v;
-  }
-  return key;
+  return level_key(idx + static_cast<size_t>(i) * (g.level.ndim + 1), g.level, g.keep);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -67,19 +58,6 @@ collapse_mark_kernel(const int32_t *__restrict__ idx, int n, const int32_t *__re
   if (key >= 0) occupied[key] = 1;
   const unsigned long long bal = __ballot(key >= 0);
   if ((threadIdx.x & 63) == 0 && bal) atomicAdd(live_rows, __popcll(bal));      // (an integer count: order-free)
-}
-
-// Exclusive scan of the prefix pass's block totals by one block; counters[0] = the cells found, counters[2] = the
-// live output rows = min(found, cap) (cap < 0: no bound).
-__global__ void __launch_bounds__(kBlock)
-collapse_scan_kernel(const int32_t *__restrict__ cnt, int32_t *__restrict__ off, int len, int cap,
-                     int32_t *__restrict__ counters) {
-  __shared__ int lds_wave[kBlock / 64];
-  const int carry = block_scan_loop(cnt, off, len, lds_wave);
-  if (threadIdx.x == 0) {
-    counters[0] = carry;
-    counters[2] = cap >= 0 && carry > cap ? cap : carry;
-  }
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -101,11 +79,11 @@ collapse_rank_kernel(const int32_t *__restrict__ idx, int n, const int32_t *__re
   }
   if (r >= 0) {
     int32_t *o = out_indices + static_cast<size_t>(r) * (g.kdim + 1);
-    const int32_t *src = idx + static_cast<size_t>(i) * (g.ndim + 1);
+    const int32_t *src = idx + static_cast<size_t>(i) * (g.level.ndim + 1);
     int c = 0;
     o[c++] = src[0];
-    for (int d = 0; d < g.ndim; ++d)
-      if (g.keep[d]) o[c++] = src[1 + d];
+    for (int d = 0; d < g.level.ndim; ++d)
+      if ((g.keep >> d) & 1u) o[c++] = src[1 + d];
   }
   const unsigned long long bal = __ballot(r >= 0);
   if ((threadIdx.x & 63) == 0 && bal) atomicAdd(kept_rows, __popcll(bal));
@@ -151,16 +129,9 @@ collapse_fwd_kernel(const void *__restrict__ feat_, int n, const int32_t *__rest
   const int G = 1 << gshift;
   for (long long item = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; item < total;
        item += static_cast<long long>(gridDim.x) * kBlock) {
-    const int r = static_cast<int>(item >> gshift);
-    const int sub = static_cast<int>(item) & (G - 1);
-    int beg = 0, end = 0;
-    if (r < live) {
-      beg = offsets[r];
-      end = offsets[r + 1];
-      beg = beg < 0 ? 0 : beg;                  // (checked, not trusted)
-      end = end > n ? n : end;
-    }
-    for (int p = sub; p < pieces; p += G) {
+    const Segment g = segment_of(item, gshift, live, offsets, n);
+    const int r = g.r, beg = g.beg, end = g.end;
+    for (int p = g.sub; p < pieces; p += G) {
       P first;
       A acc[V];
 #pragma unroll
@@ -261,20 +232,16 @@ collapse_bwd_kernel(const void *__restrict__ feat_, const void *__restrict__ out
 
 // -------------------------------------------------------------------------------------------- host side
 
-// scratch of a build: the byte map of the projected grid, the prefix pass's block totals, the counters, the rows' sort
-// keys, the radix sort's buffers
-struct CollapseWs {
-  uint8_t *occupied;
-  int32_t *blockcount, *counters;
+// scratch of a build: the numbering's head for the projected grid (byte map, block totals), the counters, the rows'
+// sort keys, the radix sort's buffers
+struct CollapseWs : RankScratch {
+  int32_t *counters;
   uint32_t *sortkey;
   void *sort;
-  int nblk;
   size_t bytes;
   CollapseWs(void *ws, size_t W, int n) {
     Carver c(ws);
-    nblk = static_cast<int>(rank_blocks(W));
-    occupied = c.take<uint8_t>(W * 32);
-    blockcount = c.take<int32_t>(nblk > 0 ? nblk : 1);
+    carve(c, W);
     counters = c.take<int32_t>(kCounters);
     sortkey = c.take<uint32_t>(n > 0 ? n : 1);
     sort = c.take<char>(radix_argsort_ws_bytes(n));
@@ -311,16 +278,12 @@ int make_build(int n, int ndim, int batch, const int *spatial_h, int axes_mask, 
   b.W = projected_words(ndim, batch, spatial_h, axes_mask, kept, &b.g.kdim);
   SPX_CHECK(b.W > 0, "the projected key space does not fit a rank map (or the grid is empty)");
   SPX_CHECK(rankmap && rankmap_bytes >= rank_bytes(b.W), "rank map missing or too small (%zu words)", b.W);
-  b.g.ndim = ndim;
-  b.g.batch = batch;
-  for (int d = 0; d < kMaxNdim; ++d) {
-    b.g.dims[d] = d < ndim ? spatial_h[d] : 1;
-    b.g.keep[d] = d < ndim && !((axes_mask >> d) & 1) ? 1 : 0;
-  }
+  b.g.level = LevelGeom(ndim, batch, spatial_h);
+  b.g.keep = ~static_cast<unsigned>(axes_mask) & ((1u << ndim) - 1u);
   return 0;
 }
 
-// fill + mark + prefix + scan: the rank map of the projected level, its size in counters[0] / [2]
+// fill + mark + number_level: the rank map of the projected level, its size in counters[0] / [2]
 int number_cells(const Build &b, const int32_t *indices, int n, const int32_t *n_live, void *rankmap, const CollapseWs &w,
                  int32_t *counters, int cap, const FillList *more, hipStream_t s) {
   {
@@ -328,8 +291,7 @@ int number_cells(const Build &b, const int32_t *indices, int n, const int32_t *n
     fills.add(w.occupied, b.W * 32, 0u);
     fills.add(w.counters, kCounters * sizeof(int32_t), 0u);
     if (counters != w.counters) fills.add(counters, 3 * sizeof(int32_t), 0u);
-    if (more)
-      for (int j = 0; j < more->jobs.n; ++j) fills.add(more->jobs.ptr[j], more->jobs.words[j] * 4, more->jobs.value[j]);
+    if (more) fills.add(*more);
     SPX_HIP(fills.launch(s));
   }
   if (n > 0) {
@@ -338,12 +300,7 @@ int number_cells(const Build &b, const int32_t *indices, int n, const int32_t *n
     SPX_LAUNCH_CHECK();
     count_collapse(kCollapseMark);
   }
-  hipLaunchKernelGGL(conv4_prefix_kernel, dim3(w.nblk), dim3(kRankThreads), 0, s,
-                     reinterpret_cast<const uint4 *>(w.occupied), static_cast<uint2 *>(rankmap),
-                     static_cast<unsigned>(b.W), w.blockcount);
-  hipLaunchKernelGGL(collapse_scan_kernel, dim3(1), dim3(kBlock), 0, s, w.blockcount, rank_blockoff(rankmap, b.W), w.nblk,
-                     cap, counters);
-  SPX_LAUNCH_CHECK();
+  SPX_HIP(number_level(w, b.W, rankmap, cap, counters, s));
   count_collapse(kCollapsePrefix);
   return 0;
 }
@@ -361,9 +318,7 @@ int list_rows(const Build &b, const int32_t *indices, int n, const int32_t *n_li
                        w.sortkey, out_indices, w.counters + 3);
     SPX_LAUNCH_CHECK();
     count_collapse(kCollapseRank);
-    int nbits = 1;
-    while (nbits < 32 && (capkey >> nbits) != 0) ++nbits;
-    if (int rc = radix_argsort(w.sortkey, n, nbits, list, w.sort, s)) return rc;
+    if (int rc = radix_argsort(w.sortkey, n, key_bits(capkey), list, w.sort, s)) return rc;
   }
   const long long items = n > cap + 1 ? n : static_cast<long long>(cap) + 1;
   hipLaunchKernelGGL(collapse_list_kernel, dim3(static_cast<unsigned>((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
@@ -373,62 +328,13 @@ int list_rows(const Build &b, const int32_t *indices, int n, const int32_t *n_li
   return 0;
 }
 
-int elem_bytes_of(int dtype) { return dtype == SPX_F64 ? 8 : dtype == SPX_F32 ? 4 : 2; }
-
-// 0 = ok: the argument checks of the two reduction calls that need no pointer
+// the argument checks of the two reduction calls that need no pointer: the bytes of an element, or -1 with the error set
 int check_reduce(int n, int n_out, int C, int dtype, int op) {
-  SPX_CHECK(dtype == SPX_F32 || dtype == SPX_F16 || dtype == SPX_BF16 || dtype == SPX_F64,
-            "dtype must be f32, f16, bf16 or f64, got %d", dtype);
+  const int eb = float_row_elem(dtype, C);
+  if (eb < 0) return eb;
   SPX_CHECK(op == kOpSum || op == kOpMean || op == kOpMax, "op must be sum (0), mean (1) or max (2), got %d", op);
-  SPX_CHECK(C >= 1, "channel count must be >= 1, got %d", C);
   SPX_CHECK(n >= 0 && n_out >= 0, "bad row counts %d / %d", n, n_out);
-  SPX_CHECK(static_cast<long long>(C) * elem_bytes_of(dtype) <= 0x7fffffffLL, "row too long");
-  return 0;
-}
-
-template <int DT, int OP>
-void launch_fwd(const void *feat, int n, const int32_t *offsets, const int32_t *list, int n_out, int C, bool vec, void *out,
-                const int32_t *n_live, hipStream_t s) {
-  constexpr int V = 16 / static_cast<int>(sizeof(typename Elem<DT>::S));
-  const int pieces = vec ? C / V : C;
-  int gshift = 0;
-  while (gshift < 6 && (1 << gshift) < pieces) ++gshift;
-  const unsigned grid = stream_blocks(static_cast<long long>(n_out) << gshift, kBlock);
-  if (vec)
-    hipLaunchKernelGGL((collapse_fwd_kernel<DT, V, OP>), dim3(grid), dim3(kBlock), 0, s, feat, n, offsets, list, n_out,
-                       pieces, gshift, out, n_live);
-  else
-    hipLaunchKernelGGL((collapse_fwd_kernel<DT, 1, OP>), dim3(grid), dim3(kBlock), 0, s, feat, n, offsets, list, n_out,
-                       pieces, gshift, out, n_live);
-}
-
-template <int DT>
-void launch_fwd_op(int op, const void *feat, int n, const int32_t *offsets, const int32_t *list, int n_out, int C, bool vec,
-                   void *out, const int32_t *n_live, hipStream_t s) {
-  if (op == kOpSum) launch_fwd<DT, kOpSum>(feat, n, offsets, list, n_out, C, vec, out, n_live, s);
-  else if (op == kOpMean) launch_fwd<DT, kOpMean>(feat, n, offsets, list, n_out, C, vec, out, n_live, s);
-  else launch_fwd<DT, kOpMax>(feat, n, offsets, list, n_out, C, vec, out, n_live, s);
-}
-
-template <int DT, int OP>
-void launch_bwd(const void *feat, const void *out, const void *dout, const int32_t *rows, const int32_t *offsets, int n,
-                int n_out, int C, bool vec, void *din, hipStream_t s) {
-  constexpr int V = 16 / static_cast<int>(sizeof(typename Elem<DT>::S));
-  const int pieces = vec ? C / V : C;
-  const unsigned grid = stream_blocks(static_cast<long long>(n) * pieces, kBlock);
-  if (vec)
-    hipLaunchKernelGGL((collapse_bwd_kernel<DT, V, OP>), dim3(grid), dim3(kBlock), 0, s, feat, out, dout, rows, offsets, n,
-                       n_out, pieces, din);
-  else
-    hipLaunchKernelGGL((collapse_bwd_kernel<DT, 1, OP>), dim3(grid), dim3(kBlock), 0, s, feat, out, dout, rows, offsets, n,
-                       n_out, pieces, din);
-}
-
-template <int DT>
-void launch_bwd_op(int op, const void *feat, const void *out, const void *dout, const int32_t *rows, const int32_t *offsets,
-                   int n, int n_out, int C, bool vec, void *din, hipStream_t s) {
-  if (op == kOpMean) launch_bwd<DT, kOpMean>(feat, out, dout, rows, offsets, n, n_out, C, vec, din, s);
-  else launch_bwd<DT, kOpMax>(feat, out, dout, rows, offsets, n, n_out, C, vec, din, s);
+  return eb;
 }
 
 }  // namespace
@@ -505,19 +411,20 @@ int spx_collapse_static(const int32_t *indices, int n, const int32_t *n_live, in
 int spx_collapse_fwd(const void *feat, int n, const int32_t *offsets, const int32_t *list, int n_out, int C, int dtype,
                      int op, void *out, const int32_t *n_live_out, spx_stream_t stream) {
   using namespace spx;
-  if (int rc = check_reduce(n, n_out, C, dtype, op)) return rc;
+  const int eb = check_reduce(n, n_out, C, dtype, op);
+  if (eb < 0) return eb;
   if (n_out == 0) return 0;
   SPX_CHECK(offsets && out && (n == 0 || (feat && list)), "feat / offsets / list / out is NULL");
-  const int eb = elem_bytes_of(dtype);
   SPX_CHECK(aligned_to(feat, eb) && aligned_to(out, eb), "pointer not aligned to its elements");
   const bool vec = (static_cast<long long>(C) * eb) % 16 == 0 && aligned_to(out, 16) && aligned_to(feat, 16);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case SPX_F32: launch_fwd_op<SPX_F32>(op, feat, n, offsets, list, n_out, C, vec, out, n_live_out, s); break;
-    case SPX_F16: launch_fwd_op<SPX_F16>(op, feat, n, offsets, list, n_out, C, vec, out, n_live_out, s); break;
-    case SPX_BF16: launch_fwd_op<SPX_BF16>(op, feat, n, offsets, list, n_out, C, vec, out, n_live_out, s); break;
-    default: launch_fwd_op<SPX_F64>(op, feat, n, offsets, list, n_out, C, vec, out, n_live_out, s); break;
-  }
+  dispatch_row(dtype, vec, [&](auto dt, auto v) {
+    const int pieces = C / v, gshift = group_shift(pieces);
+    dispatch_value<kOpSum, kOpMean, kOpMax>(op, [&](auto o) {
+      hipLaunchKernelGGL((collapse_fwd_kernel<dt, v, o>), dim3(stream_blocks(static_cast<long long>(n_out) << gshift, kBlock)),
+                         dim3(kBlock), 0, s, feat, n, offsets, list, n_out, pieces, gshift, out, n_live_out);
+    });
+  });
   SPX_LAUNCH_CHECK();
   count_collapse(kCollapseFwd);
   return 0;
@@ -526,23 +433,24 @@ int spx_collapse_fwd(const void *feat, int n, const int32_t *offsets, const int3
 int spx_collapse_bwd(const void *feat, const void *out, const void *dout, const int32_t *rows, const int32_t *offsets, int n,
                      int n_out, int C, int dtype, int op, void *din, spx_stream_t stream) {
   using namespace spx;
-  if (int rc = check_reduce(n, n_out, C, dtype, op)) return rc;
+  const int eb = check_reduce(n, n_out, C, dtype, op);
+  if (eb < 0) return eb;
   SPX_CHECK(op != kOpSum, "the gradient of a sum is a gather: spx_union_add_bwd with one operand");
   if (n == 0) return 0;
   SPX_CHECK(rows && din && (n_out == 0 || dout), "rows / dout / din is NULL");
   SPX_CHECK(n_out == 0 || (op == kOpMean ? offsets != nullptr : feat && out), "mean needs offsets, max needs feat and out");
-  const int eb = elem_bytes_of(dtype);
   SPX_CHECK(aligned_to(feat, eb) && aligned_to(out, eb) && aligned_to(dout, eb) && aligned_to(din, eb),
             "pointer not aligned to its elements");
   const bool vec = (static_cast<long long>(C) * eb) % 16 == 0 && aligned_to(feat, 16) && aligned_to(out, 16) &&
                    aligned_to(dout, 16) && aligned_to(din, 16);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case SPX_F32: launch_bwd_op<SPX_F32>(op, feat, out, dout, rows, offsets, n, n_out, C, vec, din, s); break;
-    case SPX_F16: launch_bwd_op<SPX_F16>(op, feat, out, dout, rows, offsets, n, n_out, C, vec, din, s); break;
-    case SPX_BF16: launch_bwd_op<SPX_BF16>(op, feat, out, dout, rows, offsets, n, n_out, C, vec, din, s); break;
-    default: launch_bwd_op<SPX_F64>(op, feat, out, dout, rows, offsets, n, n_out, C, vec, din, s); break;
-  }
+  dispatch_row(dtype, vec, [&](auto dt, auto v) {
+    const int pieces = C / v;
+    dispatch_value<kOpMean, kOpMax>(op, [&](auto o) {
+      hipLaunchKernelGGL((collapse_bwd_kernel<dt, v, o>), dim3(stream_blocks(static_cast<long long>(n) * pieces, kBlock)),
+                         dim3(kBlock), 0, s, feat, out, dout, rows, offsets, n, n_out, pieces, din);
+    });
+  });
   SPX_LAUNCH_CHECK();
   count_collapse(kCollapseBwd);
   return 0;

@@ -29,6 +29,8 @@ int option_int(const char *name, int dflt);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
+// bytes of one element of a feature dtype (SPX_F32 / SPX_F16 / SPX_BF16 / SPX_I8 / SPX_F64)
+inline int elem_bytes(int dtype) { return dtype == SPX_F64 ? 8 : (dtype == SPX_F32 ? 4 : (dtype == SPX_I8 ? 1 : 2)); }
 
 // Carves 256-byte aligned sub-buffers out of the caller's scratch.
 struct Carver {

@@ -1,5 +1,5 @@
-// Range fills shared by the translation units that build index structures (rulebook_*.hip, union.hip, collapse.hip, select.hip, through table.h); every
-// definition has internal linkage.
+// Range fills shared by the translation units that build index structures (rulebook_*.hip through table.h,
+// voxelize.hip, hash.hip, union.hip, collapse.hip, select.hip, interp.hip); every definition has internal linkage.
 #pragma once
 #include "common.h"
 

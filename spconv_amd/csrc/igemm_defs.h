@@ -332,8 +332,6 @@ int igemm_wgrad_impl(const void *feat, const void *dout, void *dw, const int32_t
                      const int32_t *num_per_loc, const int32_t *plan, int n_in, int n_out, int C, int K, int kv,
                      int dtype, int subm, void *ws, size_t ws_bytes, spx_stream_t stream, void *stage2_job);
 
-inline int elem_bytes(int dtype) { return dtype == SPX_F64 ? 8 : (dtype == SPX_F32 ? 4 : (dtype == SPX_I8 ? 1 : 2)); }
-
 // ---- 32-bit buffer offsets ------------------------------------------------------------------------------------------
 // The MFMA kernels address a tensor through one raw buffer resource with 32-bit byte offsets: a [rows, width] array of
 // elem_bytes-sized elements qualifies below 0x7fff0000 bytes (kOob and beyond mark out-of-range lanes).

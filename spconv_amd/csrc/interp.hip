@@ -11,7 +11,7 @@
 //   backward  dvfeat[v] = sum over the entries e = i * K + c of voxel v's group of corner_w[e] * dout[e / K]: a segment
 //             sum over the TRANSPOSED corner list, which is spx_point_groups over the flattened corner table (a stable
 //             sort: ascending e inside a group).  A voxel's row belongs to a group of G lanes as in collapse.hip, each
-//             lane walks the whole list for its pieces, four entries' loads in flight: no atomics, list order.
+//             lane walks the whole list for its pieces (the segment walk of piece.h): no atomics, list order.
 // All arithmetic is fp32 (fp64 accumulation for SPX_F64) with every operation rounded on its own, so a host loop
 // reproduces every element bit for bit.
 #include "common.h"
@@ -27,37 +27,20 @@ namespace spx {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kAhead = 4;             // list entries whose loads are in flight together (backward)
 constexpr int kDims = 3;              // ndim is 2 or 3
 constexpr int kMaxRows = 1 << 30;     // rows of a level: table_capacity(n) = 2^31 slots still fits its 32-bit mask
 
 struct CornerGeom {
-  int ndim, batch;
-  int dims[kDims];                    // grid extents, index-column (zyx) order
+  LevelGeom level;                    // batch and grid extents, index-column (zyx) order
   float vsize[kDims], lo[kDims];      // by POINT COLUMN (x, y, z): entry j belongs to grid axis ndim - 1 - j
 };
 
-// linear key of index row i (batch-major, last axis fastest), -1 for a dead row
-__device__ __forceinline__ long long row_key(const int32_t *__restrict__ idx, const int32_t *__restrict__ n_live,
-                                             const CornerGeom &g, int i) {
-  if (n_live && i >= *n_live) return -1;
-  const int32_t *r = idx + static_cast<size_t>(i) * (g.ndim + 1);
-  const int b = r[0];
-  if (static_cast<unsigned>(b) >= static_cast<unsigned>(g.batch)) return -1;
-  long long key = b;
-  for (int d = 0; d < g.ndim; ++d) {
-    const int v = r[1 + d];
-    if (static_cast<unsigned>(v) >= static_cast<unsigned>(g.dims[d])) return -1;
-    key = key * g.dims[d] + v;
-  }
-  return key;
-}
-
+// the live rows of the level into the table, by their linear key (level_key of rankmap.h over all axes)
 __global__ void __launch_bounds__(kBlock)
-corner_insert_kernel(const int32_t *__restrict__ idx, int n, const int32_t *__restrict__ n_live, CornerGeom g, Table t) {
+corner_insert_kernel(const int32_t *__restrict__ idx, int n, const int32_t *__restrict__ n_live, LevelGeom g, Table t) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const long long key = row_key(idx, n_live, g, i);
+  if (i >= n || (n_live && i >= *n_live)) return;
+  const long long key = level_key(idx + static_cast<size_t>(i) * (g.ndim + 1), g, kAllAxes);
   if (key >= 0) table_insert_min(t, key, i);      // (a duplicate coordinate: the lowest row stays)
 }
 
@@ -81,7 +64,7 @@ corner_kernel(const float *__restrict__ points, int nfeat, const int32_t *__rest
     w[c] = 0.f;
   }
   const int b = i < np ? (batch_ids ? batch_ids[i] : 0) : -1;
-  bool valid = b >= 0 && b < g.batch;
+  bool valid = b >= 0 && b < g.level.batch;
   int base[NDIM] = {};
   float f[NDIM] = {};
   if (valid) {
@@ -90,7 +73,7 @@ corner_kernel(const float *__restrict__ points, int nfeat, const int32_t *__rest
     for (int j = 0; j < NDIM; ++j) {
       const float tj = (pt[j] - g.lo[j]) / g.vsize[j];        // (the voxeliser's own expression: voxelize.hip)
       const float cell = floorf(tj);
-      valid = valid && cell >= 0.f && cell < static_cast<float>(g.dims[NDIM - 1 - j]);      // (false for NaN)
+      valid = valid && cell >= 0.f && cell < static_cast<float>(g.level.dims[NDIM - 1 - j]);      // (false for NaN)
       const float gj = tj - 0.5f;
       const float bj = floorf(gj);
       f[j] = gj - bj;
@@ -107,8 +90,8 @@ corner_kernel(const float *__restrict__ points, int nfeat, const int32_t *__rest
       for (int d = 0; d < NDIM; ++d) {                        // grid axis d = point column j = NDIM - 1 - d
         const int j = NDIM - 1 - d;
         const int v = base[j] + ((c >> j) & 1);
-        in = in && static_cast<unsigned>(v) < static_cast<unsigned>(g.dims[d]);
-        key = key * g.dims[d] + v;
+        in = in && static_cast<unsigned>(v) < static_cast<unsigned>(g.level.dims[d]);
+        key = key * g.level.dims[d] + v;
       }
 #pragma unroll
       for (int j = 0; j < NDIM; ++j) {                        // ((wx * wy) * wz)
@@ -201,9 +184,8 @@ interp_fwd_kernel(const void *__restrict__ vfeat_, int n, const int32_t *__restr
 
 // -------------------------------------------------------------------------------------------- backward
 
-// Items = (voxel row, lane of its group): G lanes per row, lane `sub` owns the pieces sub, sub + G, ... and walks the
-// whole list of the row for each of them (collapse_fwd_kernel's walk; a group is never split: that would change the
-// order of the sum).
+// Items = (voxel row, lane of its group), the segment walk of piece.h over the transposed corner list: entry e brings
+// its weight and the piece of dout row e >> kshift.
 template <int DT, int V>
 __global__ void __launch_bounds__(kBlock)
 interp_bwd_kernel(const void *__restrict__ dout_, int n_cap, int kshift, const float *__restrict__ corner_w,
@@ -221,16 +203,9 @@ interp_bwd_kernel(const void *__restrict__ dout_, int n_cap, int kshift, const f
   const int entries = n_cap << kshift;
   for (long long item = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; item < total;
        item += static_cast<long long>(gridDim.x) * kBlock) {
-    const int r = static_cast<int>(item >> gshift);
-    const int sub = static_cast<int>(item) & (G - 1);
-    int beg = 0, end = 0;
-    if (r < live) {
-      beg = offsets[r];
-      end = offsets[r + 1];
-      beg = beg < 0 ? 0 : beg;                  // (checked, not trusted)
-      end = end > entries ? entries : end;
-    }
-    for (int p = sub; p < pieces; p += G) {
+    const Segment g = segment_of(item, gshift, live, offsets, entries);
+    const int r = g.r, beg = g.beg, end = g.end;
+    for (int p = g.sub; p < pieces; p += G) {
       A acc[V];
 #pragma unroll
       for (int j = 0; j < V; ++j) acc[j] = A(0);
@@ -294,51 +269,14 @@ int check_corners(int n_cap, int nfeat, int ndim, int n, int batch, int flags) {
   return 0;
 }
 
-int elem_bytes_of(int dtype) { return dtype == SPX_F64 ? 8 : dtype == SPX_F32 ? 4 : 2; }
-
-// 0 = ok: the checks of the two interpolation calls that need no pointer
+// the checks of the two interpolation calls that need no pointer: the bytes of an element, or -1 with the error set
 int check_interp(int n_cap, int ndim, int n, int C, int dtype) {
   SPX_CHECK(ndim == 2 || ndim == 3, "ndim must be 2 or 3, got %d", ndim);
-  SPX_CHECK(dtype == SPX_F32 || dtype == SPX_F16 || dtype == SPX_BF16 || dtype == SPX_F64,
-            "dtype must be f32, f16, bf16 or f64, got %d", dtype);
-  SPX_CHECK(C >= 1, "channel count must be >= 1, got %d", C);
+  const int eb = float_row_elem(dtype, C);
+  if (eb < 0) return eb;
   SPX_CHECK(n_cap >= 0 && n >= 0, "bad point / row counts %d / %d", n_cap, n);
   SPX_CHECK((static_cast<long long>(n_cap) << ndim) < 0x80000000LL, "n_cap * 2^ndim must stay below 2^31, got %d points", n_cap);
-  SPX_CHECK(static_cast<long long>(C) * elem_bytes_of(dtype) <= 0x7fffffffLL, "row too long");
-  return 0;
-}
-
-template <int DT>
-void launch_fwd(const void *vfeat, int n, const int32_t *rows, const float *w, int n_cap, int ndim, int C, bool vec,
-                void *out, hipStream_t s) {
-  constexpr int V = 16 / static_cast<int>(sizeof(typename Elem<DT>::S));
-  const int pieces = vec ? C / V : C;
-  const long long total = static_cast<long long>(n_cap) * pieces;
-  const dim3 grid(stream_blocks(total, kBlock)), block(kBlock);
-  if (vec && ndim == 3)
-    hipLaunchKernelGGL((interp_fwd_kernel<DT, V, 8>), grid, block, 0, s, vfeat, n, rows, w, total, pieces, out);
-  else if (vec)
-    hipLaunchKernelGGL((interp_fwd_kernel<DT, V, 4>), grid, block, 0, s, vfeat, n, rows, w, total, pieces, out);
-  else if (ndim == 3)
-    hipLaunchKernelGGL((interp_fwd_kernel<DT, 1, 8>), grid, block, 0, s, vfeat, n, rows, w, total, pieces, out);
-  else
-    hipLaunchKernelGGL((interp_fwd_kernel<DT, 1, 4>), grid, block, 0, s, vfeat, n, rows, w, total, pieces, out);
-}
-
-template <int DT>
-void launch_bwd(const void *dout, int n_cap, int ndim, const float *w, const int32_t *offsets, const int32_t *list, int n,
-                int C, bool vec, const int32_t *n_live, void *dvfeat, hipStream_t s) {
-  constexpr int V = 16 / static_cast<int>(sizeof(typename Elem<DT>::S));
-  const int pieces = vec ? C / V : C;
-  int gshift = 0;
-  while (gshift < 6 && (1 << gshift) < pieces) ++gshift;
-  const dim3 grid(stream_blocks(static_cast<long long>(n) << gshift, kBlock)), block(kBlock);
-  if (vec)
-    hipLaunchKernelGGL((interp_bwd_kernel<DT, V>), grid, block, 0, s, dout, n_cap, ndim, w, offsets, list, n, pieces,
-                       gshift, n_live, dvfeat);
-  else
-    hipLaunchKernelGGL((interp_bwd_kernel<DT, 1>), grid, block, 0, s, dout, n_cap, ndim, w, offsets, list, n, pieces,
-                       gshift, n_live, dvfeat);
+  return eb;
 }
 
 }  // namespace
@@ -373,10 +311,8 @@ int spx_point_corners(const float *points, int nfeat, const int32_t *batch_ids, 
   SPX_CHECK(points && corner_rows && corner_w && (n == 0 || indices), "points / indices / corner_rows / corner_w is NULL");
   SPX_CHECK(aligned_to(corner_rows, 16) && aligned_to(corner_w, 16), "corner_rows / corner_w not aligned to 16 bytes");
   CornerGeom g;
-  g.ndim = ndim;
-  g.batch = batch;
+  g.level = LevelGeom(ndim, batch, spatial_h);
   for (int d = 0; d < kDims; ++d) {              // the host arrays are zyx: point column j is axis ndim - 1 - j
-    g.dims[d] = d < ndim ? spatial_h[d] : 1;
     g.vsize[d] = d < ndim ? vsize[ndim - 1 - d] : 1.f;
     g.lo[d] = d < ndim ? coors_range[ndim - 1 - d] : 0.f;
   }
@@ -409,7 +345,7 @@ int spx_point_corners(const float *points, int nfeat, const int32_t *batch_ids, 
     SPX_HIP(fills.launch(s));
   }
   if (n > 0) {
-    hipLaunchKernelGGL(corner_insert_kernel, dim3(div_up(n, kBlock)), block, 0, s, indices, n, n_live, g, t);
+    hipLaunchKernelGGL(corner_insert_kernel, dim3(div_up(n, kBlock)), block, 0, s, indices, n, n_live, g.level, t);
     SPX_LAUNCH_CHECK();
   }
   if (ndim == 3)
@@ -426,20 +362,22 @@ int spx_point_corners(const float *points, int nfeat, const int32_t *batch_ids, 
 int spx_interp_fwd(const void *vfeat, int n, const int32_t *corner_rows, const float *corner_w, int n_cap, int ndim, int C,
                    int dtype, void *out, spx_stream_t stream) {
   using namespace spx;
-  if (int rc = check_interp(n_cap, ndim, n, C, dtype)) return rc;
+  const int eb = check_interp(n_cap, ndim, n, C, dtype);
+  if (eb < 0) return eb;
   if (n_cap == 0) return 0;
   SPX_CHECK(corner_rows && corner_w && out && (n == 0 || vfeat), "vfeat / corner_rows / corner_w / out is NULL");
-  const int eb = elem_bytes_of(dtype);
   SPX_CHECK(aligned_to(vfeat, eb) && aligned_to(out, eb), "pointer not aligned to its elements");
   SPX_CHECK(aligned_to(corner_rows, 16) && aligned_to(corner_w, 16), "corner_rows / corner_w not aligned to 16 bytes");
   const bool vec = (static_cast<long long>(C) * eb) % 16 == 0 && aligned_to(vfeat, 16) && aligned_to(out, 16);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case SPX_F32: launch_fwd<SPX_F32>(vfeat, n, corner_rows, corner_w, n_cap, ndim, C, vec, out, s); break;
-    case SPX_F16: launch_fwd<SPX_F16>(vfeat, n, corner_rows, corner_w, n_cap, ndim, C, vec, out, s); break;
-    case SPX_BF16: launch_fwd<SPX_BF16>(vfeat, n, corner_rows, corner_w, n_cap, ndim, C, vec, out, s); break;
-    default: launch_fwd<SPX_F64>(vfeat, n, corner_rows, corner_w, n_cap, ndim, C, vec, out, s); break;
-  }
+  dispatch_row(dtype, vec, [&](auto dt, auto v) {
+    const int pieces = C / v;
+    const long long total = static_cast<long long>(n_cap) * pieces;
+    dispatch_value<2, 3>(ndim, [&](auto nd) {
+      hipLaunchKernelGGL((interp_fwd_kernel<dt, v, (1 << nd)>), dim3(stream_blocks(total, kBlock)), dim3(kBlock), 0, s, vfeat,
+                         n, corner_rows, corner_w, total, pieces, out);
+    });
+  });
   SPX_LAUNCH_CHECK();
   count_interp(kInterpFwd);
   return 0;
@@ -449,20 +387,19 @@ int spx_interp_bwd(const void *dout, int n_cap, int ndim, const float *corner_w,
                    const int32_t *list, int n, const int32_t *n_live, int C, int dtype, void *dvfeat,
                    spx_stream_t stream) {
   using namespace spx;
-  if (int rc = check_interp(n_cap, ndim, n, C, dtype)) return rc;
+  const int eb = check_interp(n_cap, ndim, n, C, dtype);
+  if (eb < 0) return eb;
   if (n == 0) return 0;
   SPX_CHECK(offsets && dvfeat && (n_cap == 0 || (dout && corner_w && list)),
             "dout / corner_w / offsets / list / dvfeat is NULL");
-  const int eb = elem_bytes_of(dtype);
   SPX_CHECK(aligned_to(dout, eb) && aligned_to(dvfeat, eb), "pointer not aligned to its elements");
   const bool vec = (static_cast<long long>(C) * eb) % 16 == 0 && aligned_to(dout, 16) && aligned_to(dvfeat, 16);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case SPX_F32: launch_bwd<SPX_F32>(dout, n_cap, ndim, corner_w, offsets, list, n, C, vec, n_live, dvfeat, s); break;
-    case SPX_F16: launch_bwd<SPX_F16>(dout, n_cap, ndim, corner_w, offsets, list, n, C, vec, n_live, dvfeat, s); break;
-    case SPX_BF16: launch_bwd<SPX_BF16>(dout, n_cap, ndim, corner_w, offsets, list, n, C, vec, n_live, dvfeat, s); break;
-    default: launch_bwd<SPX_F64>(dout, n_cap, ndim, corner_w, offsets, list, n, C, vec, n_live, dvfeat, s); break;
-  }
+  dispatch_row(dtype, vec, [&](auto dt, auto v) {
+    const int pieces = C / v, gshift = group_shift(pieces);
+    hipLaunchKernelGGL((interp_bwd_kernel<dt, v>), dim3(stream_blocks(static_cast<long long>(n) << gshift, kBlock)),
+                       dim3(kBlock), 0, s, dout, n_cap, ndim, corner_w, offsets, list, n, pieces, gshift, n_live, dvfeat);
+  });
   SPX_LAUNCH_CHECK();
   count_interp(kInterpBwd);
   return 0;

@@ -143,23 +143,6 @@ pv_decorate_kernel(const float *__restrict__ points, int nfeat, long long total,
   }
 }
 
-template <int DT>
-void launch_decorate(const float *points, int nfeat, int n_cap, const int32_t *rows, const int32_t *indices,
-                     const DecoGeom &g, const float *mean, int flags, void *out, int C_out, hipStream_t s) {
-  constexpr int EB = static_cast<int>(sizeof(typename Elem<DT>::S));
-  constexpr int V = 16 / EB;
-  const bool vec = (static_cast<long long>(C_out) * EB) % 16 == 0 && aligned_to(out, 16);
-  const int pieces = vec ? C_out / V : C_out;
-  const long long total = static_cast<long long>(n_cap) * pieces;
-  const unsigned grid = stream_blocks(total, kBlock);
-  if (vec)
-    hipLaunchKernelGGL((pv_decorate_kernel<DT, V>), dim3(grid), dim3(kBlock), 0, s, points, nfeat, total, pieces, rows,
-                       indices, g, mean, flags, out);
-  else
-    hipLaunchKernelGGL((pv_decorate_kernel<DT, 1>), dim3(grid), dim3(kBlock), 0, s, points, nfeat, total, pieces, rows,
-                       indices, g, mean, flags, out);
-}
-
 template <typename P>
 void launch_gather(const void *vfeat, int num_voxels, const int32_t *rows, int n_cap, int pieces, const void *fill16,
                    void *out, hipStream_t s) {
@@ -216,9 +199,7 @@ int spx_point_groups(const void *ids, int id_bytes, int n_cap, const int32_t *n_
       hipLaunchKernelGGL(pv_key_kernel<int32_t>, gp, dim3(kBlock), 0, s, static_cast<const int32_t *>(ids), n_cap,
                          n_points_dev, num_voxels, rows, w.sortkey);
     SPX_LAUNCH_CHECK();
-    int nbits = 1;                    // keys 0 .. num_voxels
-    while (nbits < 32 && (static_cast<uint32_t>(num_voxels) >> nbits) != 0) ++nbits;
-    if (int rc = radix_argsort(w.sortkey, n_cap, nbits, list, w.sort, s)) return rc;
+    if (int rc = radix_argsort(w.sortkey, n_cap, key_bits(static_cast<uint32_t>(num_voxels)), list, w.sort, s)) return rc;
   }
   // (n_cap = 0: the bisection touches neither the keys nor the list)
   hipLaunchKernelGGL(pv_offsets_kernel, dim3(static_cast<unsigned>((static_cast<long long>(num_voxels) + kBlock) / kBlock)),
@@ -271,7 +252,8 @@ int spx_point_decorate(const float *points, int nfeat, int n_cap, const int32_t 
   SPX_CHECK(points && rows && out, "points / rows / out is NULL");
   SPX_CHECK(!(flags & 1) || cluster_mean, "the cluster offset needs cluster_mean");
   SPX_CHECK(!(flags & 2) || (indices && vsize && coors_range), "the centre offset needs indices, vsize and coors_range");
-  SPX_CHECK(aligned_to(out, out_dtype == SPX_F32 ? 4 : 2), "out not aligned to its elements");
+  const int eb = elem_bytes(out_dtype);
+  SPX_CHECK(aligned_to(out, eb), "out not aligned to its elements");
   DecoGeom g;
   g.ndim = ndim;
   for (int j = 0; j < kMaxNdim; ++j) {              // the host arrays are zyx: point column j is axis ndim - 1 - j
@@ -280,9 +262,13 @@ int spx_point_decorate(const float *points, int nfeat, int n_cap, const int32_t 
     g.lo[j] = in ? coors_range[ndim - 1 - j] : 0.f;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (out_dtype == SPX_F32) launch_decorate<SPX_F32>(points, nfeat, n_cap, rows, indices, g, cluster_mean, flags, out, C_out, s);
-  else if (out_dtype == SPX_F16) launch_decorate<SPX_F16>(points, nfeat, n_cap, rows, indices, g, cluster_mean, flags, out, C_out, s);
-  else launch_decorate<SPX_BF16>(points, nfeat, n_cap, rows, indices, g, cluster_mean, flags, out, C_out, s);
+  const bool vec = (static_cast<long long>(C_out) * eb) % 16 == 0 && aligned_to(out, 16);
+  dispatch_row_of<SPX_F32, SPX_F16, SPX_BF16>(out_dtype, vec, [&](auto dt, auto v) {
+    const int pieces = C_out / v;
+    const long long total = static_cast<long long>(n_cap) * pieces;
+    hipLaunchKernelGGL((pv_decorate_kernel<dt, v>), dim3(stream_blocks(total, kBlock)), dim3(kBlock), 0, s, points, nfeat,
+                       total, pieces, rows, indices, g, cluster_mean, flags, out);
+  });
   SPX_LAUNCH_CHECK();
   count_pointvoxel(kPvDecorate);
   return 0;

@@ -1,12 +1,52 @@
-// The RANK MAP of a level (rulebook_sorted.hip, "outputs numbered by KEY RANK"; rulebook_subm.hip; union.hip;
-// collapse.hip): its layout in the caller's buffer,
-// the prefix pass that builds it from a byte-per-cell occupancy map, and the lookup.  Shared by the translation units
-// that build or read one; every definition has internal linkage.
+// A LEVEL and its RANK MAP ("outputs numbered by KEY RANK"): the level's geometry and the linear key of an index row;
+// the map's layout in the caller's buffer, the lookup, and the numbering that builds it from a byte-per-cell occupancy
+// map (prefix pass + totals scan, with the head of the scratch it needs).  Shared by the translation units that build
+// or read one (rulebook_sorted.hip, rulebook_subm.hip, voxelize.hip, union.hip, collapse.hip, select.hip, interp.hip);
+// every definition has internal linkage.
 #pragma once
 #include "common.h"
+#include "scan.h"
 
 namespace spx {
 namespace {
+// A level: batch x grid, the extents in index-column order (unused axes are 1).
+struct LevelGeom {
+  int ndim, batch;
+  int dims[kMaxNdim];
+  LevelGeom() = default;
+  LevelGeom(int ndim_, int batch_, const int *spatial_h) : ndim(ndim_), batch(batch_) {
+    for (int d = 0; d < kMaxNdim; ++d) dims[d] = d < ndim ? spatial_h[d] : 1;
+  }
+};
+
+// The index row r = {batch index, coordinates} against the level: -1 when the batch index or ANY coordinate -- one
+// that does not enter the key included -- is outside its extent; otherwise, KEYED, the linear key over the axes whose
+// bit is set in `axes` (batch-major, the last of them fastest), and 0 when only the range checks are asked for.
+// Whether the row is live at all (n_live) is the caller's to test.
+template <bool KEYED>
+__device__ __forceinline__ long long level_row(const int32_t *__restrict__ r, const LevelGeom &g, unsigned axes) {
+  const int b = r[0];
+  if (static_cast<unsigned>(b) >= static_cast<unsigned>(g.batch)) return -1;
+  long long key = KEYED ? b : 0;
+  for (int d = 0; d < g.ndim; ++d) {
+    const int v = r[1 + d];
+    if (static_cast<unsigned>(v) >= static_cast<unsigned>(g.dims[d])) return -1;
+    if (KEYED && ((axes >> d) & 1u)) key = key * g.dims[d] + v;
+  }
+  return key;
+}
+constexpr unsigned kAllAxes = (1u << kMaxNdim) - 1u;
+
+// the linear key of a row, -1 for one outside the level
+__device__ __forceinline__ long long level_key(const int32_t *__restrict__ r, const LevelGeom &g, unsigned axes) {
+  return level_row<true>(r, g, axes);
+}
+
+// the range checks alone, for a grid that need not fit a key
+__device__ __forceinline__ bool level_holds(const int32_t *__restrict__ r, const LevelGeom &g) {
+  return level_row<false>(r, g, 0u) == 0;
+}
+
 constexpr int kRankThreads = 256;     // threads of a prefix-pass workgroup
 constexpr int kRankWords = 2048;      // words (65536 cells) per prefix block
 constexpr int kRankPer = kRankWords / kRankThreads;
@@ -106,6 +146,42 @@ size_t rank_blocks(size_t W) { return (W + kRankWords - 1) / kRankWords; }
 size_t rank_bytes(size_t W) { return W ? rank_cells_bytes(W) + align_up(rank_blocks(W) * sizeof(int32_t), 256) : 0; }
 int32_t *rank_blockoff(void *rankmap, size_t W) {
   return reinterpret_cast<int32_t *>(static_cast<char *>(rankmap) + rank_cells_bytes(W));
+}
+
+// ------------------------------------------------------------ numbering a level from its byte map
+// head of the scratch of a numbering: the byte-per-cell map (32 bytes per word) and the prefix pass's block totals
+struct RankScratch {
+  uint8_t *occupied;
+  int32_t *blockcount;
+  int nblk;
+  void carve(Carver &c, size_t W) {
+    nblk = static_cast<int>(rank_blocks(W));
+    occupied = c.take<uint8_t>(W * 32);
+    blockcount = c.take<int32_t>(nblk > 0 ? nblk : 1);
+  }
+};
+
+// Exclusive scan of the prefix pass's block totals by one block (block_scan_loop of scan.h); counters[0] = the cells
+// found, counters[2] = the live output rows = min(found, cap) (cap < 0: no bound).
+__global__ void __launch_bounds__(kScanThreads)
+rank_totals_kernel(const int32_t *__restrict__ cnt, int32_t *__restrict__ off, int len, int cap,
+                   int32_t *__restrict__ counters) {
+  __shared__ int lds_wave[kScanThreads / 64];
+  const int carry = block_scan_loop(cnt, off, len, lds_wave);
+  if (threadIdx.x == 0) {
+    counters[0] = carry;
+    counters[2] = cap >= 0 && carry > cap ? cap : carry;
+  }
+}
+
+// prefix pass + totals scan over a marked byte map: the rank map of the level, its size in counters[0] / [2]
+hipError_t number_level(const RankScratch &w, size_t W, void *rankmap, int cap, int32_t *counters, hipStream_t s) {
+  hipLaunchKernelGGL(conv4_prefix_kernel, dim3(w.nblk), dim3(kRankThreads), 0, s,
+                     reinterpret_cast<const uint4 *>(w.occupied), static_cast<uint2 *>(rankmap),
+                     static_cast<unsigned>(W), w.blockcount);
+  hipLaunchKernelGGL(rank_totals_kernel, dim3(1), dim3(kScanThreads), 0, s, w.blockcount, rank_blockoff(rankmap, W), w.nblk,
+                     cap, counters);
+  return hipGetLastError();
 }
 }  // namespace
 }  // namespace spx

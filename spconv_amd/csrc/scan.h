@@ -1,7 +1,7 @@
 // Block-level prefix primitives of the count -> scan -> scatter pipelines: the rank of a thread among the flagged
 // threads of its workgroup, and the exclusive scan of a sequence of int32 counts by one workgroup.  Shared by the
 // translation units that number rows (rulebook_*.hip through rulebook.h, voxelize.hip, hash.hip, rowsort.hip, dense.hip,
-// union.hip, collapse.hip, select.hip); every
+// union.hip, collapse.hip, select.hip) and, through rankmap.h, by every unit that includes that (interp.hip); every
 // definition has internal linkage.  Workgroups are kScanThreads wide: a unit asserts that its own kBlock agrees.
 #pragma once
 #include "common.h"

@@ -233,26 +233,17 @@ topk_flags_kernel(TopkRows r, const uint32_t *__restrict__ state, int32_t *__res
 
 // -------------------------------------------------------------------------------------------- row selection
 
-struct SelGeom {
-  int ndim, batch;
-  int dims[kMaxNdim];
-};
-
 struct SelRows {
   const int32_t *indices;
   const int32_t *n_live;
   const uint8_t *keep;
   int n, invert;
-  SelGeom g;
+  LevelGeom g;
 };
 
+// a live row inside the level (level_holds of rankmap.h: the grid of a selection need not fit a key)
 __device__ __forceinline__ bool sel_live(const SelRows &r, int nl, long long i) {
-  if (i >= nl) return false;
-  const int32_t *row = r.indices + static_cast<size_t>(i) * (r.g.ndim + 1);
-  if (static_cast<unsigned>(row[0]) >= static_cast<unsigned>(r.g.batch)) return false;
-  for (int d = 0; d < r.g.ndim; ++d)
-    if (static_cast<unsigned>(row[1 + d]) >= static_cast<unsigned>(r.g.dims[d])) return false;
-  return true;
+  return i < nl && level_holds(r.indices + static_cast<size_t>(i) * (r.g.ndim + 1), r.g);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -320,31 +311,6 @@ select_scatter_kernel(SelRows r, const int32_t *__restrict__ blockoff, int nblk,
 
 // -------------------------------------------------------------------------------------------- host side
 
-int elem_bytes_of(int dtype) { return dtype == SPX_F64 ? 8 : dtype == SPX_F32 ? 4 : 2; }
-
-template <int DT, int OP>
-void launch_score(const void *feat, int n, int C, bool vec, bool aligned, const int32_t *n_live, float *score,
-                  hipStream_t s) {
-  constexpr int V = 16 / static_cast<int>(sizeof(typename Elem<DT>::S));
-  const int pieces = vec ? C / V : C;
-  int gshift = 0;
-  while (gshift < 6 && (1 << gshift) < pieces) ++gshift;
-  const unsigned grid = stream_blocks(static_cast<long long>(n) << gshift, kBlock);
-  if (vec)
-    hipLaunchKernelGGL((score_kernel<DT, V, OP>), dim3(grid), dim3(kBlock), 0, s, feat, n, C, pieces, gshift,
-                       aligned ? 1 : 0, n_live, score);
-  else
-    hipLaunchKernelGGL((score_kernel<DT, 1, OP>), dim3(grid), dim3(kBlock), 0, s, feat, n, C, pieces, gshift, 0, n_live,
-                       score);
-}
-
-template <int DT>
-void launch_score_op(int op, const void *feat, int n, int C, bool vec, bool aligned, const int32_t *n_live, float *score,
-                     hipStream_t s) {
-  if (op == kOpMean) launch_score<DT, kOpMean>(feat, n, C, vec, aligned, n_live, score, s);
-  else launch_score<DT, kOpMax>(feat, n, C, vec, aligned, n_live, score, s);
-}
-
 // scratch of a top-k call: the four digits' histograms, the select's state, the blocks' tie counts and their scan
 struct TopkWs {
   int32_t *hist;
@@ -380,15 +346,13 @@ struct SelectWs {
 
 // 0 = ok: the checks every selection call shares, none of which looks at a pointer's target
 int make_select(int n, int ndim, int batch, const int *spatial_h, int invert, const void *rankmap, size_t rankmap_bytes,
-                SelGeom &g) {
+                LevelGeom &g) {
   SPX_CHECK(ndim >= 1 && ndim <= kMaxNdim, "ndim must be in [1,4], got %d", ndim);
   SPX_CHECK(invert == 0 || invert == 1, "invert must be 0 or 1, got %d", invert);
   SPX_CHECK(n >= 0, "bad row count %d", n);
   SPX_CHECK(batch >= 1, "batch must be >= 1, got %d", batch);
   SPX_CHECK(spatial_h, "spatial shape is NULL");
-  g.ndim = ndim;
-  g.batch = batch;
-  for (int d = 0; d < kMaxNdim; ++d) g.dims[d] = d < ndim ? spatial_h[d] : 1;
+  g = LevelGeom(ndim, batch, spatial_h);
   if (rankmap) {
     const size_t W = rank_words(ndim, batch, spatial_h);
     SPX_CHECK(W > 0 && rankmap_bytes >= rank_bytes(W), "rank map too small, or the key space does not fit one (%zu words)", W);
@@ -440,24 +404,22 @@ extern "C" {
 int spx_row_score(const void *feat, int n, int C, int dtype, int op, const int32_t *n_live, float *score,
                   spx_stream_t stream) {
   using namespace spx;
-  SPX_CHECK(dtype == SPX_F32 || dtype == SPX_F16 || dtype == SPX_BF16 || dtype == SPX_F64,
-            "dtype must be f32, f16, bf16 or f64, got %d", dtype);
+  const int eb = float_row_elem(dtype, C);
+  if (eb < 0) return eb;
   SPX_CHECK(op == kOpMean || op == kOpMax, "op must be absmean (0) or absmax (1), got %d", op);
-  SPX_CHECK(C >= 1, "channel count must be >= 1, got %d", C);
   SPX_CHECK(n >= 0, "bad row count %d", n);
-  const int eb = elem_bytes_of(dtype);
-  SPX_CHECK(static_cast<long long>(C) * eb <= 0x7fffffffLL, "row too long");
   if (n == 0) return 0;
   SPX_CHECK(feat && score, "feat / score is NULL");
   SPX_CHECK(aligned_to(feat, eb) && aligned_to(score, 4), "pointer not aligned to its elements");
   const bool vec = (static_cast<long long>(C) * eb) % 16 == 0, aligned = aligned_to(feat, 16);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case SPX_F32: launch_score_op<SPX_F32>(op, feat, n, C, vec, aligned, n_live, score, s); break;
-    case SPX_F16: launch_score_op<SPX_F16>(op, feat, n, C, vec, aligned, n_live, score, s); break;
-    case SPX_BF16: launch_score_op<SPX_BF16>(op, feat, n, C, vec, aligned, n_live, score, s); break;
-    default: launch_score_op<SPX_F64>(op, feat, n, C, vec, aligned, n_live, score, s); break;
-  }
+  dispatch_row(dtype, vec, [&](auto dt, auto v) {
+    const int pieces = C / v, gshift = group_shift(pieces);
+    dispatch_value<kOpMean, kOpMax>(op, [&](auto o) {
+      hipLaunchKernelGGL((score_kernel<dt, v, o>), dim3(stream_blocks(static_cast<long long>(n) << gshift, kBlock)),
+                         dim3(kBlock), 0, s, feat, n, C, pieces, gshift, vec && aligned ? 1 : 0, n_live, score);
+    });
+  });
   SPX_LAUNCH_CHECK();
   count_select(kSelScore);
   return 0;
@@ -521,7 +483,7 @@ size_t spx_select_ws_bytes(int ndim, long long n) {
 int spx_select_count(const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch, const int *spatial_h,
                      const uint8_t *keep, int invert, void *ws, size_t ws_bytes, int *result_h, spx_stream_t stream) {
   using namespace spx;
-  SelGeom g;
+  LevelGeom g;
   if (int rc = make_select(n, ndim, batch, spatial_h, invert, nullptr, 0, g)) return rc;
   SPX_CHECK(result_h && (n == 0 || (indices && keep)), "result_h / indices / keep is NULL");
   SelectWs w(ws, n);
@@ -542,7 +504,7 @@ int spx_select_fill(const int32_t *indices, int n, const int32_t *n_live, int nd
                     void *rankmap, size_t rankmap_bytes, int32_t *violation, const void *ws, size_t ws_bytes,
                     spx_stream_t stream) {
   using namespace spx;
-  SelGeom g;
+  LevelGeom g;
   if (int rc = make_select(n, ndim, batch, spatial_h, invert, rankmap, rankmap_bytes, g)) return rc;
   SPX_CHECK(n_out >= 0 && n_out <= n, "n_out = %d outside [0, rows = %d]", n_out, n);
   SPX_CHECK((n == 0 || (indices && keep && rows)) && (n_out == 0 || (out_indices && src)),
@@ -559,7 +521,7 @@ int spx_select_static(const int32_t *indices, int n, const int32_t *n_live, int 
                       int32_t *src, int32_t *n_out_dev, void *rankmap, size_t rankmap_bytes, int32_t *violation,
                       void *ws, size_t ws_bytes, spx_stream_t stream) {
   using namespace spx;
-  SelGeom g;
+  LevelGeom g;
   if (int rc = make_select(n, ndim, batch, spatial_h, invert, rankmap, rankmap_bytes, g)) return rc;
   SPX_CHECK(n_out_cap > 0 && n_out_dev && out_indices && src, "n_out_cap must be > 0, and n_out_dev / out_indices / src not NULL");
   SPX_CHECK(n == 0 || (indices && keep && rows), "indices / keep / rows is NULL");

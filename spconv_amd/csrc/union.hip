@@ -39,11 +39,6 @@ static_assert(kBlock == kScanThreads, "scan.h's primitives are written for this 
 constexpr int kMaxOps = SPX_UNION_MAX_OPERANDS;
 constexpr int kCounters = 4 + kMaxOps;       // {union size, duplicate flag, live output rows, -, live rows of operand t}
 
-struct UnionGeom {
-  int ndim, batch;
-  int dims[kMaxNdim];
-};
-
 // The operands of a build: index rows, device-side live counts (or null), and where each operand's rows start in the
 // flat row space the kernels are launched over.
 struct UnionOps {
@@ -62,24 +57,15 @@ __device__ __forceinline__ int operand_of(const int (&off)[kMaxOps + 1], int T, 
   return t;
 }
 
-// linear key of row i of operand t (batch-major, last axis fastest), -1 for a dead row
-__device__ __forceinline__ long long key_of(const UnionOps &ops, const UnionGeom &g, int t, int i) {
+// linear key of row i of operand t (level_key of rankmap.h over all axes), -1 for a dead row
+__device__ __forceinline__ long long key_of(const UnionOps &ops, const LevelGeom &g, int t, int i) {
   const int32_t *nl = ops.n_live[t];
   if (nl && i >= *nl) return -1;
-  const int32_t *r = ops.idx[t] + static_cast<size_t>(i) * (g.ndim + 1);
-  const int b = r[0];
-  if (static_cast<unsigned>(b) >= static_cast<unsigned>(g.batch)) return -1;
-  long long key = b;
-  for (int d = 0; d < g.ndim; ++d) {
-    const int v = r[1 + d];
-    if (static_cast<unsigned>(v) >= static_cast<unsigned>(g.dims[d])) return -1;
-    key = key * g.dims[d] + v;
-  }
-  return key;
+  return level_key(ops.idx[t] + static_cast<size_t>(i) * (g.ndim + 1), g, kAllAxes);
 }
 
 __global__ void __launch_bounds__(kBlock)
-union_mark_kernel(UnionOps ops, UnionGeom g, uint8_t *__restrict__ occupied) {
+union_mark_kernel(UnionOps ops, LevelGeom g, uint8_t *__restrict__ occupied) {
   const int row = blockIdx.x * kBlock + threadIdx.x;
   if (row >= ops.off[ops.T]) return;
   const int t = operand_of(ops.off, ops.T, row);
@@ -87,24 +73,11 @@ union_mark_kernel(UnionOps ops, UnionGeom g, uint8_t *__restrict__ occupied) {
   if (key >= 0) occupied[key] = 1;
 }
 
-// Exclusive scan of the prefix pass's block totals by one block (block_scan_loop of scan.h); counters[0] =
-// the union's size, counters[2] = the live output rows = min(size, cap) (cap < 0: no bound).
-__global__ void __launch_bounds__(kBlock)
-union_scan_kernel(const int32_t *__restrict__ cnt, int32_t *__restrict__ off, int len, int cap,
-                  int32_t *__restrict__ counters) {
-  __shared__ int lds_wave[kBlock / 64];
-  const int carry = block_scan_loop(cnt, off, len, lds_wave);
-  if (threadIdx.x == 0) {
-    counters[0] = carry;
-    counters[2] = cap >= 0 && carry > cap ? cap : carry;
-  }
-}
-
 // owner[t * stride + rank] = the highest row of operand t with that key; ranks >= cap are dropped.  DIRECT (static
 // form: row = rank): rows_t and out_indices are written here as well.
 template <bool DIRECT>
 __global__ void __launch_bounds__(kBlock)
-union_claim_kernel(UnionOps ops, UnionGeom g, const uint2 *__restrict__ cells, const int32_t *__restrict__ blockoff,
+union_claim_kernel(UnionOps ops, LevelGeom g, const uint2 *__restrict__ cells, const int32_t *__restrict__ blockoff,
                    int32_t *__restrict__ owner, int stride, int cap, int32_t *__restrict__ counters,
                    int32_t *__restrict__ live_count, int32_t *__restrict__ out_indices) {
   const int row = blockIdx.x * kBlock + threadIdx.x;
@@ -142,7 +115,7 @@ union_claim_kernel(UnionOps ops, UnionGeom g, const uint2 *__restrict__ cells, c
 // them: src[t][j] for every operand t and output row j.  base < 0: output row j holds rank j; base = b: output row j is
 // row j of operand b (which covers the union and holds no coordinate twice: the host has seen both).
 __global__ void __launch_bounds__(kBlock)
-union_fill_kernel(UnionOps ops, UnionGeom g, const uint2 *__restrict__ cells, const int32_t *__restrict__ blockoff,
+union_fill_kernel(UnionOps ops, LevelGeom g, const uint2 *__restrict__ cells, const int32_t *__restrict__ blockoff,
                   const int32_t *__restrict__ owner, int stride, int n_out, int base,
                   int32_t *__restrict__ out_indices, int32_t *__restrict__ src) {
   const long long item = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
@@ -263,17 +236,13 @@ union_add_bwd_kernel(BwdOps ops, const P *__restrict__ dout, int n_out, int piec
 
 // -------------------------------------------------------------------------------------------- host side
 
-// scratch of a build: the byte map, the prefix pass's block totals, the counters, the owner tables [T][n_total]
-struct UnionWs {
-  uint8_t *occupied;
-  int32_t *blockcount, *counters, *owner;
-  int nblk;
+// scratch of a build: the numbering's head (byte map, block totals), the counters, the owner tables [T][n_total]
+struct UnionWs : RankScratch {
+  int32_t *counters, *owner;
   size_t bytes;
   UnionWs(void *ws, size_t W, int T, long long n_total) {
     Carver c(ws);
-    nblk = static_cast<int>(rank_blocks(W));
-    occupied = c.take<uint8_t>(W * 32);
-    blockcount = c.take<int32_t>(nblk > 0 ? nblk : 1);
+    carve(c, W);
     counters = c.take<int32_t>(kCounters);
     owner = c.take<int32_t>(static_cast<size_t>(T) * static_cast<size_t>(n_total > 0 ? n_total : 1));
     bytes = c.off;
@@ -282,7 +251,7 @@ struct UnionWs {
 
 struct Build {
   UnionOps ops;
-  UnionGeom g;
+  LevelGeom g;
   size_t W;
   int n_total;
 };
@@ -295,9 +264,7 @@ int make_build(const int32_t *const *indices_h, const int *n_h, const int32_t *c
   SPX_CHECK(indices_h && n_h && spatial_h, "indices / row counts / spatial shape is NULL");
   b.W = rank_words(ndim, batch, spatial_h);
   SPX_CHECK(b.W > 0 && rankmap && rankmap_bytes >= rank_bytes(b.W), "rank map missing or too small (%zu words)", b.W);
-  b.g.ndim = ndim;
-  b.g.batch = batch;
-  for (int d = 0; d < kMaxNdim; ++d) b.g.dims[d] = d < ndim ? spatial_h[d] : 1;
+  b.g = LevelGeom(ndim, batch, spatial_h);
   long long total = 0;
   b.ops.T = T;
   for (int t = 0; t < kMaxOps; ++t) {
@@ -318,7 +285,7 @@ int make_build(const int32_t *const *indices_h, const int *n_h, const int32_t *c
   return 0;
 }
 
-// fill + mark + prefix + scan: the rank map of the union and its size in counters[0] / [2]
+// fill + mark + number_level: the rank map of the union and its size in counters[0] / [2]
 int number_union(const Build &b, void *rankmap, const UnionWs &w, int32_t *counters, int cap, const FillList *more,
                  hipStream_t s) {
   {
@@ -326,8 +293,7 @@ int number_union(const Build &b, void *rankmap, const UnionWs &w, int32_t *count
     fills.add(w.occupied, b.W * 32, 0u);
     fills.add(w.counters, kCounters * sizeof(int32_t), 0u);
     if (counters != w.counters) fills.add(counters, 3 * sizeof(int32_t), 0u);
-    if (more)
-      for (int j = 0; j < more->jobs.n; ++j) fills.add(more->jobs.ptr[j], more->jobs.words[j] * 4, more->jobs.value[j]);
+    if (more) fills.add(*more);
     SPX_HIP(fills.launch(s));
   }
   if (b.n_total > 0) {
@@ -335,28 +301,9 @@ int number_union(const Build &b, void *rankmap, const UnionWs &w, int32_t *count
     SPX_LAUNCH_CHECK();
     count_union(kUnionMark);
   }
-  hipLaunchKernelGGL(conv4_prefix_kernel, dim3(w.nblk), dim3(kRankThreads), 0, s,
-                     reinterpret_cast<const uint4 *>(w.occupied), static_cast<uint2 *>(rankmap),
-                     static_cast<unsigned>(b.W), w.blockcount);
-  hipLaunchKernelGGL(union_scan_kernel, dim3(1), dim3(kBlock), 0, s, w.blockcount, rank_blockoff(rankmap, b.W), w.nblk, cap,
-                     counters);
-  SPX_LAUNCH_CHECK();
+  SPX_HIP(number_level(w, b.W, rankmap, cap, counters, s));
   count_union(kUnionPrefix);
   return 0;
-}
-
-template <int DT>
-void launch_add_fwd(const AddOps &ops, const int32_t *src, int n_out, int C, bool vec, void *out, const int32_t *n_live,
-                    hipStream_t s) {
-  constexpr int V = 16 / static_cast<int>(sizeof(typename Elem<DT>::S));
-  if (vec) {
-    const int pieces = C / V;
-    hipLaunchKernelGGL((union_add_fwd_kernel<DT, V>), dim3(stream_blocks(static_cast<long long>(n_out) * pieces, kBlock)),
-                       dim3(kBlock), 0, s, ops, src, n_out, pieces, out, n_live);
-  } else {
-    hipLaunchKernelGGL((union_add_fwd_kernel<DT, 1>), dim3(stream_blocks(static_cast<long long>(n_out) * C, kBlock)), dim3(kBlock),
-                       0, s, ops, src, n_out, C, out, n_live);
-  }
 }
 
 template <typename P>
@@ -473,13 +420,11 @@ int spx_union_add_fwd(const void *const *feat_h, const int *n_h, int T, const in
                       void *out, const int32_t *n_live, spx_stream_t stream) {
   using namespace spx;
   SPX_CHECK(T >= 1 && T <= kMaxOps, "sum of %d operands: 1 to %d", T, kMaxOps);
-  SPX_CHECK(dtype == SPX_F32 || dtype == SPX_F16 || dtype == SPX_BF16 || dtype == SPX_F64,
-            "dtype must be f32, f16, bf16 or f64, got %d", dtype);
-  SPX_CHECK(n_out >= 0 && C >= 1 && feat_h && n_h, "bad row count %d / channel count %d / NULL operand list", n_out, C);
+  const int eb = float_row_elem(dtype, C);
+  if (eb < 0) return eb;
+  SPX_CHECK(n_out >= 0 && feat_h && n_h, "bad row count %d / NULL operand list", n_out);
   if (n_out == 0) return 0;
   SPX_CHECK(src && out, "src / out is NULL");
-  const int eb = dtype == SPX_F64 ? 8 : dtype == SPX_F32 ? 4 : 2;
-  SPX_CHECK(static_cast<long long>(C) * eb <= 0x7fffffffLL, "row too long");
   AddOps ops;
   ops.T = T;
   bool vec = (static_cast<long long>(C) * eb) % 16 == 0 && aligned_to(out, 16);
@@ -496,12 +441,11 @@ int spx_union_add_fwd(const void *const *feat_h, const int *n_h, int T, const in
   }
   SPX_CHECK(aligned_to(out, eb), "pointer not aligned to its elements");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case SPX_F32: launch_add_fwd<SPX_F32>(ops, src, n_out, C, vec, out, n_live, s); break;
-    case SPX_F16: launch_add_fwd<SPX_F16>(ops, src, n_out, C, vec, out, n_live, s); break;
-    case SPX_BF16: launch_add_fwd<SPX_BF16>(ops, src, n_out, C, vec, out, n_live, s); break;
-    default: launch_add_fwd<SPX_F64>(ops, src, n_out, C, vec, out, n_live, s); break;
-  }
+  dispatch_row(dtype, vec, [&](auto dt, auto v) {
+    const int pieces = C / v;
+    hipLaunchKernelGGL((union_add_fwd_kernel<dt, v>), dim3(stream_blocks(static_cast<long long>(n_out) * pieces, kBlock)),
+                       dim3(kBlock), 0, s, ops, src, n_out, pieces, out, n_live);
+  });
   SPX_LAUNCH_CHECK();
   count_union(kUnionAddFwd);
   return 0;

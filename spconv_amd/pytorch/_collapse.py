@@ -22,7 +22,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from spconv_amd import _lib
-from spconv_amd.pytorch._rulebook import _DTYPES, _ptr, _require_gpu, _stream, _tag_rank_map, _ws
+from spconv_amd.pytorch._rulebook import _float_code, _ptr, _require_gpu, _stream, _tag_rank_map, _ws
 
 OPS = {"sum": _lib.COLLAPSE_SUM, "mean": _lib.COLLAPSE_MEAN, "max": _lib.COLLAPSE_MAX}
 
@@ -118,17 +118,11 @@ def _op(reduce: str) -> int:
         raise ValueError(f"sparse_collapse: reduce must be 'sum', 'mean' or 'max', got {reduce!r}") from None
 
 
-def _dtype(t: torch.Tensor) -> int:
-    if t.is_quantized or t.dtype not in _DTYPES:
-        raise NotImplementedError(f"sparse_collapse: features must be float16, bfloat16, float32 or float64, got {t.dtype}")
-    return _DTYPES[t.dtype]
-
-
 def fwd(feat: torch.Tensor, c: Collapse, reduce: str = "sum", n_live: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[r] = reduce of feat[list[offsets[r] : offsets[r + 1]]] in list order (spx_collapse_fwd); rows at or beyond
     *n_live are zeros."""
     _require_gpu(feat, "features")
-    op, dt = _op(reduce), _dtype(feat)
+    op, dt = _op(reduce), _float_code(feat, "sparse_collapse")
     feat = feat.contiguous()
     C = int(feat.shape[1])
     out = torch.empty((c.n_out, C), dtype=feat.dtype, device=feat.device)
@@ -143,7 +137,7 @@ def bwd(dout: torch.Tensor, c: Collapse, reduce: str, feat: Optional[torch.Tenso
         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Gradient of `fwd` with respect to feat: sum -> din[i] = dout[rows[i]] (spx_union_add_bwd, one operand); mean and
     max -> spx_collapse_bwd (max needs the forward's feat and out).  Dead and dropped rows get zeros."""
-    op, dt = _op(reduce), _dtype(dout)
+    op, dt = _op(reduce), _float_code(dout, "sparse_collapse")
     dout = dout.contiguous()
     if reduce == "sum":
         from spconv_amd.pytorch import _union

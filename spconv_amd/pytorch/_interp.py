@@ -26,7 +26,7 @@ from torch.autograd.function import once_differentiable
 from spconv_amd import _lib
 from spconv_amd.pytorch import _pointvoxel
 from spconv_amd.pytorch._pointvoxel import PointGroups
-from spconv_amd.pytorch._rulebook import _DTYPES, _ptr, _rankmap_of, _require_gpu, _stream, _ws
+from spconv_amd.pytorch._rulebook import _check_count, _float_code, _ptr, _rankmap_of, _require_gpu, _stream, _ws
 
 
 class PointCorners(NamedTuple):
@@ -57,11 +57,6 @@ def _geometry(vsize_xyz: Sequence[float], coors_range_xyz: Sequence[float]):
         raise ValueError(f"point_corners: voxel sizes must be positive, got {list(vsize_xyz)}")
     vsize, _, _, coors_range = calc_point2voxel_meta_data(list(vsize_xyz), list(coors_range_xyz))
     return ndim, vsize, coors_range
-
-
-def _check_count(t: Optional[torch.Tensor], what: str) -> None:
-    if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.numel() >= 1):
-        raise ValueError(f"point_corners: {what} is a CUDA int32 tensor of one element")
 
 
 def level_rankmap(indices: torch.Tensor, batch_size: int, spatial_shape) -> Optional[torch.Tensor]:
@@ -128,9 +123,9 @@ def point_corners(points: torch.Tensor, batch_ids: Optional[torch.Tensor], x, vs
         if batch_ids.shape != (N,) or batch_ids.dtype != torch.int32 or not batch_ids.is_cuda:
             raise ValueError("point_corners: batch_ids is a CUDA int32 tensor [N]")
         batch_ids = batch_ids.contiguous()
-    _check_count(n_points, "n_points")
+    _check_count(n_points, "point_corners: n_points")
     n_live = getattr(x, "n_live_dev", None)
-    _check_count(n_live, "n_live")
+    _check_count(n_live, "point_corners: n_live")
     if with_groups is None:
         with_groups = bool(x.features.requires_grad and torch.is_grad_enabled())
     dev = points.device
@@ -148,15 +143,9 @@ def point_corners(points: torch.Tensor, batch_ids: Optional[torch.Tensor], x, vs
     return PointCorners(rows, weights, groups, n, n_points, n_live)
 
 
-def _interp_dtype(t: torch.Tensor, what: str) -> int:
-    if t.is_quantized or t.dtype not in _DTYPES:
-        raise NotImplementedError(f"{what}: features must be float16, bfloat16, float32 or float64, got {t.dtype}")
-    return _DTYPES[t.dtype]
-
-
 def interp_fwd(vfeat: torch.Tensor, corners: PointCorners) -> torch.Tensor:
     """out[i] = sum_c weights[i, c] * vfeat[rows[i, c]] (spx_interp_fwd: one launch)."""
-    dt = _interp_dtype(vfeat, "voxels_to_points_trilinear")
+    dt = _float_code(vfeat, "voxels_to_points_trilinear")
     vfeat = vfeat.contiguous()
     N, K = (int(v) for v in corners.rows.shape)
     n, C = int(vfeat.shape[0]), int(vfeat.shape[1])
@@ -170,7 +159,7 @@ def interp_fwd(vfeat: torch.Tensor, corners: PointCorners) -> torch.Tensor:
 def interp_bwd(dout: torch.Tensor, corners: PointCorners) -> torch.Tensor:
     """dvfeat[v] = sum over the entries e of voxel v's group of weights_flat[e] * dout[e // K], in ascending e
     (spx_interp_bwd: one launch, no atomics); zeros for an empty group and for rows at or beyond *n_live."""
-    dt = _interp_dtype(dout, "voxels_to_points_trilinear")
+    dt = _float_code(dout, "voxels_to_points_trilinear")
     dout = dout.contiguous()
     N, K = (int(v) for v in corners.rows.shape)
     n, C = corners.num_voxels, int(dout.shape[1])
@@ -207,7 +196,7 @@ def voxels_to_points_trilinear(vfeat: torch.Tensor, corners: PointCorners) -> to
     Differentiable in vfeat (a segment sum over the transposed corner list, in ascending entry: identical run to run);
     there is no gradient with respect to the points or the weights."""
     _require_gpu(vfeat, "voxel features")
-    _interp_dtype(vfeat, "voxels_to_points_trilinear")
+    _float_code(vfeat, "voxels_to_points_trilinear")
     if vfeat.dim() != 2 or vfeat.shape[0] != corners.num_voxels:
         raise ValueError(f"voxels_to_points_trilinear: one row per voxel ([{corners.num_voxels}, C]), got "
                          f"{tuple(vfeat.shape)}")

@@ -21,7 +21,7 @@ from torch.autograd.function import once_differentiable
 
 from spconv_amd import _lib
 from spconv_amd.pytorch import _collapse
-from spconv_amd.pytorch._rulebook import _DTYPES, _ptr, _require_gpu, _stream, _ws
+from spconv_amd.pytorch._rulebook import _float_code, _ptr, _require_gpu, _stream, _ws
 
 _OUT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 _BITS = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
@@ -77,11 +77,6 @@ def point_groups(pc_voxel_id: torch.Tensor, num_voxels: int, n_points: Optional[
     return PointGroups(rows, offsets, lst, int(num_voxels), n_points, n_live)
 
 
-def _reduce_dtype(t: torch.Tensor, what: str) -> None:
-    if t.is_quantized or t.dtype not in _DTYPES:
-        raise NotImplementedError(f"{what}: features must be float16, bfloat16, float32 or float64, got {t.dtype}")
-
-
 def _check_rows(feat: torch.Tensor, groups: PointGroups, what: str) -> None:
     if feat.dim() != 2 or feat.shape[0] != groups.rows.shape[0]:
         raise ValueError(f"{what}: one feature row per point ([{groups.rows.shape[0]}, C]), got {tuple(feat.shape)}")
@@ -113,7 +108,7 @@ def points_to_voxels(feat: torch.Tensor, groups: PointGroups, reduce: str = "max
     if reduce not in _collapse.OPS:
         raise ValueError(f"points_to_voxels: reduce must be 'sum', 'mean' or 'max', got {reduce!r}")
     _require_gpu(feat, "features")
-    _reduce_dtype(feat, "points_to_voxels")
+    _float_code(feat, "points_to_voxels")
     _check_rows(feat, groups, "points_to_voxels")
     if groups.offsets is None:
         raise ValueError("points_to_voxels: these groups carry rows only; build them with point_groups")
@@ -165,7 +160,7 @@ def voxels_to_points(vfeat: torch.Tensor, groups: PointGroups, invalid_value=0) 
     with torch.cuda.device(vfeat.device):
         if not (vfeat.requires_grad and torch.is_grad_enabled()):
             return gather_rows(vfeat, groups.rows, invalid_value)
-        _reduce_dtype(vfeat, "voxels_to_points (with a gradient)")
+        _float_code(vfeat, "voxels_to_points (with a gradient)")
         if groups.offsets is None:
             raise ValueError("voxels_to_points: a gradient needs full groups; build them with point_groups")
         return VoxelsToPointsFunction.apply(vfeat, groups, invalid_value)

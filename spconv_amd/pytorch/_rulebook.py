@@ -77,6 +77,20 @@ def _dtype_code(t: torch.Tensor, codes=_DTYPES, what: str = "feature") -> int:
         raise NotImplementedError(f"unsupported {what} dtype {t.dtype}") from None
 
 
+def _float_code(t: torch.Tensor, what: str) -> int:
+    """dtype code of the feature rows a row op takes (the union, collapse, select, interp and point-voxel wrappers):
+    the four floating dtypes, nothing quantized."""
+    if t.is_quantized or t.dtype not in _DTYPES:
+        raise NotImplementedError(f"{what}: features must be float16, bfloat16, float32 or float64, got {t.dtype}")
+    return _DTYPES[t.dtype]
+
+
+def _check_count(t: Optional[torch.Tensor], what: str) -> None:
+    """A device-side count (n_live, n_points) is None or a CUDA int32 tensor whose first element is read."""
+    if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.numel() >= 1):
+        raise ValueError(f"{what} is a CUDA int32 tensor of one element")
+
+
 def _kv(ksize) -> int:
     return int(functools.reduce(lambda a, b: a * b, ksize, 1))
 

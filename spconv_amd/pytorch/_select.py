@@ -25,7 +25,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from spconv_amd import _lib
-from spconv_amd.pytorch._rulebook import _DTYPES, _ptr, _require_gpu, _stream, _tag_rank_map, _ws
+from spconv_amd.pytorch._rulebook import _check_count, _float_code, _ptr, _require_gpu, _stream, _tag_rank_map, _ws
 
 OPS = {"absmean": _lib.SCORE_ABSMEAN, "absmax": _lib.SCORE_ABSMAX}
 
@@ -43,12 +43,6 @@ class Select(NamedTuple):
     live_rows: Optional[int]
 
 
-def _dtype(t: torch.Tensor, what: str) -> int:
-    if t.is_quantized or t.dtype not in _DTYPES:
-        raise NotImplementedError(f"{what}: features must be float16, bfloat16, float32 or float64, got {t.dtype}")
-    return _DTYPES[t.dtype]
-
-
 def _check_indices(indices: torch.Tensor, ndim: int, what: str) -> None:
     _require_gpu(indices, "indices")
     if indices.dtype != torch.int32:
@@ -57,21 +51,16 @@ def _check_indices(indices: torch.Tensor, ndim: int, what: str) -> None:
         raise ValueError(f"{what}: indices is a CUDA int32 tensor [n, ndim + 1]")
 
 
-def _check_n_live(n_live: Optional[torch.Tensor], what: str) -> None:
-    if n_live is not None and not (n_live.is_cuda and n_live.dtype == torch.int32 and n_live.numel() >= 1):
-        raise ValueError(f"{what}: n_live is a CUDA int32 tensor of one element")
-
-
 def row_score(features: torch.Tensor, op: str = "absmean", n_live: Optional[torch.Tensor] = None) -> torch.Tensor:
     """score[i] = mean ("absmean") or maximum ("absmax") of |features[i, :]| as fp32, -inf for rows at or beyond
     *n_live (spx_row_score: one launch, a summation order that depends on C and the dtype only)."""
     _require_gpu(features, "features")
-    dt = _dtype(features, "row_score")
+    dt = _float_code(features, "row_score")
     if op not in OPS:
         raise ValueError(f"row_score: op must be 'absmean' or 'absmax', got {op!r}")
     if features.dim() != 2 or features.shape[1] < 1:
         raise ValueError("row_score: features is [n, C] with C >= 1")
-    _check_n_live(n_live, "row_score")
+    _check_count(n_live, "row_score: n_live")
     feat = features.detach().contiguous()
     n, C = int(feat.shape[0]), int(feat.shape[1])
     with torch.cuda.device(feat.device):
@@ -115,7 +104,7 @@ def topk_flags(score: torch.Tensor, k=None, ratio=None, indices: Optional[torch.
         if indices.shape[0] != n or not 1 <= ndim <= 4 or B < 1:
             raise ValueError("topk_mask: indices is [n, ndim + 1] with ndim in [1, 4], batch_size >= 1")
         indices = indices.contiguous()
-    _check_n_live(n_live, "topk_mask")
+    _check_count(n_live, "topk_mask: n_live")
     L = _lib.load()
     with torch.cuda.device(score.device):
         keep = torch.empty((n,), dtype=torch.uint8, device=score.device)
@@ -144,7 +133,7 @@ def select_build(indices: torch.Tensor, batch_size: int, spatial_shape: Sequence
         keep = keep.view(torch.uint8)
     elif keep.dtype != torch.uint8:
         raise ValueError(f"sparse_select: keep must be bool or uint8, got {keep.dtype}")
-    _check_n_live(n_live, "sparse_select")
+    _check_count(n_live, "sparse_select: n_live")
     with torch.cuda.device(indices.device):         # (kernels, fills and scratch belong to the device of the data)
         return _build(indices.contiguous(), int(batch_size), spatial_shape, keep.contiguous(), bool(invert), n_live,
                       static_num_out, rank_map, violation)
@@ -189,7 +178,7 @@ def _build(indices, B, spatial_shape, keep, invert, n_live, static_num_out, rank
 def fwd(feat: torch.Tensor, s: Select) -> torch.Tensor:
     """out[r] = feat[src[r]], zeros where src[r] < 0 (spx_voxel_to_point with a zero fill): a row keeps its bits."""
     _require_gpu(feat, "features")
-    _dtype(feat, "sparse_select")
+    _float_code(feat, "sparse_select")
     feat = feat.contiguous()
     C = int(feat.shape[1])
     if s.n_out == 0 or C == 0:

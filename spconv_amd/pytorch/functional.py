@@ -383,13 +383,11 @@ def sparse_collapse(x, axes, reduce="sum", static_num_out=None, owner=None):
     suffices), nothing read back, n_live_dev = the live rows found; `owner` (the calling module) keeps the
     device-side counters {found, 0, live} of its last call in `_static_n_out_dev`."""
     from spconv_amd.pytorch import _collapse
-    from spconv_amd.pytorch._rulebook import _require_gpu
+    from spconv_amd.pytorch._rulebook import _float_code, _require_gpu
     from spconv_amd.pytorch.core import SparseConvTensor
     feat = x.features
     _require_gpu(feat, "features")
-    if feat.is_quantized or feat.dtype not in _UNION_DTYPES:
-        raise NotImplementedError(f"sparse_collapse: features must be float16, bfloat16, float32 or float64, "
-                                  f"got {feat.dtype}")
+    _float_code(feat, "sparse_collapse")
     if reduce not in _collapse.OPS:
         raise ValueError(f"sparse_collapse: reduce must be 'sum', 'mean' or 'max', got {reduce!r}")
     n_live_in = getattr(x, "n_live_dev", None)
@@ -446,11 +444,10 @@ class SparseSelectFunction(Function):
 
 
 def _select_checks(x, what):
-    from spconv_amd.pytorch._rulebook import _require_gpu
+    from spconv_amd.pytorch._rulebook import _float_code, _require_gpu
     feat = x.features
     _require_gpu(feat, "features")
-    if feat.is_quantized or feat.dtype not in _UNION_DTYPES:
-        raise NotImplementedError(f"{what}: features must be float16, bfloat16, float32 or float64, got {feat.dtype}")
+    _float_code(feat, what)
     _require_gpu(x.indices, "indices")
     if x.indices.dtype != torch.int32:
         raise NotImplementedError(f"{what}: indices must be int32, got {x.indices.dtype}")

@@ -215,6 +215,41 @@ def test_forward_long_groups(cuda, dtype):
                          dtype, 2.0 ** -24, name="mean")
 
 
+def group_lengths_scene():
+    """columns of 1 to 9 rows on a 10 x 4 x 4 grid collapsed along its first axis, the rows in a shuffled order; with
+    room for 12 output rows the static form adds three groups of length 0"""
+    shape, cap = [10, 4, 4], 12
+    rows = [(0, z, k // 4, k % 4) for k in range(9) for z in range(k + 1)]
+    idx = np.array(rows, np.int32)[np.random.default_rng(5).permutation(len(rows))]
+    ref = rc.build(idx, 1, shape, (0,), None, cap)
+    assert sorted(np.diff(ref.offsets).tolist()) == list(range(1, 10)) and ref.live == 9
+    return idx, shape, cap, ref
+
+
+@pytest.mark.parametrize("C", [3, 8])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float32], ids=lambda v: str(v).replace("torch.", ""))
+def test_forward_every_group_length_0_to_9(cuda, dtype, C):
+    """the walk fetches four list entries at a time: every group length from 0 to 9 crosses each of its boundaries
+    (an empty group, a partial first round, exactly one and two rounds, a partial last round)"""
+    from spconv_amd.pytorch import _collapse
+    idx, shape, cap, ref = group_lengths_scene()
+    c = native_build(cuda, idx, 1, shape, (0,), cap=cap)
+    check_static(c, ref, idx.shape[0], cap)
+    feat = rc.features(idx.shape[0], C, dtype, 70 + C)
+    dev = feat.to(cuda)
+    mean, A, lens = rc.mean_f64(feat, ref)
+    # with the live count the tail rows are skipped; without it they are walked as groups of length 0 (flat offsets)
+    for n_live in (c.n_out_dev[2:3], None):
+        for op in OPS:
+            out = _collapse.fwd(dev, c, op, n_live)
+            assert tuple(out.shape) == (cap, C) and not bool(out[ref.live:].any()), op
+            if op != "mean":
+                assert torch.equal(bits(out[:ref.live]), bits(rc.reduce(feat, ref, op))), op
+            else:
+                assert_close_abs_sum(out[:ref.live].double().cpu().numpy(), mean, A * (lens[:, None] + 2), dtype,
+                                     2.0 ** -24, name=f"mean {dtype} C={C}")
+
+
 # ---------------------------------------------------------------------------------------- backward
 def mean_bwd_bound(ref_din, dtype):
     name = str(dtype).replace("torch.", "")

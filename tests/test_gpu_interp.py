@@ -447,6 +447,40 @@ def test_backward_bit_for_bit_and_identical_run_to_run(cuda, main, C, name):
     assert bool((grads[0][sc.long_row] != 0).all())
 
 
+def group_lengths_table():
+    """a corner table of 24 points over 10 voxels in which voxel v is a corner of exactly v points (v = 0 .. 9), the
+    corners of a point all different voxels, the other slots empty"""
+    n, N, K = 10, 24, 8
+    rows = np.full((N, K), -1, np.int32)
+    used = np.zeros(N, np.int64)
+    for v in range(n):
+        for t in range(v):
+            i = (3 * v + t) % N
+            rows[i, used[i]] = v
+            used[i] += 1
+    w = np.random.default_rng(12).random((N, K)).astype(np.float32) * (rows >= 0)
+    assert np.diff(ri.transposed(rows, n)[0]).tolist() == list(range(n))
+    return n, rows, w
+
+
+@pytest.mark.parametrize("C", [3, 8])
+@pytest.mark.parametrize("name", ["f16", "f32"])
+def test_backward_every_group_length_0_to_9(cuda, name, C):
+    """the walk fetches four list entries at a time: every group length from 0 to 9 crosses each of its boundaries
+    (an empty group, a partial first round, exactly one and two rounds, a partial last round)"""
+    from spconv_amd.pytorch import _interp
+    n, rows, w = group_lengths_table()
+    dev_rows = torch.from_numpy(rows).to(cuda)
+    groups = _interp.corner_groups(dev_rows, n)
+    np.testing.assert_array_equal(groups.offsets.cpu().numpy(), ri.transposed(rows, n)[0])
+    c = _interp.PointCorners(dev_rows, torch.from_numpy(w).to(cuda), groups, n)
+    host, ddout = features(rows.shape[0], C, name, 400 + C, cuda)
+    got = _interp.interp_bwd(ddout, c)
+    want = torch.from_numpy(ri.backward(raised(host, name), rows, w, n)).to(DTYPES[name])
+    np.testing.assert_array_equal(bits(got), bits(want))
+    assert bool((got[0] == 0).all()) and bool((got[1:] != 0).any(dim=1).all())
+
+
 @pytest.mark.parametrize("name,C", [("f32", 8), ("f16", 20)])
 def test_backward_gives_zeros_to_rows_behind_the_live_count_whose_groups_are_not_empty(cuda, name, C):
     """corners and groups built WITHOUT a live count find the ghost rows; the backward is then handed a count"""

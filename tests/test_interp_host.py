@@ -157,12 +157,13 @@ def test_unsupported_dtypes_are_refused_in_the_wording_of_the_reductions():
     from spconv_amd.pytorch import _interp, _pointvoxel
     t = torch.zeros((3, 4), dtype=torch.int32)
     with pytest.raises(NotImplementedError) as mine:
-        _interp._interp_dtype(t, "op")
+        _interp._float_code(t, "op")
     with pytest.raises(NotImplementedError) as theirs:
-        _pointvoxel._reduce_dtype(t, "op")
+        _pointvoxel._float_code(t, "op")
     assert str(mine.value) == str(theirs.value)
+    assert str(mine.value) == "op: features must be float16, bfloat16, float32 or float64, got torch.int32"
     for dt in (torch.float16, torch.bfloat16, torch.float32, torch.float64):
-        _interp._interp_dtype(torch.zeros((1, 1), dtype=dt), "op")
+        _interp._float_code(torch.zeros((1, 1), dtype=dt), "op")
 
 
 def test_new_names_and_signatures():
