@@ -119,6 +119,10 @@ int spx_set_option(const char *name_h, int value);
  *                                                  spx_topk_flags (hist and pick once per 8-bit digit: four each; ties:
  *                                                  the blocks' tie counts and their scan, counted once); the passes of a
  *                                                  selection build (map: spx_rankmap_from_sorted over the result)
+ *   serialize/keys, serialize/sort, serialize/offsets, serialize/plan, serialize/bwd
+ *                                                  voxel serialisation: calls of spx_curve_keys; sorted orders of
+ *                                                  spx_serialize (one per key row, none for n = 0); its offsets launch;
+ *                                                  calls of spx_patch_plan and of spx_patch_rows_bwd
  * COUT in {16, 32, 64, 128, 256}, NKS in {1, 2}, PK in {1, 2, 4, 8, 16, 32}.  A well-formed key of an instance that is
  * never built counts 0; anything else is unknown.
  * float64 (SPX_F64) has a family and keys of its own, outside the dt vocabulary above:
@@ -1154,6 +1158,72 @@ int spx_select_static(const int32_t *indices, int n, const int32_t *n_live, int 
                       const uint8_t *keep, int invert, int n_out_cap, int32_t *out_indices, int32_t *rows,
                       int32_t *src, int32_t *n_out_dev, void *rankmap, size_t rankmap_bytes, int32_t *violation,
                       void *ws, size_t ws_bytes, spx_stream_t stream);
+
+/* ---- voxel serialisation (csrc/serialize.hip) --------------------------------------------------------------
+ * The rows of a sparse level ordered along space-filling curves and cut into fixed-size patches: what the serialised
+ * point / voxel transformers (Point Transformer V3, OctFormer, FlatFormer-style blocks) do between the SubM layers
+ * they keep for positional encoding.  Stands where a torch composite would: a Hilbert encoder written as a Python loop
+ * over bits and axes, argsort on int64, a scatter for the inverse, bincount + cumsum, padding arithmetic with read-backs,
+ * none of it aware of dead rows or a device-side live count.  Every call: the caller allocates, nothing is read back,
+ * every grid depends on host-known sizes only (hipGraph-safe), and the argument checks that need no pointer come
+ * before any pointer is looked at.  Every output is an integer or a moved row: a host loop reproduces it bit for bit.
+ *
+ * KEYS.  spx_curve_keys: indices = int32 [n, ndim + 1] (batch index first), ndim in [1, 4]; n_live = NULL or a device
+ * int32; depth in [1, 16] = bits per axis; orders_h = HOST array of n_orders (1 .. 8) order codes SPX_ORDER_*; axes_h
+ * = HOST array [ndim], a permutation of the spatial axes 0 .. ndim - 1 (axis a = index column a + 1): the coordinates
+ * X[0 .. ndim) a curve takes, X[0] the most significant.  The _TRANS orders swap X[0] and X[1] (ndim = 1: no change).
+ * keys = uint64 [n_orders, n]: key[k, i] = (batch << (ndim * depth)) | code_k(X).  Requires ndim * depth +
+ * bit_length(batch) <= 63.
+ *   SPX_ORDER_Z: bit b of X[j] lands at bit b * ndim + (ndim - 1 - j).
+ *   SPX_ORDER_HILBERT: Skilling's AxesToTranspose (AIP Conf. Proc. 707, 2004) on X -- the inverse-undo loop from Q =
+ *   2^(depth - 1) down to 2, then the Gray encode -- and the result interleaved as above.  The code of a cell at depth
+ *   d - 1 is the code of any of its children at depth d shifted right by ndim.
+ *   A row is DEAD when its batch index is outside [0, batch), a coordinate is outside [0, 2^depth), or it lies at or
+ *   beyond *n_live: its key is all 64 bits set in every order (-1 when read as int64).  One launch, one thread per row.
+ *
+ * ORDERS.  spx_serialize: keys as above (key_bits = ndim * depth + bit_length(batch) bits in use, batch_shift = ndim *
+ * depth); order int32 [n_orders, n]: order[k, t] = the row with the t-th smallest key of row k, equal keys in ascending
+ * row (a stable LSD radix sort over exactly the key_bits low bits, 8- or 9-bit digits, three launches per digit), so
+ * dead rows follow every live row in ascending row; inverse int32 [n_orders, n]: inverse[k, order[k, t]] = t, a full
+ * permutation; offsets int32 [batch + 1]: offsets[b] = live rows with a batch index below b (a bisection of the first
+ * order), offsets[batch] = live rows.  Keys of at most 32 bits are narrowed by one launch and sorted by the 32-bit
+ * sort of spx_mask_argsort, the inverse then takes one launch for all orders; wider keys take the 64-bit passes, every
+ * order in the same three launches per digit, whose last scatter writes the inverse.  n = 0 writes offsets only.
+ *   spx_serialize_ws_bytes: its scratch; monotone in n, 0 for arguments that are refused (n < 0, n_orders outside
+ *   [1, 8], key_bits outside [1, 63]).
+ *
+ * PATCHES.  spx_patch_plan: order = ONE row of the above, int32 [n]; K = patch_size >= 1; the layout has P_cap = n / K +
+ * batch patches of K slots (an upper bound of the sum over scenes of ceil(c_b / K), c_b = offsets[b + 1] - offsets[b]).
+ * Scene b starts on a patch boundary and fills ceil(c_b / K) patches; slot j < c_b of the scene holds order[offsets[b]
+ * + j].  The tail slots of a scene's last patch hold -1 (SPX_PAD_MASK), or (SPX_PAD_BORROW) the row held K slots earlier
+ * when c_b >= K and -1 otherwise.  Outputs: patch_rows [P_cap, K]; patch_rows_canon [P_cap, K] = the same with borrowed
+ * slots as -1; row_slot [n] = the canonical slot of a row, -1 for a dead row; row_slot2 [n] = its one borrowed slot or
+ * -1; patch_scene [P_cap] = batch index, -1 for patches not in use; n_patches_dev [1] = patches in use.  Two launches:
+ * a prefix over the scenes by one workgroup, then one thread per slot; every element written exactly once.  Requires
+ * P_cap * K < 2^31.  spx_patch_plan_ws_bytes: its scratch; 0 for arguments that are refused.
+ *
+ * ROWS.  Rows into patches and back are spx_voxel_to_point over patch_rows / row_slot (gradient of the way back:
+ * over patch_rows_canon), with a zero fill.  spx_patch_rows_bwd is the gradient of the way in: g = [slots, C] (slots =
+ * P_cap * K), g_feat[r, :] = g[row_slot[r], :] + g[row_slot2[r], :], the canonical term first, added in fp32 (fp64 for
+ * SPX_F64) and rounded once; a row with one slot keeps that slot's bits, a dead row gets zeros.  16-byte pieces where
+ * the row and the pointers allow, element by element otherwise.  One launch, no atomics, identical run to run. */
+#define SPX_ORDER_Z 0
+#define SPX_ORDER_Z_TRANS 1
+#define SPX_ORDER_HILBERT 2
+#define SPX_ORDER_HILBERT_TRANS 3
+#define SPX_PAD_MASK 0
+#define SPX_PAD_BORROW 1
+int spx_curve_keys(const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch, int depth, int n_orders,
+                   const int *orders_h, const int *axes_h, uint64_t *keys, spx_stream_t stream);
+size_t spx_serialize_ws_bytes(int n, int n_orders, int key_bits);
+int spx_serialize(const uint64_t *keys, int n, int n_orders, int key_bits, int batch, int batch_shift, int32_t *order,
+                  int32_t *inverse, int32_t *offsets, void *ws, size_t ws_bytes, spx_stream_t stream);
+size_t spx_patch_plan_ws_bytes(int n, int batch, int patch_size);
+int spx_patch_plan(const int32_t *order, const int32_t *offsets, int n, int batch, int patch_size, int pad,
+                   int32_t *patch_rows, int32_t *patch_rows_canon, int32_t *row_slot, int32_t *row_slot2,
+                   int32_t *patch_scene, int32_t *n_patches_dev, void *ws, size_t ws_bytes, spx_stream_t stream);
+int spx_patch_rows_bwd(const void *g, int slots, const int32_t *row_slot, const int32_t *row_slot2, int n, int C,
+                       int dtype, void *g_feat, spx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -201,6 +201,15 @@ SIGNATURES = {
                                        ctypes.c_int, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp]),
     "spx_select_static": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, c_int_p, vp, ctypes.c_int,
                                          ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp]),
+    "spx_curve_keys": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      c_int_p, c_int_p, vp, vp]),
+    "spx_serialize_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "spx_serialize": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp,
+                                     vp, ctypes.c_size_t, vp]),
+    "spx_patch_plan_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "spx_patch_plan": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp,
+                                      vp, vp, ctypes.c_size_t, vp]),
+    "spx_patch_rows_bwd": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
 }
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_I8, DTYPE_F64 = 0, 1, 2, 3, 4

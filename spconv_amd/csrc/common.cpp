@@ -39,6 +39,7 @@ std::atomic<long long> g_union_launches[kUnionCount];
 std::atomic<long long> g_collapse_launches[kCollapseCount];
 std::atomic<long long> g_pointvoxel_launches[kPvCount];
 std::atomic<long long> g_interp_launches[kInterpCount];
+std::atomic<long long> g_serialize_launches[kSerCount];
 std::atomic<long long> g_select_launches[kSelInstCount];
 std::atomic<long long> g_pool_launches[kPoolCount];
 std::atomic<long long> g_rulebook_launches[kRbCount];
@@ -169,6 +170,15 @@ std::atomic<long long> *pointvoxel_counter(const char *key) {
   return nullptr;
 }
 
+// counter of a voxel-serialisation key (spx_launch_count), or null
+std::atomic<long long> *serialize_counter(const char *key) {
+  static const char *names[kSerCount] = {"serialize/keys", "serialize/sort", "serialize/offsets", "serialize/plan",
+                                         "serialize/bwd"};
+  for (int i = 0; i < kSerCount; ++i)
+    if (strcmp(key, names[i]) == 0) return &g_serialize_launches[i];
+  return nullptr;
+}
+
 // counter of a trilinear-devoxelisation key (spx_launch_count), or null
 std::atomic<long long> *interp_counter(const char *key) {
   static const char *names[kInterpCount] = {"interp/corners_ranked", "interp/corners_hash", "interp/fwd", "interp/bwd"};
@@ -263,6 +273,7 @@ long long spx_launch_count(const char *family_h) {
   if (std::atomic<long long> *c = spx::collapse_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pointvoxel_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::interp_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::serialize_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::select_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pool_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::rulebook_counter(family_h)) return c->load(std::memory_order_relaxed);

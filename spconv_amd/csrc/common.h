@@ -221,6 +221,13 @@ enum InterpInst { kInterpCornersRanked = 0, kInterpCornersHash, kInterpFwd, kInt
 extern std::atomic<long long> g_interp_launches[kInterpCount];
 inline void count_interp(InterpInst i) { g_interp_launches[i].fetch_add(1, std::memory_order_relaxed); }
 
+// voxel serialisation (serialize.hip): keys once per spx_curve_keys call, sort once per sorted order, offsets once per
+// spx_serialize call, plan once per spx_patch_plan call, bwd once per spx_patch_rows_bwd call.
+// Keys serialize/keys, serialize/sort, serialize/offsets, serialize/plan, serialize/bwd.
+enum SerializeInst { kSerKeys = 0, kSerSort, kSerOffsets, kSerPlan, kSerBwd, kSerCount };
+extern std::atomic<long long> g_serialize_launches[kSerCount];
+inline void count_serialize(SerializeInst i) { g_serialize_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
 // voxel pruning (select.hip): one counter per pass, counted once per launch (a top-k call counts hist and pick four
 // times each: once per digit).
 // Keys select/score, select/hist, select/pick, select/ties, select/flags, select/count, select/scan, select/scatter,
@@ -263,5 +270,10 @@ namespace spx {
 // stable LSD radix argsort behind spx_mask_argsort (rowsort.hip)
 size_t radix_argsort_ws_bytes(int n);
 int radix_argsort(const uint32_t *keys, int n, int nbits, int32_t *order_out, void *ws, hipStream_t s);
+// the same over 64-bit keys (1 .. 64 bits), `sorts` independent sorts of n keys each ([sorts, n] arrays) pass by pass
+// together; inverse_out (or null): inverse_out[k, order_out[k, t]] = t
+size_t radix_argsort64_ws_bytes(int n, int sorts);
+int radix_argsort64(const uint64_t *keys, int n, int sorts, int nbits, int32_t *order_out, int32_t *inverse_out, void *ws,
+                    hipStream_t s);
 
 }  // namespace spx

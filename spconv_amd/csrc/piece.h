@@ -2,7 +2,8 @@
 // piece a lane moves, the index arithmetic of the group reductions' segment walk, and the host side of a row launch: the checks of a
 // floating feature row, the way from (dtype, vec) to a kernel instance, the lanes of a group, the bits of a sort key,
 // the grid of a streaming launch.  Shared by the translation units that merge, reduce, score, interpolate or decorate
-// rows (union.hip, collapse.hip, select.hip, interp.hip, pointvoxel.hip); every definition has internal linkage.
+// rows (union.hip, collapse.hip, select.hip, interp.hip, pointvoxel.hip, serialize.hip); every definition has internal
+// linkage.
 #pragma once
 #include <initializer_list>
 #include <type_traits>

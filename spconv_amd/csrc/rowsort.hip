@@ -110,6 +110,107 @@ radix_scatter_kernel(const uint32_t *__restrict__ keys_in, const int32_t *__rest
   }
 }
 
+// ---- the same two passes over 64-bit keys (radix_argsort64: the curve keys of serialize.hip) --------------------------
+// A digit is read from anywhere in the 64 bits; the scan between the passes is the same.  blockIdx.y = one of several
+// independent sorts of n entries each (arrays [sorts, n], histograms [sorts, R, nblk]): a pass over all of them is
+// three launches, where a launch per sort sits at its latency floor.  The last pass of a sort writes no keys
+// (`keys_out` null) and may write the inverse permutation: inverse[row] = its position.
+template <int BITS>
+__global__ void __launch_bounds__(1 << BITS)
+radix_count64_kernel(const uint64_t *__restrict__ keys_all, int n, int shift, int nblk,
+                     int32_t *__restrict__ hist_all /*[sorts][R][nblk]*/) {
+  constexpr int R = 1 << BITS, T = R;
+  __shared__ int lds_hist[R];
+  const uint64_t *keys = keys_all + static_cast<size_t>(blockIdx.y) * n;
+  int32_t *hist = hist_all + static_cast<size_t>(blockIdx.y) * R * nblk;
+  lds_hist[threadIdx.x] = 0;
+  __syncthreads();
+  const int begin = blockIdx.x * kSortItems;
+#pragma unroll
+  for (int it = 0; it < (kSortItems + T - 1) / T; ++it) {
+    const int e = begin + it * T + threadIdx.x;
+    if (e < n && it * T + static_cast<int>(threadIdx.x) < kSortItems)
+      atomicAdd(&lds_hist[static_cast<int>((keys[e] >> shift) & (R - 1))], 1);
+  }
+  __syncthreads();
+  hist[static_cast<size_t>(threadIdx.x) * nblk + blockIdx.x] = lds_hist[threadIdx.x];
+}
+
+template <int BITS>
+__global__ void __launch_bounds__(1 << BITS)
+radix_scatter64_kernel(const uint64_t *__restrict__ keys_in_all, const int32_t *__restrict__ vals_in_all,
+                       int n, int shift, int nblk, const int32_t *__restrict__ hist_off_all,
+                       const int32_t *__restrict__ totals_all, uint64_t *__restrict__ keys_out_all,
+                       int32_t *__restrict__ vals_out_all, int32_t *__restrict__ inverse_all) {
+  constexpr int R = 1 << BITS, T = R, NW = T / 64;
+  const size_t at = static_cast<size_t>(blockIdx.y) * n;
+  const uint64_t *keys_in = keys_in_all + at;
+  const int32_t *vals_in = vals_in_all ? vals_in_all + at : nullptr;
+  const int32_t *hist_off = hist_off_all + static_cast<size_t>(blockIdx.y) * R * nblk;
+  const int32_t *totals = totals_all + static_cast<size_t>(blockIdx.y) * R;
+  uint64_t *keys_out = keys_out_all ? keys_out_all + at : nullptr;
+  int32_t *vals_out = vals_out_all + at;
+  int32_t *inverse = inverse_all ? inverse_all + at : nullptr;
+  __shared__ int lds_base[R];
+  __shared__ int lds_cnt[NW][R];
+  __shared__ int lds_wave[NW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  {   // exclusive scan of the R digit totals
+    const int v = totals[threadIdx.x];
+    int incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int u = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += u;
+    }
+    if (lane == 63) lds_wave[wave] = incl;
+    __syncthreads();
+    int prefix = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w)
+      if (w < wave) prefix += lds_wave[w];
+    lds_base[threadIdx.x] = prefix + incl - v + hist_off[static_cast<size_t>(threadIdx.x) * nblk + blockIdx.x];
+  }
+  const int begin = blockIdx.x * kSortItems;
+  for (int it = 0; it < (kSortItems + T - 1) / T; ++it) {
+#pragma unroll
+    for (int w = 0; w < NW; ++w) lds_cnt[w][threadIdx.x] = 0;
+    __syncthreads();
+    const int e = begin + it * T + threadIdx.x;
+    const bool valid = e < n && it * T + static_cast<int>(threadIdx.x) < kSortItems;
+    const uint64_t key = valid ? keys_in[e] : 0ull;
+    const int val = valid ? (vals_in ? vals_in[e] : e) : 0;
+    const int digit = valid ? static_cast<int>((key >> shift) & (R - 1)) : -1;
+    unsigned long long same = __ballot(valid);
+#pragma unroll
+    for (int bit = 0; bit < BITS; ++bit) {
+      const unsigned long long bal = __ballot((digit >> bit) & 1);
+      same &= ((digit >> bit) & 1) ? bal : ~bal;
+    }
+    const int rank_in_wave = __popcll(same & ((1ull << lane) - 1ull));
+    if (valid && rank_in_wave == 0) lds_cnt[wave][digit] = __popcll(same);
+    __syncthreads();
+    if (valid) {
+      int prior = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w)
+        if (w < wave) prior += lds_cnt[w][digit];
+      const int dst = lds_base[digit] + prior + rank_in_wave;
+      if (keys_out) keys_out[dst] = key;
+      vals_out[dst] = val;
+      if (inverse && static_cast<unsigned>(val) < static_cast<unsigned>(n)) inverse[val] = dst;
+    }
+    __syncthreads();
+    {
+      int sum = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) sum += lds_cnt[w][threadIdx.x];
+      lds_base[threadIdx.x] += sum;
+    }
+    __syncthreads();
+  }
+}
+
 // ---- rows of a level in coordinate-key order (spx_key_argsort) --------------------------------------------------------
 // Keys of one level are UNIQUE (a voxeliser's output; spx_rankmap_from_sorted checks it), which buys a sort in four
 // launches instead of thirteen: ONE stable radix pass (count | scan | scatter, above) on the UPPER key bits groups the
@@ -572,6 +673,59 @@ int radix_argsort(const uint32_t *keys, int n, int nbits, int32_t *order_out, vo
     uint32_t *kout = (pass & 1) ? kA : kB;
     if (bits == 9) radix_pass<9>(kin, vin, n, pass * bits, nblk, hist, hist_off, totals, kout, vout, s);
     else radix_pass<8>(kin, vin, n, pass * bits, nblk, hist, hist_off, totals, kout, vout, s);
+    kin = kout;
+    vin = vout;
+  }
+  SPX_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t radix_argsort64_ws_bytes(int n_in, int sorts_in) {
+  const size_t n = n_in > 0 ? n_in : 1, sorts = sorts_in > 0 ? sorts_in : 1;
+  const size_t nblk = (n + kSortItems - 1) / kSortItems;
+  return 2 * align_up(sorts * n * 8, 256) + 2 * align_up(sorts * n * 4, 256) + 2 * align_up(sorts * 512 * nblk * 4, 256) +
+         align_up(sorts * 512 * 4, 256) + 256;
+}
+
+// The 64-bit entry: `sorts` independent stable LSD radix argsorts of n 64-bit keys each (keys, order_out, inverse_out =
+// [sorts, n]) on their low `nbits` bits (1 .. 64), passes as above, every pass one set of three launches for all of
+// them.  order_out[k, t] = index of the t-th smallest key of row k; inverse_out (or null): inverse_out[k, order_out[k,
+// t]] = t, written by the last scatter.  `keys` is not modified.
+int radix_argsort64(const uint64_t *keys, int n, int sorts, int nbits, int32_t *order_out, int32_t *inverse_out, void *ws,
+                    hipStream_t s) {
+  if (n <= 0 || sorts <= 0) return 0;
+  if (nbits < 1) nbits = 1;
+  if (nbits > 64) nbits = 64;
+  const int bits = (nbits + 8) / 9 < (nbits + 7) / 8 ? 9 : 8;
+  const int nblk = div_up(n, kSortItems);
+  Carver cv(ws);
+  const size_t all = static_cast<size_t>(sorts) * n;
+  uint64_t *kA = cv.take<uint64_t>(all), *kB = cv.take<uint64_t>(all);
+  int32_t *vA = cv.take<int32_t>(all), *vB = cv.take<int32_t>(all);
+  int32_t *hist = cv.take<int32_t>(static_cast<size_t>(sorts) * 512 * nblk);
+  int32_t *hist_off = cv.take<int32_t>(static_cast<size_t>(sorts) * 512 * nblk);
+  int32_t *totals = cv.take<int32_t>(static_cast<size_t>(sorts) * 512);
+  const int passes = div_up(nbits, bits);
+  const dim3 grid(nblk, sorts);
+  const uint64_t *kin = keys;
+  const int32_t *vin = nullptr;
+  for (int pass = 0; pass < passes; ++pass) {
+    const bool last = pass == passes - 1;
+    int32_t *vout = last ? order_out : ((pass & 1) ? vA : vB);
+    uint64_t *kout = last ? nullptr : ((pass & 1) ? kA : kB);
+    int32_t *inv = last ? inverse_out : nullptr;
+    const int shift = pass * bits;
+    if (bits == 9) {
+      hipLaunchKernelGGL(radix_count64_kernel<9>, grid, dim3(512), 0, s, kin, n, shift, nblk, hist);
+      hipLaunchKernelGGL(scan_kernel, dim3(512 * sorts), dim3(kBlock), 0, s, hist, hist_off, nblk, totals);
+      hipLaunchKernelGGL(radix_scatter64_kernel<9>, grid, dim3(512), 0, s, kin, vin, n, shift, nblk, hist_off,
+                         totals, kout, vout, inv);
+    } else {
+      hipLaunchKernelGGL(radix_count64_kernel<8>, grid, dim3(256), 0, s, kin, n, shift, nblk, hist);
+      hipLaunchKernelGGL(scan_kernel, dim3(256 * sorts), dim3(kBlock), 0, s, hist, hist_off, nblk, totals);
+      hipLaunchKernelGGL(radix_scatter64_kernel<8>, grid, dim3(256), 0, s, kin, vin, n, shift, nblk, hist_off,
+                         totals, kout, vout, inv);
+    }
     kin = kout;
     vin = vout;
   }

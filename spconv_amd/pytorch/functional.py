@@ -590,3 +590,96 @@ from spconv_amd.pytorch._pointvoxel import (PointGroups, decorate_points, point_
 # level and the interpolation of its rows to the points
 from spconv_amd.pytorch._interp import (PointCorners, point_corners, point_corners_into,  # noqa: E402,F401
                                         voxels_to_points_trilinear)
+
+# voxel serialisation (csrc/serialize.hip; not part of the reference): rows ordered along Z-order / Hilbert curves and
+# cut into fixed-size patches, for the serialised point / voxel transformers
+from spconv_amd.pytorch import _serialize  # noqa: E402
+from spconv_amd.pytorch._serialize import PatchPlan, Serialization  # noqa: E402,F401
+
+
+def serialize(x_or_indices, spatial_shape=None, batch_size=None, orders=("z", "z-trans", "hilbert", "hilbert-trans"),
+              depth=None, axes=None, n_live=None):
+    """The rows of a level in the order of space-filling curves, on the kernels of csrc/serialize.hip.  x_or_indices: a
+    SparseConvTensor (which supplies indices, spatial shape, batch size and its n_live_dev) or int32 indices [n, ndim +
+    1] with `batch_size` and a `spatial_shape` or `depth`.  orders: up to 8 of "z", "z-trans", "hilbert",
+    "hilbert-trans".  A curve takes the spatial index columns through `axes`, the first entry the most significant:
+    by default the columns reversed -- (x, y, z) for [batch, z, y, x] --, the -trans orders with the first two entries
+    swapped.  depth (bits per axis, 1 .. 16; default: the bit length of max(spatial_shape) - 1) is known on the host,
+    and ndim * depth + bit_length(batch_size) may not exceed 63.  Returns a Serialization: code int64 [K, n] = (batch <<
+    (ndim * depth)) | curve code, order / inverse int32 [K, n], offsets int32 [batch_size + 1], depth, orders.  A row
+    is dead when its batch index is outside [0, batch_size), a coordinate is outside [0, 2^depth) or it lies at or beyond
+    *n_live: its code is -1 and it follows every live row, in ascending row.  The sort is stable.  Nothing is read
+    back: the call can sit inside a captured graph.  No gradients: every output is an integer."""
+    if hasattr(x_or_indices, "indices") and hasattr(x_or_indices, "spatial_shape"):
+        x = x_or_indices
+        indices = x.indices
+        spatial_shape = list(x.spatial_shape) if spatial_shape is None else spatial_shape
+        batch_size = x.batch_size if batch_size is None else batch_size
+        n_live = getattr(x, "n_live_dev", None) if n_live is None else n_live
+    else:
+        indices = x_or_indices
+        if batch_size is None:
+            raise ValueError("serialize: indices need a batch_size")
+    return _serialize.serialize(indices, int(batch_size), spatial_shape, orders, depth, axes, n_live)
+
+
+def patch_plan(ser, patch_size, which=0, pad="borrow"):
+    """The fixed-shape patch layout of order `which` of a Serialization (spx_patch_plan): P_cap = n // patch_size +
+    batch_size patches of patch_size slots, a host-known bound.  Every scene starts on a patch boundary; the tail slots
+    of a scene's last patch hold -1 (pad="mask") or the row held patch_size slots earlier (pad="borrow", as Point
+    Transformer V3 pads; scenes shorter than one patch: -1) -- borrowed duplicates serve as attention keys, never as
+    results.  Returns a PatchPlan; nothing is read back (n_patches_dev stays on the device)."""
+    return _serialize.patch_plan(ser, patch_size, which, pad)
+
+
+# A row move casts nothing: under autocast the rows keep their dtype and their bits (custom_fwd without cast_inputs; the
+# convolutions' _FWD would turn every floating argument into float16 and rebuild the plan tuple on the way).
+_FWD_ROWS = _amp.custom_fwd(device_type="cuda")
+
+
+class RowsToPatchesFunction(Function):
+    """[n, C] -> [P_cap, K, C] over patch_rows (one gather launch); the backward adds a row's canonical and borrowed
+    slot in fp32 (fp64), rounded once (spx_patch_rows_bwd: one launch, no atomics)."""
+
+    @staticmethod
+    @_FWD_ROWS
+    def forward(ctx, features, plan):
+        ctx.plan = plan
+        return _serialize.rows_fwd(features.detach(), plan)
+
+    @staticmethod
+    @once_differentiable
+    @_BWD
+    def backward(ctx, grad_output):
+        return _serialize.rows_bwd(grad_output, ctx.plan), None
+
+
+class PatchesToRowsFunction(Function):
+    """[P_cap, K, C] -> [n, C] over row_slot; the backward is the gather over patch_rows_canon.  Bytes move, nothing is
+    added: a row keeps its bits."""
+
+    @staticmethod
+    @_FWD_ROWS
+    def forward(ctx, patches, plan):
+        ctx.plan = plan
+        return _serialize.patches_fwd(patches.detach(), plan)
+
+    @staticmethod
+    @once_differentiable
+    @_BWD
+    def backward(ctx, grad_output):
+        return _serialize.patches_bwd(grad_output, ctx.plan), None
+
+
+def rows_to_patches(features, plan):
+    """Feature rows [n, C] into the patches of a PatchPlan: [P_cap, patch_size, C], zeros in the -1 slots.
+    Differentiable in the features over the four floating dtypes; a borrowed slot's gradient is added to its row's."""
+    _serialize.check_rows(features, plan, "rows_to_patches")
+    return RowsToPatchesFunction.apply(features, plan)
+
+
+def patches_to_rows(patches, plan):
+    """Patches [P_cap, patch_size, C] back to rows [n, C]: every live row reads its canonical slot, dead rows get zeros.
+    Differentiable in the patches; borrowed and empty slots get a zero gradient."""
+    _serialize.check_patches(patches, plan, "patches_to_rows")
+    return PatchesToRowsFunction.apply(patches, plan)
