@@ -341,7 +341,9 @@ extern "C" int orc_point2voxel(const float *points, int n, int nfeat, int ndim, 
     bool failed = false;
     for (int j = 0; j < ndim; ++j) {
       const float v = std::floor((points[static_cast<size_t>(i) * nfeat + (ndim - 1 - j)] - coors_range[j]) / vsize[j]);
-      if (v < 0 || v >= static_cast<float>(grid_size[j])) {
+      // (a NaN fails both comparisons: a point with a non-finite coordinate is outside the range, as the reference's
+      // conversion to int before its comparison makes it)
+      if (!(v >= 0 && v < static_cast<float>(grid_size[j]))) {
         failed = true;
         break;
       }

@@ -35,7 +35,10 @@ def calc_point2voxel_meta_data(vsize_xyz: List[float], coors_range_xyz: List[flo
 
 
 class PointToVoxel(object):
-    """WARNING: you MUST construct PointToVoxel AFTER set device."""
+    """WARNING: you MUST construct PointToVoxel AFTER set device.
+
+    A point with a non-finite coordinate (NaN, +inf, -inf) is outside the range: it makes no voxel and its
+    ``pc_voxel_id`` is -1; non-finite values in the feature columns behind the coordinates are stored as they are."""
 
     def __init__(self, vsize_xyz: List[float], coors_range_xyz: List[float], num_point_features: int,
                  max_num_voxels: int, max_num_points_per_voxel: int,

@@ -363,6 +363,26 @@ def _npz(name):
     return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name))
 
 
+def test_point2voxel_restatement_drops_non_finite_coordinates():
+    """A point with a NaN or infinite coordinate is outside the range: id -1, no voxel (the kernels' contract; the
+    reference's loop converts to int before it compares and drops it too)."""
+    vs, cr, grid = [0.1, 0.1, 0.1], [0.0, 0.0, 0.0, 1.0, 1.0, 1.0], [10, 10, 10]
+    good = np.array([[0.55, 0.55, 0.55, 1.0], [0.15, 0.25, 0.35, 2.0]], np.float32)
+    bad = np.tile(np.array([[0.5, 0.5, 0.5, 3.0]], np.float32), (9, 1))
+    for col in range(3):
+        for k, v in enumerate((np.nan, np.inf, -np.inf)):
+            bad[col * 3 + k, col] = v
+    pts = np.concatenate([good[:1], bad, good[1:]])
+    for empty_mean in (False, True):
+        v, i, c, pid = oracle.point2voxel(pts, vs, cr, grid, 10, 2, empty_mean)
+        v0, i0, c0, pid0 = oracle.point2voxel(good, vs, cr, grid, 10, 2, empty_mean)
+        np.testing.assert_array_equal(pid, [0] + [-1] * 9 + [1])
+        np.testing.assert_array_equal(i, i0)
+        np.testing.assert_array_equal(i, [[5, 5, 5], [3, 2, 1]])
+        np.testing.assert_array_equal(c, c0)
+        np.testing.assert_array_equal(v, v0)
+
+
 @pytest.mark.parametrize("tag", ["plain", "mean", "capped_mean"])
 def test_point2voxel_restatement_equals_reference_executed_vectors(tag):
     d = _npz("p2v_ref.npz")
