@@ -114,6 +114,9 @@ int spx_set_option(const char *name_h, int value);
  *   interp/corners_ranked, interp/corners_hash, interp/fwd, interp/bwd
  *                                                  trilinear devoxelisation: calls of spx_point_corners by lookup form,
  *                                                  of spx_interp_fwd and of spx_interp_bwd
+ *   query/ranked, query/hash, query/group_fwd, query/group_bwd
+ *                                                  voxel query and grouping: calls of spx_voxel_query by lookup form,
+ *                                                  of spx_group_fwd and of spx_group_bwd
  *   select/score, select/hist, select/pick, select/ties, select/flags, select/count, select/scan, select/scatter,
  *   select/map                                     voxel pruning, one count per launch: spx_row_score; the passes of
  *                                                  spx_topk_flags (hist and pick once per 8-bit digit: four each; ties:
@@ -1078,6 +1081,67 @@ int spx_interp_fwd(const void *vfeat, int n, const int32_t *corner_rows, const f
 int spx_interp_bwd(const void *dout, int n_cap, int ndim, const float *corner_w, const int32_t *offsets,
                    const int32_t *list, int n, const int32_t *n_live, int C, int dtype, void *dvfeat,
                    spx_stream_t stream);
+
+/* ---- voxel query and neighbour grouping (csrc/query.hip) ---------------------------------------------------
+ * Per query point the first `nsample` voxels of a sparse level inside a window of cells, optionally inside a radius,
+ * and their rows gathered: the voxel_query / grouping_operation pair of the two-stage detectors over sparse backbones
+ * (Voxel R-CNN's Voxel RoI pooling, the voxel set abstraction of the PV-RCNN family).  Stands where a torch composite
+ * would: one hash query per window cell, a topk per query, index_select, an index_add_ backward (float atomics: not
+ * reproducible).  Every call: the caller allocates, nothing is read back, nothing synchronises, every grid depends on
+ * host-known sizes only (hipGraph-safe).  The argument checks that need no pointer come before any pointer is looked
+ * at.  There is no gradient with respect to the queries.
+ *
+ *   spx_voxel_query: queries = fp32 [n_cap, nfeat], the first ndim columns x, y, z; batch_ids = int32 [n_cap] or NULL
+ *   (all batch 0); n_queries_dev = NULL or a device int32: rows at or beyond it are no queries; ndim = 2 or 3; vsize
+ *   [ndim], coors_range [2 * ndim], indices, n, n_live, batch, spatial_h, rankmap: as spx_point_corners takes them;
+ *   query_range [ndim] = HOST ints in index-column (zyx) order, each in 0 .. 15; nsample in 1 .. 128; r2 = the squared
+ *   radius, computed by the caller in fp32; flags = 1 (apply the radius test) | 2 (pad = first) | w << 8 (w = 0: the
+ *   group width is chosen from the window; w = 1 .. 7: 2^(w - 1) lanes per query -- the result is the same).
+ *   Outputs (device): rows int32 [n_cap, nsample], count int32 [n_cap], offsets fp32 [n_cap, nsample, ndim] or NULL.
+ *   Per point column j (x = 0; grid axis ndim - 1 - j): t_j = (q_j - lo_j) / vsize_j, cell_j = floorf(t_j).  A query
+ *   is VALID when it lies below *n_queries, its batch id is in [0, batch) and cell_j is in [0, extent_j) on every
+ *   axis (false for NaN).  Its CANDIDATES are the cells cell + o with |o_d| <= query_range[d], visited in ascending
+ *   linear key: axis 0 outermost, the last axis innermost, every offset ascending.  A candidate is a HIT when it lies
+ *   inside the grid, a LIVE row holds it (a row below *n_live with its batch index and coordinates in range; a
+ *   coordinate held twice goes to the lowest row) and, with flag 1, d2 < r2 where, all in fp32 and every operation
+ *   rounded on its own (no FMA), v_j being the candidate's coordinate:
+ *     centre_j = (float(v_j) + 0.5f) * vsize_j + lo_j,  d_j = centre_j - q_j,
+ *     d2 = (d_0 * d_0 + d_1 * d_1) + d_2 * d_2          (ndim 2: d_0 * d_0 + d_1 * d_1)
+ *   The first nsample hits in visiting order are kept: rows[i, s] = the row of hit s, offsets[i, s, j] = its d_j,
+ *   count[i] = min(hits, nsample).  Slots at or beyond count[i] hold row -1 and offsets 0, or, with flag 2 and
+ *   count[i] > 0, slot 0 again.  An invalid query has count 0 and rows -1.
+ *   A query belongs to a group of 1 .. 64 lanes which test the candidates of one round together and stop once nsample
+ *   slots are taken.  With a rank map the caller vouches that the live rows are in ascending, unique key order; the
+ *   unit of work is then a line of the window along the last axis (one or two words of the map, consecutive rows): one
+ *   launch, ws may be NULL.  With rankmap = NULL the call builds the hash table of the index builders in ws and
+ *   probes it per cell: a fill, the insert pass, the query pass.  Both forms return identical results for a
+ *   key-ordered, duplicate-free level.  Requires n_cap * nsample < 2^31, at most 2^30 rows, and batch x grid within a
+ *   63-bit key.
+ *   spx_voxel_query_ws_bytes: scratch of the hash form (ranked = 0), monotone in n; 0 for ranked != 0 and for
+ *   arguments that are refused.
+ *
+ *   spx_group_fwd: out[e, :] = vfeat[rows[e], :] for the entries e = i * nsample + s ([n, C] -> [n_cap, nsample, C],
+ *   contiguous; SPX_F16 / SPX_BF16 / SPX_F32 / SPX_F64), zeros where rows[e] is outside [0, n).  The bits move
+ *   unchanged.  Rows whose byte size is a multiple of 16 (and 16-byte aligned pointers) move as 16-byte pieces per
+ *   lane, other widths element by element.  One launch, every output element written exactly once.
+ *
+ *   spx_group_bwd: the gradient with respect to the voxel rows over the TRANSPOSED list: offsets [n + 1] and list
+ *   [n_cap * nsample] = spx_point_groups(ids = rows flattened, id_bytes 4, n_cap * nsample entries, num_voxels = n).
+ *   dvfeat[v, :] = sum over e in list[offsets[v] .. offsets[v + 1]) of dout[e, :], in list order (ascending e), fp32
+ *   accumulation (fp64 for SPX_F64) from zero, one round-to-nearest-even into the feature type; zeros for an empty
+ *   group and for rows at or beyond *n_live.  No atomics, identical run to run; the walk of spx_interp_bwd.  One
+ *   launch. */
+size_t spx_voxel_query_ws_bytes(int n_cap, int nsample, int ndim, int n, int ranked);
+int spx_voxel_query(const float *queries, int nfeat, const int32_t *batch_ids, int n_cap,
+                    const int32_t *n_queries_dev, int ndim, const float *vsize, const float *coors_range,
+                    const int32_t *indices, int n, const int32_t *n_live, int batch, const int *spatial_h,
+                    const void *rankmap, size_t rankmap_bytes, const int *query_range, int nsample, float r2,
+                    int flags, int32_t *rows, int32_t *count, float *offsets, void *ws, size_t ws_bytes,
+                    spx_stream_t stream);
+int spx_group_fwd(const void *vfeat, int n, const int32_t *rows, int n_cap, int nsample, int C, int dtype, void *out,
+                  spx_stream_t stream);
+int spx_group_bwd(const void *dout, int n_cap, int nsample, const int32_t *offsets, const int32_t *list, int n,
+                  const int32_t *n_live, int C, int dtype, void *dvfeat, spx_stream_t stream);
 
 /* ---- voxel pruning (csrc/select.hip) ---------------------------------------------------------------------
  * Keep the most important rows of a sparse tensor and drop, or process separately, the rest: the pruned down-sampling

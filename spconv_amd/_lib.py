@@ -190,6 +190,14 @@ SIGNATURES = {
                                       vp, vp]),
     "spx_interp_bwd": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int,
                                       ctypes.c_int, vp, vp]),
+    "spx_voxel_query_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "spx_voxel_query": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, c_float_p, c_float_p, vp,
+                                       ctypes.c_int, vp, ctypes.c_int, c_int_p, vp, ctypes.c_size_t, c_int_p, ctypes.c_int,
+                                       ctypes.c_float, ctypes.c_int, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "spx_group_fwd": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp,
+                                     vp]),
+    "spx_group_bwd": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int,
+                                     ctypes.c_int, vp, vp]),
     "spx_row_score": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
     "spx_topk_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "spx_topk_flags": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

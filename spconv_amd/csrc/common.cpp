@@ -39,6 +39,7 @@ std::atomic<long long> g_union_launches[kUnionCount];
 std::atomic<long long> g_collapse_launches[kCollapseCount];
 std::atomic<long long> g_pointvoxel_launches[kPvCount];
 std::atomic<long long> g_interp_launches[kInterpCount];
+std::atomic<long long> g_query_launches[kQueryCount];
 std::atomic<long long> g_serialize_launches[kSerCount];
 std::atomic<long long> g_select_launches[kSelInstCount];
 std::atomic<long long> g_pool_launches[kPoolCount];
@@ -187,6 +188,14 @@ std::atomic<long long> *interp_counter(const char *key) {
   return nullptr;
 }
 
+// counter of a voxel-query key (spx_launch_count), or null
+std::atomic<long long> *query_counter(const char *key) {
+  static const char *names[kQueryCount] = {"query/ranked", "query/hash", "query/group_fwd", "query/group_bwd"};
+  for (int i = 0; i < kQueryCount; ++i)
+    if (strcmp(key, names[i]) == 0) return &g_query_launches[i];
+  return nullptr;
+}
+
 // counter of a voxel-pruning key (spx_launch_count), or null
 std::atomic<long long> *select_counter(const char *key) {
   static const char *names[kSelInstCount] = {"select/score", "select/hist", "select/pick", "select/ties", "select/flags",
@@ -273,6 +282,7 @@ long long spx_launch_count(const char *family_h) {
   if (std::atomic<long long> *c = spx::collapse_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pointvoxel_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::interp_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::query_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::serialize_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::select_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pool_counter(family_h)) return c->load(std::memory_order_relaxed);

@@ -221,6 +221,12 @@ enum InterpInst { kInterpCornersRanked = 0, kInterpCornersHash, kInterpFwd, kInt
 extern std::atomic<long long> g_interp_launches[kInterpCount];
 inline void count_interp(InterpInst i) { g_interp_launches[i].fetch_add(1, std::memory_order_relaxed); }
 
+// voxel query and neighbour grouping (query.hip): one counter per entry point and lookup form.
+// Keys query/ranked, query/hash, query/group_fwd, query/group_bwd.
+enum QueryInst { kQueryRanked = 0, kQueryHash, kQueryGroupFwd, kQueryGroupBwd, kQueryCount };
+extern std::atomic<long long> g_query_launches[kQueryCount];
+inline void count_query(QueryInst i) { g_query_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
 // voxel serialisation (serialize.hip): keys once per spx_curve_keys call, sort once per sorted order, offsets once per
 // spx_serialize call, plan once per spx_patch_plan call, bwd once per spx_patch_rows_bwd call.
 // Keys serialize/keys, serialize/sort, serialize/offsets, serialize/plan, serialize/bwd.

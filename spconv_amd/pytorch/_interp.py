@@ -46,15 +46,15 @@ def _floats(values):
     return (ctypes.c_float * len(values))(*values)
 
 
-def _geometry(vsize_xyz: Sequence[float], coors_range_xyz: Sequence[float]):
+def _geometry(vsize_xyz: Sequence[float], coors_range_xyz: Sequence[float], what: str = "point_corners"):
     from spconv_amd.pytorch.utils import calc_point2voxel_meta_data
     ndim = len(vsize_xyz)
     if ndim not in (2, 3):
-        raise ValueError(f"point_corners: ndim must be 2 or 3, got {ndim}")
+        raise ValueError(f"{what}: ndim must be 2 or 3, got {ndim}")
     if len(coors_range_xyz) != 2 * ndim:
-        raise ValueError(f"point_corners: coors_range_xyz holds {2 * ndim} values for ndim = {ndim}")
+        raise ValueError(f"{what}: coors_range_xyz holds {2 * ndim} values for ndim = {ndim}")
     if not min(float(v) for v in vsize_xyz) > 0:
-        raise ValueError(f"point_corners: voxel sizes must be positive, got {list(vsize_xyz)}")
+        raise ValueError(f"{what}: voxel sizes must be positive, got {list(vsize_xyz)}")
     vsize, _, _, coors_range = calc_point2voxel_meta_data(list(vsize_xyz), list(coors_range_xyz))
     return ndim, vsize, coors_range
 

@@ -591,6 +591,11 @@ from spconv_amd.pytorch._pointvoxel import (PointGroups, decorate_points, point_
 from spconv_amd.pytorch._interp import (PointCorners, point_corners, point_corners_into,  # noqa: E402,F401
                                         voxels_to_points_trilinear)
 
+# voxel query and neighbour grouping (csrc/query.hip; not part of the reference): the first nsample voxels of a level
+# around each query point, and their rows gathered
+from spconv_amd.pytorch._query import (VoxelNeighbors, group_voxels, voxel_query,  # noqa: E402,F401
+                                       voxel_query_into)
+
 # voxel serialisation (csrc/serialize.hip; not part of the reference): rows ordered along Z-order / Hilbert curves and
 # cut into fixed-size patches, for the serialised point / voxel transformers
 from spconv_amd.pytorch import _serialize  # noqa: E402

@@ -1,6 +1,7 @@
 """``spconv.pytorch.spatial`` (reference ``spconv/pytorch/spatial.py:28-45``), and ``SparseCollapse``: the hand-over
 from a 3-D backbone to a sparse 2-D head on the kernels of csrc/collapse.hip; ``SparsePrune`` (csrc/select.hip);
-``TrilinearDevoxelize``: a sparse level read out at points (csrc/interp.hip)."""
+``TrilinearDevoxelize``: a sparse level read out at points (csrc/interp.hip); ``VoxelQueryAndGroup``: the voxels around
+query points, gathered (csrc/query.hip)."""
 from typing import Optional, Sequence
 
 import torch
@@ -128,3 +129,48 @@ class TrilinearDevoxelize(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return f"vsize_xyz={self.vsize_xyz}, coors_range_xyz={self.coors_range_xyz}, normalize={self.normalize}"
+
+
+class VoxelQueryAndGroup(torch.nn.Module):
+    """The voxels of a sparse level around query points, gathered for a shared MLP (``functional.voxel_query`` +
+    ``functional.group_voxels``, the kernels of csrc/query.hip): the ``voxel_query_wrapper`` / ``grouping_operation``
+    pair of Voxel R-CNN's Voxel RoI pooling and of the PV-RCNN family's voxel set abstraction.  Not part of the
+    reference.
+
+    ``query_range``: ndim ints in index-column (zyx) order, each in 0 .. 15: the window of cells around a query's own
+    cell; ``nsample`` in 1 .. 128: the first so many voxels of the window, in ascending linear key, are kept;
+    ``radius``: None, or the distance below which a voxel centre must lie; ``vsize_xyz`` / ``coors_range_xyz`` as the
+    voxelisers take them, the voxel size being that of the level being read (a level behind strided layers: the
+    voxeliser's size times the stride).  ``forward(x, queries, batch_ids) -> ([M, nsample, C (+ ndim)], count [M])``:
+    queries fp32 [M, >= ndim], batch_ids int32 [M] or None.  With ``use_xyz`` the offsets from the query to the voxel
+    centres, cast to the feature dtype, come in front of the C feature columns.  Empty slots repeat slot 0
+    (pad="first"), so the caller's MLP and a plain ``max(1)`` follow in torch; a query without any voxel gets zeros and
+    count 0.  Key-ordered levels (an index tensor that carries its rank map) are looked up without a hash table.  The
+    gradient goes to x's features only, added in a fixed order without atomics; there is no gradient with respect to
+    the queries."""
+
+    def __init__(self, query_range: Sequence[int], nsample: int, radius: Optional[float] = None, use_xyz: bool = True, *,
+                 vsize_xyz: Sequence[float], coors_range_xyz: Sequence[float]):
+        super().__init__()
+        from spconv_amd.pytorch import _query
+        ndim, _, _ = _query._geometry(vsize_xyz, coors_range_xyz, "VoxelQueryAndGroup")
+        self.query_range = _query._check_window(query_range, nsample, ndim, "first")
+        _query.squared_radius(radius)
+        self.nsample = int(nsample)
+        self.radius = None if radius is None else float(radius)
+        self.use_xyz = bool(use_xyz)
+        self.vsize_xyz = [float(v) for v in vsize_xyz]
+        self.coors_range_xyz = [float(v) for v in coors_range_xyz]
+
+    def forward(self, x: SparseConvTensor, queries: torch.Tensor, batch_ids: Optional[torch.Tensor] = None):
+        from spconv_amd.pytorch import functional as F
+        nb = F.voxel_query(queries, batch_ids, x, self.vsize_xyz, self.coors_range_xyz, self.query_range, self.nsample,
+                           self.radius, "first", self.use_xyz)
+        grouped = F.group_voxels(x.features, nb)
+        if self.use_xyz:
+            grouped = torch.cat([nb.offsets.to(grouped.dtype), grouped], dim=2)
+        return grouped, nb.count
+
+    def extra_repr(self) -> str:
+        return (f"query_range={self.query_range}, nsample={self.nsample}, radius={self.radius}, use_xyz={self.use_xyz}, "
+                f"vsize_xyz={self.vsize_xyz}, coors_range_xyz={self.coors_range_xyz}")
