@@ -271,8 +271,12 @@ extern std::atomic<long long> g_rulebook_launches[kRbCount];
 inline void count_rulebook(RulebookPass p) { g_rulebook_launches[p].fetch_add(1, std::memory_order_relaxed); }
 }  // namespace spx
 
-// ---- row orders (rowsort.hip) ---------------------------------------------------------------------
+// ---- row orders (rowsort.hip) and the row gather (pointvoxel.hip) ----------------------------------
 namespace spx {
+// out[i] = src[rows[i]] or the fill element (fill16: it repeated over 16 bytes) where rows[i] is outside [0, n_src);
+// rows of C elements of elem_bytes bytes, the bits moved unchanged.  Neither counts nor validates.  0 = ok.
+int gather_rows(const void *src, int n_src, const int32_t *rows, long long n_rows, int C, int elem_bytes,
+                const void *fill16, void *out, hipStream_t s);
 // stable LSD radix argsort behind spx_mask_argsort (rowsort.hip)
 size_t radix_argsort_ws_bytes(int n);
 int radix_argsort(const uint32_t *keys, int n, int nbits, int32_t *order_out, void *ws, hipStream_t s);

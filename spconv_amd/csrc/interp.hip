@@ -4,8 +4,8 @@
 //
 //   corners   per point the K = 2^ndim voxels whose centres surround it: corner_rows [n_cap, K] (row of the level, -1:
 //             outside the grid or no live row there) and corner_w [n_cap, K] (the multilinear weight, 0 where the row
-//             is -1).  A coordinate lookup is one load of the level's rank map (rankmap.h) for a key-ordered level, or
-//             a probe of the builders' hash table (table.h), built here from the level's rows, for rows in any order.
+//             is -1).  A coordinate lookup is lookup.h's: one load of the level's rank map for a key-ordered level, or
+//             a probe of the builders' hash table, built from the level's rows, for rows in any order.
 //   forward   out[i] = sum_c corner_w[i, c] * vfeat[corner_rows[i, c]]: one item per (point, piece), the K loads of a
 //             piece in flight together, the sum in ascending c.
 //   backward  dvfeat[v] = sum over the entries e = i * K + c of voxel v's group of corner_w[e] * dout[e / K]: a segment
@@ -15,10 +15,8 @@
 // All arithmetic is fp32 (fp64 accumulation for SPX_F64) with every operation rounded on its own, so a host loop
 // reproduces every element bit for bit.
 #include "common.h"
-#include "fill.h"
+#include "lookup.h"
 #include "piece.h"
-#include "rankmap.h"
-#include "table.h"
 
 // no multiply-add pair of this unit may be contracted into an FMA (see pointvoxel.hip)
 #pragma clang fp contract(off)
@@ -27,35 +25,17 @@ namespace spx {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kDims = 3;              // ndim is 2 or 3
-constexpr int kMaxRows = 1 << 30;     // rows of a level: table_capacity(n) = 2^31 slots still fits its 32-bit mask
-
-struct CornerGeom {
-  LevelGeom level;                    // batch and grid extents, index-column (zyx) order
-  float vsize[kDims], lo[kDims];      // by POINT COLUMN (x, y, z): entry j belongs to grid axis ndim - 1 - j
-};
-
-// the live rows of the level into the table, by their linear key (level_key of rankmap.h over all axes)
-__global__ void __launch_bounds__(kBlock)
-corner_insert_kernel(const int32_t *__restrict__ idx, int n, const int32_t *__restrict__ n_live, LevelGeom g, Table t) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n || (n_live && i >= *n_live)) return;
-  const long long key = level_key(idx + static_cast<size_t>(i) * (g.ndim + 1), g, kAllAxes);
-  if (key >= 0) table_insert_min(t, key, i);      // (a duplicate coordinate: the lowest row stays)
-}
 
 // One thread per point.  RANKED: the lookup is rank_of over the level's rank map, else a probe of the table.
 template <int NDIM, bool RANKED>
 __global__ void __launch_bounds__(kBlock)
 corner_kernel(const float *__restrict__ points, int nfeat, const int32_t *__restrict__ batch_ids, int n_cap,
-              const int32_t *__restrict__ n_points, CornerGeom g, int n, const int32_t *__restrict__ n_live,
-              const uint2 *__restrict__ cells, const int32_t *__restrict__ blockoff, Table t, int normalise,
+              const int32_t *__restrict__ n_points, PointGeom g, LevelLookup look, int normalise,
               int32_t *__restrict__ corner_rows, float *__restrict__ corner_w) {
   constexpr int K = 1 << NDIM;
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n_cap) return;
-  const int np = n_points ? *n_points : n_cap;
-  const int live = n_live ? min(*n_live, n) : n;
+  const RowFinder<RANKED> row_at(look);
   int rows[K];
   float w[K];
 #pragma unroll
@@ -63,17 +43,16 @@ corner_kernel(const float *__restrict__ points, int nfeat, const int32_t *__rest
     rows[c] = -1;
     w[c] = 0.f;
   }
-  const int b = i < np ? (batch_ids ? batch_ids[i] : 0) : -1;
-  bool valid = b >= 0 && b < g.level.batch;
+  int b;
+  bool valid = point_batch(g, batch_ids, n_cap, n_points, i, b);
   int base[NDIM] = {};
   float f[NDIM] = {};
   if (valid) {
     const float *pt = points + static_cast<size_t>(i) * nfeat;
 #pragma unroll
     for (int j = 0; j < NDIM; ++j) {
-      const float tj = (pt[j] - g.lo[j]) / g.vsize[j];        // (the voxeliser's own expression: voxelize.hip)
-      const float cell = floorf(tj);
-      valid = valid && cell >= 0.f && cell < static_cast<float>(g.level.dims[NDIM - 1 - j]);      // (false for NaN)
+      float cell;
+      const float tj = point_cell<NDIM>(g, j, pt[j], cell, valid);
       const float gj = tj - 0.5f;
       const float bj = floorf(gj);
       f[j] = gj - bj;
@@ -98,9 +77,8 @@ corner_kernel(const float *__restrict__ points, int nfeat, const int32_t *__rest
         const float wj = ((c >> j) & 1) ? f[j] : 1.0f - f[j];
         wc = j == 0 ? wj : wc * wj;
       }
-      int r = -1;
-      if (in) r = RANKED ? rank_of(cells, blockoff, static_cast<unsigned long long>(key)) : table_find(t, key);
-      if (static_cast<unsigned>(r) < static_cast<unsigned>(live)) {
+      const int r = in ? row_at(key) : -1;
+      if (r >= 0) {
         rows[c] = r;
         w[c] = wc;
       }
@@ -145,9 +123,7 @@ interp_fwd_kernel(const void *__restrict__ vfeat_, int n, const int32_t *__restr
   P *out = static_cast<P *>(out_);
   for (long long item = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; item < total;
        item += static_cast<long long>(gridDim.x) * kBlock) {
-    const long long i = total <= 0x7fffffffLL
-                            ? static_cast<long long>(static_cast<unsigned>(item) / static_cast<unsigned>(pieces))
-                            : item / pieces;
+    const long long i = row_of(item, total, pieces);
     const int p = static_cast<int>(item - i * pieces);
     int r[K];
     float w[K];
@@ -242,30 +218,10 @@ interp_bwd_kernel(const void *__restrict__ dout_, int n_cap, int kshift, const f
 
 // -------------------------------------------------------------------------------------------- host side
 
-// scratch of a hash-form corners call: the table (room for the wide form, 12 bytes per slot)
-struct CornerWs {
-  hkey_t *keys;
-  int32_t *vals;
-  uint32_t cap;
-  size_t bytes;
-  CornerWs(void *ws, int n) {
-    Carver c(ws);
-    cap = table_capacity(static_cast<size_t>(n > 0 ? n : 0));
-    keys = c.take<hkey_t>(cap);
-    vals = c.take<int32_t>(cap);
-    bytes = c.off;
-  }
-};
-
-// 0 = ok: the checks of a corners call that need no pointer
-int check_corners(int n_cap, int nfeat, int ndim, int n, int batch, int flags) {
-  SPX_CHECK(ndim == 2 || ndim == 3, "ndim must be 2 or 3, got %d", ndim);
+// 0 = ok: the counts of a corner table [n_cap, 2^ndim] over n rows (ndim checked before)
+int check_table(int n_cap, int ndim, int n) {
   SPX_CHECK(n_cap >= 0 && n >= 0, "bad point / row counts %d / %d", n_cap, n);
   SPX_CHECK((static_cast<long long>(n_cap) << ndim) < 0x80000000LL, "n_cap * 2^ndim must stay below 2^31, got %d points", n_cap);
-  SPX_CHECK(n <= kMaxRows, "at most 2^30 voxel rows (the table holds two slots per row), got %d", n);
-  SPX_CHECK(nfeat >= ndim, "points need at least %d columns, got %d", ndim, nfeat);
-  SPX_CHECK(batch >= 1, "batch must be >= 1, got %d", batch);
-  SPX_CHECK(flags == 0 || flags == 1, "flags must be 0 or 1 (normalise), got %d", flags);
   return 0;
 }
 
@@ -273,9 +229,7 @@ int check_corners(int n_cap, int nfeat, int ndim, int n, int batch, int flags) {
 int check_interp(int n_cap, int ndim, int n, int C, int dtype) {
   SPX_CHECK(ndim == 2 || ndim == 3, "ndim must be 2 or 3, got %d", ndim);
   const int eb = float_row_elem(dtype, C);
-  if (eb < 0) return eb;
-  SPX_CHECK(n_cap >= 0 && n >= 0, "bad point / row counts %d / %d", n_cap, n);
-  SPX_CHECK((static_cast<long long>(n_cap) << ndim) < 0x80000000LL, "n_cap * 2^ndim must stay below 2^31, got %d points", n_cap);
+  if (eb < 0 || check_table(n_cap, ndim, n)) return -1;
   return eb;
 }
 
@@ -287,7 +241,7 @@ extern "C" {
 size_t spx_point_corners_ws_bytes(int n_cap, int ndim, int n) {
   if ((ndim != 2 && ndim != 3) || n_cap < 0 || n < 0) return 0;
   if ((static_cast<long long>(n_cap) << ndim) >= 0x80000000LL || n > spx::kMaxRows) return 0;
-  return spx::CornerWs(nullptr, n).bytes;
+  return spx::LevelTableWs(nullptr, n).bytes;
 }
 
 int spx_point_corners(const float *points, int nfeat, const int32_t *batch_ids, int n_cap, const int32_t *n_points_dev,
@@ -295,67 +249,28 @@ int spx_point_corners(const float *points, int nfeat, const int32_t *batch_ids, 
                       const int32_t *n_live, int batch, const int *spatial_h, const void *rankmap, size_t rankmap_bytes,
                       int flags, int32_t *corner_rows, float *corner_w, void *ws, size_t ws_bytes, spx_stream_t stream) {
   using namespace spx;
-  if (int rc = check_corners(n_cap, nfeat, ndim, n, batch, flags)) return rc;
-  SPX_CHECK(vsize && coors_range && spatial_h, "vsize / coors_range / spatial shape is NULL");
-  unsigned long long cells_total = static_cast<unsigned long long>(batch);
-  for (int d = 0; d < ndim; ++d) {
-    SPX_CHECK(spatial_h[d] >= 1, "empty grid axis %d", d);
-    SPX_CHECK(vsize[d] > 0.f, "voxel size of axis %d must be positive", d);
-    SPX_CHECK(cells_total <= (0x7fffffffffffffffULL / static_cast<unsigned long long>(spatial_h[d])),
-              "the key space of batch x grid does not fit 63 bits");
-    cells_total *= static_cast<unsigned long long>(spatial_h[d]);
-  }
-  const size_t W = rankmap ? rank_words(ndim, batch, spatial_h) : 0;      // (the pointer's value, not its target)
-  SPX_CHECK(!rankmap || (W > 0 && rankmap_bytes >= rank_bytes(W)), "rank map too small for this level (%zu words)", W);
+  LevelLookup look;
+  if (int rc = check_level("points", ndim, nfeat, n, n_live, batch, spatial_h, vsize, coors_range, rankmap, rankmap_bytes,
+                           &look))
+    return rc;
+  if (int rc = check_table(n_cap, ndim, n)) return rc;
+  SPX_CHECK(flags == 0 || flags == 1, "flags must be 0 or 1 (normalise), got %d", flags);
   if (n_cap == 0) return 0;
   SPX_CHECK(points && corner_rows && corner_w && (n == 0 || indices), "points / indices / corner_rows / corner_w is NULL");
   SPX_CHECK(aligned_to(corner_rows, 16) && aligned_to(corner_w, 16), "corner_rows / corner_w not aligned to 16 bytes");
-  CornerGeom g;
-  g.level = LevelGeom(ndim, batch, spatial_h);
-  for (int d = 0; d < kDims; ++d) {              // the host arrays are zyx: point column j is axis ndim - 1 - j
-    g.vsize[d] = d < ndim ? vsize[ndim - 1 - d] : 1.f;
-    g.lo[d] = d < ndim ? coors_range[ndim - 1 - d] : 0.f;
-  }
+  const PointGeom g(ndim, batch, spatial_h, vsize, coors_range);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(div_up(n_cap, kBlock)), block(kBlock);
-  const int norm = flags & 1;
-  Table t = {};
-  if (rankmap) {
-    void *rm = const_cast<void *>(rankmap);
-    const uint2 *cells = static_cast<const uint2 *>(rm);
-    const int32_t *blockoff = rank_blockoff(rm, W);
-    if (ndim == 3)
-      hipLaunchKernelGGL((corner_kernel<3, true>), grid, block, 0, s, points, nfeat, batch_ids, n_cap, n_points_dev, g, n,
-                         n_live, cells, blockoff, t, norm, corner_rows, corner_w);
-    else
-      hipLaunchKernelGGL((corner_kernel<2, true>), grid, block, 0, s, points, nfeat, batch_ids, n_cap, n_points_dev, g, n,
-                         n_live, cells, blockoff, t, norm, corner_rows, corner_w);
-    SPX_LAUNCH_CHECK();
-    count_interp(kInterpCornersRanked);
-    return 0;
-  }
-  CornerWs w(ws, n);
-  SPX_CHECK(ws && ws_bytes >= w.bytes, "workspace too small: %zu < %zu", ws_bytes, w.bytes);
-  int dims4[4] = {1, 1, 1, 1};
-  for (int d = 0; d < ndim; ++d) dims4[d] = spatial_h[d];
-  table_place(t, w.keys, w.vals, w.cap, keys_fit_u32(batch, dims4, 4));
-  {
-    FillList fills;
-    table_fill(fills, t);
-    SPX_HIP(fills.launch(s));
-  }
-  if (n > 0) {
-    hipLaunchKernelGGL(corner_insert_kernel, dim3(div_up(n, kBlock)), block, 0, s, indices, n, n_live, g.level, t);
-    SPX_LAUNCH_CHECK();
-  }
-  if (ndim == 3)
-    hipLaunchKernelGGL((corner_kernel<3, false>), grid, block, 0, s, points, nfeat, batch_ids, n_cap, n_points_dev, g, n,
-                       n_live, nullptr, nullptr, t, norm, corner_rows, corner_w);
-  else
-    hipLaunchKernelGGL((corner_kernel<2, false>), grid, block, 0, s, points, nfeat, batch_ids, n_cap, n_points_dev, g, n,
-                       n_live, nullptr, nullptr, t, norm, corner_rows, corner_w);
+  const bool ranked = rankmap != nullptr;
+  if (!ranked)
+    if (int rc = build_level_table(ws, ws_bytes, indices, n, n_live, g.level, &look.table, s)) return rc;
+  dispatch_value<2, 3>(ndim, [&](auto nd) {
+    dispatch_value<0, 1>(ranked, [&](auto rk) {
+      hipLaunchKernelGGL((corner_kernel<nd, rk != 0>), dim3(div_up(n_cap, kBlock)), dim3(kBlock), 0, s, points, nfeat,
+                         batch_ids, n_cap, n_points_dev, g, look, flags & 1, corner_rows, corner_w);
+    });
+  });
   SPX_LAUNCH_CHECK();
-  count_interp(kInterpCornersHash);
+  count_interp(ranked ? kInterpCornersRanked : kInterpCornersHash);
   return 0;
 }
 

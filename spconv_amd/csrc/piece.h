@@ -1,9 +1,10 @@
 // Feature rows as PIECES: the storage / accumulator types of the four floating dtypes, the 16-byte (or one-element)
-// piece a lane moves, the index arithmetic of the group reductions' segment walk, and the host side of a row launch: the checks of a
+// piece a lane moves, the index arithmetic of the group reductions' segment walk and of an item = (row, piece) launch
+// (row_of), and the host side of a row launch: the checks of a
 // floating feature row, the way from (dtype, vec) to a kernel instance, the lanes of a group, the bits of a sort key,
 // the grid of a streaming launch.  Shared by the translation units that merge, reduce, score, interpolate or decorate
-// rows (union.hip, collapse.hip, select.hip, interp.hip, pointvoxel.hip, serialize.hip); every definition has internal
-// linkage.
+// rows (union.hip, collapse.hip, select.hip, interp.hip, query.hip, pointvoxel.hip, serialize.hip); every definition has
+// internal linkage.
 #pragma once
 #include <initializer_list>
 #include <type_traits>
@@ -81,6 +82,12 @@ __device__ __forceinline__ Segment segment_of(long long item, int gshift, int li
     g.end = g.end > limit ? limit : g.end;
   }
   return g;
+}
+
+// row of an item = (row, piece): a 32-bit division wherever the item count allows one
+__device__ __forceinline__ long long row_of(long long item, long long total, int pieces) {
+  return total <= 0x7fffffffLL ? static_cast<long long>(static_cast<unsigned>(item) / static_cast<unsigned>(pieces))
+                               : item / pieces;
 }
 
 inline bool aligned_to(const void *p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }

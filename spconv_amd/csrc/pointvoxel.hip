@@ -65,12 +65,6 @@ pv_offsets_kernel(const uint32_t *__restrict__ sortkey, const int32_t *__restric
   offsets[v] = static_cast<int32_t>(lo);
 }
 
-// row of an item = (row, piece): a 32-bit division wherever the item count allows one
-__device__ __forceinline__ long long row_of(long long item, long long total, int pieces) {
-  return total <= 0x7fffffffLL ? static_cast<long long>(static_cast<unsigned>(item) / static_cast<unsigned>(pieces))
-                               : item / pieces;
-}
-
 // -------------------------------------------------------------------------------------------- gather
 
 // One item per (point, piece), consecutive lanes on consecutive pieces of a row.  pshift >= 0: pieces = 1 << pshift.
@@ -144,14 +138,14 @@ pv_decorate_kernel(const float *__restrict__ points, int nfeat, long long total,
 }
 
 template <typename P>
-void launch_gather(const void *vfeat, int num_voxels, const int32_t *rows, int n_cap, int pieces, const void *fill16,
+void launch_gather(const void *vfeat, int num_voxels, const int32_t *rows, long long n_rows, int pieces, const void *fill16,
                    void *out, hipStream_t s) {
   P fill;
   memcpy(&fill, fill16, sizeof(P));
   int pshift = -1;
   for (int b = 0; b < 31; ++b)
     if (pieces == (1 << b)) pshift = b;
-  const long long total = static_cast<long long>(n_cap) * pieces;
+  const long long total = n_rows * pieces;
   hipLaunchKernelGGL(pv_gather_kernel<P>, dim3(stream_blocks(total, kBlock)), dim3(kBlock), 0, s,
                      static_cast<const P *>(vfeat), num_voxels, rows, total, pieces, pshift, fill, static_cast<P *>(out));
 }
@@ -170,6 +164,22 @@ struct GroupsWs {
 };
 
 }  // namespace
+
+// the gather declared in common.h (its callers: spx_voxel_to_point, spx_group_fwd of query.hip): 16-byte pieces where
+// the row's byte count and both pointers allow them, else one element of 1, 2, 4 or 8 bytes
+int gather_rows(const void *src, int n_src, const int32_t *rows, long long n_rows, int C, int elem_bytes,
+                const void *fill16, void *out, hipStream_t s) {
+  const long long row_bytes = static_cast<long long>(C) * elem_bytes;
+  const bool vec = row_bytes % 16 == 0 && aligned_to(src, 16) && aligned_to(out, 16);
+  if (vec) launch_gather<uint4>(src, n_src, rows, n_rows, static_cast<int>(row_bytes / 16), fill16, out, s);
+  else if (elem_bytes == 8) launch_gather<unsigned long long>(src, n_src, rows, n_rows, C, fill16, out, s);
+  else if (elem_bytes == 4) launch_gather<uint32_t>(src, n_src, rows, n_rows, C, fill16, out, s);
+  else if (elem_bytes == 2) launch_gather<uint16_t>(src, n_src, rows, n_rows, C, fill16, out, s);
+  else launch_gather<uint8_t>(src, n_src, rows, n_rows, C, fill16, out, s);
+  SPX_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace spx
 
 extern "C" {
@@ -220,17 +230,9 @@ int spx_voxel_to_point(const void *vfeat, int num_voxels, const int32_t *rows, i
   if (n_cap == 0) return 0;
   SPX_CHECK(rows && out && (num_voxels == 0 || vfeat), "vfeat / rows / out is NULL");
   SPX_CHECK(aligned_to(vfeat, elem_bytes) && aligned_to(out, elem_bytes), "pointer not aligned to its elements");
-  const long long row_bytes = static_cast<long long>(C) * elem_bytes;
-  const bool vec = row_bytes % 16 == 0 && aligned_to(vfeat, 16) && aligned_to(out, 16);
   unsigned char fill16[16];
   for (int b = 0; b < 16; ++b) fill16[b] = static_cast<unsigned char>((static_cast<unsigned long long>(fill_bits) >> (8 * (b % elem_bytes))) & 0xffu);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (vec) launch_gather<uint4>(vfeat, num_voxels, rows, n_cap, static_cast<int>(row_bytes / 16), fill16, out, s);
-  else if (elem_bytes == 8) launch_gather<unsigned long long>(vfeat, num_voxels, rows, n_cap, C, fill16, out, s);
-  else if (elem_bytes == 4) launch_gather<uint32_t>(vfeat, num_voxels, rows, n_cap, C, fill16, out, s);
-  else if (elem_bytes == 2) launch_gather<uint16_t>(vfeat, num_voxels, rows, n_cap, C, fill16, out, s);
-  else launch_gather<uint8_t>(vfeat, num_voxels, rows, n_cap, C, fill16, out, s);
-  SPX_LAUNCH_CHECK();
+  if (int rc = gather_rows(vfeat, num_voxels, rows, n_cap, C, elem_bytes, fill16, out, static_cast<hipStream_t>(stream))) return rc;
   count_pointvoxel(kPvGather);
   return 0;
 }

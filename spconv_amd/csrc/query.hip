@@ -11,23 +11,22 @@
 //             A query belongs to a GROUP of W = 2^wshift lanes (1 .. 64, chosen on the host from the window); the
 //             lanes of a group test the candidates of one round together and the round's hits take their slots in
 //             visiting order, so the result does not depend on W.  The group leaves once nsample slots are taken.
-//               hash form    a candidate is a CELL: a probe of the builders' table (table.h), built here from the
-//                            level's live rows; a ballot and a popcount of the lanes below give the slot.
+//               hash form    a candidate is a CELL: a probe of the builders' table (table.h), built by lookup.h from
+//                            the level's live rows; a ballot and a popcount of the lanes below give the slot.
 //               ranked form  a candidate is an X-RUN, the 2 * range + 1 (at most 31) cells of one line of the window:
 //                            one or two words of the rank map (rankmap.h) give its occupancy bits, the row of its
 //                            first occupied cell is the number of occupied cells before the run, later ones take
 //                            consecutive rows (the level is in key order).  A lane may bring several hits, so the
 //                            slots come from a prefix sum over the lanes of the group.
-//   forward   out[e] = vfeat[rows[e]] (zeros for -1): one item per (entry, piece), the bits moved unchanged.
+//   forward   out[e] = vfeat[rows[e]] (zeros for -1): gather_rows of pointvoxel.hip over the flattened rows, one item per
+//             (entry, piece), the bits moved unchanged.
 //   backward  dvfeat[v] = sum of dout[e] over the entries e of voxel v's group, the segment walk of piece.h over the
 //             transposed list (spx_point_groups over the flattened rows): no atomics, ascending e.
 // The radius test and the offsets are fp32 with every operation rounded on its own, so a host loop reproduces every
 // element bit for bit.
 #include "common.h"
-#include "fill.h"
+#include "lookup.h"
 #include "piece.h"
-#include "rankmap.h"
-#include "table.h"
 
 // no multiply-add pair of this unit may be contracted into an FMA (see pointvoxel.hip)
 #pragma clang fp contract(off)
@@ -36,17 +35,13 @@ namespace spx {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kDims = 3;              // ndim is 2 or 3
-constexpr int kMaxRows = 1 << 30;     // rows of a level: table_capacity(n) = 2^31 slots still fits its 32-bit mask
 constexpr int kMaxRange = 15;         // a window line of 31 cells spans at most two 32-cell words of the rank map
 constexpr int kMaxSample = 128;
 static_assert(kRankWords == 1 << 11, "blockoff is indexed by word >> 11");
 constexpr int kFlagRadius = 1, kFlagPadFirst = 2, kFlagWidthShift = 8;      // (flags >> 8: 0, or 1 + log2 of a forced W)
 
-struct QueryGeom {
-  LevelGeom level;                    // batch and grid extents, index-column (zyx) order
-  float vsize[kDims], lo[kDims];      // by POINT COLUMN (x, y, z): entry j belongs to grid axis ndim - 1 - j
-  int range[kDims];                   // by grid axis (index-column order)
+struct QueryGeom : PointGeom {
+  int range[kPointDims];              // by grid axis (index-column order)
 };
 
 struct QueryArgs {
@@ -55,23 +50,12 @@ struct QueryArgs {
   const int32_t *batch_ids;
   int n_cap;
   const int32_t *n_queries;
-  int n;
-  const int32_t *n_live;
   int wshift, nsample;
   float r2;
   int flags;
   int32_t *rows, *count;
   float *offsets;
 };
-
-// the live rows of the level into the table, by their linear key
-__global__ void __launch_bounds__(kBlock)
-query_insert_kernel(const int32_t *__restrict__ idx, int n, const int32_t *__restrict__ n_live, LevelGeom g, Table t) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n || (n_live && i >= *n_live)) return;
-  const long long key = level_key(idx + static_cast<size_t>(i) * (g.ndim + 1), g, kAllAxes);
-  if (key >= 0) table_insert_min(t, key, i);      // (a duplicate coordinate: the lowest row stays)
-}
 
 // A query: its batch, its own cell by grid axis, its coordinates by point column.
 template <int NDIM> struct Query {
@@ -84,9 +68,7 @@ template <int NDIM> struct Query {
 template <int NDIM>
 __device__ __forceinline__ Query<NDIM> load_query(const QueryArgs &a, const QueryGeom &g, long long qi) {
   Query<NDIM> r;
-  const int nq = a.n_queries ? *a.n_queries : a.n_cap;
-  r.b = qi < nq ? (a.batch_ids ? a.batch_ids[qi] : 0) : -1;
-  r.valid = r.b >= 0 && r.b < g.level.batch;
+  r.valid = point_batch(g, a.batch_ids, a.n_cap, a.n_queries, qi, r.b);
 #pragma unroll
   for (int j = 0; j < NDIM; ++j) {
     r.q[j] = 0.f;
@@ -97,9 +79,8 @@ __device__ __forceinline__ Query<NDIM> load_query(const QueryArgs &a, const Quer
 #pragma unroll
     for (int j = 0; j < NDIM; ++j) {
       r.q[j] = pt[j];
-      const float tj = (r.q[j] - g.lo[j]) / g.vsize[j];       // (corner_kernel's own expression: interp.hip)
-      const float cell = floorf(tj);
-      r.valid = r.valid && cell >= 0.f && cell < static_cast<float>(g.level.dims[NDIM - 1 - j]);      // (false for NaN)
+      float cell;
+      point_cell<NDIM>(g, j, r.q[j], cell, r.valid);
       r.cell[NDIM - 1 - j] = r.valid ? static_cast<int>(cell) : 0;
     }
   }
@@ -139,13 +120,13 @@ __device__ __forceinline__ void finish_query(const QueryArgs &a, long long qi, i
 // Hash form.  Lane `sub` of the group tests candidate base + sub of the round.
 template <int NDIM>
 __global__ void __launch_bounds__(kBlock)
-query_hash_kernel(QueryArgs a, QueryGeom g, Table t) {
+query_hash_kernel(QueryArgs a, QueryGeom g, LevelLookup look) {
   const long long qi = (static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x) >> a.wshift;
   if (qi >= a.n_cap) return;                                  // (a whole group: kBlock is a multiple of W)
   const int W = 1 << a.wshift, sub = threadIdx.x & (W - 1);
   const int gbase = (threadIdx.x & 63) & ~(W - 1);
   const unsigned long long gmask = W == 64 ? ~0ull : ((1ull << W) - 1ull);
-  const int live = a.n_live ? min(*a.n_live, a.n) : a.n;
+  const RowFinder<false> row_at(look);
   const Query<NDIM> q = load_query<NDIM>(a, g, qi);
   int ext[NDIM], total = 1;
 #pragma unroll
@@ -178,10 +159,7 @@ query_hash_kernel(QueryArgs a, QueryGeom g, Table t) {
           key = key * g.level.dims[d] + v;
           dj[NDIM - 1 - d] = centre_offset(g, NDIM - 1 - d, v, q.q[NDIM - 1 - d]);
         }
-        if (in && (!(a.flags & kFlagRadius) || dist2<NDIM>(dj) < a.r2)) {
-          const int r = table_find(t, key);
-          if (static_cast<unsigned>(r) < static_cast<unsigned>(live)) row = r;
-        }
+        if (in && (!(a.flags & kFlagRadius) || dist2<NDIM>(dj) < a.r2)) row = row_at(key);
       }
       const unsigned long long hits = (__ballot(row >= 0) >> gbase) & gmask;
       if (row >= 0) {
@@ -210,13 +188,15 @@ query_hash_kernel(QueryArgs a, QueryGeom g, Table t) {
 // every axis but the last, clipped to the grid.
 template <int NDIM>
 __global__ void __launch_bounds__(kBlock)
-query_ranked_kernel(QueryArgs a, QueryGeom g, const uint2 *__restrict__ cells, const int32_t *__restrict__ blockoff) {
+query_ranked_kernel(QueryArgs a, QueryGeom g, LevelLookup look) {
   const long long qi = (static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x) >> a.wshift;
   if (qi >= a.n_cap) return;
   const int W = 1 << a.wshift, sub = threadIdx.x & (W - 1);
   const int gbase = (threadIdx.x & 63) & ~(W - 1);
   const unsigned long long gmask = W == 64 ? ~0ull : ((1ull << W) - 1ull);
-  const int live = a.n_live ? min(*a.n_live, a.n) : a.n;
+  const int live = look.live();
+  const uint2 *cells = look.cells;                            // (the words themselves: an x-run reads one or two)
+  const int32_t *blockoff = look.blockoff;
   const Query<NDIM> q = load_query<NDIM>(a, g, qi);
   constexpr int X = NDIM - 1;                                 // the axis of a run; point column 0
   int ext[NDIM], runs = 1;
@@ -316,26 +296,6 @@ query_ranked_kernel(QueryArgs a, QueryGeom g, const uint2 *__restrict__ cells, c
 
 // -------------------------------------------------------------------------------------------- grouping
 
-// One item per (entry, piece): the piece of the entry's row, or zeros.
-template <int DT, int V>
-__global__ void __launch_bounds__(kBlock)
-group_fwd_kernel(const void *__restrict__ vfeat_, int n, const int32_t *__restrict__ rows, long long total, int pieces,
-                 void *__restrict__ out_) {
-  using P = Piece<typename Elem<DT>::S, V>;
-  const P *vfeat = static_cast<const P *>(vfeat_);
-  P *out = static_cast<P *>(out_);
-  for (long long item = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; item < total;
-       item += static_cast<long long>(gridDim.x) * kBlock) {
-    const long long e = total <= 0x7fffffffLL
-                            ? static_cast<long long>(static_cast<unsigned>(item) / static_cast<unsigned>(pieces))
-                            : item / pieces;
-    const int p = static_cast<int>(item - e * pieces);
-    const int r = rows[e];
-    if (static_cast<unsigned>(r) < static_cast<unsigned>(n)) out[item] = vfeat[static_cast<long long>(r) * pieces + p];
-    else out[item] = P{};
-  }
-}
-
 // Items = (voxel row, lane of its group), the segment walk of piece.h over the transposed list: entry e brings the
 // piece of dout row e.  (interp_bwd_kernel without the weight: its load and multiply would not fold away there.)
 template <int DT, int V>
@@ -388,21 +348,6 @@ group_bwd_kernel(const void *__restrict__ dout_, int entries, const int32_t *__r
 
 // -------------------------------------------------------------------------------------------- host side
 
-// scratch of a hash-form query: the table (room for the wide form, 12 bytes per slot)
-struct QueryWs {
-  hkey_t *keys;
-  int32_t *vals;
-  uint32_t cap;
-  size_t bytes;
-  QueryWs(void *ws, int n) {
-    Carver c(ws);
-    cap = table_capacity(static_cast<size_t>(n > 0 ? n : 0));
-    keys = c.take<hkey_t>(cap);
-    vals = c.take<int32_t>(cap);
-    bytes = c.off;
-  }
-};
-
 // 0 = ok: the checks of a query / grouping call over [n_cap, nsample] entries that need no pointer
 int check_entries(int n_cap, int nsample, int n) {
   SPX_CHECK(n_cap >= 0 && n >= 0, "bad query / row counts %d / %d", n_cap, n);
@@ -441,7 +386,7 @@ extern "C" {
 size_t spx_voxel_query_ws_bytes(int n_cap, int nsample, int ndim, int n, int ranked) {
   if ((ndim != 2 && ndim != 3) || n_cap < 0 || n < 0 || n > spx::kMaxRows) return 0;
   if (nsample < 1 || nsample > spx::kMaxSample || static_cast<long long>(n_cap) * nsample >= 0x80000000LL) return 0;
-  return ranked ? 0 : spx::QueryWs(nullptr, n).bytes;
+  return ranked ? 0 : spx::LevelTableWs(nullptr, n).bytes;
 }
 
 int spx_voxel_query(const float *queries, int nfeat, const int32_t *batch_ids, int n_cap, const int32_t *n_queries_dev,
@@ -450,75 +395,45 @@ int spx_voxel_query(const float *queries, int nfeat, const int32_t *batch_ids, i
                     const int *query_range, int nsample, float r2, int flags, int32_t *rows, int32_t *count,
                     float *offsets, void *ws, size_t ws_bytes, spx_stream_t stream) {
   using namespace spx;
-  SPX_CHECK(ndim == 2 || ndim == 3, "ndim must be 2 or 3, got %d", ndim);
+  LevelLookup look;
+  if (int rc = check_level("queries", ndim, nfeat, n, n_live, batch, spatial_h, vsize, coors_range, rankmap, rankmap_bytes,
+                           &look))
+    return rc;
   if (int rc = check_entries(n_cap, nsample, n)) return rc;
-  SPX_CHECK(n <= kMaxRows, "at most 2^30 voxel rows (the table holds two slots per row), got %d", n);
-  SPX_CHECK(nfeat >= ndim, "queries need at least %d columns, got %d", ndim, nfeat);
-  SPX_CHECK(batch >= 1, "batch must be >= 1, got %d", batch);
   SPX_CHECK((flags & ~(kFlagRadius | kFlagPadFirst | (7 << kFlagWidthShift))) == 0,
             "flags must be radius (1) | pad first (2) | a group width (log2 + 1) << 8, got %d", flags);
   SPX_CHECK(!(flags & kFlagRadius) || r2 >= 0.f, "the squared radius must be >= 0 (and no NaN)");
-  SPX_CHECK(vsize && coors_range && spatial_h && query_range, "vsize / coors_range / spatial shape / query_range is NULL");
-  unsigned long long cells_total = static_cast<unsigned long long>(batch);
+  SPX_CHECK(query_range, "query_range is NULL");
+  QueryGeom g{PointGeom(ndim, batch, spatial_h, vsize, coors_range), {}};
   int window = 1, runs = 1;
-  for (int d = 0; d < ndim; ++d) {
-    SPX_CHECK(spatial_h[d] >= 1, "empty grid axis %d", d);
-    SPX_CHECK(vsize[d] > 0.f, "voxel size of axis %d must be positive", d);
-    SPX_CHECK(query_range[d] >= 0 && query_range[d] <= kMaxRange, "query_range of axis %d must be in 0 .. %d, got %d", d,
-              kMaxRange, query_range[d]);
-    SPX_CHECK(cells_total <= (0x7fffffffffffffffULL / static_cast<unsigned long long>(spatial_h[d])),
-              "the key space of batch x grid does not fit 63 bits");
-    cells_total *= static_cast<unsigned long long>(spatial_h[d]);
-    window *= 2 * query_range[d] + 1;
-    if (d < ndim - 1) runs *= 2 * query_range[d] + 1;
+  for (int d = 0; d < kPointDims; ++d) {
+    g.range[d] = d < ndim ? query_range[d] : 0;
+    SPX_CHECK(g.range[d] >= 0 && g.range[d] <= kMaxRange, "query_range of axis %d must be in 0 .. %d, got %d", d, kMaxRange,
+              g.range[d]);
+    window *= 2 * g.range[d] + 1;
+    if (d < ndim - 1) runs *= 2 * g.range[d] + 1;
   }
-  const size_t W = rankmap ? rank_words(ndim, batch, spatial_h) : 0;      // (the pointer's value, not its target)
-  SPX_CHECK(!rankmap || (W > 0 && rankmap_bytes >= rank_bytes(W)), "rank map too small for this level (%zu words)", W);
   if (n_cap == 0) return 0;
   SPX_CHECK(queries && rows && count && (n == 0 || indices), "queries / indices / rows / count is NULL");
   SPX_CHECK(aligned_to(queries, 4) && aligned_to(rows, 4) && aligned_to(count, 4) && aligned_to(offsets, 4),
             "pointer not aligned to its elements");
-  QueryGeom g;
-  g.level = LevelGeom(ndim, batch, spatial_h);
-  for (int d = 0; d < kDims; ++d) {              // the host arrays are zyx: point column j is axis ndim - 1 - j
-    g.vsize[d] = d < ndim ? vsize[ndim - 1 - d] : 1.f;
-    g.lo[d] = d < ndim ? coors_range[ndim - 1 - d] : 0.f;
-    g.range[d] = d < ndim ? query_range[d] : 0;
-  }
-  QueryArgs a = {queries, nfeat, batch_ids, n_cap, n_queries_dev, n, n_live, 0, nsample, r2, flags, rows, count, offsets};
+  QueryArgs a = {queries, nfeat, batch_ids, n_cap, n_queries_dev, 0, nsample, r2, flags, rows, count, offsets};
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 block(kBlock);
   auto grid = [&](int wshift) { return dim3(static_cast<unsigned>(((static_cast<long long>(n_cap) << wshift) + kBlock - 1) / kBlock)); };
   if (rankmap) {
-    void *rm = const_cast<void *>(rankmap);
-    const uint2 *cells = static_cast<const uint2 *>(rm);
-    const int32_t *blockoff = rank_blockoff(rm, W);
     a.wshift = width_shift(runs, 3, flags);
     dispatch_value<2, 3>(ndim, [&](auto nd) {
-      hipLaunchKernelGGL((query_ranked_kernel<nd>), grid(a.wshift), block, 0, s, a, g, cells, blockoff);
+      hipLaunchKernelGGL((query_ranked_kernel<nd>), grid(a.wshift), block, 0, s, a, g, look);
     });
     SPX_LAUNCH_CHECK();
     count_query(kQueryRanked);
     return 0;
   }
-  QueryWs w(ws, n);
-  SPX_CHECK(ws && ws_bytes >= w.bytes, "workspace too small: %zu < %zu", ws_bytes, w.bytes);
-  Table t = {};
-  int dims4[4] = {1, 1, 1, 1};
-  for (int d = 0; d < ndim; ++d) dims4[d] = spatial_h[d];
-  table_place(t, w.keys, w.vals, w.cap, keys_fit_u32(batch, dims4, 4));
-  {
-    FillList fills;
-    table_fill(fills, t);
-    SPX_HIP(fills.launch(s));
-  }
-  if (n > 0) {
-    hipLaunchKernelGGL(query_insert_kernel, dim3(div_up(n, kBlock)), block, 0, s, indices, n, n_live, g.level, t);
-    SPX_LAUNCH_CHECK();
-  }
+  if (int rc = build_level_table(ws, ws_bytes, indices, n, n_live, g.level, &look.table, s)) return rc;
   a.wshift = width_shift(window, 2, flags);
   dispatch_value<2, 3>(ndim, [&](auto nd) {
-    hipLaunchKernelGGL((query_hash_kernel<nd>), grid(a.wshift), block, 0, s, a, g, t);
+    hipLaunchKernelGGL((query_hash_kernel<nd>), grid(a.wshift), block, 0, s, a, g, look);
   });
   SPX_LAUNCH_CHECK();
   count_query(kQueryHash);
@@ -533,15 +448,10 @@ int spx_group_fwd(const void *vfeat, int n, const int32_t *rows, int n_cap, int 
   if (n_cap == 0) return 0;
   SPX_CHECK(rows && out && (n == 0 || vfeat), "vfeat / rows / out is NULL");
   SPX_CHECK(aligned_to(vfeat, eb) && aligned_to(out, eb) && aligned_to(rows, 4), "pointer not aligned to its elements");
-  const bool vec = (static_cast<long long>(C) * eb) % 16 == 0 && aligned_to(vfeat, 16) && aligned_to(out, 16);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dispatch_row(dtype, vec, [&](auto dt, auto v) {
-    const int pieces = C / v;
-    const long long total = static_cast<long long>(n_cap) * nsample * pieces;
-    hipLaunchKernelGGL((group_fwd_kernel<dt, v>), dim3(stream_blocks(total, kBlock)), dim3(kBlock), 0, s, vfeat, n, rows,
-                       total, pieces, out);
-  });
-  SPX_LAUNCH_CHECK();
+  const unsigned char zeros[16] = {};             // (the gather of pointvoxel.hip: the bits moved, zeros for a row of -1)
+  if (int rc = gather_rows(vfeat, n, rows, static_cast<long long>(n_cap) * nsample, C, eb, zeros, out,
+                           static_cast<hipStream_t>(stream)))
+    return rc;
   count_query(kQueryGroupFwd);
   return 0;
 }

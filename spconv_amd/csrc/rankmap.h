@@ -1,8 +1,8 @@
 // A LEVEL and its RANK MAP ("outputs numbered by KEY RANK"): the level's geometry and the linear key of an index row;
 // the map's layout in the caller's buffer, the lookup, and the numbering that builds it from a byte-per-cell occupancy
 // map (prefix pass + totals scan, with the head of the scratch it needs).  Shared by the translation units that build
-// or read one (rulebook_sorted.hip, rulebook_subm.hip, voxelize.hip, union.hip, collapse.hip, select.hip, interp.hip);
-// every definition has internal linkage.
+// or read one (rulebook_sorted.hip, rulebook_subm.hip, voxelize.hip, union.hip, collapse.hip, select.hip, and through
+// lookup.h interp.hip and query.hip); every definition has internal linkage.
 #pragma once
 #include "common.h"
 #include "scan.h"

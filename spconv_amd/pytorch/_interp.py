@@ -16,7 +16,6 @@ gives none either).
 """
 from __future__ import annotations
 
-import ctypes
 from typing import NamedTuple, Optional, Sequence
 
 import torch
@@ -24,9 +23,10 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from spconv_amd import _lib
-from spconv_amd.pytorch import _pointvoxel
+from spconv_amd.pytorch._level import _floats, _geometry, check_points, flat_groups, grad_rows, groups_missing
+from spconv_amd.pytorch._level import flat_groups as corner_groups  # noqa: F401  (the name tests and tools reach)
 from spconv_amd.pytorch._pointvoxel import PointGroups
-from spconv_amd.pytorch._rulebook import _check_count, _float_code, _ptr, _rankmap_of, _require_gpu, _stream, _ws
+from spconv_amd.pytorch._rulebook import _float_code, _ptr, _require_gpu, _stream, _ws
 
 
 class PointCorners(NamedTuple):
@@ -40,30 +40,6 @@ class PointCorners(NamedTuple):
     num_voxels: int
     n_points: Optional[torch.Tensor] = None
     n_live: Optional[torch.Tensor] = None
-
-
-def _floats(values):
-    return (ctypes.c_float * len(values))(*values)
-
-
-def _geometry(vsize_xyz: Sequence[float], coors_range_xyz: Sequence[float], what: str = "point_corners"):
-    from spconv_amd.pytorch.utils import calc_point2voxel_meta_data
-    ndim = len(vsize_xyz)
-    if ndim not in (2, 3):
-        raise ValueError(f"{what}: ndim must be 2 or 3, got {ndim}")
-    if len(coors_range_xyz) != 2 * ndim:
-        raise ValueError(f"{what}: coors_range_xyz holds {2 * ndim} values for ndim = {ndim}")
-    if not min(float(v) for v in vsize_xyz) > 0:
-        raise ValueError(f"{what}: voxel sizes must be positive, got {list(vsize_xyz)}")
-    vsize, _, _, coors_range = calc_point2voxel_meta_data(list(vsize_xyz), list(coors_range_xyz))
-    return ndim, vsize, coors_range
-
-
-def level_rankmap(indices: torch.Tensor, batch_size: int, spatial_shape) -> Optional[torch.Tensor]:
-    """The rank map attached to exactly this index tensor, if it describes this level and the tensor has not been
-    written since (``_rulebook._rankmap_of``'s validation).  That function also gates on a layer's kernel volume, which
-    means nothing for a lookup: 27 is passed only because it is inside the gate."""
-    return _rankmap_of(indices, int(batch_size), spatial_shape, int(indices.shape[0]), 27)
 
 
 def corners_ws_bytes(n_cap: int, ndim: int, n: int) -> int:
@@ -86,13 +62,6 @@ def point_corners_into(points: torch.Tensor, batch_ids: Optional[torch.Tensor], 
         _stream(points)))
 
 
-def corner_groups(rows: torch.Tensor, num_voxels: int, n_live: Optional[torch.Tensor] = None) -> Optional[PointGroups]:
-    """The transposed corner list: ``spx_point_groups`` over the flattened table (None for an empty table or level)."""
-    if rows.numel() == 0 or num_voxels < 1:
-        return None
-    return _pointvoxel.point_groups(rows.reshape(-1), num_voxels, None, n_live)
-
-
 def point_corners(points: torch.Tensor, batch_ids: Optional[torch.Tensor], x, vsize_xyz: Sequence[float],
                   coors_range_xyz: Sequence[float], normalize: bool = True, n_points: Optional[torch.Tensor] = None,
                   with_groups: Optional[bool] = None) -> PointCorners:
@@ -106,40 +75,21 @@ def point_corners(points: torch.Tensor, batch_ids: Optional[torch.Tensor], x, vs
     the hash table otherwise; a static tensor's n_live_dev is passed through.  with_groups (default: x's features
     require a gradient) builds the transposed list the gradient in the voxel rows walks.  No gradient with respect to
     the points: raw coordinates need none."""
-    _require_gpu(points, "points")
     ndim, vsize, coors_range = _geometry(vsize_xyz, coors_range_xyz)
-    indices, spatial_shape, B = x.indices, [int(v) for v in x.spatial_shape], int(x.batch_size)
-    _require_gpu(indices, "indices")
-    if len(spatial_shape) != ndim:
-        raise ValueError(f"point_corners: the level has {len(spatial_shape)} spatial axes, vsize_xyz {ndim}")
-    if points.dim() != 2 or points.dtype != torch.float32 or points.shape[1] < ndim:
-        raise ValueError(f"point_corners: points is a float32 tensor [N, >= {ndim}], got {tuple(points.shape)} {points.dtype}")
-    if indices.dtype != torch.int32 or indices.dim() != 2 or indices.shape[1] != ndim + 1:
-        raise ValueError(f"point_corners: indices is an int32 tensor [n, {ndim + 1}]")
-    N, n, K = int(points.shape[0]), int(indices.shape[0]), 1 << ndim
-    if N * K >= 1 << 31:
-        raise ValueError(f"point_corners: {N} points x {K} corners do not fit 32-bit entries")
-    if batch_ids is not None:
-        if batch_ids.shape != (N,) or batch_ids.dtype != torch.int32 or not batch_ids.is_cuda:
-            raise ValueError("point_corners: batch_ids is a CUDA int32 tensor [N]")
-        batch_ids = batch_ids.contiguous()
-    _check_count(n_points, "point_corners: n_points")
-    n_live = getattr(x, "n_live_dev", None)
-    _check_count(n_live, "point_corners: n_live")
-    if with_groups is None:
-        with_groups = bool(x.features.requires_grad and torch.is_grad_enabled())
-    dev = points.device
+    K = 1 << ndim
+    indices, spatial_shape, B, n_live, rankmap, with_groups = check_points("point_corners", "points", points, batch_ids,
+                                                                           n_points, x, ndim, K, with_groups)
+    N, n, dev = int(points.shape[0]), int(indices.shape[0]), points.device
     with torch.cuda.device(dev), torch.no_grad():
         points = points.detach().contiguous()
-        rankmap = level_rankmap(indices, B, spatial_shape)
-        indices = indices.contiguous()
+        batch_ids = None if batch_ids is None else batch_ids.contiguous()
         rows = torch.empty((N, K), dtype=torch.int32, device=dev)
         weights = torch.empty((N, K), dtype=torch.float32, device=dev)
         if N > 0:
             ws = None if rankmap is not None else _ws(corners_ws_bytes(N, ndim, n), dev)
             point_corners_into(points, batch_ids, n_points, _floats(vsize), _floats(coors_range), indices, n_live, B,
                                spatial_shape, rankmap, normalize, rows, weights, ws)
-        groups = corner_groups(rows, n, n_live) if with_groups else None
+        groups = flat_groups(rows, n, n_live) if with_groups else None
     return PointCorners(rows, weights, groups, n, n_points, n_live)
 
 
@@ -159,20 +109,13 @@ def interp_fwd(vfeat: torch.Tensor, corners: PointCorners) -> torch.Tensor:
 def interp_bwd(dout: torch.Tensor, corners: PointCorners) -> torch.Tensor:
     """dvfeat[v] = sum over the entries e of voxel v's group of weights_flat[e] * dout[e // K], in ascending e
     (spx_interp_bwd: one launch, no atomics); zeros for an empty group and for rows at or beyond *n_live."""
-    dt = _float_code(dout, "voxels_to_points_trilinear")
-    dout = dout.contiguous()
-    N, K = (int(v) for v in corners.rows.shape)
-    n, C = corners.num_voxels, int(dout.shape[1])
-    g = corners.groups
-    if n == 0 or C == 0 or N == 0:
-        return torch.zeros((n, C), dtype=dout.dtype, device=dout.device)
-    if g is None or g.offsets is None:
-        raise ValueError("voxels_to_points_trilinear: a gradient needs the corner groups; call point_corners with "
-                         "with_groups=True")
-    dvfeat = torch.empty((n, C), dtype=dout.dtype, device=dout.device)
-    _lib.check(_lib.load().spx_interp_bwd(dout.data_ptr(), N, K.bit_length() - 1, corners.weights.data_ptr(),
-                                          g.offsets.data_ptr(), g.list.data_ptr(), n, _ptr(corners.n_live), C, dt,
-                                          dvfeat.data_ptr(), _stream(dout)))
+    dt, dout, dvfeat, g = grad_rows("voxels_to_points_trilinear", dout, corners, "corner", "point_corners")
+    if g is not None:
+        N, K = corners.rows.shape
+        _lib.check(_lib.load().spx_interp_bwd(dout.data_ptr(), N, K.bit_length() - 1, corners.weights.data_ptr(),
+                                              g.offsets.data_ptr(), g.list.data_ptr(), corners.num_voxels,
+                                              _ptr(corners.n_live), int(dout.shape[1]), dt, dvfeat.data_ptr(),
+                                              _stream(dout)))
     return dvfeat
 
 
@@ -204,6 +147,5 @@ def voxels_to_points_trilinear(vfeat: torch.Tensor, corners: PointCorners) -> to
         if not (vfeat.requires_grad and torch.is_grad_enabled()):
             return interp_fwd(vfeat, corners)
         if corners.groups is None and corners.rows.numel() > 0 and corners.num_voxels > 0:
-            raise ValueError("voxels_to_points_trilinear: a gradient needs the corner groups; call point_corners with "
-                             "with_groups=True")
+            raise groups_missing("voxels_to_points_trilinear", "corner", "point_corners")
         return TrilinearFunction.apply(vfeat, corners)

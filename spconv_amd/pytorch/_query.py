@@ -23,10 +23,10 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from spconv_amd import _lib
-from spconv_amd.pytorch import _pointvoxel
-from spconv_amd.pytorch._interp import _floats, _geometry, level_rankmap
+from spconv_amd.pytorch._level import _floats, _geometry, check_points, flat_groups, grad_rows, groups_missing
+from spconv_amd.pytorch._level import flat_groups as neighbor_groups, level_rankmap  # noqa: F401  (names tests and tools reach)
 from spconv_amd.pytorch._pointvoxel import PointGroups
-from spconv_amd.pytorch._rulebook import _check_count, _float_code, _ptr, _require_gpu, _stream, _ws
+from spconv_amd.pytorch._rulebook import _float_code, _ptr, _require_gpu, _stream, _ws
 
 MAX_RANGE, MAX_NSAMPLE = 15, 128
 _FLAG_RADIUS, _FLAG_PAD_FIRST = 1, 2
@@ -97,13 +97,6 @@ def voxel_query_into(queries: torch.Tensor, batch_ids: Optional[torch.Tensor], n
         _ptr(offsets), _ptr(ws), 0 if ws is None else ws.numel(), _stream(queries)))
 
 
-def neighbor_groups(rows: torch.Tensor, num_voxels: int, n_live: Optional[torch.Tensor] = None) -> Optional[PointGroups]:
-    """The transposed list: ``spx_point_groups`` over the flattened rows (None for an empty table or level)."""
-    if rows.numel() == 0 or num_voxels < 1:
-        return None
-    return _pointvoxel.point_groups(rows.reshape(-1), num_voxels, None, n_live)
-
-
 def voxel_query(queries: torch.Tensor, batch_ids: Optional[torch.Tensor], x, vsize_xyz: Sequence[float],
                 coors_range_xyz: Sequence[float], query_range: Sequence[int], nsample: int,
                 radius: Optional[float] = None, pad: str = "none", with_offsets: bool = False,
@@ -124,35 +117,15 @@ def voxel_query(queries: torch.Tensor, batch_ids: Optional[torch.Tensor], x, vsi
     n_live_dev is passed through.  with_groups (default: x's features require a gradient) builds the transposed list
     the gradient of ``group_voxels`` walks.  No gradient with respect to the queries: raw coordinates need none."""
     ndim, vsize, coors_range = _geometry(vsize_xyz, coors_range_xyz, "voxel_query")
-    indices, spatial_shape, B = x.indices, [int(v) for v in x.spatial_shape], int(x.batch_size)
-    if len(spatial_shape) != ndim:
-        raise ValueError(f"voxel_query: the level has {len(spatial_shape)} spatial axes, vsize_xyz {ndim} (ndim mismatch)")
     query_range = _check_window(query_range, nsample, ndim, pad)
     r2 = squared_radius(radius)
-    if queries.dim() != 2 or queries.dtype != torch.float32 or queries.shape[1] < ndim:
-        raise ValueError(f"voxel_query: queries is a float32 tensor [M, >= {ndim}], got {tuple(queries.shape)} {queries.dtype}")
-    if indices.dtype != torch.int32 or indices.dim() != 2 or indices.shape[1] != ndim + 1:
-        raise ValueError(f"voxel_query: indices is an int32 tensor [n, {ndim + 1}]")
-    M, n, nsample = int(queries.shape[0]), int(indices.shape[0]), int(nsample)
-    if M * nsample >= 1 << 31:
-        raise ValueError(f"voxel_query: {M} queries x {nsample} samples do not fit 32-bit entries")
-    if batch_ids is not None and (batch_ids.shape != (M,) or batch_ids.dtype != torch.int32):
-        raise ValueError("voxel_query: batch_ids is a CUDA int32 tensor [M]")
-    _require_gpu(queries, "queries")
-    _require_gpu(indices, "indices")
-    if batch_ids is not None:
-        _require_gpu(batch_ids, "batch_ids")
-        batch_ids = batch_ids.contiguous()
-    _check_count(n_queries, "voxel_query: n_queries")
-    n_live = getattr(x, "n_live_dev", None)
-    _check_count(n_live, "voxel_query: n_live")
-    if with_groups is None:
-        with_groups = bool(x.features.requires_grad and torch.is_grad_enabled())
-    dev = queries.device
+    nsample = int(nsample)
+    indices, spatial_shape, B, n_live, rankmap, with_groups = check_points("voxel_query", "queries", queries, batch_ids,
+                                                                           n_queries, x, ndim, nsample, with_groups)
+    M, n, dev = int(queries.shape[0]), int(indices.shape[0]), queries.device
     with torch.cuda.device(dev), torch.no_grad():
         queries = queries.detach().contiguous()
-        rankmap = level_rankmap(indices, B, spatial_shape)
-        indices = indices.contiguous()
+        batch_ids = None if batch_ids is None else batch_ids.contiguous()
         rows = torch.empty((M, nsample), dtype=torch.int32, device=dev)
         count = torch.empty((M,), dtype=torch.int32, device=dev)
         offsets = torch.empty((M, nsample, ndim), dtype=torch.float32, device=dev) if with_offsets else None
@@ -160,7 +133,7 @@ def voxel_query(queries: torch.Tensor, batch_ids: Optional[torch.Tensor], x, vsi
             ws = None if rankmap is not None else _ws(query_ws_bytes(M, nsample, ndim, n, False), dev)
             voxel_query_into(queries, batch_ids, n_queries, _floats(vsize), _floats(coors_range), indices, n_live, B,
                              spatial_shape, rankmap, query_range, nsample, r2, pad == "first", rows, count, offsets, ws)
-        groups = neighbor_groups(rows, n, n_live) if with_groups else None
+        groups = flat_groups(rows, n, n_live) if with_groups else None
     return VoxelNeighbors(rows, count, offsets, groups, n, n_queries, n_live)
 
 
@@ -180,18 +153,11 @@ def group_fwd(vfeat: torch.Tensor, nb: VoxelNeighbors) -> torch.Tensor:
 def group_bwd(dout: torch.Tensor, nb: VoxelNeighbors) -> torch.Tensor:
     """dvfeat[v] = sum of dout[e] over the entries e of voxel v's group, in ascending e (spx_group_bwd: one launch, no
     atomics); zeros for an empty group and for rows at or beyond *n_live."""
-    dt = _float_code(dout, "group_voxels")
-    dout = dout.contiguous()
-    M, S = (int(v) for v in nb.rows.shape)
-    n, C = nb.num_voxels, int(dout.shape[-1])
-    g = nb.groups
-    if n == 0 or C == 0 or M == 0:
-        return torch.zeros((n, C), dtype=dout.dtype, device=dout.device)
-    if g is None or g.offsets is None:
-        raise ValueError("group_voxels: a gradient needs the neighbour groups; call voxel_query with with_groups=True")
-    dvfeat = torch.empty((n, C), dtype=dout.dtype, device=dout.device)
-    _lib.check(_lib.load().spx_group_bwd(dout.data_ptr(), M, S, g.offsets.data_ptr(), g.list.data_ptr(), n,
-                                         _ptr(nb.n_live), C, dt, dvfeat.data_ptr(), _stream(dout)))
+    dt, dout, dvfeat, g = grad_rows("group_voxels", dout, nb, "neighbour", "voxel_query")
+    if g is not None:
+        M, S = nb.rows.shape
+        _lib.check(_lib.load().spx_group_bwd(dout.data_ptr(), M, S, g.offsets.data_ptr(), g.list.data_ptr(), nb.num_voxels,
+                                             _ptr(nb.n_live), int(dout.shape[-1]), dt, dvfeat.data_ptr(), _stream(dout)))
     return dvfeat
 
 
@@ -218,7 +184,7 @@ def group_voxels(vfeat: torch.Tensor, nb: VoxelNeighbors) -> torch.Tensor:
     _float_code(vfeat, "group_voxels")
     needs_grad = vfeat.requires_grad and torch.is_grad_enabled()
     if needs_grad and nb.groups is None and nb.rows.numel() > 0 and nb.num_voxels > 0:
-        raise ValueError("group_voxels: a gradient needs the neighbour groups; call voxel_query with with_groups=True")
+        raise groups_missing("group_voxels", "neighbour", "voxel_query")
     _require_gpu(vfeat, "voxel features")
     with torch.cuda.device(vfeat.device):
         if not needs_grad:

@@ -115,8 +115,8 @@ class TrilinearDevoxelize(torch.nn.Module):
 
     def __init__(self, vsize_xyz: Sequence[float], coors_range_xyz: Sequence[float], normalize: bool = True):
         super().__init__()
-        from spconv_amd.pytorch import _interp
-        _interp._geometry(vsize_xyz, coors_range_xyz)
+        from spconv_amd.pytorch import _level
+        _level._geometry(vsize_xyz, coors_range_xyz)
         self.vsize_xyz = [float(v) for v in vsize_xyz]
         self.coors_range_xyz = [float(v) for v in coors_range_xyz]
         self.normalize = bool(normalize)
@@ -152,8 +152,8 @@ class VoxelQueryAndGroup(torch.nn.Module):
     def __init__(self, query_range: Sequence[int], nsample: int, radius: Optional[float] = None, use_xyz: bool = True, *,
                  vsize_xyz: Sequence[float], coors_range_xyz: Sequence[float]):
         super().__init__()
-        from spconv_amd.pytorch import _query
-        ndim, _, _ = _query._geometry(vsize_xyz, coors_range_xyz, "VoxelQueryAndGroup")
+        from spconv_amd.pytorch import _level, _query
+        ndim, _, _ = _level._geometry(vsize_xyz, coors_range_xyz, "VoxelQueryAndGroup")
         self.query_range = _query._check_window(query_range, nsample, ndim, "first")
         _query.squared_radius(radius)
         self.nsample = int(nsample)

@@ -276,7 +276,7 @@ class StaticPointToVoxel(object):
         scratch are allocated once per (index tensor, level shape, normalize, with_groups), at first use -- a second call
         with the same four overwrites the first one's result -- so the call can be recorded in a stream
         capture behind ``run()``.  No gradient with respect to the points."""
-        from spconv_amd.pytorch import _interp, _pointvoxel
+        from spconv_amd.pytorch import _interp, _level, _pointvoxel
         if x is None:
             indices, shape, B, n_live = self.indices, list(self.grid_size), self.batch_size, self.n_voxels[0:1]
             vsize_xyz = self.vsize_xyz if vsize_xyz is None else vsize_xyz
@@ -285,12 +285,12 @@ class StaticPointToVoxel(object):
                 raise ValueError("point_corners: a level other than the voxeliser's own needs its voxel size (vsize_xyz)")
             indices, shape, B = x.indices, [int(v) for v in x.spatial_shape], int(x.batch_size)
             n_live = getattr(x, "n_live_dev", None)
-        ndim, vsize, coors_range = _interp._geometry(vsize_xyz, self.coors_range_xyz)
+        ndim, vsize, coors_range = _level._geometry(vsize_xyz, self.coors_range_xyz)
         if ndim != self.ndim or len(shape) != ndim or B != self.batch_size:
             raise ValueError("point_corners: the level does not match the voxeliser's dimensions or batch size")
         n, K, N = int(indices.shape[0]), 1 << ndim, self.max_num_points
         with torch.cuda.device(self.device):
-            rankmap = _interp.level_rankmap(indices, B, shape)
+            rankmap = _level.level_rankmap(indices, B, shape)
             key = (indices.data_ptr(), tuple(shape), n, rankmap is None, bool(normalize), bool(with_groups))
             cache = self._corners
             if key not in cache:
@@ -306,9 +306,9 @@ class StaticPointToVoxel(object):
                               u8(self._L.spx_point_groups_ws_bytes(N * K, n)))
                 cache[key] = (rows, weights, ws, groups)
             rows, weights, ws, groups = cache[key]
-            f = lambda v: (ctypes.c_float * len(v))(*v)
-            _interp.point_corners_into(self.points, self.batch_ids, self.n_points, f(vsize), f(coors_range),
-                                       indices, n_live, B, shape, rankmap, normalize, rows, weights, ws)
+            _interp.point_corners_into(self.points, self.batch_ids, self.n_points, _level._floats(vsize),
+                                       _level._floats(coors_range), indices, n_live, B, shape, rankmap, normalize, rows,
+                                       weights, ws)
             g = None
             if groups is not None:
                 g, gws = groups
