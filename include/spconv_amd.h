@@ -117,6 +117,7 @@ int spx_set_option(const char *name_h, int value);
  *   query/ranked, query/hash, query/group_fwd, query/group_bwd
  *                                                  voxel query and grouping: calls of spx_voxel_query by lookup form,
  *                                                  of spx_group_fwd and of spx_group_bwd
+ *   sample/fps, sample/ball_query                  raw-point sampling: calls of spx_fps and of spx_ball_query that launch
  *   select/score, select/hist, select/pick, select/ties, select/flags, select/count, select/scan, select/scatter,
  *   select/map                                     voxel pruning, one count per launch: spx_row_score; the passes of
  *                                                  spx_topk_flags (hist and pick once per 8-bit digit: four each; ties:
@@ -1142,6 +1143,53 @@ int spx_group_fwd(const void *vfeat, int n, const int32_t *rows, int n_cap, int 
                   spx_stream_t stream);
 int spx_group_bwd(const void *dout, int n_cap, int nsample, const int32_t *offsets, const int32_t *list, int n,
                   const int32_t *n_live, int C, int dtype, void *dvfeat, spx_stream_t stream);
+
+/* ---- farthest-point sampling and ball query over raw points (csrc/sample.hip) -------------------------------
+ * The keypoint stage of the point-voxel detectors (PV-RCNN, PV-RCNN++, Voxel R-CNN's raw-point source): keypoints are
+ * chosen from the raw cloud by farthest-point sampling, and every keypoint collects the first `nsample` raw points
+ * inside a radius -- the furthest_point_sample / ball_query extensions of pointnet2_stack.  The rows a ball query
+ * returns are what spx_group_fwd / spx_group_bwd take, with the points as the "level".  Every call: the caller
+ * allocates, nothing is read back, nothing synchronises, every grid depends on host-known sizes only (hipGraph-safe).
+ * The argument checks that need no pointer come before any pointer is looked at.  No gradient with respect to
+ * coordinates.
+ *
+ * SCENES.  points = fp32 [n_cap, nfeat], the first ndim (2 or 3) columns x, y, z.  offsets int32 [batch + 1] and list
+ * int32 [n_cap] are spx_point_groups(ids = the points' batch ids, num_voxels = batch): the points of scene b are
+ * list[offsets[b] .. offsets[b + 1]), in ascending point index; ids outside [0, batch) and rows at or beyond the
+ * device point count given to spx_point_groups are in no scene.  A point is additionally INVALID when one of its
+ * first ndim coordinates is not finite; an invalid point is never a sample and never a hit.  All distances are fp32
+ * with every operation rounded on its own (no FMA):
+ *     d2 = (d_0 * d_0 + d_1 * d_1) + d_2 * d_2          (ndim 2: d_0 * d_0 + d_1 * d_1)
+ *
+ *   spx_fps: num_samples = K in 1 .. 65536, the same for every scene.  Per scene: slot 0 is the lowest valid point
+ *   index; every valid point keeps t[i], +inf at first; at each step, with c the last chosen point and d_j = p_j[i] -
+ *   p_j[c], t[i] = d2 < t[i] ? d2 : t[i], and the next sample is the not-yet-chosen valid point with the largest t,
+ *   ties to the LOWEST point index.  A chosen point stops being a candidate, so the indices of a scene are distinct
+ *   (pointnet2 repeats an index once only duplicates are left; otherwise the sequences agree).  idx int32 [batch, K]
+ *   = point indices, -1 in slots at or beyond count[b]; count int32 [batch] = min(valid points of b, K).
+ *   One workgroup of 1024 lanes per scene, one barrier per step.  A scene of up to spx_fps_resident_points() points
+ *   keeps coordinates and t in registers; a larger one streams 16-byte {x, y, z, t} records, staged in ws in scene
+ *   order.  The tier is chosen in the kernel from the scene's own count.  One launch.
+ *   spx_fps_ws_bytes: the scratch (16 bytes per point of n_cap); monotone in n_cap; 0 for refused arguments.
+ *
+ *   spx_ball_query: queries = fp32 [m_cap, q_nfeat], q_batch_ids = int32 [m_cap] or NULL (all scene 0), n_queries_dev
+ *   = NULL or a device int32: rows at or beyond it are no queries.  A query is VALID when it lies below *n_queries,
+ *   its batch id is in [0, batch) and none of its first ndim coordinates is NaN.  Its hits are the valid points of ITS
+ *   scene with d2 < r2, d_j = p_j - q_j, visited in ASCENDING POINT INDEX; the first nsample (1 .. 128) are kept:
+ *   rows int32 [m_cap, nsample] = point indices, count int32 [m_cap] = min(hits, nsample), out_offsets fp32 [m_cap,
+ *   nsample, ndim] (or NULL) = d_j.  Slots at or beyond count hold -1 / 0, or, with flag 2 (pad = first) and count >
+ *   0, slot 0 again.  An invalid query has count 0.  flags = 0 | 2.  r2 = the squared radius, computed by the caller
+ *   in fp32, >= 0.  Requires m_cap * nsample < 2^31.  One lane per query, workgroups of 256 consecutive queries
+ *   which walk the scenes of their queries in ascending order and stage that scene's points in LDS.  One launch. */
+int spx_fps_resident_points(void);
+size_t spx_fps_ws_bytes(int n_cap, int batch, int ndim);
+int spx_fps(const float *points, int nfeat, int n_cap, int ndim, const int32_t *offsets, const int32_t *list,
+            int batch, int num_samples, int32_t *idx, int32_t *count, void *ws, size_t ws_bytes,
+            spx_stream_t stream);
+int spx_ball_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids, int m_cap,
+                   const int32_t *n_queries_dev, const float *points, int nfeat, int n_cap, int ndim,
+                   const int32_t *offsets, const int32_t *list, int batch, int nsample, float r2, int flags,
+                   int32_t *rows, int32_t *count, float *out_offsets, spx_stream_t stream);
 
 /* ---- voxel pruning (csrc/select.hip) ---------------------------------------------------------------------
  * Keep the most important rows of a sparse tensor and drop, or process separately, the rest: the pruned down-sampling

@@ -198,6 +198,13 @@ SIGNATURES = {
                                      vp]),
     "spx_group_bwd": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int,
                                      ctypes.c_int, vp, vp]),
+    "spx_fps_resident_points": (ctypes.c_int, []),
+    "spx_fps_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "spx_fps": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp,
+                               vp, ctypes.c_size_t, vp]),
+    "spx_ball_query": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, vp,
+                                      vp, vp, vp]),
     "spx_row_score": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
     "spx_topk_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "spx_topk_flags": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -40,6 +40,7 @@ std::atomic<long long> g_collapse_launches[kCollapseCount];
 std::atomic<long long> g_pointvoxel_launches[kPvCount];
 std::atomic<long long> g_interp_launches[kInterpCount];
 std::atomic<long long> g_query_launches[kQueryCount];
+std::atomic<long long> g_sample_launches[kSampleCount];
 std::atomic<long long> g_serialize_launches[kSerCount];
 std::atomic<long long> g_select_launches[kSelInstCount];
 std::atomic<long long> g_pool_launches[kPoolCount];
@@ -196,6 +197,14 @@ std::atomic<long long> *query_counter(const char *key) {
   return nullptr;
 }
 
+// counter of a raw-point sampling key (spx_launch_count), or null
+std::atomic<long long> *sample_counter(const char *key) {
+  static const char *names[kSampleCount] = {"sample/fps", "sample/ball_query"};
+  for (int i = 0; i < kSampleCount; ++i)
+    if (strcmp(key, names[i]) == 0) return &g_sample_launches[i];
+  return nullptr;
+}
+
 // counter of a voxel-pruning key (spx_launch_count), or null
 std::atomic<long long> *select_counter(const char *key) {
   static const char *names[kSelInstCount] = {"select/score", "select/hist", "select/pick", "select/ties", "select/flags",
@@ -283,6 +292,7 @@ long long spx_launch_count(const char *family_h) {
   if (std::atomic<long long> *c = spx::pointvoxel_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::interp_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::query_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::sample_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::serialize_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::select_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pool_counter(family_h)) return c->load(std::memory_order_relaxed);

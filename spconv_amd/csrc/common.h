@@ -227,6 +227,12 @@ enum QueryInst { kQueryRanked = 0, kQueryHash, kQueryGroupFwd, kQueryGroupBwd, k
 extern std::atomic<long long> g_query_launches[kQueryCount];
 inline void count_query(QueryInst i) { g_query_launches[i].fetch_add(1, std::memory_order_relaxed); }
 
+// farthest-point sampling and ball query over raw points (sample.hip): one counter per entry point.
+// Keys sample/fps, sample/ball_query.
+enum SampleInst { kSampleFps = 0, kSampleBallQuery, kSampleCount };
+extern std::atomic<long long> g_sample_launches[kSampleCount];
+inline void count_sample(SampleInst i) { g_sample_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
 // voxel serialisation (serialize.hip): keys once per spx_curve_keys call, sort once per sorted order, offsets once per
 // spx_serialize call, plan once per spx_patch_plan call, bwd once per spx_patch_rows_bwd call.
 // Keys serialize/keys, serialize/sort, serialize/offsets, serialize/plan, serialize/bwd.

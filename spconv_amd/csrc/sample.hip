@@ -1,0 +1,542 @@
+// Farthest-point sampling and ball query over raw points (spx_fps, spx_ball_query): the keypoint stage of the
+// point-voxel detectors (PV-RCNN, PV-RCNN++, the raw-point source of Voxel R-CNN's set abstraction) -- the
+// furthest_point_sample / ball_query extensions of pointnet2_stack.  The rows of a ball query are what spx_group_fwd /
+// spx_group_bwd (query.hip) gather and transpose, with the points standing where a level's rows do.
+//
+//   scenes    the points of scene b are list[offsets[b] .. offsets[b + 1]) of spx_point_groups over the batch ids: any
+//             input order, ascending point index inside a scene.  A point with a coordinate that is not finite is
+//             INVALID: never a sample, never a hit.
+//   fps       one workgroup of 1024 lanes per scene, sequential in the K samples.  Every valid point keeps t (+inf at
+//             first); a step folds the squared distance to the last sample into t and picks the candidate with the
+//             largest t, ties to the lowest point index; a chosen point stops being a candidate.  The argmax is one
+//             64-bit key per lane -- the bits of t (a non-negative float: its bits order as an integer) above the
+//             inverted scene position -- reduced over the wave by DPP moves and readlane; every wave's winner goes to
+//             LDS WITH its coordinates, in slots alternated by step parity, and every lane reads the 16 slots behind
+//             ONE barrier per step.  A scene of up to kResident points keeps coordinates and t in registers (no global load in a
+//             step); a larger one streams {x, y, z, t} records staged in ws, each lane its own.  The tier is a uniform
+//             branch on the scene's own count.  No workgroup waits for another.
+//   ball      one lane per query, workgroups of 256 consecutive queries.  The workgroup walks the scenes of its valid
+//             queries in ascending order (scene-contiguous queries: at most two), stages tiles of that scene's points
+//             in LDS, and every lane of the scene tests the staged point all lanes read together (a broadcast),
+//             appending while it has room.  The workgroup leaves a scene once none of its lanes has room.
+// Every barrier sits in control flow that is uniform over the workgroup: trip counts come from values every lane reads
+// from the same LDS words or from the scene's offsets.  The distances are fp32 with every operation rounded on its
+// own, so a host loop reproduces every output bit for bit.
+#include <limits.h>
+
+#include "common.h"
+
+// no multiply-add pair of this unit may be contracted into an FMA (see pointvoxel.hip)
+#pragma clang fp contract(off)
+
+namespace spx {
+namespace {
+
+constexpr int kFpsBlock = 1024, kFpsWaves = kFpsBlock / kWave;
+constexpr int kFpsPer = 16;                          // points per lane of the register tier
+constexpr int kFpsResident = kFpsBlock * kFpsPer;
+constexpr int kFpsAhead = 6;                         // records of a batch of the streamed tier; a lane keeps two batches
+constexpr int kMaxSamples = 1 << 16;
+constexpr int kBallBlock = 256, kBallWaves = kBallBlock / kWave, kBallTile = 1024;
+constexpr int kBallAhead = 8;                        // staged points a lane tests together
+static_assert(kBallTile % kBallAhead == 0, "a padded tile stays inside the staged array");
+constexpr int kMaxSample = 128;
+constexpr int kFlagPadFirst = 2;
+
+typedef unsigned long long u64;
+
+struct __attribute__((aligned(16))) FpsRec {
+  float x, y, z, t;
+};
+
+template <int NDIM> __device__ __forceinline__ float dist2(const float (&d)[NDIM]) {
+  float s = d[0] * d[0] + d[1] * d[1];
+  if (NDIM == 3) s = s + d[NDIM - 1] * d[NDIM - 1];
+  return s;
+}
+
+__device__ __forceinline__ bool finite(float v) { return fabsf(v) < __builtin_huge_valf(); }      // (false for NaN)
+
+// Position `pos` of a scene (its list starts at list_b): the point's coordinates; false for an index outside the
+// points and for a coordinate that is not finite.
+template <int NDIM>
+__device__ __forceinline__ bool load_point(const float *__restrict__ points, int nfeat, int n_cap,
+                                           const int32_t *__restrict__ list_b, int pos, float (&p)[NDIM], int &pi) {
+  pi = list_b[pos];
+  bool ok = static_cast<unsigned>(pi) < static_cast<unsigned>(n_cap);
+#pragma unroll
+  for (int j = 0; j < NDIM; ++j) {
+    p[j] = ok ? points[static_cast<size_t>(pi) * nfeat + j] : 0.f;
+    ok = ok && finite(p[j]);
+  }
+  return ok;
+}
+
+// -------------------------------------------------------------------------------------------- farthest-point sampling
+
+// A lane's best candidate: its t (< 0: none), scene position and coordinates.  A lane meets its positions in ascending
+// order, so the strict compare keeps the LOWEST position of equal t.
+template <int NDIM> struct Best {
+  float t;
+  int pos;
+  float c[NDIM];
+  __device__ __forceinline__ void clear() {
+    t = -1.f;
+    pos = 0;
+#pragma unroll
+    for (int j = 0; j < NDIM; ++j) c[j] = 0.f;
+  }
+  // bits(t) << 32 | ~position: a non-negative float orders as its bits, equal t by the lower position; 0: none
+  __device__ __forceinline__ u64 key() const {
+    return t >= 0.f ? (static_cast<u64>(__float_as_uint(t)) << 32) | static_cast<uint32_t>(~pos) : 0ull;
+  }
+};
+
+// t < 0 marks a point that is no candidate (invalid, absent or chosen)
+template <int NDIM>
+__device__ __forceinline__ void consider(Best<NDIM> &best, float t, int pos, const float (&p)[NDIM]) {
+  const bool take = t > best.t;                       // (selects: a branch per point would split every step)
+  best.t = take ? t : best.t;
+  best.pos = take ? pos : best.pos;
+#pragma unroll
+  for (int j = 0; j < NDIM; ++j) best.c[j] = take ? p[j] : best.c[j];
+}
+
+template <int NDIM> __device__ __forceinline__ float fold(float t, const float (&p)[NDIM], const float (&c)[NDIM]) {
+  float d[NDIM];
+#pragma unroll
+  for (int j = 0; j < NDIM; ++j) d[j] = p[j] - c[j];
+  const float d2 = dist2<NDIM>(d);
+  return d2 < t ? d2 : t;                             // (false for t < 0: a non-candidate stays one)
+}
+
+// The register tier: lane `tid` holds positions tid + 1024 j, j < 16.  Every loop is unrolled with constant bounds (the
+// arrays live in registers); the test against n is uniform.
+template <int NDIM> struct ResidentPoints {
+  float p[kFpsPer][NDIM], t[kFpsPer];
+  __device__ __forceinline__ int init(const float *points, int nfeat, int n_cap, const int32_t *list_b, int n, int tid,
+                                      FpsRec *, Best<NDIM> &best) {
+    int valid = 0;
+#pragma unroll
+    for (int j = 0; j < kFpsPer; ++j) {
+      const int pos = tid + j * kFpsBlock;
+      t[j] = -1.f;
+#pragma unroll
+      for (int k = 0; k < NDIM; ++k) p[j][k] = 0.f;
+      if (j * kFpsBlock < n) {
+        int pi;
+        if (pos < n && load_point<NDIM>(points, nfeat, n_cap, list_b, pos, p[j], pi)) {
+          t[j] = __builtin_huge_valf();
+          ++valid;
+        }
+        consider<NDIM>(best, t[j], pos, p[j]);
+      }
+      __builtin_amdgcn_sched_barrier(0);                // (one point's loads at a time: sixteen in flight spill)
+    }
+    return valid;
+  }
+  __device__ __forceinline__ void step(const float (&c)[NDIM], int chosen, int n, int tid, Best<NDIM> &best) {
+#pragma unroll
+    for (int j = 0; j < kFpsPer; ++j) {
+      const int pos = tid + j * kFpsBlock;
+      if (j * kFpsBlock < n) {
+        t[j] = pos == chosen ? -1.f : fold<NDIM>(t[j], p[j], c);
+        consider<NDIM>(best, t[j], pos, p[j]);
+      }
+      if (j % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+};
+
+// The streamed tier: lane `tid` owns the records of positions tid + 1024 j of its scene, in scene order.
+template <int NDIM> struct StreamedPoints {
+  FpsRec *rec;
+  __device__ __forceinline__ int init(const float *points, int nfeat, int n_cap, const int32_t *list_b, int n, int tid,
+                                      FpsRec *recs, Best<NDIM> &best) {
+    rec = recs;
+    int valid = 0;
+    for (int pos = tid; pos < n; pos += kFpsBlock) {
+      float p[NDIM];
+      int pi;
+      const bool ok = load_point<NDIM>(points, nfeat, n_cap, list_b, pos, p, pi);
+      const float t = ok ? __builtin_huge_valf() : -1.f;
+      FpsRec r = {p[0], p[1], NDIM == 3 ? p[NDIM - 1] : 0.f, t};
+      rec[pos] = r;
+      valid += ok ? 1 : 0;
+      consider<NDIM>(best, t, pos, p);
+    }
+    return valid;
+  }
+  // the records of positions base + 1024 u, u < kFpsAhead (t = -1 beyond the scene): their loads in flight together
+  __device__ __forceinline__ void load(FpsRec (&r)[kFpsAhead], int base, int n) const {
+#pragma unroll
+    for (int u = 0; u < kFpsAhead; ++u) {
+      const int pos = base + u * kFpsBlock;
+      r[u].x = r[u].y = r[u].z = 0.f;
+      r[u].t = -1.f;
+      if (pos < n) r[u] = rec[pos];
+    }
+  }
+  // Two batches deep: the loads of the next batch are issued BEFORE the stores of this one, so waiting for them does not
+  // wait for the stores' acknowledgements (loads and stores share one counter).  Worth 2 % of a step at 75 000 points
+  // (profiles/sample_probe.json; DESIGN.md section 3.30 says what a step of this tier costs).
+  __device__ __forceinline__ void step(const float (&c)[NDIM], int chosen, int n, int tid, Best<NDIM> &best) {
+    FpsRec r[kFpsAhead];
+    load(r, tid, n);
+    for (int base = tid; base < n; base += kFpsAhead * kFpsBlock) {
+      FpsRec ahead[kFpsAhead];
+      load(ahead, base + kFpsAhead * kFpsBlock, n);
+#pragma unroll
+      for (int u = 0; u < kFpsAhead; ++u) {             // (ascending position)
+        const int pos = base + u * kFpsBlock;
+        float p[NDIM];
+        p[0] = r[u].x;
+        p[1] = r[u].y;
+        if (NDIM == 3) p[NDIM - 1] = r[u].z;
+        const float t = pos == chosen ? -1.f : fold<NDIM>(r[u].t, p, c);
+        if (pos < n) rec[pos].t = t;
+        consider<NDIM>(best, t, pos, p);
+      }
+#pragma unroll
+      for (int u = 0; u < kFpsAhead; ++u) r[u] = ahead[u];
+    }
+  }
+};
+
+// max(k, k of the lane the DPP control names): both halves move with the same control
+template <int CTRL> __device__ __forceinline__ u64 dpp_max(u64 k) {
+  const uint32_t lo = static_cast<uint32_t>(
+      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<uint32_t>(k)), CTRL, 0xf, 0xf, false));
+  const uint32_t hi = static_cast<uint32_t>(
+      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<uint32_t>(k >> 32)), CTRL, 0xf, 0xf, false));
+  const u64 o = (static_cast<u64>(hi) << 32) | lo;
+  return o > k ? o : k;
+}
+
+// The maximum over the wave, in every lane (all 64 active).  Inside a row of 16 lanes a butterfly of DPP moves -- lane ^
+// 1, lane ^ 2 (quad permutes), then the mirrored half row and the mirrored row, which reach the other quad / half row: a
+// maximum does not mind which lane of it -- and the four row results through readlane.
+__device__ __forceinline__ u64 wave_max(u64 k) {
+  k = dpp_max<0xB1>(k);                                 // quad_perm:[1,0,3,2]
+  k = dpp_max<0x4E>(k);                                 // quad_perm:[2,3,0,1]
+  k = dpp_max<0x141>(k);                                // row_half_mirror
+  k = dpp_max<0x140>(k);                                // row_mirror
+  u64 r = 0ull;
+#pragma unroll
+  for (int row = 0; row < kWave; row += 16) {
+    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(k)), row));
+    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(k >> 32)), row));
+    const u64 o = (static_cast<u64>(hi) << 32) | lo;
+    r = o > r ? o : r;
+  }
+  return r;
+}
+
+struct FpsShared {
+  u64 key[2][kFpsWaves];
+  float4 pt[2][kFpsWaves];
+  int valid[kFpsWaves];
+};
+
+// One scene of n >= 1 points, all 1024 lanes inside.  out: the scene's row of idx.
+template <int NDIM, typename Points>
+__device__ __forceinline__ void fps_scene(FpsShared &sh, const float *points, int nfeat, int n_cap, const int32_t *list_b,
+                                          int n, int K, FpsRec *recs, int32_t *out, int32_t *count_b) {
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  Points pts;
+  Best<NDIM> best;
+  best.clear();
+  int valid = pts.init(points, nfeat, n_cap, list_b, n, tid, recs, best);
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) valid += __shfl_xor(valid, m, kWave);
+  if (lane == 0) sh.valid[wave] = valid;
+  __syncthreads();
+  int total = 0;
+#pragma unroll
+  for (int w = 0; w < kFpsWaves; ++w) total += sh.valid[w];
+  const int trips = total < K ? total : K;              // the same LDS words for every lane: uniform
+  for (int s = 0; s < trips; ++s) {
+    const int par = s & 1;
+    const u64 mine = best.key();
+    const u64 wmax = wave_max(mine);
+    if (wmax != 0ull ? mine == wmax : lane == 0) {  // (keys are unique: one lane)
+      sh.key[par][wave] = wmax;
+      sh.pt[par][wave] = make_float4(best.c[0], best.c[1], NDIM == 3 ? best.c[NDIM - 1] : 0.f, 0.f);
+    }
+    __syncthreads();
+    u64 win = 0ull;
+    int slot = 0;
+#pragma unroll
+    for (int h = 0; h < kFpsWaves; h += 8) {            // (two batches of reads: sixteen keys in flight would not fit)
+#pragma unroll
+      for (int w = h; w < h + 8; ++w) {
+        const u64 k = sh.key[par][w];
+        if (k > win) {
+          win = k;
+          slot = w;
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // every lane holds the same winner: kept in scalar registers for the pass over the lane's points
+    slot = __builtin_amdgcn_readfirstlane(slot);
+    const float4 cw = sh.pt[par][slot];
+    const int chosen = __builtin_amdgcn_readfirstlane(static_cast<int>(~static_cast<uint32_t>(win)));
+    if (tid == 0) out[s] = chosen;                      // (the scene position; turned into the point index below)
+    if (s + 1 < trips) {
+      float c[NDIM];
+      c[0] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(cw.x)));
+      c[1] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(cw.y)));
+      if (NDIM == 3) c[NDIM - 1] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(cw.z)));
+      best.clear();
+      pts.step(c, chosen, n, tid, best);
+    }
+  }
+  __syncthreads();                                      // lane 0's positions are visible to the workgroup
+  for (int s = tid; s < K; s += kFpsBlock) {
+    int v = -1;
+    if (s < trips) {
+      const int pos = out[s];
+      v = static_cast<unsigned>(pos) < static_cast<unsigned>(n) ? list_b[pos] : -1;
+    }
+    out[s] = v;
+  }
+  if (tid == 0) *count_b = trips;
+}
+
+template <int NDIM>
+__global__ void __launch_bounds__(kFpsBlock)
+fps_kernel(const float *__restrict__ points, int nfeat, int n_cap, const int32_t *__restrict__ offsets,
+           const int32_t *__restrict__ list, int K, int32_t *idx, int32_t *__restrict__ count, FpsRec *recs) {
+  __shared__ FpsShared sh;
+  const int b = blockIdx.x;
+  int beg = offsets[b], end = offsets[b + 1];
+  beg = min(max(beg, 0), n_cap);
+  end = min(max(end, beg), n_cap);
+  const int n = end - beg;                              // uniform: the scene's own count
+  int32_t *out = idx + static_cast<long long>(b) * K;
+  if (n == 0) {                                         // before the first barrier
+    for (int s = threadIdx.x; s < K; s += kFpsBlock) out[s] = -1;
+    if (threadIdx.x == 0) count[b] = 0;
+    return;
+  }
+  if (n <= kFpsResident || recs == nullptr)             // (the host refuses n_cap > kFpsResident without scratch)
+    fps_scene<NDIM, ResidentPoints<NDIM>>(sh, points, nfeat, n_cap, list + beg, min(n, kFpsResident), K, nullptr, out,
+                                          count + b);
+  else
+    fps_scene<NDIM, StreamedPoints<NDIM>>(sh, points, nfeat, n_cap, list + beg, n, K, recs + beg, out, count + b);
+}
+
+// -------------------------------------------------------------------------------------------- ball query
+
+struct BallArgs {
+  const float *queries;
+  int q_nfeat;
+  const int32_t *q_batch_ids;
+  int m_cap;
+  const int32_t *n_queries;
+  const float *points;
+  int nfeat, n_cap;
+  const int32_t *offsets, *list;
+  int batch, nsample;
+  float r2;
+  int flags;
+  int32_t *rows, *count;
+  float *out_offsets;
+};
+
+template <int NDIM>
+__global__ void __launch_bounds__(kBallBlock)
+ball_query_kernel(BallArgs a) {
+  __shared__ float4 s_pt[kBallTile];                    // {x, y, z, the point index as bits}; x = NaN: invalid
+  __shared__ int s_next[2][kBallWaves];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const long long qi = static_cast<long long>(blockIdx.x) * kBallBlock + tid;
+  const int nq = a.n_queries ? min(*a.n_queries, a.m_cap) : a.m_cap;
+  const bool exists = qi < a.m_cap;                     // (a lane without a query still takes every barrier)
+  bool valid = qi < nq;
+  int b = -1;
+  float q[NDIM];
+#pragma unroll
+  for (int j = 0; j < NDIM; ++j) q[j] = 0.f;
+  if (valid) {
+    b = a.q_batch_ids ? a.q_batch_ids[qi] : 0;
+    valid = b >= 0 && b < a.batch;
+  }
+  if (valid) {
+#pragma unroll
+    for (int j = 0; j < NDIM; ++j) {
+      q[j] = a.queries[static_cast<size_t>(qi) * a.q_nfeat + j];
+      valid = valid && q[j] == q[j];
+    }
+  }
+  const int mine = valid ? b : INT_MAX;
+  int32_t *ro = a.rows + qi * a.nsample;
+  float *oo = a.out_offsets ? a.out_offsets + qi * a.nsample * NDIM : nullptr;
+  int cnt = 0, first_row = -1;
+  float first_off[NDIM] = {};
+  int cur = -1;
+  for (int it = 0;; ++it) {
+    // the lowest scene above `cur` among the workgroup's queries
+    int cand = mine > cur ? mine : INT_MAX;
+#pragma unroll
+    for (int m = kWave / 2; m >= 1; m >>= 1) cand = min(cand, __shfl_xor(cand, m, kWave));
+    if (lane == 0) s_next[it & 1][wave] = cand;
+    __syncthreads();
+    int next = INT_MAX;
+#pragma unroll
+    for (int w = 0; w < kBallWaves; ++w) next = min(next, s_next[it & 1][w]);
+    if (next == INT_MAX) break;                         // the same LDS words for every lane: uniform
+    cur = next;
+    int beg = a.offsets[next], end = a.offsets[next + 1];
+    beg = min(max(beg, 0), a.n_cap);
+    end = min(max(end, beg), a.n_cap);
+    bool active = mine == next;
+    for (int tile0 = beg; tile0 < end; tile0 += kBallTile) {
+      const int tn = min(kBallTile, end - tile0);
+      const int padded = (tn + kBallAhead - 1) / kBallAhead * kBallAhead;        // (the tile is a multiple of kBallAhead)
+      for (int k = tid; k < padded; k += kBallBlock) {
+        float p[NDIM] = {};
+        int pi = -1;
+        const bool ok = k < tn && load_point<NDIM>(a.points, a.nfeat, a.n_cap, a.list + tile0, k, p, pi);
+        s_pt[k] = make_float4(ok ? p[0] : __builtin_nanf(""), p[1], NDIM == 3 ? p[NDIM - 1] : 0.f, __int_as_float(pi));
+      }
+      __syncthreads();
+      // kBallAhead staged points at a time: their reads and distances are independent, a hit is rare
+      for (int k0 = 0; k0 < padded && active; k0 += kBallAhead) {
+        float4 p[kBallAhead];
+        float d[kBallAhead][NDIM];
+        unsigned hits = 0u;
+#pragma unroll
+        for (int u = 0; u < kBallAhead; ++u) p[u] = s_pt[k0 + u];
+#pragma unroll
+        for (int u = 0; u < kBallAhead; ++u) {
+          d[u][0] = p[u].x - q[0];
+          d[u][1] = p[u].y - q[1];
+          if (NDIM == 3) d[u][NDIM - 1] = p[u].z - q[NDIM - 1];
+          hits |= dist2<NDIM>(d[u]) < a.r2 ? 1u << u : 0u;   // (false for an invalid point: its d2 is NaN)
+        }
+        if (hits == 0u) continue;
+#pragma unroll
+        for (int u = 0; u < kBallAhead; ++u) {              // (ascending point index)
+          if (!(hits >> u & 1u) || cnt >= a.nsample) continue;
+          const int pi = __float_as_int(p[u].w);
+          ro[cnt] = pi;
+          if (oo) {
+#pragma unroll
+            for (int j = 0; j < NDIM; ++j) oo[cnt * NDIM + j] = d[u][j];
+          }
+          if (cnt == 0) {
+            first_row = pi;
+#pragma unroll
+            for (int j = 0; j < NDIM; ++j) first_off[j] = d[u][j];
+          }
+          ++cnt;
+        }
+        active = cnt < a.nsample;
+      }
+      if (!__syncthreads_or(active ? 1 : 0)) break;     // no lane of this scene has room: uniform
+    }
+  }
+  if (exists) {
+    const bool pad = (a.flags & kFlagPadFirst) && cnt > 0;
+    for (int s = cnt; s < a.nsample; ++s) {
+      ro[s] = pad ? first_row : -1;
+      if (oo) {
+#pragma unroll
+        for (int j = 0; j < NDIM; ++j) oo[s * NDIM + j] = pad ? first_off[j] : 0.f;
+      }
+    }
+    a.count[qi] = cnt;
+  }
+}
+
+// -------------------------------------------------------------------------------------------- host side
+
+inline bool aligned_to(const void *p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
+// 0 = ok: the checks of a scene list that need no pointer
+int check_scenes(int ndim, int nfeat, int n_cap, int batch) {
+  SPX_CHECK(ndim == 2 || ndim == 3, "ndim must be 2 or 3, got %d", ndim);
+  SPX_CHECK(n_cap >= 0, "bad point counts %d", n_cap);
+  SPX_CHECK(nfeat >= ndim, "points need at least %d columns, got %d", ndim, nfeat);
+  SPX_CHECK(batch >= 1, "batch must be >= 1, got %d", batch);
+  return 0;
+}
+
+}  // namespace
+}  // namespace spx
+
+extern "C" {
+
+int spx_fps_resident_points(void) { return spx::kFpsResident; }
+
+size_t spx_fps_ws_bytes(int n_cap, int batch, int ndim) {
+  if ((ndim != 2 && ndim != 3) || n_cap < 0 || batch < 1) return 0;
+  return spx::align_up(static_cast<size_t>(n_cap) * sizeof(spx::FpsRec), 256);
+}
+
+int spx_fps(const float *points, int nfeat, int n_cap, int ndim, const int32_t *offsets, const int32_t *list, int batch,
+            int num_samples, int32_t *idx, int32_t *count, void *ws, size_t ws_bytes, spx_stream_t stream) {
+  using namespace spx;
+  if (int rc = check_scenes(ndim, nfeat, n_cap, batch)) return rc;
+  SPX_CHECK(num_samples >= 1 && num_samples <= kMaxSamples, "num_samples must be in 1 .. %d, got %d", kMaxSamples,
+            num_samples);
+  SPX_CHECK(static_cast<long long>(batch) * num_samples < 0x80000000LL, "batch * num_samples must stay below 2^31, got %d x %d",
+            batch, num_samples);
+  SPX_CHECK(offsets && idx && count && (n_cap == 0 || (points && list)), "points / offsets / list / idx / count is NULL");
+  SPX_CHECK(aligned_to(points, 4) && aligned_to(offsets, 4) && aligned_to(list, 4) && aligned_to(idx, 4) &&
+                aligned_to(count, 4), "pointer not aligned to its elements");
+  if (n_cap > kFpsResident) {                           // a scene may need the streamed tier
+    SPX_CHECK(ws && ws_bytes >= spx_fps_ws_bytes(n_cap, batch, ndim), "workspace too small: %zu < %zu", ws_bytes,
+              spx_fps_ws_bytes(n_cap, batch, ndim));
+    SPX_CHECK(aligned_to(ws, 16), "workspace not aligned to 16 bytes");
+  } else {
+    ws = nullptr;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  FpsRec *recs = static_cast<FpsRec *>(ws);
+  if (ndim == 3)
+    hipLaunchKernelGGL((fps_kernel<3>), dim3(batch), dim3(kFpsBlock), 0, s, points, nfeat, n_cap, offsets, list, num_samples,
+                       idx, count, recs);
+  else
+    hipLaunchKernelGGL((fps_kernel<2>), dim3(batch), dim3(kFpsBlock), 0, s, points, nfeat, n_cap, offsets, list, num_samples,
+                       idx, count, recs);
+  SPX_LAUNCH_CHECK();
+  count_sample(kSampleFps);
+  return 0;
+}
+
+int spx_ball_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids, int m_cap, const int32_t *n_queries_dev,
+                   const float *points, int nfeat, int n_cap, int ndim, const int32_t *offsets, const int32_t *list,
+                   int batch, int nsample, float r2, int flags, int32_t *rows, int32_t *count, float *out_offsets,
+                   spx_stream_t stream) {
+  using namespace spx;
+  if (int rc = check_scenes(ndim, nfeat, n_cap, batch)) return rc;
+  SPX_CHECK(m_cap >= 0, "bad query counts %d", m_cap);
+  SPX_CHECK(q_nfeat >= ndim, "queries need at least %d columns, got %d", ndim, q_nfeat);
+  SPX_CHECK(nsample >= 1 && nsample <= kMaxSample, "nsample must be in 1 .. %d, got %d", kMaxSample, nsample);
+  SPX_CHECK(static_cast<long long>(m_cap) * nsample < 0x80000000LL, "m_cap * nsample must stay below 2^31, got %d x %d",
+            m_cap, nsample);
+  SPX_CHECK((flags & ~kFlagPadFirst) == 0, "flags must be 0 or pad first (2), got %d", flags);
+  SPX_CHECK(r2 >= 0.f, "the squared radius must be >= 0 (and no NaN)");
+  if (m_cap == 0) return 0;
+  SPX_CHECK(queries && rows && count && offsets && (n_cap == 0 || (points && list)),
+            "queries / points / offsets / list / rows / count is NULL");
+  SPX_CHECK(aligned_to(queries, 4) && aligned_to(points, 4) && aligned_to(rows, 4) && aligned_to(count, 4) &&
+                aligned_to(out_offsets, 4) && aligned_to(offsets, 4) && aligned_to(list, 4),
+            "pointer not aligned to its elements");
+  BallArgs a = {queries, q_nfeat, q_batch_ids, m_cap, n_queries_dev, points, nfeat, n_cap, offsets, list,
+                batch,   nsample, r2,          flags, rows,          count,  out_offsets};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(static_cast<unsigned>((static_cast<long long>(m_cap) + kBallBlock - 1) / kBallBlock));
+  if (ndim == 3)
+    hipLaunchKernelGGL((ball_query_kernel<3>), grid, dim3(kBallBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL((ball_query_kernel<2>), grid, dim3(kBallBlock), 0, s, a);
+  SPX_LAUNCH_CHECK();
+  count_sample(kSampleBallQuery);
+  return 0;
+}
+
+}  // extern "C"

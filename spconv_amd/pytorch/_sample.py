@@ -1,0 +1,222 @@
+"""Farthest-point sampling and ball query over raw points on the HIP kernels of csrc/sample.hip
+(``functional.farthest_point_sample`` / ``gather_samples`` / ``ball_query``, ``spatial.FarthestPointSample`` /
+``BallQueryAndGroup``).  Not part of the reference; the point-voxel detectors (PV-RCNN, PV-RCNN++, Voxel R-CNN's raw-point
+source) call them as the ``furthest_point_sample`` / ``ball_query`` CUDA extensions of ``pointnet2_stack``.
+
+  * scenes                  the points of scene b are ``list[offsets[b] : offsets[b + 1]]`` of ``point_groups`` over the
+                            batch ids: any input order, ascending point index inside a scene; both operations accept a
+                            ready ``PointGroups`` (``scene_groups``) so a caller builds it once
+  * ``farthest_point_sample``  K samples per scene (``spx_fps``: one workgroup per scene, one launch), ties to the lowest
+                            point index, distinct indices, -1 past the scene's valid points
+  * ``gather_samples``      the sampled rows, NaN in dead slots (``gather_rows``): a dead slot is an invalid query for
+                            ``voxel_query``, ``point_corners`` and ``ball_query`` alike
+  * ``ball_query``          per query the first ``nsample`` points of its scene inside a radius, in ascending point
+                            index (``spx_ball_query``), as the ``VoxelNeighbors`` that ``group_voxels`` and its
+                            gradient take, the points standing where a level's rows do
+
+There is no gradient with respect to coordinates: raw coordinates need none.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+import torch
+
+from spconv_amd import _lib
+from spconv_amd.pytorch import _pointvoxel
+from spconv_amd.pytorch._level import flat_groups
+from spconv_amd.pytorch._pointvoxel import PointGroups, gather_rows
+from spconv_amd.pytorch._query import MAX_NSAMPLE, VoxelNeighbors, squared_radius
+from spconv_amd.pytorch._rulebook import _check_count, _ptr, _require_gpu, _stream, _ws
+
+MAX_SAMPLES = 1 << 16
+_FLAG_PAD_FIRST = 2
+
+
+class PointSamples(NamedTuple):
+    """The samples of every scene: idx int32 [B, K] (point index, -1 at or beyond count[b]), count int32 [B] =
+    min(valid points of b, K), batch_ids int32 [B * K] (b for every slot of scene b: the batch ids of the gathered
+    samples as queries)."""
+    idx: torch.Tensor
+    count: torch.Tensor
+    batch_ids: torch.Tensor
+
+
+def resident_points() -> int:
+    """The largest scene ``spx_fps`` keeps in registers; a larger one streams staged records from scratch."""
+    return int(_lib.load().spx_fps_resident_points())
+
+
+def fps_ws_bytes(n_cap: int, batch_size: int, ndim: int) -> int:
+    return int(_lib.load().spx_fps_ws_bytes(int(n_cap), int(batch_size), int(ndim)))
+
+
+def _check_cloud(op: str, noun: str, points: torch.Tensor, batch_ids: Optional[torch.Tensor], batch_size: int,
+                 ndim: int) -> int:
+    """The ValueErrors of a cloud (`noun`: what `op` calls it); they come before the refusal of a CPU tensor
+    (``_require_cloud``)."""
+    if ndim not in (2, 3):
+        raise ValueError(f"{op}: ndim must be 2 or 3, got {ndim}")
+    if int(batch_size) < 1:
+        raise ValueError(f"{op}: batch_size must be >= 1, got {batch_size}")
+    if points.dim() != 2 or points.dtype != torch.float32 or points.shape[1] < ndim:
+        raise ValueError(f"{op}: {noun} is a float32 tensor [N, >= {ndim}], got {tuple(points.shape)} {points.dtype}")
+    N = int(points.shape[0])
+    if batch_ids is not None and (batch_ids.shape != (N,) or batch_ids.dtype != torch.int32):
+        raise ValueError(f"{op}: the batch_ids of the {noun} are a CUDA int32 tensor [N]")
+    return N
+
+
+def _require_cloud(op: str, noun: str, points: torch.Tensor, batch_ids: Optional[torch.Tensor],
+                   count: Optional[torch.Tensor]) -> None:
+    _require_gpu(points, noun)
+    if batch_ids is not None:
+        _require_gpu(batch_ids, "batch_ids")
+    _check_count(count, f"{op}: n_{noun}")
+
+
+def _check_groups(op: str, groups: PointGroups, N: int, batch_size: int) -> None:
+    if groups.offsets is None or groups.list is None or groups.num_voxels != int(batch_size) or groups.list.shape[0] != N:
+        raise ValueError(f"{op}: groups are the point_groups of the {N} batch ids over {batch_size} scenes "
+                         f"(scene_groups), got {groups.num_voxels} groups over {tuple(groups.rows.shape)} points")
+
+
+def scene_groups(batch_ids: Optional[torch.Tensor], n: int, batch_size: int, n_points: Optional[torch.Tensor] = None,
+                 device=None) -> PointGroups:
+    """The points of every scene: ``point_groups(batch_ids, batch_size, n_points)``, all scene 0 for batch_ids None.
+    Ids outside [0, batch_size) and rows at or beyond *n_points belong to no scene."""
+    dev = batch_ids.device if batch_ids is not None else device
+    with torch.cuda.device(dev):
+        if int(n) == 0:
+            empty = torch.empty((0,), dtype=torch.int32, device=dev)
+            return PointGroups(empty, torch.zeros((int(batch_size) + 1,), dtype=torch.int32, device=dev), empty,
+                               int(batch_size), n_points, None)
+        ids = batch_ids if batch_ids is not None else torch.zeros((int(n),), dtype=torch.int32, device=dev)
+        return _pointvoxel.point_groups(ids, int(batch_size), n_points)
+
+
+def sample_batch_ids(batch_size: int, num_samples: int, device) -> torch.Tensor:
+    """int32 [B * K]: b for every slot of scene b (built from host values; nothing is read)."""
+    b = torch.arange(int(batch_size), dtype=torch.int32, device=device)
+    return b.view(-1, 1).expand(int(batch_size), int(num_samples)).reshape(-1)
+
+
+def fps_into(points: torch.Tensor, groups: PointGroups, num_samples: int, ndim: int, idx: torch.Tensor,
+             count: torch.Tensor, ws: Optional[torch.Tensor]) -> None:
+    """The one C call into buffers the caller owns (no allocation: capturable).  idx int32 [B, K], count int32 [B], ws:
+    ``fps_ws_bytes`` bytes (needed once the cloud holds more than ``resident_points()`` points)."""
+    _lib.check(_lib.load().spx_fps(points.data_ptr(), int(points.shape[1]), int(points.shape[0]), int(ndim),
+                                   groups.offsets.data_ptr(), groups.list.data_ptr(), int(groups.num_voxels),
+                                   int(num_samples), idx.data_ptr(), count.data_ptr(), _ptr(ws),
+                                   0 if ws is None else ws.numel(), _stream(points)))
+
+
+def farthest_point_sample(points: torch.Tensor, batch_ids: Optional[torch.Tensor], batch_size: int, num_samples: int, *,
+                          ndim: int = 3, n_points: Optional[torch.Tensor] = None,
+                          groups: Optional[PointGroups] = None) -> PointSamples:
+    """`num_samples` (K, 1 .. 65 536, the same for every scene) points of every scene by farthest-point sampling.
+    points fp32 [N, >= ndim] (x, y, z first), batch_ids int32 [N] or None (all scene 0); rows at or beyond *n_points and
+    ids outside [0, batch_size) belong to no scene, a point with a coordinate that is not finite is never a sample.
+    Slot 0 of a scene is its lowest valid point index; every valid point keeps t (+inf at first); a step sets ``t[i] =
+    d2 < t[i] ? d2 : t[i]`` with d2 the fp32 squared distance to the last sample, every operation rounded on its own,
+    and picks the not-yet-chosen point with the largest t, ties to the LOWEST point index.  A chosen point stops being a
+    candidate: the indices of a scene are distinct (pointnet2 repeats one once only duplicates are left; for distinct
+    points the sequences agree).  Returns PointSamples(idx [B, K] with -1 at or beyond count[b], count [B] = min(valid
+    points, K), batch_ids [B * K]).  `groups`: a ready ``scene_groups`` of the cloud.  One launch, nothing read back.
+    No gradient with respect to coordinates."""
+    K, B = int(num_samples), int(batch_size)
+    N = _check_cloud("farthest_point_sample", "points", points, batch_ids, B, ndim)
+    if not 1 <= K <= MAX_SAMPLES:
+        raise ValueError(f"farthest_point_sample: num_samples must be in 1 .. {MAX_SAMPLES}, got {num_samples}")
+    if B * K >= 1 << 31:
+        raise ValueError(f"farthest_point_sample: {B} scenes x {K} samples do not fit 32-bit entries")
+    if groups is not None:
+        _check_groups("farthest_point_sample", groups, N, B)
+    _require_cloud("farthest_point_sample", "points", points, batch_ids, n_points)
+    dev = points.device
+    with torch.cuda.device(dev), torch.no_grad():
+        points = points.detach().contiguous()
+        if groups is None:
+            groups = scene_groups(None if batch_ids is None else batch_ids.contiguous(), N, B, n_points, dev)
+        idx = torch.empty((B, K), dtype=torch.int32, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        ws = _ws(fps_ws_bytes(N, B, ndim), dev) if N > resident_points() else None
+        fps_into(points, groups, K, ndim, idx, count, ws)
+        return PointSamples(idx, count, sample_batch_ids(B, K, dev))
+
+
+def gather_samples(points: torch.Tensor, samples: PointSamples) -> torch.Tensor:
+    """[B * K, nfeat]: the rows of the samples, NaN in the slots at or beyond count[b] -- an invalid query for
+    ``voxel_query``, ``point_corners`` and ``ball_query`` alike (``gather_rows``: one launch)."""
+    if points.dim() != 2 or not points.dtype.is_floating_point:
+        raise ValueError(f"gather_samples: points is a floating tensor [N, nfeat], got {tuple(points.shape)} {points.dtype}")
+    _require_gpu(points, "points")
+    with torch.cuda.device(points.device), torch.no_grad():
+        return gather_rows(points.detach(), samples.idx.reshape(-1), float("nan"))
+
+
+def _check_ball(nsample: int, pad: str) -> int:
+    if not 1 <= int(nsample) <= MAX_NSAMPLE:
+        raise ValueError(f"ball_query: nsample must be in 1 .. {MAX_NSAMPLE}, got {nsample}")
+    if pad not in ("none", "first"):
+        raise ValueError(f"ball_query: pad is 'none' or 'first', got {pad!r}")
+    return int(nsample)
+
+
+def ball_query_into(queries: torch.Tensor, q_batch_ids: Optional[torch.Tensor], n_queries: Optional[torch.Tensor],
+                    points: torch.Tensor, groups: PointGroups, ndim: int, nsample: int, r2: float, pad_first: bool,
+                    rows: torch.Tensor, count: torch.Tensor, offsets: Optional[torch.Tensor]) -> None:
+    """The one C call into buffers the caller owns (no allocation: capturable).  r2: ``squared_radius``; rows int32
+    [M, nsample], count int32 [M], offsets fp32 [M, nsample, ndim] or None."""
+    _lib.check(_lib.load().spx_ball_query(
+        queries.data_ptr(), int(queries.shape[1]), _ptr(q_batch_ids), int(queries.shape[0]), _ptr(n_queries),
+        points.data_ptr(), int(points.shape[1]), int(points.shape[0]), int(ndim), groups.offsets.data_ptr(),
+        groups.list.data_ptr(), int(groups.num_voxels), int(nsample), float(r2), _FLAG_PAD_FIRST if pad_first else 0,
+        rows.data_ptr(), count.data_ptr(), _ptr(offsets), _stream(queries)))
+
+
+def ball_query(queries: torch.Tensor, q_batch_ids: Optional[torch.Tensor], points: torch.Tensor,
+               p_batch_ids: Optional[torch.Tensor], batch_size: int, radius: float, nsample: int, *, ndim: int = 3,
+               pad: str = "none", with_offsets: bool = False, n_queries: Optional[torch.Tensor] = None,
+               n_points: Optional[torch.Tensor] = None, with_groups: bool = False,
+               groups: Optional[PointGroups] = None) -> VoxelNeighbors:
+    """The first `nsample` (1 .. 128) points of its scene inside `radius` of each query.  queries fp32 [M, >= ndim],
+    points fp32 [N, >= ndim] (x, y, z first), q_batch_ids / p_batch_ids int32 or None (all scene 0).  A query's hits are
+    the valid points of ITS scene (a point below *n_points, with a batch id in [0, batch_size) and finite coordinates)
+    with ``d2 < float32(radius) ** 2``, d = point - query and d2 in fp32 with every operation rounded on its own; they
+    are visited in ASCENDING POINT INDEX and the first nsample are kept: rows [M, nsample] (point indices), count [M] =
+    min(hits, nsample), and with with_offsets the point-minus-query vectors [M, nsample, ndim].  Slots at or beyond
+    count hold -1 / 0; pad="first" repeats slot 0 there when count > 0, as pointnet2 does.  A query with a NaN
+    coordinate, with a batch id outside [0, batch_size) or at or beyond *n_queries has count 0.  The result does not
+    depend on how queries or points are ordered across scenes.  Returns the ``VoxelNeighbors`` of the points
+    (num_voxels = N, n_live = n_points): ``group_voxels(point_feats, nb)`` and its gradient work on [N, C] point
+    features; with_groups builds the transposed list that gradient walks.  `groups`: a ready ``scene_groups`` of the
+    points.  One launch, nothing read back.  No gradient with respect to coordinates."""
+    B = int(batch_size)
+    M = _check_cloud("ball_query", "queries", queries, q_batch_ids, B, ndim)
+    N = _check_cloud("ball_query", "points", points, p_batch_ids, B, ndim)
+    nsample = _check_ball(nsample, pad)
+    if radius is None:
+        raise ValueError("ball_query: radius must be >= 0, got None")
+    r2 = squared_radius(radius)
+    if M * nsample >= 1 << 31:
+        raise ValueError(f"ball_query: {M} queries x {nsample} entries each do not fit 32-bit entries")
+    if groups is not None:
+        _check_groups("ball_query", groups, N, B)
+        n_points = groups.n_points if n_points is None else n_points
+    _require_cloud("ball_query", "queries", queries, q_batch_ids, n_queries)
+    _require_cloud("ball_query", "points", points, p_batch_ids, n_points)
+    dev = queries.device
+    with torch.cuda.device(dev), torch.no_grad():
+        queries, points = queries.detach().contiguous(), points.detach().contiguous()
+        q_batch_ids = None if q_batch_ids is None else q_batch_ids.contiguous()
+        if groups is None:
+            groups = scene_groups(None if p_batch_ids is None else p_batch_ids.contiguous(), N, B, n_points, dev)
+        rows = torch.empty((M, nsample), dtype=torch.int32, device=dev)
+        count = torch.empty((M,), dtype=torch.int32, device=dev)
+        offsets = torch.empty((M, nsample, ndim), dtype=torch.float32, device=dev) if with_offsets else None
+        if M > 0:
+            ball_query_into(queries, q_batch_ids, n_queries, points, groups, ndim, nsample, r2, pad == "first", rows, count,
+                            offsets)
+        flat = flat_groups(rows, N, n_points) if with_groups else None
+    return VoxelNeighbors(rows, count, offsets, flat, N, n_queries, n_points)

@@ -596,6 +596,11 @@ from spconv_amd.pytorch._interp import (PointCorners, point_corners, point_corne
 from spconv_amd.pytorch._query import (VoxelNeighbors, group_voxels, voxel_query,  # noqa: E402,F401
                                        voxel_query_into)
 
+# farthest-point sampling and ball query over raw points (csrc/sample.hip; not part of the reference): keypoints of a
+# cloud, and the first nsample raw points around each query as the neighbour table group_voxels gathers
+from spconv_amd.pytorch._sample import (PointSamples, ball_query, ball_query_into,  # noqa: E402,F401
+                                        farthest_point_sample, fps_into, gather_samples, scene_groups)
+
 # voxel serialisation (csrc/serialize.hip; not part of the reference): rows ordered along Z-order / Hilbert curves and
 # cut into fixed-size patches, for the serialised point / voxel transformers
 from spconv_amd.pytorch import _serialize  # noqa: E402

@@ -1,7 +1,8 @@
 """``spconv.pytorch.spatial`` (reference ``spconv/pytorch/spatial.py:28-45``), and ``SparseCollapse``: the hand-over
 from a 3-D backbone to a sparse 2-D head on the kernels of csrc/collapse.hip; ``SparsePrune`` (csrc/select.hip);
 ``TrilinearDevoxelize``: a sparse level read out at points (csrc/interp.hip); ``VoxelQueryAndGroup``: the voxels around
-query points, gathered (csrc/query.hip)."""
+query points, gathered (csrc/query.hip); ``FarthestPointSample`` / ``BallQueryAndGroup``: keypoints of a raw cloud and the
+raw points around query points, gathered (csrc/sample.hip)."""
 from typing import Optional, Sequence
 
 import torch
@@ -174,3 +175,73 @@ class VoxelQueryAndGroup(torch.nn.Module):
     def extra_repr(self) -> str:
         return (f"query_range={self.query_range}, nsample={self.nsample}, radius={self.radius}, use_xyz={self.use_xyz}, "
                 f"vsize_xyz={self.vsize_xyz}, coors_range_xyz={self.coors_range_xyz}")
+
+
+class FarthestPointSample(torch.nn.Module):
+    """Keypoints of a raw cloud by farthest-point sampling (``functional.farthest_point_sample``, the kernel of
+    csrc/sample.hip): the ``furthest_point_sample`` of ``pointnet2_stack``.  Not part of the reference.
+
+    ``num_samples`` in 1 .. 65 536: samples per scene, the same for every scene.  ``forward(points, batch_ids,
+    batch_size, n_points=None, groups=None) -> PointSamples(idx [B, K], count [B], batch_ids [B * K])``: points fp32
+    [N, >= ndim], batch_ids int32 [N] or None.  Ties go to the lowest point index, the indices of a scene are distinct,
+    slots beyond a scene's valid points hold -1.  ``functional.gather_samples(points, samples)`` gives the sampled rows
+    (NaN in dead slots).  No gradient with respect to coordinates."""
+
+    def __init__(self, num_samples: int, ndim: int = 3):
+        super().__init__()
+        from spconv_amd.pytorch import _sample
+        if not 1 <= int(num_samples) <= _sample.MAX_SAMPLES:
+            raise ValueError(f"FarthestPointSample: num_samples must be in 1 .. {_sample.MAX_SAMPLES}, got {num_samples}")
+        if ndim not in (2, 3):
+            raise ValueError(f"FarthestPointSample: ndim must be 2 or 3, got {ndim}")
+        self.num_samples, self.ndim = int(num_samples), int(ndim)
+
+    def forward(self, points: torch.Tensor, batch_ids: Optional[torch.Tensor], batch_size: int,
+                n_points: Optional[torch.Tensor] = None, groups=None):
+        from spconv_amd.pytorch import functional as F
+        return F.farthest_point_sample(points, batch_ids, batch_size, self.num_samples, ndim=self.ndim, n_points=n_points,
+                                       groups=groups)
+
+    def extra_repr(self) -> str:
+        return f"num_samples={self.num_samples}, ndim={self.ndim}"
+
+
+class BallQueryAndGroup(torch.nn.Module):
+    """The raw points around query points, gathered for a shared MLP (``functional.ball_query`` +
+    ``functional.group_voxels``, the kernels of csrc/sample.hip and csrc/query.hip): the ``ball_query`` /
+    ``grouping_operation`` pair of ``pointnet2_stack``'s set abstraction over the raw-point source.  Not part of the
+    reference.
+
+    ``radius`` >= 0; ``nsample`` in 1 .. 128: the first so many points of the query's scene inside the radius, in
+    ascending point index, are kept.  ``forward(points, p_batch_ids, feats, queries, q_batch_ids, batch_size) -> ([M,
+    nsample, (ndim +) C], count [M])``: points fp32 [N, >= ndim], feats [N, C], queries fp32 [M, >= ndim], batch ids
+    int32 or None.  With ``use_xyz`` the offsets from the query to the points, cast to the feature dtype, come in front of
+    the C feature columns.  Empty slots repeat slot 0 (pad="first"), so the caller's MLP and a plain ``max(1)`` follow
+    in torch; a query without any point gets zeros and count 0.  The gradient goes to feats only, added in a fixed order
+    without atomics; there is no gradient with respect to coordinates."""
+
+    def __init__(self, radius: float, nsample: int, use_xyz: bool = True, ndim: int = 3):
+        super().__init__()
+        from spconv_amd.pytorch import _query, _sample
+        if radius is None:
+            raise ValueError("BallQueryAndGroup: radius must be >= 0, got None")
+        _query.squared_radius(radius)
+        self.nsample = _sample._check_ball(nsample, "first")
+        if ndim not in (2, 3):
+            raise ValueError(f"BallQueryAndGroup: ndim must be 2 or 3, got {ndim}")
+        self.radius, self.use_xyz, self.ndim = float(radius), bool(use_xyz), int(ndim)
+
+    def forward(self, points: torch.Tensor, p_batch_ids: Optional[torch.Tensor], feats: torch.Tensor, queries: torch.Tensor,
+                q_batch_ids: Optional[torch.Tensor], batch_size: int, n_queries: Optional[torch.Tensor] = None,
+                n_points: Optional[torch.Tensor] = None, groups=None):
+        from spconv_amd.pytorch import functional as F
+        nb = F.ball_query(queries, q_batch_ids, points, p_batch_ids, batch_size, self.radius, self.nsample, ndim=self.ndim,
+                          pad="first", with_offsets=self.use_xyz, n_queries=n_queries, n_points=n_points,
+                          with_groups=bool(feats.requires_grad and torch.is_grad_enabled()), groups=groups)
+        grouped = F.group_voxels(feats, nb)
+        if self.use_xyz:
+            grouped = torch.cat([nb.offsets.to(grouped.dtype), grouped], dim=2)
+        return grouped, nb.count
+
+    def extra_repr(self) -> str:
+        return f"radius={self.radius}, nsample={self.nsample}, use_xyz={self.use_xyz}, ndim={self.ndim}"
