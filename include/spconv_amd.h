@@ -117,7 +117,9 @@ int spx_set_option(const char *name_h, int value);
  *   query/ranked, query/hash, query/group_fwd, query/group_bwd
  *                                                  voxel query and grouping: calls of spx_voxel_query by lookup form,
  *                                                  of spx_group_fwd and of spx_group_bwd
- *   sample/fps, sample/ball_query                  raw-point sampling: calls of spx_fps and of spx_ball_query that launch
+ *   sample/fps, sample/ball_query, sample/knn_query
+ *                                                  raw-point sampling: calls of spx_fps, of spx_ball_query and of
+ *                                                  spx_knn_query that launch
  *   select/score, select/hist, select/pick, select/ties, select/flags, select/count, select/scan, select/scatter,
  *   select/map                                     voxel pruning, one count per launch: spx_row_score; the passes of
  *                                                  spx_topk_flags (hist and pick once per 8-bit digit: four each; ties:
@@ -1190,6 +1192,47 @@ int spx_ball_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids
                    const int32_t *n_queries_dev, const float *points, int nfeat, int n_cap, int ndim,
                    const int32_t *offsets, const int32_t *list, int batch, int nsample, float r2, int flags,
                    int32_t *rows, int32_t *count, float *out_offsets, spx_stream_t stream);
+
+/* ---- k-nearest-neighbour query and inverse-distance weights over raw points (csrc/knn.hip) ------------------
+ * The way back from few points to many, and grouping by nearest neighbours instead of by radius: three_nn +
+ * three_interpolate of pointnet2's feature propagation (PointNet++, PointRCNN, 3DSSD, IA-SSD, the point heads of the
+ * PV-RCNN family) and knn_query of pointops (Point Transformer grouping, unpooling interpolation, DGCNN-style edge
+ * features).  The call returns tables the library already blends and gathers: rows + weights at width 4 or 8 are what
+ * spx_interp_fwd / spx_interp_bwd take, rows at width k what spx_group_fwd / spx_group_bwd take, with the points as
+ * the "level".  The caller allocates, there is no workspace, nothing is read back, nothing synchronises, the grid
+ * depends on host-known sizes only (hipGraph-safe), and the argument checks that need no pointer come before any
+ * pointer is looked at.  No gradient with respect to coordinates or weights.
+ *
+ *   spx_knn_query: SCENES, the validity of a point (below the device point count given to spx_point_groups, a batch id
+ *   in [0, batch), its first ndim coordinates finite) and d2 are those of the section above; queries, q_batch_ids and
+ *   n_queries_dev as spx_ball_query takes them.  A query is VALID when it lies below *n_queries, its batch id is in
+ *   [0, batch) and its first ndim coordinates are FINITE (stricter than the ball query, which turns down NaN only).
+ *   With d_j = p_j - q_j, the result of a valid query is the count = min(valid points of its scene, k) smallest
+ *   candidates under the TOTAL ORDER (d2, point index), written in that order: equal distances go to the lower point
+ *   index.  (A non-negative float orders as its bits: the 64-bit key d2 bits << 32 | index decides both fields with
+ *   one compare.)  The result does not depend on the order in which points are visited, nor on how queries or points
+ *   are arranged across scenes.  k in 1 .. spx_knn_max_k() = 64; width >= k is the row stride of every table:
+ *       rows        int32 [m_cap, width]           point indices
+ *       count       int32 [m_cap]
+ *       dist2       fp32  [m_cap, width]           (or NULL) d2
+ *       weights     fp32  [m_cap, width]           (or NULL) see below
+ *       out_offsets fp32  [m_cap, width, ndim]     (or NULL) d_j
+ *   Slots in [count, k) hold -1 / 0, or, with flag 2 (pad = first) and count > 0, slot 0 again with weight 0; slots in
+ *   [k, width) always hold -1 / 0.  An invalid query has count 0.  flags = 0 | 2.
+ *   WEIGHTS are pointnet2's, in fp32 with every operation rounded on its own (square root and division correctly
+ *   rounded), eps finite and >= 0:
+ *       r_s = 1 / (sqrt(d2_s) + eps)       norm = ((r_0 + r_1) + r_2) ... over s < count, in ascending slot
+ *       w_s = r_s / norm
+ *   Squared distances that overflow fp32 are outside the contract.  Requires m_cap * width < 2^31.  One lane per query,
+ *   workgroups of 256 consecutive queries which walk the scenes of their queries in ascending order and stage that
+ *   scene's points in LDS; a lane keeps its k best keys sorted in registers (lists of 4, 16 or 64 by k).  Brute force
+ *   per scene: no spatial index.  One launch (none for m_cap = 0). */
+int spx_knn_max_k(void);
+int spx_knn_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids, int m_cap,
+                  const int32_t *n_queries_dev, const float *points, int nfeat, int n_cap, int ndim,
+                  const int32_t *offsets, const int32_t *list, int batch, int k, int width, float eps, int flags,
+                  int32_t *rows, int32_t *count, float *dist2, float *weights, float *out_offsets,
+                  spx_stream_t stream);
 
 /* ---- voxel pruning (csrc/select.hip) ---------------------------------------------------------------------
  * Keep the most important rows of a sparse tensor and drop, or process separately, the rest: the pruned down-sampling

@@ -205,6 +205,10 @@ SIGNATURES = {
     "spx_ball_query": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, vp,
                                       vp, vp, vp]),
+    "spx_knn_max_k": (ctypes.c_int, []),
+    "spx_knn_query": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                     ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     "spx_row_score": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
     "spx_topk_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "spx_topk_flags": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -199,7 +199,7 @@ std::atomic<long long> *query_counter(const char *key) {
 
 // counter of a raw-point sampling key (spx_launch_count), or null
 std::atomic<long long> *sample_counter(const char *key) {
-  static const char *names[kSampleCount] = {"sample/fps", "sample/ball_query"};
+  static const char *names[kSampleCount] = {"sample/fps", "sample/ball_query", "sample/knn_query"};
   for (int i = 0; i < kSampleCount; ++i)
     if (strcmp(key, names[i]) == 0) return &g_sample_launches[i];
   return nullptr;

@@ -227,9 +227,9 @@ enum QueryInst { kQueryRanked = 0, kQueryHash, kQueryGroupFwd, kQueryGroupBwd, k
 extern std::atomic<long long> g_query_launches[kQueryCount];
 inline void count_query(QueryInst i) { g_query_launches[i].fetch_add(1, std::memory_order_relaxed); }
 
-// farthest-point sampling and ball query over raw points (sample.hip): one counter per entry point.
-// Keys sample/fps, sample/ball_query.
-enum SampleInst { kSampleFps = 0, kSampleBallQuery, kSampleCount };
+// farthest-point sampling and ball query over raw points (sample.hip) and the k-nearest-neighbour query (knn.hip): one
+// counter per entry point.  Keys sample/fps, sample/ball_query, sample/knn_query.
+enum SampleInst { kSampleFps = 0, kSampleBallQuery, kSampleKnnQuery, kSampleCount };
 extern std::atomic<long long> g_sample_launches[kSampleCount];
 inline void count_sample(SampleInst i) { g_sample_launches[i].fetch_add(1, std::memory_order_relaxed); }
 

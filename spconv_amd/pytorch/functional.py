@@ -601,6 +601,12 @@ from spconv_amd.pytorch._query import (VoxelNeighbors, group_voxels, voxel_query
 from spconv_amd.pytorch._sample import (PointSamples, ball_query, ball_query_into,  # noqa: E402,F401
                                         farthest_point_sample, fps_into, gather_samples, scene_groups)
 
+# k-nearest-neighbour query and inverse-distance interpolation over raw points (csrc/knn.hip; not part of the reference):
+# the k points that come first under (squared distance, point index), as the tables group_voxels gathers and
+# voxels_to_points_trilinear blends
+from spconv_amd.pytorch._knn import (PointKNN, knn_interpolate, knn_query, knn_query_into,  # noqa: E402,F401
+                                     three_nn)
+
 # voxel serialisation (csrc/serialize.hip; not part of the reference): rows ordered along Z-order / Hilbert curves and
 # cut into fixed-size patches, for the serialised point / voxel transformers
 from spconv_amd.pytorch import _serialize  # noqa: E402

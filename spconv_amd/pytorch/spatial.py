@@ -2,7 +2,8 @@
 from a 3-D backbone to a sparse 2-D head on the kernels of csrc/collapse.hip; ``SparsePrune`` (csrc/select.hip);
 ``TrilinearDevoxelize``: a sparse level read out at points (csrc/interp.hip); ``VoxelQueryAndGroup``: the voxels around
 query points, gathered (csrc/query.hip); ``FarthestPointSample`` / ``BallQueryAndGroup``: keypoints of a raw cloud and the
-raw points around query points, gathered (csrc/sample.hip)."""
+raw points around query points, gathered (csrc/sample.hip); ``KNNInterpolate`` / ``KNNQueryAndGroup``: features carried
+to many points from their nearest few, and the nearest raw points of query points, gathered (csrc/knn.hip)."""
 from typing import Optional, Sequence
 
 import torch
@@ -245,3 +246,78 @@ class BallQueryAndGroup(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return f"radius={self.radius}, nsample={self.nsample}, use_xyz={self.use_xyz}, ndim={self.ndim}"
+
+
+class KNNInterpolate(torch.nn.Module):
+    """Features carried from few known points to many unknown ones by inverse-distance interpolation over the k nearest
+    (``functional.knn_query`` + ``functional.knn_interpolate``, the kernels of csrc/knn.hip and csrc/interp.hip): the
+    ``three_nn`` / ``three_interpolate`` pair of pointnet2's feature propagation at k = 3.  Not part of the reference.
+
+    ``k`` in 1 .. 8 (the blend takes a table of 4 entries for k <= 4 and of 8 otherwise); ``eps`` >= 0: ``w = 1 /
+    (sqrt(d2) + eps)``, normalised over the kept neighbours.  ``forward(known_points, known_batch_ids, known_feats,
+    unknown_points, unknown_batch_ids, batch_size) -> [M, C]``: known_points fp32 [N, >= ndim], known_feats [N, C],
+    unknown_points fp32 [M, >= ndim], batch ids int32 or None.  Equal distances go to the lower point index; an unknown
+    point whose scene holds no valid known point gets zeros.  The gradient goes to known_feats only, added in a fixed
+    order without atomics; there is no gradient with respect to coordinates or weights."""
+
+    def __init__(self, k: int = 3, eps: float = 1e-8, ndim: int = 3):
+        super().__init__()
+        from spconv_amd.pytorch import _knn
+        if not 1 <= int(k) <= 8:
+            raise ValueError(f"KNNInterpolate: k must be in 1 .. 8 (the blend is at most 8 wide), got {k}")
+        _knn._check_knn("KNNInterpolate", k, None, "none", eps)
+        if ndim not in (2, 3):
+            raise ValueError(f"KNNInterpolate: ndim must be 2 or 3, got {ndim}")
+        self.k, self.eps, self.ndim = int(k), float(eps), int(ndim)
+        self.width = 4 if self.k <= 4 else 8
+
+    def forward(self, known_points: torch.Tensor, known_batch_ids: Optional[torch.Tensor], known_feats: torch.Tensor,
+                unknown_points: torch.Tensor, unknown_batch_ids: Optional[torch.Tensor], batch_size: int,
+                n_unknown: Optional[torch.Tensor] = None, n_known: Optional[torch.Tensor] = None, groups=None):
+        from spconv_amd.pytorch import functional as F
+        knn = F.knn_query(unknown_points, unknown_batch_ids, known_points, known_batch_ids, batch_size, self.k,
+                          ndim=self.ndim, width=self.width, with_dist2=False, with_weights=True, eps=self.eps,
+                          n_queries=n_unknown, n_points=n_known,
+                          with_groups=bool(known_feats.requires_grad and torch.is_grad_enabled()), groups=groups)
+        return F.knn_interpolate(known_feats, knn)
+
+    def extra_repr(self) -> str:
+        return f"k={self.k}, eps={self.eps}, ndim={self.ndim}"
+
+
+class KNNQueryAndGroup(torch.nn.Module):
+    """The k nearest raw points of every query, gathered for a shared MLP (``functional.knn_query`` +
+    ``functional.group_voxels``, the kernels of csrc/knn.hip and csrc/query.hip): the ``knn_query`` / ``grouping`` pair
+    of pointops.  Not part of the reference.
+
+    ``k`` in 1 .. 64: the points of the query's scene that come first under (squared distance, point index).
+    ``forward(points, p_batch_ids, feats, queries, q_batch_ids, batch_size) -> ([M, k, (ndim +) C], count [M])``:
+    points fp32 [N, >= ndim], feats [N, C], queries fp32 [M, >= ndim], batch ids int32 or None.  With ``use_xyz`` the
+    offsets from the query to the points, cast to the feature dtype, come in front of the C feature columns.  Slots
+    beyond a scene's valid points repeat slot 0 (pad="first"), mirroring ``BallQueryAndGroup``; a query without any
+    point gets zeros and count 0.  The gradient goes to feats only, added in a fixed order without atomics; there is
+    no gradient with respect to coordinates."""
+
+    def __init__(self, k: int, use_xyz: bool = True, ndim: int = 3):
+        super().__init__()
+        from spconv_amd.pytorch import _knn
+        self.k, _ = _knn._check_knn("KNNQueryAndGroup", k, None, "first", 0.0)
+        if ndim not in (2, 3):
+            raise ValueError(f"KNNQueryAndGroup: ndim must be 2 or 3, got {ndim}")
+        self.use_xyz, self.ndim = bool(use_xyz), int(ndim)
+
+    def forward(self, points: torch.Tensor, p_batch_ids: Optional[torch.Tensor], feats: torch.Tensor, queries: torch.Tensor,
+                q_batch_ids: Optional[torch.Tensor], batch_size: int, n_queries: Optional[torch.Tensor] = None,
+                n_points: Optional[torch.Tensor] = None, groups=None):
+        from spconv_amd.pytorch import functional as F
+        knn = F.knn_query(queries, q_batch_ids, points, p_batch_ids, batch_size, self.k, ndim=self.ndim, pad="first",
+                          with_dist2=False, with_offsets=self.use_xyz, n_queries=n_queries, n_points=n_points,
+                          with_groups=bool(feats.requires_grad and torch.is_grad_enabled()), groups=groups)
+        nb = knn.neighbors()
+        grouped = F.group_voxels(feats, nb)
+        if self.use_xyz:
+            grouped = torch.cat([nb.offsets.to(grouped.dtype), grouped], dim=2)
+        return grouped, nb.count
+
+    def extra_repr(self) -> str:
+        return f"k={self.k}, use_xyz={self.use_xyz}, ndim={self.ndim}"
