@@ -382,6 +382,26 @@ int spx_table_to_native(const int32_t *table, int subm, int kv, int n, int32_t *
  * (spx_igemm_fwd_stats: *slots_used_h = 0), and the fused backward stays at C <= 128. */
 size_t spx_igemm_acc_bytes(int n_dst, int cout, int kv);
 
+/* What the gather-GEMM entries may be handed (spx_igemm_fwd / _fwd_stats / _fwd_int8 / _dgrad / _wgrad / _bwd / _bwd_rows /
+ * _bwd_deferred + spx_wgrad_stage2_batch, spx_bias_act_inplace); tests/test_gpu_gemm_isolation.py holds every kernel family
+ * to it:
+ *   (a) Dirty memory on entry.  Outputs, workspaces and statistics records may hold any bytes on entry: every element the
+ *       caller reads afterwards has been stored, no region of a workspace is read before it is written.
+ *   (b) Rows that no pair names.  A feature row or dout row that no table column, list entry or identity offset names may
+ *       hold anything, NaN and Inf included (the dead rows of a static-shape tensor are such rows); it changes no output
+ *       bit.  An identity offset (identity_k >= 0; subm = 1 in the backward entries, whose centre list is the identity
+ *       over all rows) NAMES every row: a caller with dead rows in a SubM layer keeps them finite, or passes
+ *       identity_k = -1 / explicit lists and leaves them out of the tables.  spx_igemm_bwd_rows reads its whole table.
+ *   (c) Row outputs.  An element of out / din is NaN, +Inf or -Inf exactly where the sum over the existing pairs is, and
+ *       this holds through bias and activation with torch's semantics: relu(NaN) = NaN, relu(-Inf) = 0,
+ *       sigmoid(+-Inf) = 1 / 0, leaky slope x Inf keeps its sign.  (The fused BatchNorm + ReLU apply of
+ *       spx_batchnorm_fwd does the same.)
+ *   (d) Weight gradient.  Every element that is non-finite in the sum over the listed pairs is non-finite in dW (nothing
+ *       is swallowed).  A non-finite dW[kk, k, c] occurs only if some NAMED feat row is non-finite in channel c or some
+ *       named dout row is non-finite in column kk.  It may occur at an offset k the sum itself is finite at: the row-tile
+ *       form (spx_igemm_bwd_rows) multiplies a tile's feat rows with the zero row an absent pair gathers, 0 x Inf = NaN.
+ *   (e) Non-finite weights, bias or int8 scales are outside the contract: MFMA tiles multiply absent pairs as zero rows. */
+
 /* Output-stationary implicit GEMM (atomics-free):
  *   out[o,:] = sum_k [pair[k][o] >= 0] feat[pair[k][o],:] * W[:,k,:]^T  (+bias, act)
  * Replaces ConvGemmOps.implicit_gemm forward (csrc/sparse/convops.py:2073-2243,

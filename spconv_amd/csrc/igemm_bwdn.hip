@@ -185,13 +185,18 @@ bwdn_kernel(BwdnParams p) {
       w[nb] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rW, (off + dcol) | (dcol & kOob), 0, 0));
     }
   };
-  auto load_feat = [&](int tile_of, uint4 (&f)[FPT]) __attribute__((always_inline)) {
+  // A row that no pair names (mask word 0: a dead row of a static-shape tensor) may hold anything, NaN included, and
+  // an absent pair is a ZERO dout row in the weight-gradient product: 0 x NaN would reach dW.  Such a row goes to the
+  // stage as zeros; its mask word travels with it (no dependent trip) and decides at the LDS write.
+  auto load_feat = [&](int tile_of, uint4 (&f)[FPT], uint32_t (&fm)[FPT]) __attribute__((always_inline)) {
 #pragma unroll
     for (int q = 0; q < FPT; ++q) {
       const int pc = tid + q * NT, r = pc / SLC, sl = pc % SLC;
       const int row = tile_of * kBnTile + r;
-      const uint32_t off = (tile_of >= 0 && row < p.n_in && pc < kBnTile * SLC) ? static_cast<uint32_t>(row) * rowF + sl * 16u : kOob;
-      f[q] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rF, off, 0, 0));
+      const bool in = tile_of >= 0 && row < p.n_in && pc < kBnTile * SLC;
+      f[q] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
+          rF, in ? static_cast<uint32_t>(row) * rowF + sl * 16u : kOob, 0, 0));
+      fm[q] = __builtin_amdgcn_raw_buffer_load_b32(rM, in ? static_cast<uint32_t>(row) * 4u : kOob, 0, 0);
     }
   };
 
@@ -215,7 +220,8 @@ bwdn_kernel(BwdnParams p) {
     load_idx(la_t_pending, la_r_pending, ixn);
   }
   uint4 fpre[FPT];
-  load_feat(my_tiles > 0 ? static_cast<int>(blockIdx.x) : -1, fpre);
+  uint32_t fmask[FPT];
+  load_feat(my_tiles > 0 ? static_cast<int>(blockIdx.x) : -1, fpre, fmask);
 
   int stage = 0;
   for (int j = 0; j < my_tiles; ++j) {
@@ -225,9 +231,10 @@ bwdn_kernel(BwdnParams p) {
 #pragma unroll
     for (int q = 0; q < FPT; ++q) {
       const int pc = tid + q * NT;
-      if (pc < kBnTile * SLC) *reinterpret_cast<uint4 *>(sF + ctr_slot(pc / SLC, pc % SLC)) = fpre[q];
+      if (pc < kBnTile * SLC)
+        *reinterpret_cast<uint4 *>(sF + ctr_slot(pc / SLC, pc % SLC)) = (fmask[q] & kvmask) ? fpre[q] : make_uint4(0u, 0u, 0u, 0u);
     }
-    load_feat(j + 1 < my_tiles ? tile + G : -1, fpre);      // the next tile's rows: in flight during this tile
+    load_feat(j + 1 < my_tiles ? tile + G : -1, fpre, fmask);      // the next tile's rows: in flight during this tile
 
     f32x4 acc_d[MB][NBC];
 #pragma unroll

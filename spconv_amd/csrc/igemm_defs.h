@@ -436,7 +436,7 @@ int with_elem_type(int dtype, F &&f) {
 }
 
 __device__ __forceinline__ float apply_act(float v, int act, float alpha) {
-  if (act == SPX_ACT_RELU) return v > 0.f ? v : 0.f;
+  if (act == SPX_ACT_RELU) return !(v <= 0.f) ? v : 0.f;      // (NaN stays NaN, as torch.relu has it)
   if (act == SPX_ACT_LEAKY_RELU) return v > 0.f ? v : v * alpha;
   if (act == SPX_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
   return v;

@@ -45,7 +45,7 @@ __device__ __forceinline__ f64x4 mfma_f64(double a, double b, f64x4 c) {
 }
 
 __device__ __forceinline__ double act_f64(double v, int act, float alpha) {
-  if (act == SPX_ACT_RELU) return v > 0.0 ? v : 0.0;
+  if (act == SPX_ACT_RELU) return !(v <= 0.0) ? v : 0.0;      // (NaN stays NaN, as torch.relu has it)
   if (act == SPX_ACT_LEAKY_RELU) return v > 0.0 ? v : v * static_cast<double>(alpha);
   if (act == SPX_ACT_SIGMOID) return 1.0 / (1.0 + exp(-v));
   return v;

@@ -477,7 +477,7 @@ bn_apply_kernel(const u32x4 *__restrict__ x, u32x4 *__restrict__ y, long long pi
 #pragma unroll
       for (int e = 0; e < VPL; ++e) {
         float o = f[e] * l_sc[c0 + e] + l_sh[c0 + e];
-        if (relu) o = o > 0.f ? o : 0.f;
+        if (relu) o = !(o <= 0.f) ? o : 0.f;          // (NaN stays NaN, as torch.relu has it)
         f[e] = r < live ? o : 0.f;
       }
       __builtin_nontemporal_store(Vec<DT>::pack(f), &y[r * blk.Prow]);
@@ -511,7 +511,7 @@ bn_apply_kernel(const u32x4 *__restrict__ x, u32x4 *__restrict__ y, long long pi
 #pragma unroll
     for (int e = 0; e < VPL; ++e) {
       float r = f[e] * l_sc[c0 + e] + l_sh[c0 + e];
-      if (relu) r = r > 0.f ? r : 0.f;
+      if (relu) r = !(r <= 0.f) ? r : 0.f;
       f[e] = i < live ? r : 0.f;
     }
     __builtin_nontemporal_store(Vec<DT>::pack(f), &y[i]);      // (not read again by this launch)

@@ -166,3 +166,93 @@ def test_ref_empty_scene_and_dead_rows():
     f = torch.ones((3, 4), dtype=torch.float64)
     r = ref_conv(idx, 1, shape, f, w, None, ks, [1] * 3, [1] * 3, [1] * 3, True)
     assert float(r.out[2].abs().sum()) == 0.0 and float(r.out[0, 0]) == 8.0
+
+
+# ---------------------------------------------------------------- non-finite operands
+# The isolation tests (test_gpu_gemm_isolation.py) compare the kernels' NaN / +Inf / -Inf placement with the reference's.
+# Here the reference's placement is held to tests/nonfinite.py, which derives it from the pair lists by set arithmetic
+# alone (which non-finite operand reaches which element, with which sign): no floating sum is formed there.
+NONFINITE_CASES = [
+    # shape, n, bs, ksize, stride, pad, dil, subm
+    ([10, 10, 10], 400, 2, [3] * 3, [1] * 3, [1] * 3, [1] * 3, True),
+    ([12, 12, 12], 500, 1, [3] * 3, [2] * 3, [1] * 3, [1] * 3, False),
+    ([12, 12, 12], 500, 1, [2] * 3, [2] * 3, [0] * 3, [1] * 3, False),
+    ([9, 9, 9], 250, 1, [5, 3, 3], [1] * 3, [2, 1, 1], [1] * 3, True),
+]
+
+
+def _same_classes(t, cls, name):
+    from nonfinite import masks_of
+    for kind, got, want in zip(("NaN", "+Inf", "-Inf"), masks_of(t), (cls.nan, cls.pinf, cls.ninf)):
+        assert torch.equal(got, want), f"{name}: {kind} at {int(got.sum())} elements, set arithmetic gives {int(want.sum())}"
+    assert bool(cls.nan.any()) and bool(cls.pinf.any()) and bool(cls.ninf.any()), f"{name}: a class does not occur"
+
+
+@pytest.mark.parametrize("shape,n,bs,ksize,stride,pad,dil,subm", NONFINITE_CASES)
+def test_ref_places_non_finite_values_as_set_arithmetic_does(shape, n, bs, ksize, stride, pad, dil, subm):
+    from nonfinite import classify_dw, classify_rows, poison_rows, poisoned
+    from refconv import conv_from_pairs, pairs
+    idx = scene(shape, n, bs, 5)
+    rng = np.random.default_rng(3)
+    C, K = 5, 6
+    out_idx, cand = pairs(idx, bs, shape, ksize, stride, pad, dil, subm)
+    n_in, n_out = idx.shape[0], out_idx.shape[0]
+    f = torch.from_numpy(rng.uniform(-1, 1, (n_in, C)))
+    w = torch.from_numpy(rng.uniform(0.1, 1, (K, *ksize, C)) * rng.choice([-1.0, 1.0], (K, *ksize, C)))    # nonzero
+    g = torch.from_numpy(rng.uniform(-1, 1, (n_out, K)))
+    f[3, 1] = 0.0                                       # (an exact zero next to an Inf partner in dW: Inf x 0 = NaN)
+    f = poisoned(f, poison_rows(cand, n_in, C, 1))
+    g = poisoned(g, poison_rows(cand, n_out, K, 2, swap=True))
+    ref = conv_from_pairs(out_idx, cand, f, w, g)
+    w3 = w.reshape(K, -1, C)
+    out_cls = classify_rows(cand, f, w3, n_out)
+    _same_classes(ref.out, out_cls, "out")
+    assert bool(out_cls.mixed.any()), "no output receives +Inf and -Inf together"
+    _same_classes(ref.din, classify_rows([(k, o, i) for k, i, o in cand], g, w3, n_in, transposed=True), "din")
+    _same_classes(ref.dW.reshape(K, -1, C), classify_dw(cand, f, g, (K, w3.shape[1], C)), "dW")
+    # the magnitude sums are non-finite exactly where the values are (finite elements keep a finite bound)
+    assert torch.equal(torch.isfinite(ref.out), torch.isfinite(ref.out_abs))
+    assert torch.equal(torch.isfinite(ref.din), torch.isfinite(ref.din_abs))
+    assert torch.equal(torch.isfinite(ref.dW), torch.isfinite(ref.dW_abs))
+
+
+def _isolation_cases():
+    import test_gpu_gemm_isolation as iso
+    return iso.CASES + iso.ACT_CASES
+
+
+def _iso_id(c):
+    import test_gpu_gemm_isolation as iso
+    return iso._id(c)
+
+
+@pytest.mark.parametrize("c", _isolation_cases(), ids=[_iso_id(c) for c in _isolation_cases()])
+def test_isolation_inputs_meet_their_conditions(c):
+    """A condition on the INPUTS of test_gpu_gemm_isolation.py's named-rows group, not a measurement: with the rows that
+    group poisons, between 1 % and 50 % of the rows of every row output are non-finite in the reference, and at least one
+    element receives +Inf and -Inf together (NaN out of infinities alone)."""
+    import test_gpu_gemm_isolation as iso
+    import test_gpu_kernel_matrix as M
+    from nonfinite import classify_rows
+    from refconv import conv_from_pairs, pairs
+    idx, shape, bs = M.scene_indices(c["scene"])
+    ks, st, pd, dl, subm = M.GEOMS[c["geom"]]
+    out_idx, cand = pairs(idx, bs, shape, ks, st, pd, dl, subm)      # (on the CPU, past the matrix's device-side cache)
+    n_in, n_out = idx.shape[0], out_idx.shape[0]
+    f, w, d, _ = M._operands(c, n_in, n_out, ks, "cpu")
+    assert bool((w != 0).all()), "a zero weight"
+    f, d = iso.named_inputs(c, cand, f, d)
+    ref = conv_from_pairs(out_idx, cand, f, w, d)
+    w3 = w.reshape(c["K"], -1, c["C"])
+    checks = []
+    if c["entry"] != "dgrad":
+        checks.append(("out", ref.out, lambda: classify_rows(cand, f, w3, n_out)))
+    if d is not None and c["entry"] != "wgrad":
+        checks.append(("din", ref.din, lambda: classify_rows([(k, o, i) for k, i, o in cand], d, w3, n_in, transposed=True)))
+    for name, t, classes in checks:
+        frac = float((~torch.isfinite(t)).any(1).double().mean())
+        assert 0.01 <= frac <= 0.5, f"{name}: {frac:.3%} of the rows are non-finite"
+        assert bool(classes().mixed.any()), f"{name}: no element receives +Inf and -Inf together"
+    if d is not None:
+        bad = ~torch.isfinite(ref.dW)
+        assert bool(bad.any()) and not bool(bad.all())
