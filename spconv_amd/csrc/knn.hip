@@ -1,14 +1,15 @@
 // k-nearest-neighbour query over raw points with inverse-distance weights (spx_knn_query): the three_nn of pointnet2's
 // feature propagation (k = 3, width 4: the table spx_interp_fwd / spx_interp_bwd blend) and the knn_query of pointops
-// (the rows spx_group_fwd / spx_group_bwd gather).  Scenes, validity of a point and the distance are sample.hip's.
+// (the rows spx_group_fwd / spx_group_bwd gather).  Scenes (sample.hip says what one is), the validity of a point and of
+// a query, the distance, the scene walk and the host checks of such a call are scenes.h's.
 //
 //   result    per valid query the min(valid points of its scene, k) smallest candidates under the TOTAL ORDER (d2, point
 //             index), in that order.  One 64-bit key per candidate -- the bits of d2 (a non-negative float orders as its
 //             bits) above the point index -- decides both fields with one compare, so the result does not depend on the
 //             order in which points are met.
 //   kernel    one lane per query, workgroups of 256 consecutive queries, the scene walk and the staged tiles of
-//             ball_query_kernel: ascending scenes of the workgroup's queries, tiles of 1024 {x, y, z, index} records in
-//             LDS, eight staged points tested at a time.  The gate is one float compare per point against the d2 of the
+//             scenes.h: ascending scenes of the workgroup's queries, tiles of 1024 {x, y, z, index} records in LDS,
+//             eight staged points tested at a time.  The gate is one float compare per point against the d2 of the
 //             lane's worst kept key; only a point that passes it builds its key.
 //   list      a lane keeps T = 4 / 16 / 64 keys sorted ascending in registers (the tier: the smallest T >= k).  Slots
 //             [0, T - k) hold key 0 and never move, the k best are slots [T - k, T): the worst kept key is the STATIC
@@ -17,9 +18,8 @@
 //             sentinel {+inf, 0xffffffff}, above every real key.
 // Every barrier sits in control flow that is uniform over the workgroup (see sample.hip).  Distances, square roots and
 // divisions are fp32 operations rounded on their own, so a host loop reproduces every output bit for bit.
-#include <limits.h>
-
 #include "common.h"
+#include "scenes.h"
 
 // no multiply-add pair of this unit may be contracted into an FMA (see pointvoxel.hip)
 #pragma clang fp contract(off)
@@ -27,49 +27,12 @@
 namespace spx {
 namespace {
 
-constexpr int kKnnBlock = 256, kKnnWaves = kKnnBlock / kWave, kKnnTile = 1024;
-constexpr int kKnnAhead = 8;                         // staged points a lane tests together
 constexpr int kKnnChain = 8;                         // slots of a block of an insertion
-static_assert(kKnnTile % kKnnAhead == 0, "a padded tile stays inside the staged array");
 constexpr int kKnnMaxK = 64;
-constexpr int kFlagPadFirst = 2;
-
-typedef unsigned long long u64;
 constexpr u64 kEmpty = (0x7f800000ull << 32) | 0xffffffffull;    // d2 = +inf, no point index
 
-template <int NDIM> __device__ __forceinline__ float dist2(const float (&d)[NDIM]) {
-  float s = d[0] * d[0] + d[1] * d[1];
-  if (NDIM == 3) s = s + d[NDIM - 1] * d[NDIM - 1];
-  return s;
-}
-
-__device__ __forceinline__ bool finite(float v) { return fabsf(v) < __builtin_huge_valf(); }      // (false for NaN)
-
-// Position `pos` of a scene (its list starts at list_b): the point's coordinates; false for an index outside the
-// points and for a coordinate that is not finite.
-template <int NDIM>
-__device__ __forceinline__ bool load_point(const float *__restrict__ points, int nfeat, int n_cap,
-                                           const int32_t *__restrict__ list_b, int pos, float (&p)[NDIM], int &pi) {
-  pi = list_b[pos];
-  bool ok = static_cast<unsigned>(pi) < static_cast<unsigned>(n_cap);
-#pragma unroll
-  for (int j = 0; j < NDIM; ++j) {
-    p[j] = ok ? points[static_cast<size_t>(pi) * nfeat + j] : 0.f;
-    ok = ok && finite(p[j]);
-  }
-  return ok;
-}
-
-struct KnnArgs {
-  const float *queries;
-  int q_nfeat;
-  const int32_t *q_batch_ids;
-  int m_cap;
-  const int32_t *n_queries;
-  const float *points;
-  int nfeat, n_cap;
-  const int32_t *offsets, *list;
-  int batch, k, width;
+struct KnnArgs : SceneArgs {
+  int k, width;
   float eps;
   int flags;
   int32_t *rows, *count;
@@ -104,74 +67,40 @@ template <int T> struct KnnList {
 };
 
 template <int NDIM, int T>
-__global__ void __launch_bounds__(kKnnBlock)
+__global__ void __launch_bounds__(kSceneBlock)
 knn_query_kernel(KnnArgs a) {
-  __shared__ float4 s_pt[kKnnTile];                     // {x, y, z, the point index as bits}; x = NaN: invalid
-  __shared__ int s_next[2][kKnnWaves];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const long long qi = static_cast<long long>(blockIdx.x) * kKnnBlock + tid;
-  const int nq = a.n_queries ? min(*a.n_queries, a.m_cap) : a.m_cap;
+  __shared__ float4 s_pt[kSceneTile];                   // {x, y, z, the point index as bits}; x = NaN: invalid
+  __shared__ int s_next[2][kSceneWaves];
+  const long long qi = static_cast<long long>(blockIdx.x) * kSceneBlock + threadIdx.x;
   const bool exists = qi < a.m_cap;                     // (a lane without a query still takes every barrier)
   const int dead = T - a.k;
-  bool valid = qi < nq;
-  int b = -1;
   float q[NDIM];
-#pragma unroll
-  for (int j = 0; j < NDIM; ++j) q[j] = 0.f;
-  if (valid) {
-    b = a.q_batch_ids ? a.q_batch_ids[qi] : 0;
-    valid = b >= 0 && b < a.batch;
-  }
-  if (valid) {
-#pragma unroll
-    for (int j = 0; j < NDIM; ++j) {
-      q[j] = a.queries[static_cast<size_t>(qi) * a.q_nfeat + j];
-      valid = valid && finite(q[j]);
-    }
-  }
-  const int mine = valid ? b : INT_MAX;
+  const int mine = load_scene_query<NDIM>(a, qi, q);
   KnnList<T> best;
   best.clear(dead);
   int cur = -1;
   for (int it = 0;; ++it) {
-    // the lowest scene above `cur` among the workgroup's queries
-    int cand = mine > cur ? mine : INT_MAX;
-#pragma unroll
-    for (int m = kWave / 2; m >= 1; m >>= 1) cand = min(cand, __shfl_xor(cand, m, kWave));
-    if (lane == 0) s_next[it & 1][wave] = cand;
-    __syncthreads();
-    int next = INT_MAX;
-#pragma unroll
-    for (int w = 0; w < kKnnWaves; ++w) next = min(next, s_next[it & 1][w]);
+    const int next = next_scene(mine, cur, it, s_next);
     if (next == INT_MAX) break;                         // the same LDS words for every lane: uniform
     cur = next;
-    int beg = a.offsets[next], end = a.offsets[next + 1];
-    beg = min(max(beg, 0), a.n_cap);
-    end = min(max(end, beg), a.n_cap);
+    int beg, end;
+    scene_range(a.offsets, a.n_cap, next, beg, end);
     const bool active = mine == next;
-    for (int tile0 = beg; tile0 < end; tile0 += kKnnTile) {
-      const int tn = min(kKnnTile, end - tile0);
-      const int padded = (tn + kKnnAhead - 1) / kKnnAhead * kKnnAhead;        // (the tile is a multiple of kKnnAhead)
-      for (int k = tid; k < padded; k += kKnnBlock) {
-        float p[NDIM] = {};
-        int pi = -1;
-        const bool ok = k < tn && load_point<NDIM>(a.points, a.nfeat, a.n_cap, a.list + tile0, k, p, pi);
-        s_pt[k] = make_float4(ok ? p[0] : __builtin_nanf(""), p[1], NDIM == 3 ? p[NDIM - 1] : 0.f, __int_as_float(pi));
-      }
-      __syncthreads();
-      // kKnnAhead staged points at a time: their reads and distances are independent, a point that enters the list is
+    for (int tile0 = beg; tile0 < end; tile0 += kSceneTile) {
+      const int padded = stage_tile<NDIM>(a, tile0, end, s_pt);
+      // kSceneAhead staged points at a time: their reads and distances are independent, a point that enters the list is
       // rare.  A wave none of whose lanes belongs to this scene skips the tile (a uniform branch); a lane of another
       // scene inside a busy wave never passes the gate.
       const bool wave_active = __ballot(active) != 0ull;
-      for (int k0 = 0; k0 < padded && wave_active; k0 += kKnnAhead) {
-        float4 p[kKnnAhead];
-        float d2[kKnnAhead];
+      for (int k0 = 0; k0 < padded && wave_active; k0 += kSceneAhead) {
+        float4 p[kSceneAhead];
+        float d2[kSceneAhead];
         const float gate = active ? best.worst_d2() : -1.f;          // (no d2 is <= -1: a lane of another scene)
         unsigned hits = 0u;
 #pragma unroll
-        for (int u = 0; u < kKnnAhead; ++u) p[u] = s_pt[k0 + u];
+        for (int u = 0; u < kSceneAhead; ++u) p[u] = s_pt[k0 + u];
 #pragma unroll
-        for (int u = 0; u < kKnnAhead; ++u) {
+        for (int u = 0; u < kSceneAhead; ++u) {
           float d[NDIM];
           d[0] = p[u].x - q[0];
           d[1] = p[u].y - q[1];
@@ -186,7 +115,7 @@ knn_query_kernel(KnnArgs a) {
           hits &= hits - 1u;
           uint32_t hi = __float_as_uint(d2[0]), lo = __float_as_uint(p[0].w);
 #pragma unroll
-          for (int v = 1; v < kKnnAhead; ++v) {
+          for (int v = 1; v < kSceneAhead; ++v) {
             hi = u == v ? __float_as_uint(d2[v]) : hi;
             lo = u == v ? __float_as_uint(p[v].w) : lo;
           }
@@ -250,15 +179,13 @@ knn_query_kernel(KnnArgs a) {
   a.count[qi] = cnt;
 }
 
-inline bool aligned_to(const void *p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
 template <int NDIM> void launch_knn(const KnnArgs &a, dim3 grid, hipStream_t s) {
   if (a.k <= 4)
-    hipLaunchKernelGGL((knn_query_kernel<NDIM, 4>), grid, dim3(kKnnBlock), 0, s, a);
+    hipLaunchKernelGGL((knn_query_kernel<NDIM, 4>), grid, dim3(kSceneBlock), 0, s, a);
   else if (a.k <= 16)
-    hipLaunchKernelGGL((knn_query_kernel<NDIM, 16>), grid, dim3(kKnnBlock), 0, s, a);
+    hipLaunchKernelGGL((knn_query_kernel<NDIM, 16>), grid, dim3(kSceneBlock), 0, s, a);
   else
-    hipLaunchKernelGGL((knn_query_kernel<NDIM, 64>), grid, dim3(kKnnBlock), 0, s, a);
+    hipLaunchKernelGGL((knn_query_kernel<NDIM, 64>), grid, dim3(kSceneBlock), 0, s, a);
 }
 
 }  // namespace
@@ -273,28 +200,15 @@ int spx_knn_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids,
                   int batch, int k, int width, float eps, int flags, int32_t *rows, int32_t *count, float *dist2,
                   float *weights, float *out_offsets, spx_stream_t stream) {
   using namespace spx;
-  SPX_CHECK(ndim == 2 || ndim == 3, "ndim must be 2 or 3, got %d", ndim);
-  SPX_CHECK(n_cap >= 0 && m_cap >= 0, "bad point / query counts %d / %d", n_cap, m_cap);
-  SPX_CHECK(nfeat >= ndim && q_nfeat >= ndim, "points and queries need at least %d columns, got %d / %d", ndim, nfeat,
-            q_nfeat);
-  SPX_CHECK(batch >= 1, "batch must be >= 1, got %d", batch);
   SPX_CHECK(k >= 1 && k <= kKnnMaxK, "k must be in 1 .. %d, got %d", kKnnMaxK, k);
   SPX_CHECK(width >= k, "width must be >= k, got %d < %d", width, k);
-  SPX_CHECK(static_cast<long long>(m_cap) * width < 0x80000000LL, "m_cap * width must stay below 2^31, got %d x %d", m_cap,
-            width);
-  SPX_CHECK((flags & ~kFlagPadFirst) == 0, "flags must be 0 or pad first (2), got %d", flags);
   SPX_CHECK(eps >= 0.f && eps < __builtin_huge_valf(), "eps must be finite and >= 0");
+  const KnnArgs a = {{queries, q_nfeat, q_batch_ids, m_cap, n_queries_dev, points, nfeat, n_cap, offsets, list, batch},
+                     k, width, eps, flags, rows, count, dist2, weights, out_offsets};
+  if (int rc = check_scene_query(a, ndim, width, flags, rows, count, {dist2, weights, out_offsets})) return rc;
   if (m_cap == 0) return 0;
-  SPX_CHECK(queries && rows && count && offsets && (n_cap == 0 || (points && list)),
-            "queries / points / offsets / list / rows / count is NULL");
-  SPX_CHECK(aligned_to(queries, 4) && aligned_to(points, 4) && aligned_to(rows, 4) && aligned_to(count, 4) &&
-                aligned_to(dist2, 4) && aligned_to(weights, 4) && aligned_to(out_offsets, 4) && aligned_to(offsets, 4) &&
-                aligned_to(list, 4),
-            "pointer not aligned to its elements");
-  KnnArgs a = {queries, q_nfeat, q_batch_ids, m_cap, n_queries_dev, points, nfeat, n_cap, offsets, list,       batch,
-               k,       width,   eps,         flags, rows,          count,  dist2, weights, out_offsets};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(static_cast<unsigned>((static_cast<long long>(m_cap) + kKnnBlock - 1) / kKnnBlock));
+  const dim3 grid(static_cast<unsigned>((static_cast<long long>(m_cap) + kSceneBlock - 1) / kSceneBlock));
   if (ndim == 3)
     launch_knn<3>(a, grid, s);
   else

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "lookup.h"
 #include "piece.h"
+#include "scenes.h"
 
 // no multiply-add pair of this unit may be contracted into an FMA (see pointvoxel.hip)
 #pragma clang fp contract(off)
@@ -38,7 +39,7 @@ constexpr int kBlock = 256;
 constexpr int kMaxRange = 15;         // a window line of 31 cells spans at most two 32-cell words of the rank map
 constexpr int kMaxSample = 128;
 static_assert(kRankWords == 1 << 11, "blockoff is indexed by word >> 11");
-constexpr int kFlagRadius = 1, kFlagPadFirst = 2, kFlagWidthShift = 8;      // (flags >> 8: 0, or 1 + log2 of a forced W)
+constexpr int kFlagRadius = 1, kFlagWidthShift = 8;      // (flags >> 8: 0, or 1 + log2 of a forced W; 2: kFlagPadFirst)
 
 struct QueryGeom : PointGeom {
   int range[kPointDims];              // by grid axis (index-column order)
@@ -91,12 +92,6 @@ __device__ __forceinline__ Query<NDIM> load_query(const QueryArgs &a, const Quer
 __device__ __forceinline__ float centre_offset(const QueryGeom &g, int j, int v, float qj) {
   const float centre = (static_cast<float>(v) + 0.5f) * g.vsize[j] + g.lo[j];
   return centre - qj;
-}
-
-template <int NDIM> __device__ __forceinline__ float dist2(const float (&d)[NDIM]) {
-  float s = d[0] * d[0] + d[1] * d[1];
-  if (NDIM == 3) s = s + d[NDIM - 1] * d[NDIM - 1];
-  return s;
 }
 
 // the slots behind the kept hits: -1 / 0, or the first hit again (pad = first)

@@ -15,16 +15,16 @@
 //             ONE barrier per step.  A scene of up to kResident points keeps coordinates and t in registers (no global load in a
 //             step); a larger one streams {x, y, z, t} records staged in ws, each lane its own.  The tier is a uniform
 //             branch on the scene's own count.  No workgroup waits for another.
-//   ball      one lane per query, workgroups of 256 consecutive queries.  The workgroup walks the scenes of its valid
-//             queries in ascending order (scene-contiguous queries: at most two), stages tiles of that scene's points
-//             in LDS, and every lane of the scene tests the staged point all lanes read together (a broadcast),
-//             appending while it has room.  The workgroup leaves a scene once none of its lanes has room.
+//   ball      one lane per query, workgroups of 256 consecutive queries, on the scene walk of scenes.h (with the
+//             distance, the validity of a point and the host checks, shared with knn.hip).  The workgroup walks the
+//             scenes of its valid queries in ascending order (scene-contiguous queries: at most two), stages tiles of
+//             that scene's points in LDS, and every lane of the scene tests the staged point all lanes read together (a
+//             broadcast), appending while it has room.  The workgroup leaves a scene once none of its lanes has room.
 // Every barrier sits in control flow that is uniform over the workgroup: trip counts come from values every lane reads
 // from the same LDS words or from the scene's offsets.  The distances are fp32 with every operation rounded on its
 // own, so a host loop reproduces every output bit for bit.
-#include <limits.h>
-
 #include "common.h"
+#include "scenes.h"
 
 // no multiply-add pair of this unit may be contracted into an FMA (see pointvoxel.hip)
 #pragma clang fp contract(off)
@@ -37,40 +37,11 @@ constexpr int kFpsPer = 16;                          // points per lane of the r
 constexpr int kFpsResident = kFpsBlock * kFpsPer;
 constexpr int kFpsAhead = 6;                         // records of a batch of the streamed tier; a lane keeps two batches
 constexpr int kMaxSamples = 1 << 16;
-constexpr int kBallBlock = 256, kBallWaves = kBallBlock / kWave, kBallTile = 1024;
-constexpr int kBallAhead = 8;                        // staged points a lane tests together
-static_assert(kBallTile % kBallAhead == 0, "a padded tile stays inside the staged array");
 constexpr int kMaxSample = 128;
-constexpr int kFlagPadFirst = 2;
-
-typedef unsigned long long u64;
 
 struct __attribute__((aligned(16))) FpsRec {
   float x, y, z, t;
 };
-
-template <int NDIM> __device__ __forceinline__ float dist2(const float (&d)[NDIM]) {
-  float s = d[0] * d[0] + d[1] * d[1];
-  if (NDIM == 3) s = s + d[NDIM - 1] * d[NDIM - 1];
-  return s;
-}
-
-__device__ __forceinline__ bool finite(float v) { return fabsf(v) < __builtin_huge_valf(); }      // (false for NaN)
-
-// Position `pos` of a scene (its list starts at list_b): the point's coordinates; false for an index outside the
-// points and for a coordinate that is not finite.
-template <int NDIM>
-__device__ __forceinline__ bool load_point(const float *__restrict__ points, int nfeat, int n_cap,
-                                           const int32_t *__restrict__ list_b, int pos, float (&p)[NDIM], int &pi) {
-  pi = list_b[pos];
-  bool ok = static_cast<unsigned>(pi) < static_cast<unsigned>(n_cap);
-#pragma unroll
-  for (int j = 0; j < NDIM; ++j) {
-    p[j] = ok ? points[static_cast<size_t>(pi) * nfeat + j] : 0.f;
-    ok = ok && finite(p[j]);
-  }
-  return ok;
-}
 
 // -------------------------------------------------------------------------------------------- farthest-point sampling
 
@@ -310,9 +281,8 @@ fps_kernel(const float *__restrict__ points, int nfeat, int n_cap, const int32_t
            const int32_t *__restrict__ list, int K, int32_t *idx, int32_t *__restrict__ count, FpsRec *recs) {
   __shared__ FpsShared sh;
   const int b = blockIdx.x;
-  int beg = offsets[b], end = offsets[b + 1];
-  beg = min(max(beg, 0), n_cap);
-  end = min(max(end, beg), n_cap);
+  int beg, end;
+  scene_range(offsets, n_cap, b, beg, end);
   const int n = end - beg;                              // uniform: the scene's own count
   int32_t *out = idx + static_cast<long long>(b) * K;
   if (n == 0) {                                         // before the first barrier
@@ -329,16 +299,8 @@ fps_kernel(const float *__restrict__ points, int nfeat, int n_cap, const int32_t
 
 // -------------------------------------------------------------------------------------------- ball query
 
-struct BallArgs {
-  const float *queries;
-  int q_nfeat;
-  const int32_t *q_batch_ids;
-  int m_cap;
-  const int32_t *n_queries;
-  const float *points;
-  int nfeat, n_cap;
-  const int32_t *offsets, *list;
-  int batch, nsample;
+struct BallArgs : SceneArgs {
+  int nsample;
   float r2;
   int flags;
   int32_t *rows, *count;
@@ -346,14 +308,15 @@ struct BallArgs {
 };
 
 template <int NDIM>
-__global__ void __launch_bounds__(kBallBlock)
+__global__ void __launch_bounds__(kSceneBlock)
 ball_query_kernel(BallArgs a) {
-  __shared__ float4 s_pt[kBallTile];                    // {x, y, z, the point index as bits}; x = NaN: invalid
-  __shared__ int s_next[2][kBallWaves];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const long long qi = static_cast<long long>(blockIdx.x) * kBallBlock + tid;
-  const int nq = a.n_queries ? min(*a.n_queries, a.m_cap) : a.m_cap;
+  __shared__ float4 s_pt[kSceneTile];                   // {x, y, z, the point index as bits}; x = NaN: invalid
+  __shared__ int s_next[2][kSceneWaves];
+  const long long qi = static_cast<long long>(blockIdx.x) * kSceneBlock + threadIdx.x;
   const bool exists = qi < a.m_cap;                     // (a lane without a query still takes every barrier)
+  // load_scene_query with a NaN-only test of the coordinates, kept here: the finite test gives the same results (an
+  // infinite coordinate makes every d2 +inf or NaN, never < r2) but cost 0.6 % of a call (see scenes.h)
+  const int nq = a.n_queries ? min(*a.n_queries, a.m_cap) : a.m_cap;
   bool valid = qi < nq;
   int b = -1;
   float q[NDIM];
@@ -377,40 +340,23 @@ ball_query_kernel(BallArgs a) {
   float first_off[NDIM] = {};
   int cur = -1;
   for (int it = 0;; ++it) {
-    // the lowest scene above `cur` among the workgroup's queries
-    int cand = mine > cur ? mine : INT_MAX;
-#pragma unroll
-    for (int m = kWave / 2; m >= 1; m >>= 1) cand = min(cand, __shfl_xor(cand, m, kWave));
-    if (lane == 0) s_next[it & 1][wave] = cand;
-    __syncthreads();
-    int next = INT_MAX;
-#pragma unroll
-    for (int w = 0; w < kBallWaves; ++w) next = min(next, s_next[it & 1][w]);
+    const int next = next_scene(mine, cur, it, s_next);
     if (next == INT_MAX) break;                         // the same LDS words for every lane: uniform
     cur = next;
-    int beg = a.offsets[next], end = a.offsets[next + 1];
-    beg = min(max(beg, 0), a.n_cap);
-    end = min(max(end, beg), a.n_cap);
+    int beg, end;
+    scene_range(a.offsets, a.n_cap, next, beg, end);
     bool active = mine == next;
-    for (int tile0 = beg; tile0 < end; tile0 += kBallTile) {
-      const int tn = min(kBallTile, end - tile0);
-      const int padded = (tn + kBallAhead - 1) / kBallAhead * kBallAhead;        // (the tile is a multiple of kBallAhead)
-      for (int k = tid; k < padded; k += kBallBlock) {
-        float p[NDIM] = {};
-        int pi = -1;
-        const bool ok = k < tn && load_point<NDIM>(a.points, a.nfeat, a.n_cap, a.list + tile0, k, p, pi);
-        s_pt[k] = make_float4(ok ? p[0] : __builtin_nanf(""), p[1], NDIM == 3 ? p[NDIM - 1] : 0.f, __int_as_float(pi));
-      }
-      __syncthreads();
-      // kBallAhead staged points at a time: their reads and distances are independent, a hit is rare
-      for (int k0 = 0; k0 < padded && active; k0 += kBallAhead) {
-        float4 p[kBallAhead];
-        float d[kBallAhead][NDIM];
+    for (int tile0 = beg; tile0 < end; tile0 += kSceneTile) {
+      const int padded = stage_tile<NDIM>(a, tile0, end, s_pt);
+      // kSceneAhead staged points at a time: their reads and distances are independent, a hit is rare
+      for (int k0 = 0; k0 < padded && active; k0 += kSceneAhead) {
+        float4 p[kSceneAhead];
+        float d[kSceneAhead][NDIM];
         unsigned hits = 0u;
 #pragma unroll
-        for (int u = 0; u < kBallAhead; ++u) p[u] = s_pt[k0 + u];
+        for (int u = 0; u < kSceneAhead; ++u) p[u] = s_pt[k0 + u];
 #pragma unroll
-        for (int u = 0; u < kBallAhead; ++u) {
+        for (int u = 0; u < kSceneAhead; ++u) {
           d[u][0] = p[u].x - q[0];
           d[u][1] = p[u].y - q[1];
           if (NDIM == 3) d[u][NDIM - 1] = p[u].z - q[NDIM - 1];
@@ -418,7 +364,7 @@ ball_query_kernel(BallArgs a) {
         }
         if (hits == 0u) continue;
 #pragma unroll
-        for (int u = 0; u < kBallAhead; ++u) {              // (ascending point index)
+        for (int u = 0; u < kSceneAhead; ++u) {              // (ascending point index)
           if (!(hits >> u & 1u) || cnt >= a.nsample) continue;
           const int pi = __float_as_int(p[u].w);
           ro[cnt] = pi;
@@ -451,21 +397,10 @@ ball_query_kernel(BallArgs a) {
   }
 }
 
-// -------------------------------------------------------------------------------------------- host side
-
-inline bool aligned_to(const void *p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
-// 0 = ok: the checks of a scene list that need no pointer
-int check_scenes(int ndim, int nfeat, int n_cap, int batch) {
-  SPX_CHECK(ndim == 2 || ndim == 3, "ndim must be 2 or 3, got %d", ndim);
-  SPX_CHECK(n_cap >= 0, "bad point counts %d", n_cap);
-  SPX_CHECK(nfeat >= ndim, "points need at least %d columns, got %d", ndim, nfeat);
-  SPX_CHECK(batch >= 1, "batch must be >= 1, got %d", batch);
-  return 0;
-}
-
 }  // namespace
 }  // namespace spx
+
+// -------------------------------------------------------------------------------------------- host side
 
 extern "C" {
 
@@ -512,28 +447,18 @@ int spx_ball_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids
                    int batch, int nsample, float r2, int flags, int32_t *rows, int32_t *count, float *out_offsets,
                    spx_stream_t stream) {
   using namespace spx;
-  if (int rc = check_scenes(ndim, nfeat, n_cap, batch)) return rc;
-  SPX_CHECK(m_cap >= 0, "bad query counts %d", m_cap);
-  SPX_CHECK(q_nfeat >= ndim, "queries need at least %d columns, got %d", ndim, q_nfeat);
   SPX_CHECK(nsample >= 1 && nsample <= kMaxSample, "nsample must be in 1 .. %d, got %d", kMaxSample, nsample);
-  SPX_CHECK(static_cast<long long>(m_cap) * nsample < 0x80000000LL, "m_cap * nsample must stay below 2^31, got %d x %d",
-            m_cap, nsample);
-  SPX_CHECK((flags & ~kFlagPadFirst) == 0, "flags must be 0 or pad first (2), got %d", flags);
   SPX_CHECK(r2 >= 0.f, "the squared radius must be >= 0 (and no NaN)");
+  const BallArgs a = {{queries, q_nfeat, q_batch_ids, m_cap, n_queries_dev, points, nfeat, n_cap, offsets, list, batch},
+                      nsample, r2, flags, rows, count, out_offsets};
+  if (int rc = check_scene_query(a, ndim, nsample, flags, rows, count, {out_offsets})) return rc;
   if (m_cap == 0) return 0;
-  SPX_CHECK(queries && rows && count && offsets && (n_cap == 0 || (points && list)),
-            "queries / points / offsets / list / rows / count is NULL");
-  SPX_CHECK(aligned_to(queries, 4) && aligned_to(points, 4) && aligned_to(rows, 4) && aligned_to(count, 4) &&
-                aligned_to(out_offsets, 4) && aligned_to(offsets, 4) && aligned_to(list, 4),
-            "pointer not aligned to its elements");
-  BallArgs a = {queries, q_nfeat, q_batch_ids, m_cap, n_queries_dev, points, nfeat, n_cap, offsets, list,
-                batch,   nsample, r2,          flags, rows,          count,  out_offsets};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(static_cast<unsigned>((static_cast<long long>(m_cap) + kBallBlock - 1) / kBallBlock));
+  const dim3 grid(static_cast<unsigned>((static_cast<long long>(m_cap) + kSceneBlock - 1) / kSceneBlock));
   if (ndim == 3)
-    hipLaunchKernelGGL((ball_query_kernel<3>), grid, dim3(kBallBlock), 0, s, a);
+    hipLaunchKernelGGL((ball_query_kernel<3>), grid, dim3(kSceneBlock), 0, s, a);
   else
-    hipLaunchKernelGGL((ball_query_kernel<2>), grid, dim3(kBallBlock), 0, s, a);
+    hipLaunchKernelGGL((ball_query_kernel<2>), grid, dim3(kSceneBlock), 0, s, a);
   SPX_LAUNCH_CHECK();
   count_sample(kSampleBallQuery);
   return 0;

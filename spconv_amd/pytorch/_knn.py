@@ -29,10 +29,9 @@ from spconv_amd.pytorch._level import flat_groups
 from spconv_amd.pytorch._pointvoxel import PointGroups
 from spconv_amd.pytorch._query import VoxelNeighbors
 from spconv_amd.pytorch._rulebook import _ptr, _stream
-from spconv_amd.pytorch._sample import _check_cloud, _check_groups, _require_cloud, scene_groups
+from spconv_amd.pytorch._sample import _FLAG_PAD_FIRST, _check_pad, _scene_query
 
 MAX_K = 64
-_FLAG_PAD_FIRST = 2
 
 
 class PointKNN(NamedTuple):
@@ -81,8 +80,7 @@ def _check_knn(op: str, k: int, width: Optional[int], pad: str, eps: float) -> t
     width = int(k) if width is None else int(width)
     if width < int(k):
         raise ValueError(f"{op}: width must be >= k, got {width} < {k}")
-    if pad not in ("none", "first"):
-        raise ValueError(f"{op}: pad is 'none' or 'first', got {pad!r}")
+    _check_pad(op, pad)
     if eps is None or not (0.0 <= float(eps) < math.inf):
         raise ValueError(f"{op}: eps must be finite and >= 0, got {eps}")
     return int(k), width
@@ -123,23 +121,10 @@ def knn_query(queries: torch.Tensor, q_batch_ids: Optional[torch.Tensor], points
     ascending slot, in fp32.  Returns a ``PointKNN``; with_groups builds the transposed list the gradients of
     ``group_voxels`` / ``knn_interpolate`` walk.  `groups`: a ready ``scene_groups`` of the points.  One launch, nothing
     read back.  No gradient with respect to coordinates or weights."""
-    B = int(batch_size)
-    M = _check_cloud("knn_query", "queries", queries, q_batch_ids, B, ndim)
-    N = _check_cloud("knn_query", "points", points, p_batch_ids, B, ndim)
     k, width = _check_knn("knn_query", k, width, pad, eps)
-    if M * width >= 1 << 31:
-        raise ValueError(f"knn_query: {M} queries x {width} entries each do not fit 32-bit entries")
-    if groups is not None:
-        _check_groups("knn_query", groups, N, B)
-        n_points = groups.n_points if n_points is None else n_points
-    _require_cloud("knn_query", "queries", queries, q_batch_ids, n_queries)
-    _require_cloud("knn_query", "points", points, p_batch_ids, n_points)
-    dev = queries.device
+    queries, q_batch_ids, points, groups, n_points, M, N, dev = _scene_query(
+        "knn_query", queries, q_batch_ids, points, p_batch_ids, batch_size, ndim, width, n_queries, n_points, groups)
     with torch.cuda.device(dev), torch.no_grad():
-        queries, points = queries.detach().contiguous(), points.detach().contiguous()
-        q_batch_ids = None if q_batch_ids is None else q_batch_ids.contiguous()
-        if groups is None:
-            groups = scene_groups(None if p_batch_ids is None else p_batch_ids.contiguous(), N, B, n_points, dev)
         rows = torch.empty((M, width), dtype=torch.int32, device=dev)
         count = torch.empty((M,), dtype=torch.int32, device=dev)
         dist2 = torch.empty((M, width), dtype=torch.float32, device=dev) if with_dist2 else None

@@ -155,12 +155,40 @@ def gather_samples(points: torch.Tensor, samples: PointSamples) -> torch.Tensor:
         return gather_rows(points.detach(), samples.idx.reshape(-1), float("nan"))
 
 
+def _check_pad(op: str, pad: str) -> None:
+    if pad not in ("none", "first"):
+        raise ValueError(f"{op}: pad is 'none' or 'first', got {pad!r}")
+
+
 def _check_ball(nsample: int, pad: str) -> int:
     if not 1 <= int(nsample) <= MAX_NSAMPLE:
         raise ValueError(f"ball_query: nsample must be in 1 .. {MAX_NSAMPLE}, got {nsample}")
-    if pad not in ("none", "first"):
-        raise ValueError(f"ball_query: pad is 'none' or 'first', got {pad!r}")
+    _check_pad("ball_query", pad)
     return int(nsample)
+
+
+def _scene_query(op: str, queries: torch.Tensor, q_batch_ids: Optional[torch.Tensor], points: torch.Tensor,
+                 p_batch_ids: Optional[torch.Tensor], batch_size: int, ndim: int, entries: int,
+                 n_queries: Optional[torch.Tensor], n_points: Optional[torch.Tensor], groups: Optional[PointGroups]):
+    """The prologue of ``ball_query`` and ``knn_query`` (`entries` slots per query): every ValueError, then the refusal
+    of CPU tensors, then the inputs detached and contiguous and the scene groups of the points (built when none are
+    given).  Returns (queries, q_batch_ids, points, groups, n_points, M, N, dev)."""
+    B = int(batch_size)
+    M = _check_cloud(op, "queries", queries, q_batch_ids, B, ndim)
+    N = _check_cloud(op, "points", points, p_batch_ids, B, ndim)
+    if M * entries >= 1 << 31:
+        raise ValueError(f"{op}: {M} queries x {entries} entries each do not fit 32-bit entries")
+    if groups is not None:
+        _check_groups(op, groups, N, B)
+        n_points = groups.n_points if n_points is None else n_points
+    _require_cloud(op, "queries", queries, q_batch_ids, n_queries)
+    _require_cloud(op, "points", points, p_batch_ids, n_points)
+    dev = queries.device
+    queries, points = queries.detach().contiguous(), points.detach().contiguous()     # (on their own device, no graph)
+    q_batch_ids = None if q_batch_ids is None else q_batch_ids.contiguous()
+    if groups is None:
+        groups = scene_groups(None if p_batch_ids is None else p_batch_ids.contiguous(), N, B, n_points, dev)
+    return queries, q_batch_ids, points, groups, n_points, M, N, dev
 
 
 def ball_query_into(queries: torch.Tensor, q_batch_ids: Optional[torch.Tensor], n_queries: Optional[torch.Tensor],
@@ -192,26 +220,13 @@ def ball_query(queries: torch.Tensor, q_batch_ids: Optional[torch.Tensor], point
     (num_voxels = N, n_live = n_points): ``group_voxels(point_feats, nb)`` and its gradient work on [N, C] point
     features; with_groups builds the transposed list that gradient walks.  `groups`: a ready ``scene_groups`` of the
     points.  One launch, nothing read back.  No gradient with respect to coordinates."""
-    B = int(batch_size)
-    M = _check_cloud("ball_query", "queries", queries, q_batch_ids, B, ndim)
-    N = _check_cloud("ball_query", "points", points, p_batch_ids, B, ndim)
     nsample = _check_ball(nsample, pad)
     if radius is None:
         raise ValueError("ball_query: radius must be >= 0, got None")
     r2 = squared_radius(radius)
-    if M * nsample >= 1 << 31:
-        raise ValueError(f"ball_query: {M} queries x {nsample} entries each do not fit 32-bit entries")
-    if groups is not None:
-        _check_groups("ball_query", groups, N, B)
-        n_points = groups.n_points if n_points is None else n_points
-    _require_cloud("ball_query", "queries", queries, q_batch_ids, n_queries)
-    _require_cloud("ball_query", "points", points, p_batch_ids, n_points)
-    dev = queries.device
+    queries, q_batch_ids, points, groups, n_points, M, N, dev = _scene_query(
+        "ball_query", queries, q_batch_ids, points, p_batch_ids, batch_size, ndim, nsample, n_queries, n_points, groups)
     with torch.cuda.device(dev), torch.no_grad():
-        queries, points = queries.detach().contiguous(), points.detach().contiguous()
-        q_batch_ids = None if q_batch_ids is None else q_batch_ids.contiguous()
-        if groups is None:
-            groups = scene_groups(None if p_batch_ids is None else p_batch_ids.contiguous(), N, B, n_points, dev)
         rows = torch.empty((M, nsample), dtype=torch.int32, device=dev)
         count = torch.empty((M,), dtype=torch.int32, device=dev)
         offsets = torch.empty((M, nsample, ndim), dtype=torch.float32, device=dev) if with_offsets else None

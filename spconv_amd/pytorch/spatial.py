@@ -12,6 +12,15 @@ from spconv_amd.pytorch.core import SparseConvTensor
 from spconv_amd.pytorch.modules import SparseModule
 
 
+def _group(feats: torch.Tensor, nb, use_xyz: bool):
+    """([M, nsample, (ndim +) C], count [M]): the rows of `nb`, with `use_xyz` behind the offsets cast to their dtype."""
+    from spconv_amd.pytorch import functional as F
+    grouped = F.group_voxels(feats, nb)
+    if use_xyz:
+        grouped = torch.cat([nb.offsets.to(grouped.dtype), grouped], dim=2)
+    return grouped, nb.count
+
+
 class RemoveDuplicate(SparseModule):
     """Keeps one row per (batch, coordinate): the FIRST one in row order, which is also the row the
     rulebook's hash keeps for a duplicated coordinate (csrc/sparse/indices.py:1672).  The reference
@@ -168,10 +177,7 @@ class VoxelQueryAndGroup(torch.nn.Module):
         from spconv_amd.pytorch import functional as F
         nb = F.voxel_query(queries, batch_ids, x, self.vsize_xyz, self.coors_range_xyz, self.query_range, self.nsample,
                            self.radius, "first", self.use_xyz)
-        grouped = F.group_voxels(x.features, nb)
-        if self.use_xyz:
-            grouped = torch.cat([nb.offsets.to(grouped.dtype), grouped], dim=2)
-        return grouped, nb.count
+        return _group(x.features, nb, self.use_xyz)
 
     def extra_repr(self) -> str:
         return (f"query_range={self.query_range}, nsample={self.nsample}, radius={self.radius}, use_xyz={self.use_xyz}, "
@@ -239,10 +245,7 @@ class BallQueryAndGroup(torch.nn.Module):
         nb = F.ball_query(queries, q_batch_ids, points, p_batch_ids, batch_size, self.radius, self.nsample, ndim=self.ndim,
                           pad="first", with_offsets=self.use_xyz, n_queries=n_queries, n_points=n_points,
                           with_groups=bool(feats.requires_grad and torch.is_grad_enabled()), groups=groups)
-        grouped = F.group_voxels(feats, nb)
-        if self.use_xyz:
-            grouped = torch.cat([nb.offsets.to(grouped.dtype), grouped], dim=2)
-        return grouped, nb.count
+        return _group(feats, nb, self.use_xyz)
 
     def extra_repr(self) -> str:
         return f"radius={self.radius}, nsample={self.nsample}, use_xyz={self.use_xyz}, ndim={self.ndim}"
@@ -313,11 +316,7 @@ class KNNQueryAndGroup(torch.nn.Module):
         knn = F.knn_query(queries, q_batch_ids, points, p_batch_ids, batch_size, self.k, ndim=self.ndim, pad="first",
                           with_dist2=False, with_offsets=self.use_xyz, n_queries=n_queries, n_points=n_points,
                           with_groups=bool(feats.requires_grad and torch.is_grad_enabled()), groups=groups)
-        nb = knn.neighbors()
-        grouped = F.group_voxels(feats, nb)
-        if self.use_xyz:
-            grouped = torch.cat([nb.offsets.to(grouped.dtype), grouped], dim=2)
-        return grouped, nb.count
+        return _group(feats, knn.neighbors(), self.use_xyz)
 
     def extra_repr(self) -> str:
         return f"k={self.k}, use_xyz={self.use_xyz}, ndim={self.ndim}"

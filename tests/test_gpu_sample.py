@@ -219,6 +219,7 @@ def test_ball_query_device_counts_and_invalid_rows(cuda):
     pts, p_bid, q, q_bid = ss.base()
     bad_q, bad_bid = q.copy(), q_bid.copy()
     bad_q[::3, 1] = np.nan
+    bad_q[1::11, 0], bad_q[2::11, 2], bad_q[3::11] = np.inf, -np.inf, np.inf     # (the reference turns down NaN only)
     bad_bid[1::7], bad_bid[4::9] = ss.B, -1
     bad_pts, bad_pid = pts.copy(), p_bid.copy()
     bad_pts[5::7, 2], bad_pts[6::7, 0] = np.inf, np.nan
@@ -228,9 +229,15 @@ def test_ball_query_device_counts_and_invalid_rows(cuda):
                   n_points=3500)
     assert_neighbors(nb, want)
     assert nb.n_queries is not None and nb.n_live is not None
-    dead = np.isnan(bad_q).any(axis=1) | (bad_bid < 0) | (bad_bid >= ss.B) | (np.arange(ss.M) >= 500)
+    dead = ~np.isfinite(bad_q[:, :3]).all(axis=1) | (bad_bid < 0) | (bad_bid >= ss.B) | (np.arange(ss.M) >= 500)
     assert dead.sum() > 300 and bool((nb.count[torch.from_numpy(dead).to(cuda)] == 0).all())
     assert int(nb.rows.max()) < 3500 and int((nb.count > 0).sum()) > 100
+    # an infinite radius: a query with an infinite coordinate still finds nothing (its d2 is +inf or NaN, never < r2)
+    want = rs.ball_query(bad_q, bad_bid, 500, bad_pts, bad_pid, 3500, ss.B, float("inf"), ss.NSAMPLE, 3, "first")
+    nb = run_ball(cuda, bad_q, bad_bid, bad_pts, bad_pid, ss.B, float("inf"), ss.NSAMPLE, pad="first", n_queries=500,
+                  n_points=3500)
+    assert_neighbors(nb, want)
+    assert bool((nb.count[torch.from_numpy(dead).to(cuda)] == 0).all()) and int((nb.count > 0).sum()) > 100
 
 
 def test_ball_query_exact_lattice_and_empty_cases(cuda):
