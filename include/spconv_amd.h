@@ -857,6 +857,38 @@ int spx_from_dense_fill(const void *dense, int C, int elem_bytes, int ndim, int 
                         const int *spatial_h, const void *ws, size_t ws_bytes, int32_t *indices,
                         void *rows, int32_t *map, spx_stream_t stream);
 
+/* What the row operators may be handed (spx_union_count / _fill / _static, spx_union_add_fwd / _bwd, spx_collapse_count /
+ * _fill / _static, spx_collapse_fwd / _bwd, spx_point_groups, spx_row_score, spx_topk_flags, spx_select_count / _fill /
+ * _static, spx_point_corners in both lookup forms, spx_interp_fwd / _bwd, spx_group_fwd / _bwd: the operators that sit
+ * between the layers); tests/test_gpu_rowop_isolation.py holds them to it, the references to it tests/test_refrowops.py:
+ *   (a) Dirty memory on entry.  Every output, workspace, counter record (n_out_dev, sel_dev) and rank map may hold any
+ *       bytes on entry: every element the caller reads afterwards has been stored, no region of a workspace or map is
+ *       read before it is written.  The two-call forms keep their rule -- ws and rankmap unchanged between count and
+ *       fill -- and the dirt is there before the count.  Regions a section below calls unspecified (list from
+ *       offsets[n_out] on) stay unspecified.
+ *   (b) Rows that nothing names may hold anything, NaN and Inf included, and change no output bit: feature rows at or
+ *       beyond *n_live; rows whose index row is dead (batch index or a coordinate out of range); rows dropped by a cap;
+ *       dout rows of points or queries that are invalid or lie at or beyond *n_points / *n_queries; dout entries of slots
+ *       with rows == -1; corner_w entries whose corner_rows entry is -1.  Output rows past the live count are what the
+ *       sections below promise: zeros or -1.
+ *   (c) Named rows.  Nothing non-finite is swallowed: an output element is NaN, +Inf or -Inf exactly where the sequential
+ *       sum (or maximum) over the named rows is.  The payload of a COMPUTED NaN is not part of the contract; a NaN that is
+ *       moved (a copy, a gather, the max) keeps its bits.  A finite f16 / bf16 group whose fp32 sum exceeds the type's
+ *       range rounds to +-Inf: the one rounding at the end.
+ *         max (spx_collapse_fwd, SPX_COLLAPSE_MAX): NaN propagates.  The output element is the FIRST NaN of the group in
+ *         list order, bits unchanged; without a NaN the first of the largest values, -0.0 / +0.0 compared as equal.
+ *         max backward: where out[r, c] is NaN every row of the group whose feat[i, c] is NaN receives dout[r, c], the
+ *         others 0 ("ties all receive"; not torch's silent zero: the gradient does not vanish where the forward said NaN).
+ *         spx_row_score: a row with a NaN element scores a POSITIVE NaN under both ops, so it sorts above +inf.
+ *         spx_topk_flags: the key order over ALL bit patterns -- a positive NaN above +inf, a negative NaN below -inf,
+ *         NaNs among themselves by payload.  Which rows a caller's own non-finite scores select follows from that order
+ *         alone.
+ *   (d) Spreading.  spx_interp_fwd / _bwd are IEEE as written: a LIVE corner (row >= 0) whose weight is exactly 0 and whose
+ *       row holds Inf or NaN contributes 0 x Inf = NaN.  The weight of an absent corner is never multiplied.  (Parallel
+ *       to (d) of the gather-GEMM section.)
+ *   (e) Non-finite weights in corner_w at live corners, and non-finite scores handed to spx_topk_flags, are the caller's:
+ *       the arithmetic is IEEE and the key order above holds, nothing more is promised. */
+
 /* ---- misaligned add (csrc/union.hip) -----------------------------------------------------------------
  * Replace the torch composite behind the reference's spconv/pytorch/functional.py:439-545 (sparse_add_hash_based,
  * sparse_add) and tables.py AddTableMisaligned: T hash inserts + an arange whose count is read back, T queries, T
@@ -900,7 +932,8 @@ int spx_from_dense_fill(const void *dense, int C, int elem_bytes, int ndim, int 
  *   operands.  Any C >= 1: rows whose byte size is a multiple of 16 (and 16-byte aligned pointers) move as 16-byte
  *   pieces per lane, other widths element by element.  A src entry outside [0, n_h[t]) counts as -1.
  *   spx_union_add_bwd: din_h[t][i, :] = dout[rows_h[t][i], :], zeros where the entry is outside [0, n_out): a
- *   byte-moving gather for elem_bytes 2, 4 or 8, one launch for all operands. */
+ *   byte-moving gather for elem_bytes 2, 4 or 8, one launch for all operands.
+ * Dirty buffers, unnamed rows and NaN / Inf: "What the row operators may be handed" above. */
 size_t spx_union_ws_bytes(int ndim, int batch, const int *spatial_h, int T, long long n_total);
 int spx_union_count(const int32_t *const *indices_h, const int *n_h, const int32_t *const *n_live_h, int T,
                     int ndim, int batch, const int *spatial_h, void *rankmap, size_t rankmap_bytes, void *ws,
@@ -963,14 +996,17 @@ int spx_union_add_bwd(const void *dout, int n_out, void *const *din_h, const int
  *           atomics, no zero fill, every output element written exactly once: identical run to run, and reproducible
  *           on the host with a sequential loop.
  *     mean: that sum divided by the group's row count in fp32 (fp64), rounded once.
- *     max:  the maximum of the stored values (the first of equals): a copy of an input element.  NaN: unspecified.
+ *     max:  the maximum of the stored values (the first of equals): a copy of an input element.  A NaN in the group
+ *           propagates: the output is the group's first NaN in list order, bits unchanged ("What the row operators may
+ *           be handed", (c)).
  *   Rows at or beyond *n_live_out (NULL or a device int32) are written as zeros.  A list entry outside [0, n) is
  *   skipped.
  *   spx_collapse_bwd (mean and max; the gradient of a sum is spx_union_add_bwd with one operand): with r = rows[i],
  *     mean: din[i] = dout[r] / (offsets[r + 1] - offsets[r]), divided in fp32 (fp64), rounded once (feat / out unused)
- *     max:  din[i, c] = dout[r, c] where feat[i, c] == out[r, c], else 0: ties all receive, as spx_maxpool_bwd
- *           (offsets unused)
- *   zeros where rows[i] is outside [0, n_out). */
+ *     max:  din[i, c] = dout[r, c] where feat[i, c] == out[r, c], or where both are NaN, else 0: ties all receive, as
+ *           spx_maxpool_bwd, and a NaN output sends its gradient to every NaN of its group (offsets unused)
+ *   zeros where rows[i] is outside [0, n_out).
+ * Dirty buffers, unnamed rows and NaN / Inf: "What the row operators may be handed" above. */
 size_t spx_collapse_ws_bytes(int ndim, int batch, const int *spatial_h, int axes_mask, long long n);
 int spx_collapse_count(const int32_t *indices, int n, const int32_t *n_live, int ndim, int batch,
                        const int *spatial_h, int axes_mask, void *rankmap, size_t rankmap_bytes, void *ws,
@@ -1014,6 +1050,7 @@ int spx_collapse_bwd(const void *feat, const void *out, const void *dout, const 
  *   is >= v (a bisection per voxel: runs of empty voxels cost nothing extra).  n_cap = 0 is legal (offsets all 0).
  *   Launches: the key pass, three per radix pass of 8 or 9 bits, the boundary pass.
  *   spx_point_groups_ws_bytes: its scratch; 0 for n_cap < 0 or num_voxels < 1.  Monotone in both arguments.
+ *   Dirty buffers on entry: "What the row operators may be handed" (before the misaligned add), (a).
  *
  *   spx_voxel_to_point: out[i, :] = vfeat[rows[i], :] ([num_voxels, C] -> [n_cap, C], contiguous), or C copies of the
  *   fill element (the low elem_bytes bytes of fill_bits) where rows[i] is outside [0, num_voxels).  A byte-moving
@@ -1092,7 +1129,9 @@ int spx_point_decorate(const float *points, int nfeat, int n_cap, const int32_t 
  *   whose groups hold the entries e = i * K + c in ascending e.  dvfeat[v, :] = sum over e in list[offsets[v] ..
  *   offsets[v + 1]) of corner_w[e] * dout[e / K, :], in list order, accumulated and rounded as the forward; zeros for
  *   an empty group and for rows at or beyond *n_live.  No atomics, identical run to run; a voxel's row belongs to a
- *   group of lanes (the walk of spx_collapse_fwd), so long groups do not serialise on one lane.  One launch. */
+ *   group of lanes (the walk of spx_collapse_fwd), so long groups do not serialise on one lane.  One launch.
+ * Dirty buffers, unnamed rows, NaN / Inf and the zero-weight live corner (0 x Inf = NaN spreads): "What the row operators
+ * may be handed" (before the misaligned add), (a) - (e). */
 size_t spx_point_corners_ws_bytes(int n_cap, int ndim, int n);
 int spx_point_corners(const float *points, int nfeat, const int32_t *batch_ids, int n_cap,
                       const int32_t *n_points_dev, int ndim, const float *vsize, const float *coors_range,
@@ -1153,7 +1192,9 @@ int spx_interp_bwd(const void *dout, int n_cap, int ndim, const float *corner_w,
  *   dvfeat[v, :] = sum over e in list[offsets[v] .. offsets[v + 1]) of dout[e, :], in list order (ascending e), fp32
  *   accumulation (fp64 for SPX_F64) from zero, one round-to-nearest-even into the feature type; zeros for an empty
  *   group and for rows at or beyond *n_live.  No atomics, identical run to run; the walk of spx_interp_bwd.  One
- *   launch. */
+ *   launch.
+ * spx_group_fwd / _bwd on dirty buffers, unnamed rows and NaN / Inf: "What the row operators may be handed" (before the
+ * misaligned add). */
 size_t spx_voxel_query_ws_bytes(int n_cap, int nsample, int ndim, int n, int ranked);
 int spx_voxel_query(const float *queries, int nfeat, const int32_t *batch_ids, int n_cap,
                     const int32_t *n_queries_dev, int ndim, const float *vsize, const float *coors_range,
@@ -1265,7 +1306,8 @@ int spx_knn_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids,
  * ROW SCORE.  spx_row_score: score[i] (fp32 [n]) from feat [n, C] (contiguous; SPX_F16 / SPX_BF16 / SPX_F32 / SPX_F64,
  * any C >= 1); -inf for rows at or beyond *n_live (NULL or a device int32).  One launch, no atomics, every element
  * written exactly once.
- *   SPX_SCORE_ABSMAX: the maximum of |feat[i, c]| (exact in any order; NaN: unspecified), rounded to fp32 for SPX_F64.
+ *   SPX_SCORE_ABSMAX: the maximum of |feat[i, c]| (exact in any order), rounded to fp32 for SPX_F64.  A row with a NaN
+ *   element scores a positive NaN, as under SPX_SCORE_ABSMEAN ("What the row operators may be handed", (c)).
  *   SPX_SCORE_ABSMEAN: the sum of |feat[i, c]| in fp32 (fp64 for SPX_F64), divided by C in that type, rounded once to
  *   fp32.  THE ORDER OF THE SUM is a function of C and the dtype alone.  With e = the element size in bytes:
  *     V = 16 / e when C * e is a multiple of 16, else 1         (elements of a piece)
@@ -1315,7 +1357,8 @@ int spx_knn_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids,
  *   over the result: two more launches, no marks, no scan); `violation` (device int32 [1] or NULL) as there.
  *
  * FEATURE ROWS use kernels the library already has: out[r] = feat[src[r]] is spx_voxel_to_point with a zero fill, the
- * gradient din[i] = dout[rows[i]] is spx_union_add_bwd with one operand.  A row keeps its bits. */
+ * gradient din[i] = dout[rows[i]] is spx_union_add_bwd with one operand.  A row keeps its bits.
+ * Dirty buffers, unnamed rows and NaN / Inf: "What the row operators may be handed" (before the misaligned add). */
 int spx_row_score(const void *feat, int n, int C, int dtype, int op, const int32_t *n_live, float *score,
                   spx_stream_t stream);
 size_t spx_topk_ws_bytes(long long n);

@@ -162,7 +162,9 @@ collapse_fwd_kernel(const void *__restrict__ feat_, int n, const int32_t *__rest
 #pragma unroll
             for (int j = 0; j < V; ++j) {
               const A x = E::up(v[u].e[j]);
-              if (x > acc[j]) {                 // (the stored element travels: the output is a copy of an input element)
+              // (the stored element travels: the output is a copy of an input element.  !(x <= acc) is x > acc or
+              // unordered: the first NaN of the group in list order takes the element, and acc == acc keeps it there)
+              if (!(x <= acc[j]) && acc[j] == acc[j]) {
                 acc[j] = x;
                 first.e[j] = v[u].e[j];
               }
@@ -190,8 +192,9 @@ collapse_fwd_kernel(const void *__restrict__ feat_, int n, const int32_t *__rest
   }
 }
 
-// mean: din[i] = dout[r] / count[r]; max: din[i, c] = dout[r, c] where feat[i, c] == out[r, c]; r = rows[i], zeros
-// for a dead or dropped row.  One item per (input row, piece).
+// mean: din[i] = dout[r] / count[r]; max: din[i, c] = dout[r, c] where feat[i, c] == out[r, c], or where both are NaN
+// (the forward said NaN: the gradient goes to every NaN of the group, not to nobody); r = rows[i], zeros for a dead or
+// dropped row.  One item per (input row, piece).
 template <int DT, int V, int OP>
 __global__ void __launch_bounds__(kBlock)
 collapse_bwd_kernel(const void *__restrict__ feat_, const void *__restrict__ out_, const void *__restrict__ dout_,
@@ -222,8 +225,10 @@ collapse_bwd_kernel(const void *__restrict__ feat_, const void *__restrict__ out
       } else {
         const P f = feat[item], o = out[static_cast<long long>(r) * pieces + p];
 #pragma unroll
-        for (int j = 0; j < V; ++j)
-          if (E::up(f.e[j]) == E::up(o.e[j])) v.e[j] = g.e[j];      // (ties all receive, as spx_maxpool_bwd)
+        for (int j = 0; j < V; ++j) {         // (ties all receive, as spx_maxpool_bwd; a NaN output: every NaN of the group)
+          const A fv = E::up(f.e[j]), ov = E::up(o.e[j]);
+          if (fv == ov || (fv != fv && ov != ov)) v.e[j] = g.e[j];
+        }
       }
     }
     din[item] = v;

@@ -5,6 +5,8 @@
 //   score   a row belongs to a group of G lanes (G = a power of two covering the row's pieces, at most a wave); lane s
 //           adds |x| over the pieces s, s + G, ... in order, the lanes' sums meet in a butterfly whose lane 0 adds
 //           acc[s] + acc[s + d] for d = G / 2 .. 1: an order that depends on C and the dtype only.  One launch.
+//           absmax takes the larger of the two at every step, and a NaN from either side: a row with a NaN element
+//           scores a positive NaN under both ops.
 //   top-k   radix select on the order-preserving key of the fp32 score, 8 bits per digit from the top: a histogram
 //           pass over the live rows whose decided digits equal the prefix (per-wave LDS copies, merged with integer
 //           atomics), a pick by one workgroup (suffix sums of the 256 counts: the digit of the k-th largest key, the
@@ -34,6 +36,9 @@ enum { kOpMean = SPX_SCORE_ABSMEAN, kOpMax = SPX_SCORE_ABSMAX };
 
 __device__ __forceinline__ float absval(float v) { return __builtin_fabsf(v); }
 __device__ __forceinline__ double absval(double v) { return __builtin_fabs(v); }
+// IEEE 754-2019 maximum: a NaN on either side gives NaN (one v_maximum3_f32 on gfx950; fp64: a max and a select)
+__device__ __forceinline__ float nan_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ double nan_max(double a, double b) { return __builtin_elementwise_maximum(a, b); }
 
 // -------------------------------------------------------------------------------------------- row score
 
@@ -74,7 +79,7 @@ score_kernel(const void *__restrict__ feat_, int n, int C, int pieces, int gshif
         for (int j = 0; j < V; ++j) {
           const A x = absval(E::up(v.e[j]));
           if (OP == kOpMean) acc += x;
-          else acc = x > acc ? x : acc;
+          else acc = nan_max(acc, x);
         }
       }
     }
@@ -82,7 +87,7 @@ score_kernel(const void *__restrict__ feat_, int n, int C, int pieces, int gshif
     for (int d = G >> 1; d >= 1; d >>= 1) {
       const A o = __shfl_xor(acc, d, 64);
       if (OP == kOpMean) acc += o;
-      else acc = o > acc ? o : acc;
+      else acc = nan_max(acc, o);
     }
     if (sub == 0) {
       float r = -__builtin_inff();

@@ -145,3 +145,112 @@ def unnamed_rows(n, seed):
     fixed = np.array([r for r in (127, 128, 255, n - 1) if 0 <= r < n], dtype=np.int64)
     rest = rng.permutation(n)[:max(int(round(0.05 * n)) - fixed.shape[0], 0)].astype(np.int64)
     return torch.from_numpy(np.unique(np.concatenate([fixed, rest])))
+
+
+# ---------------------------------------------------------------- the row operators (tests/test_gpu_rowop_isolation.py)
+# A row operator's output element is a sum (or a maximum) over the ENTRIES of a group: the rows of a collapse group, the
+# operands present at a union row, the corners of a point, the entries of a transposed list.  The classes below are
+# derived from which entry holds what, by counting; no floating sum is formed.
+def _any_by_group(n_groups, grp, flags):
+    cnt = np.zeros((n_groups,) + flags.shape[1:], dtype=np.int64)
+    np.add.at(cnt, grp, flags.astype(np.int64))
+    return cnt > 0
+
+
+def classify_entries(n_groups, grp, x, w=None):
+    """Classes (numpy bool [n_groups, C]) of out[g] = sum over the entries e with grp[e] == g of x[e] (w given: of
+    w[e] * x[e], so a zero weight on an Inf makes a NaN).  x float64 [E, C], w float64 [E]."""
+    x = np.asarray(x, dtype=np.float64)
+    if w is None:
+        nan, pos, neg = np.isnan(x), x == np.inf, x == -np.inf
+    else:
+        w = np.asarray(w, dtype=np.float64)[:, None]
+        nan = np.isnan(x) | np.isnan(w) | (np.isinf(x) & (w == 0)) | (np.isinf(w) & (x == 0))
+        inf = (np.isinf(x) | np.isinf(w)) & ~nan
+        sign = (x < 0) ^ (w < 0)
+        pos, neg = inf & ~sign, inf & sign
+    return _finish(*[_any_by_group(n_groups, grp, f) for f in (nan, pos, neg)])
+
+
+def classify_max(n_groups, grp, x):
+    """Classes of out[g] = max over the group's entries with NaN propagating: NaN if any entry is, else +Inf if any is,
+    -Inf only when every entry is.  `mixed` is empty: +Inf and -Inf together give +Inf."""
+    x = np.asarray(x, dtype=np.float64)
+    nan = _any_by_group(n_groups, grp, np.isnan(x))
+    pos = _any_by_group(n_groups, grp, x == np.inf) & ~nan
+    some = _any_by_group(n_groups, grp, np.ones_like(x, dtype=bool))
+    neg = some & ~_any_by_group(n_groups, grp, x != -np.inf)
+    return Classes(nan, pos, neg, np.zeros_like(nan))
+
+
+def masks_np(a):
+    a = np.asarray(a, dtype=np.float64)
+    return np.isnan(a), a == np.inf, a == -np.inf
+
+
+def group_of_entries(offsets):
+    """the group of every list position: [offsets[-1]] int64"""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    return np.repeat(np.arange(offsets.shape[0] - 1), np.diff(offsets))
+
+
+# two quiet NaNs per dtype that differ in their payload, as bit patterns (positive; | the sign bit for a negative one)
+NAN_BITS = {torch.float16: (0x7e00, 0x7e55), torch.bfloat16: (0x7fc0, 0x7fd5), torch.float32: (0x7fc00000, 0x7fc12345),
+            torch.float64: (0x7ff8000000000000, 0x7ff8000000012345)}
+_INT_OF = {2: torch.int16, 4: torch.int32, 8: torch.int64}
+BIG = 60000.0           # finite in every dtype; two of them exceed float16's range (65504) in a float32 sum
+
+GroupPoison = namedtuple("GroupPoison", "cells roles channels")     # cells: [(input row, kind)], roles: {name: group}
+
+
+def poison_groups(offsets, lst, C, seed):
+    """Which rows of which groups hold what, chosen from the group table alone.  Eight groups of three rows or more take
+    one role each: nan_first / nan_last / nan_mid (one NaN at that position of the list), nan_two (two NaNs with
+    different payloads, the first of them at position 1), mixed (+Inf then -Inf: the sum is NaN, the maximum +Inf), pinf,
+    ninf, big (EVERY row holds BIG: finite rows whose float16 sum overflows); a group of one row, when there is one,
+    holds a NaN (nan_single: copied).  Two channels (one for C = 1)."""
+    offsets, lst = np.asarray(offsets, dtype=np.int64), np.asarray(lst, dtype=np.int64)
+    lens = np.diff(offsets)
+    rng = np.random.default_rng(seed)
+    long_ = rng.permutation(np.nonzero(lens >= 3)[0])
+    names = ("nan_first", "nan_last", "nan_mid", "nan_two", "mixed", "pinf", "ninf", "big")
+    assert long_.shape[0] >= len(names), "too few groups of three rows"
+    roles = {k: int(g) for k, g in zip(names, long_)}
+    at = lambda g, k: int(lst[offsets[g] + k])
+    L = lambda g: int(lens[g])
+    r = roles
+    cells = [(at(r["nan_first"], 0), "nan_a"), (at(r["nan_last"], L(r["nan_last"]) - 1), "nan_a"),
+             (at(r["nan_mid"], L(r["nan_mid"]) // 2), "nan_b"),
+             (at(r["nan_two"], 1), "nan_b"), (at(r["nan_two"], L(r["nan_two"]) - 1), "nan_a"),
+             (at(r["mixed"], 0), "pinf"), (at(r["mixed"], 1), "ninf"),
+             (at(r["pinf"], L(r["pinf"]) - 1), "pinf"), (at(r["ninf"], 0), "ninf")]
+    cells += [(at(r["big"], k), "big") for k in range(L(r["big"]))]
+    ones = np.nonzero(lens == 1)[0]
+    if ones.size:
+        roles["nan_single"] = int(ones[rng.integers(0, ones.size)])
+        cells.append((at(roles["nan_single"], 0), "nan_b"))
+    return GroupPoison(cells, roles, np.sort(rng.permutation(C)[:min(2, C)]))
+
+
+def poisoned_groups(feat, p):
+    """a copy of feat [n, C] with the cells of `p` in place (NaNs as bit patterns: the payloads are the test's)"""
+    t = feat.clone()
+    raw = t.view(_INT_OF[t.element_size()])
+    na, nb = NAN_BITS[t.dtype]
+    if t.dtype == torch.float16:
+        na, nb = na - 0x10000 if na >= 0x8000 else na, nb - 0x10000 if nb >= 0x8000 else nb
+    for row, kind in p.cells:
+        for c in p.channels.tolist():
+            if kind == "nan_a":
+                raw[row, c] = na
+            elif kind == "nan_b":
+                raw[row, c] = nb
+            else:
+                t[row, c] = {"pinf": float("inf"), "ninf": float("-inf"), "big": BIG}[kind]
+    return t
+
+
+def poison_rows_flat(grp, src, n_src, width, seed):
+    """poison_rows for ONE list of entries: entry e adds source row src[e] into group grp[e]"""
+    cand = [(0, torch.from_numpy(np.asarray(src, dtype=np.int64)), torch.from_numpy(np.asarray(grp, dtype=np.int64)))]
+    return poison_rows(cand, n_src, width, seed)

@@ -7,7 +7,8 @@ contract alone:
     the rows of a group in ascending input row
   * sum: a sequential float32 (float64) loop that starts from the first row's value, one rounding to the dtype (torch's
     CPU cast), a group of one row copied bit for bit; mean: that sum / count in float32 (float64); max: the first of the
-    largest stored values
+    largest stored values, or the group's first NaN in list order, moved with its bits; its backward gives a NaN output's
+    gradient to every NaN of the group
   * the three backwards in float64, and the magnitude means the forward's bound is relative to
 """
 from typing import NamedTuple, Optional
@@ -85,12 +86,34 @@ def _walk(feat: torch.Tensor, ref: Ref, step):
     return acc, lens
 
 
+def _max(feat: torch.Tensor, ref: Ref) -> torch.Tensor:
+    """The stored element that wins the walk, moved with its bits: a later row takes the element when it is larger, or
+    when it is the group's first NaN; a NaN is never displaced.  Zeros for an empty group."""
+    f = feat.to(torch.float64 if feat.dtype == torch.float64 else torch.float32).numpy()
+    lens = np.diff(ref.offsets)
+    C = f.shape[1]
+    src = np.full((ref.live, C), -1, dtype=np.int64)            # the input row whose element is held
+    has = np.nonzero(lens > 0)[0]
+    src[has] = ref.list[ref.offsets[:-1][has]][:, None]
+    cols = np.arange(C)[None, :]
+    for k in range(1, int(lens.max(initial=0))):
+        g = np.nonzero(lens > k)[0]
+        row = ref.list[ref.offsets[g] + k]
+        v, a = f[row], f[src[g], cols]
+        take = (v > a) | (np.isnan(v) & ~np.isnan(a))
+        src[g] = np.where(take, row[:, None], src[g])
+    out = torch.zeros((ref.live, C), dtype=feat.dtype)
+    if has.size:
+        idx = torch.from_numpy(src[has])
+        out[torch.from_numpy(has)] = feat[idx, torch.arange(C)[None, :].expand_as(idx)]
+    return out
+
+
 def reduce(feat: torch.Tensor, ref: Ref, op: str) -> torch.Tensor:
     """[live, C] in feat's dtype: what spx_collapse_fwd must produce (sum and max: bit for bit)"""
     at = _acc_type(feat.dtype)
     if op == "max":
-        acc, _ = _walk(feat, ref, lambda a, v: np.where(v > a, v, a))
-        return torch.from_numpy(acc).to(feat.dtype)             # (a stored value: the cast back is exact)
+        return _max(feat, ref)
     acc, lens = _walk(feat, ref, lambda a, v: (a + v).astype(at))
     if op == "mean":
         acc = (acc / np.maximum(lens, 1).astype(at)[:, None]).astype(at)
@@ -115,7 +138,8 @@ def mean_f64(feat: torch.Tensor, ref: Ref):
 
 
 def backward(feat: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, ref: Ref, op: str) -> np.ndarray:
-    """din [n, C] in float64: sum dout[r]; mean dout[r] / count[r]; max dout[r, c] where feat[i, c] == out[r, c]"""
+    """din [n, C] in float64: sum dout[r]; mean dout[r] / count[r]; max dout[r, c] where feat[i, c] == out[r, c] or both
+    are NaN (a NaN output: every NaN of the group receives)"""
     n, C = ref.rows.shape[0], dout.shape[1]
     din = np.zeros((n, C))
     held = np.nonzero(ref.rows >= 0)[0]
@@ -124,7 +148,8 @@ def backward(feat: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, ref: Ref
     if op == "mean":
         g = g / np.diff(ref.offsets)[r][:, None]
     elif op == "max":
-        g = np.where(feat.double().numpy()[held] == out.double().numpy()[r], g, 0.0)
+        f, o = feat.double().numpy()[held], out.double().numpy()[r]
+        g = np.where((f == o) | (np.isnan(f) & np.isnan(o)), g, 0.0)
     din[held] = g
     return din
 

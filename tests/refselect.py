@@ -150,7 +150,8 @@ def scores(kind: str, n: int, seed: int) -> np.ndarray:
     base = np.uint32(0x3f400000)                # 0.75
     if kind == "low_byte":                      # equal except the low byte: the threshold falls in the last digit
         return (base | rng.integers(0, 256, n).astype(np.uint32)).view(np.float32)
-    if kind == "top_byte":                      # equal except the top byte: signs and exponents differ, NaNs included
+    if kind == "top_byte":                      # equal except the top byte: signs and exponents differ; bit 23 is never
+        #                                         set, so the exponent is never all ones: no Inf and no NaN ("nan" has them)
         return ((rng.integers(0, 256, n).astype(np.uint32) << np.uint32(24)) | np.uint32(0x00400000)).view(np.float32)
     if kind == "mid_bytes":                     # equal except the two middle bytes
         return (base ^ (rng.integers(0, 65536, n).astype(np.uint32) << np.uint32(8))).view(np.float32)
@@ -158,10 +159,18 @@ def scores(kind: str, n: int, seed: int) -> np.ndarray:
         pool = np.array([0.0, -0.0, np.inf, -np.inf, 1e-40, -1e-40, 2.0 ** -149, -1.5, -1.5, 3.0, 3.0, 0.25],
                         dtype=np.float32)
         return pool[rng.integers(0, pool.shape[0], n)]
+    if kind == "nan":                           # NaNs of both signs and two payloads, +-inf, finite values: twelve bit
+        #                                         patterns over n rows, so every pattern's ties span the blocks
+        pool = np.array([0x7fc00000, 0x7fc12345, 0xffc00000, 0xffc12345, 0x7f800000, 0xff800000, 0x3f800000, 0x3f800000,
+                         0xbf800000, 0x00000000, 0x40400000, 0x3e800000], dtype=np.uint32)
+        return pool[rng.integers(0, pool.shape[0], n)].view(np.float32)
     raise KeyError(kind)
 
 
-SCORE_KINDS = ("normal", "equal", "low_byte", "top_byte", "mid_bytes", "special")
+NAN_KEY_ORDER = (0xffc12345, 0xffc00000, 0xff800000, 0xbf800000, 0x00000000, 0x3e800000, 0x3f800000, 0x40400000,
+                 0x7f800000, 0x7fc00000, 0x7fc12345)   # the "nan" kind's bit patterns in ascending key, written by hand
+
+SCORE_KINDS = ("normal", "equal", "low_byte", "top_byte", "mid_bytes", "special", "nan")
 
 
 def sorted_scene(bs, shape, n, seed):

@@ -168,6 +168,55 @@ def test_build(cuda, ndim, n):
         np.testing.assert_array_equal(s.rows.cpu().numpy(), cut.rows)          # cut rows in row order: -1
 
 
+SCAN_ROWS = 66000           # 258 workgroups of 256 rows: the one-workgroup scans carry into a second round of 256 counts
+
+
+@pytest.mark.parametrize("what", ["build_eager", "build_static_cut", "flags"])
+def test_scan_carries_into_a_second_round(cuda, what):
+    """select_scan_kernel (and the tie scan of the flags) walk the workgroups' counts 256 at a time and carry the sum
+    from round to round: from 257 workgroups on there is a second round, which no smaller case reaches"""
+    from spconv_amd.pytorch import _select
+    n = SCAN_ROWS
+    assert (n + 255) // 256 > 256
+    if what == "flags":
+        s = rs.scores("equal", n, 3)                                # every row ties: the kept rows are the first k
+        s[::3] = 0.25
+        for k in (1, n // 3, n - n // 3 - 1, n - n // 3, n - n // 3 + 7, n):
+            ref = rs.topk(s, k)
+            before = counts()
+            keep, sel = _select.topk_flags(torch.from_numpy(s).to(cuda), k)
+            assert delta(before) == {"hist": 4, "pick": 4, "ties": 1, "flags": 1}
+            assert sel.cpu().tolist() == ref.sel
+            np.testing.assert_array_equal(keep.cpu().numpy(), ref.keep)
+        assert rs.topk(s, n - 5).sel[3] > 65536 // 3                # ties are taken in blocks of the second round
+        return
+    shape = [40, 60, 60]
+    idx = rc.scene(2, shape, n - 8, 17, 0)                          # 8 rows no scene owns: n rows
+    rows = idx.shape[0]
+    assert rows == n
+    keep = (np.random.default_rng(18).random(rows) < 0.6).astype(np.uint8)
+    keep[-700:] = 1                                                 # selected rows in the last blocks of the second round
+    if what == "build_eager":
+        ref = rs.select(idx, 2, shape, keep, False)
+        before = counts()
+        s = native_build(cuda, idx, 2, shape, keep, False)
+        assert delta(before) == {"count": 1, "scan": 1, "scatter": 1}
+        assert s.n_out == ref.found == ref.live and s.live_rows == ref.live_rows and s.n_out_dev is None
+        np.testing.assert_array_equal(s.out_indices.cpu().numpy(), ref.out_indices)
+        np.testing.assert_array_equal(s.src.cpu().numpy(), ref.src)
+        np.testing.assert_array_equal(s.rows.cpu().numpy(), ref.rows)
+        assert int(ref.rows[256 * 256:].max()) == ref.live - 1      # the last output rows come from the second round
+    else:
+        n_live = rows - 100
+        found = rs.select(idx, 2, shape, keep, False, n_live).found
+        cap = found - 100                                           # cuts inside the second round's rows
+        ref = rs.select(idx, 2, shape, keep, False, n_live, cap=cap)
+        assert ref.src[-1] >= 256 * 256
+        s = native_build(cuda, idx, 2, shape, keep, False, n_live=n_live, cap=cap)
+        check_static(s, ref, rows, cap, 3)
+        np.testing.assert_array_equal(s.rows.cpu().numpy(), ref.rows)
+
+
 def test_build_of_no_rows(cuda):
     shape = BUILD_SHAPES[3]
     idx, keep = np.zeros((0, 4), np.int32), np.zeros((0,), np.uint8)
