@@ -125,6 +125,10 @@ int spx_set_option(const char *name_h, int value);
  *                                                  spx_topk_flags (hist and pick once per 8-bit digit: four each; ties:
  *                                                  the blocks' tie counts and their scan, counted once); the passes of a
  *                                                  selection build (map: spx_rankmap_from_sorted over the result)
+ *   box/corners, box/pairs, box/aligned, box/key, box/mask, box/reduce
+ *                                                  rotated boxes, one count per launch: spx_boxes_to_corners,
+ *                                                  spx_boxes_overlap, spx_boxes_overlap_aligned and the three kernels
+ *                                                  of spx_nms_rotated (its sort counts under serialize/sort)
  *   serialize/keys, serialize/sort, serialize/offsets, serialize/plan, serialize/bwd
  *                                                  voxel serialisation: calls of spx_curve_keys; sorted orders of
  *                                                  spx_serialize (one per key row, none for n = 0); its offsets launch;
@@ -1442,6 +1446,94 @@ int spx_patch_plan(const int32_t *order, const int32_t *offsets, int n, int batc
                    int32_t *patch_scene, int32_t *n_patches_dev, void *ws, size_t ws_bytes, spx_stream_t stream);
 int spx_patch_rows_bwd(const void *g, int slots, const int32_t *row_slot, const int32_t *row_slot2, int n, int C,
                        int dtype, void *g_feat, spx_stream_t stream);
+
+/* ---- rotated boxes: corners, overlap, IoU and non-maximum suppression (csrc/box.hip) --------------------------
+ * The iou3d_nms extension of OpenPCDet / mmdet3d: boxes_iou_bev, boxes_iou3d_gpu, its aligned form and nms_gpu -- the
+ * rotated NMS every detector head ends in (SECOND, PointPillars, CenterPoint, VoxelNeXt, Voxel R-CNN, PV-RCNN), the
+ * proposal layer of the two-stage heads and their target assignment.  nms_gpu copies its suppression mask to the host
+ * for the sequential pass; here that pass is a kernel, so the step can sit inside a captured graph.  Every call: the
+ * caller allocates, every grid depends on host-known sizes only (hipGraph-safe), nothing is read back, nothing
+ * synchronises, and the argument checks that need no pointer come before any pointer is looked at.  Every fp32
+ * operation is rounded on its own (no FMA; the divide correctly rounded), so a host loop reproduces every output bit
+ * for bit from the same corners (tests/refbox.py).  No gradient of any kind.
+ *
+ * CORNERS.  spx_boxes_to_corners: boxes fp32 [n, nfeat >= 7] = (x, y, z, dx, dy, dz, heading), z the centre;
+ * n_boxes_dev NULL or a device int32.  bev fp32 [n, 4, 2], zrange fp32 [n, 2].  With c = cosf(heading), s =
+ * sinf(heading), hx = dx * 0.5f, hy = dy * 0.5f, corner k = 0 .. 3 has (lx, ly) = (+hx, +hy), (-hx, +hy), (-hx, -hy),
+ * (+hx, -hy) and lies at (x + (lx * c - ly * s), y + (lx * s + ly * c)): counter-clockwise.  zrange = (z - dz * 0.5f,
+ * z + dz * 0.5f).  A box is VALID when it lies below min(*n_boxes, n), its seven numbers are finite and dx, dy, dz > 0;
+ * an invalid box gets NaN in all ten outputs.  One launch (none for n = 0), every element written.
+ *
+ * A CORNER TABLE (bev, zrange) may as well be the caller's own: any four corners of a convex quad in either
+ * orientation.  In every entry below a box is INVALID when it lies at or beyond the device count given for its table or
+ * one of its eight corner coordinates is not finite (SPX_BOX_IOU_3D: or one end of its z range).  bev must be 16-byte
+ * aligned, zrange 8-byte aligned.
+ *
+ * OVERLAP of the subject quad A with the quad B, in this order of operations:
+ *   a(P) = the signed area sum over the vertices in order, a = a + (x_i * y_{i+1} - x_{i+1} * y_i) from a = 0;
+ *   area(P) = |a| * 0.5f.  A quad with a < 0 is walked in reverse (3, 2, 1, 0) by everything below, its area included:
+ *   clockwise corners give the bits of the same corners counter-clockwise.
+ *   Bounding rectangles: overlap 0 when maxx(A) < minx(B), maxx(B) < minx(A), or the same in y.
+ *   Sutherland-Hodgman: A clipped against the edges e = 0 .. 3 of B, edge a = B[e] -> b = B[e + 1]: ex = b.x - a.x,
+ *   ey = b.y - a.y, d(p) = ex * (p.y - a.y) - ey * (p.x - a.x), p inside when d >= 0.  Walking the polygon p_0 ..
+ *   p_{n-1} (j = i + 1, cyclic): p_i is emitted when inside; when p_i and p_j differ in that flag, t = d_i / (d_i -
+ *   d_j) and p_i + t * (p_j - p_i) is emitted (x and y alike).  A ninth vertex of a pass is dropped.  Fewer than three
+ *   vertices after a pass: overlap 0.
+ *   inter = min(area(clipped), min(area(A), area(B))): an IoU never exceeds 1, a box with itself gives exactly 1.
+ *   SPX_BOX_OVERLAP_BEV: inter.  SPX_BOX_IOU_BEV: inter / max((area(A) + area(B)) - inter, 1e-8f).
+ *   SPX_BOX_IOU_3D: h = max(min(zmaxA, zmaxB) - max(zminA, zminB), 0), inter3 = inter * h, vol = area * (zmax - zmin),
+ *   inter3 / max((volA + volB) - inter3, 1e-6f).  A pair with an invalid box gives 0.
+ * The result is not symmetric in A and B to the last bit: the subject is the first argument.
+ *   spx_boxes_overlap: out fp32 [m, n], out[i, j] = value(A_i, B_j); rows at or beyond *n_a_dev and columns at or
+ *   beyond *n_b_dev (NULL: all exist) are written as 0: every element is written.  zrange_a / zrange_b may be NULL
+ *   unless mode is SPX_BOX_IOU_3D.  One launch over (ceil(m / 16), ceil(n / 256)) workgroups (none for m * n = 0):
+ *   lanes own consecutive columns, the 16 subjects of a tile are staged in LDS once, the two polygon buffers of the
+ *   clip are per-lane LDS slots.  n <= 65535 * 256.
+ *   spx_boxes_overlap_aligned: out fp32 [n], out[i] = value(A_i, B_i).  One launch.
+ *
+ * NMS.  spx_nms_rotated over a corner table bev [n, 4, 2] with scores fp32 [n], batch_ids / class_ids int32 [n] or
+ * NULL (all scene 0 / one class).  A CANDIDATE is a valid box whose batch id is in [0, batch), whose score is not NaN
+ * and, with use_score_thresh = 1, is above score_thresh.  The candidates of a scene are RANKED by score descending --
+ * by the total order on the fp32 bits that spx_topk_flags uses, -0.0 below +0.0 -- equal scores by ascending index;
+ * only the first pre_max of a scene take part (1 <= pre_max <= spx_nms_max_pre() = 16384, 1 <= post_max <= pre_max).
+ * A candidate is KEPT if and only if no earlier-ranked kept candidate of its scene -- with class_ids: of its scene and
+ * class -- has iou_bev(earlier, it) > thresh (strict; the earlier one is the subject).  A scene stops at post_max kept.
+ *     keep   int32 [batch, post_max]   the kept boxes' indices in rank order, -1 behind them
+ *     count  int32 [batch]
+ * every element written on every call.  Launches:
+ *   key      uint64 key = (scene << 32) | ~orderable(score), orderable = bits ^ (bits >> 31 ? 0xffffffff : 0x80000000);
+ *            all bits set for a box that is no candidate
+ *   sort     spx_serialize with n_orders = 1, key_bits = 32 + bit_length(batch), batch_shift = 32: the rank order
+ *            (stable: ties to the lower index) and the scenes' offsets
+ *   mask     for rank i of a scene and each 64-rank block jb >= i / 64 one 64-bit word, bit j - 64 jb set when j > i,
+ *            the classes agree and the IoU is above thresh; layout [rows, W], W = ceil(min(pre_max, n) / 64), a row per
+ *            (scene, rank).  Only the upper triangle is written and only it is read; a workgroup beyond its scene's
+ *            candidates leaves at once.  The ballot of a wave over its 64 columns is the word of a row.
+ *   reduce   one wave per scene; the removed set is W / 64 <= 4 words per lane (instances of 1, 2 and 4: up to 4096,
+ *            8192, 16384 ranks).  Per 64-rank block: the block's removed word is broadcast, the diagonal words are held
+ *            one per lane and resolved by a uniform loop over the ranks still standing (a lane broadcast each); then
+ *            the rows of the block's kept ranks are ORed into the removed set.
+ *   spx_nms_ws_bytes: the workspace (keys, order, offsets, the sort's scratch, the mask); monotone in its arguments, 0
+ *   for arguments that are refused.  The workspace may be handed over dirty; ws must be 256-byte aligned.
+ *   Measurement only: the option SPX_TEST_NMS_STAGES = 1 | 2 | 3 (spx_set_option) ends the call behind its key / sort /
+ *   mask step and leaves keep and count unwritten (tools/box_probe.py times the prefixes against each other).
+ * Not here: gradients, the axis-aligned nms_normal_gpu, points_in_boxes, more than 16384 candidates per scene. */
+#define SPX_BOX_OVERLAP_BEV 0
+#define SPX_BOX_IOU_BEV 1
+#define SPX_BOX_IOU_3D 2
+int spx_boxes_to_corners(const float *boxes, int nfeat, int n, const int32_t *n_boxes_dev, float *bev, float *zrange,
+                         spx_stream_t stream);
+int spx_boxes_overlap(const float *bev_a, const float *zrange_a, int m, const int32_t *n_a_dev, const float *bev_b,
+                      const float *zrange_b, int n, const int32_t *n_b_dev, int mode, float *out, spx_stream_t stream);
+int spx_boxes_overlap_aligned(const float *bev_a, const float *zrange_a, const int32_t *n_a_dev, const float *bev_b,
+                              const float *zrange_b, const int32_t *n_b_dev, int n, int mode, float *out,
+                              spx_stream_t stream);
+int spx_nms_max_pre(void);
+size_t spx_nms_ws_bytes(int n, int batch, int pre_max);
+int spx_nms_rotated(const float *bev, const float *scores, const int32_t *batch_ids, const int32_t *class_ids, int n,
+                    const int32_t *n_boxes_dev, int batch, float thresh, int use_score_thresh, float score_thresh,
+                    int pre_max, int post_max, int32_t *keep, int32_t *count, void *ws, size_t ws_bytes,
+                    spx_stream_t stream);
 
 #ifdef __cplusplus
 }

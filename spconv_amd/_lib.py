@@ -229,6 +229,13 @@ SIGNATURES = {
     "spx_patch_plan": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp,
                                       vp, vp, ctypes.c_size_t, vp]),
     "spx_patch_rows_bwd": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "spx_boxes_to_corners": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
+    "spx_boxes_overlap": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp]),
+    "spx_boxes_overlap_aligned": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "spx_nms_max_pre": (ctypes.c_int, []),
+    "spx_nms_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "spx_nms_rotated": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                       ctypes.c_float, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]),
 }
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_I8, DTYPE_F64 = 0, 1, 2, 3, 4

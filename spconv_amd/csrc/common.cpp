@@ -41,6 +41,7 @@ std::atomic<long long> g_pointvoxel_launches[kPvCount];
 std::atomic<long long> g_interp_launches[kInterpCount];
 std::atomic<long long> g_query_launches[kQueryCount];
 std::atomic<long long> g_sample_launches[kSampleCount];
+std::atomic<long long> g_box_launches[kBoxCount];
 std::atomic<long long> g_serialize_launches[kSerCount];
 std::atomic<long long> g_select_launches[kSelInstCount];
 std::atomic<long long> g_pool_launches[kPoolCount];
@@ -197,6 +198,14 @@ std::atomic<long long> *query_counter(const char *key) {
   return nullptr;
 }
 
+// counter of a rotated-box key (spx_launch_count), or null
+std::atomic<long long> *box_counter(const char *key) {
+  static const char *names[kBoxCount] = {"box/corners", "box/pairs", "box/aligned", "box/key", "box/mask", "box/reduce"};
+  for (int i = 0; i < kBoxCount; ++i)
+    if (strcmp(key, names[i]) == 0) return &g_box_launches[i];
+  return nullptr;
+}
+
 // counter of a raw-point sampling key (spx_launch_count), or null
 std::atomic<long long> *sample_counter(const char *key) {
   static const char *names[kSampleCount] = {"sample/fps", "sample/ball_query", "sample/knn_query"};
@@ -293,6 +302,7 @@ long long spx_launch_count(const char *family_h) {
   if (std::atomic<long long> *c = spx::interp_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::query_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::sample_counter(family_h)) return c->load(std::memory_order_relaxed);
+  if (std::atomic<long long> *c = spx::box_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::serialize_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::select_counter(family_h)) return c->load(std::memory_order_relaxed);
   if (std::atomic<long long> *c = spx::pool_counter(family_h)) return c->load(std::memory_order_relaxed);

@@ -233,6 +233,12 @@ enum SampleInst { kSampleFps = 0, kSampleBallQuery, kSampleKnnQuery, kSampleCoun
 extern std::atomic<long long> g_sample_launches[kSampleCount];
 inline void count_sample(SampleInst i) { g_sample_launches[i].fetch_add(1, std::memory_order_relaxed); }
 
+// rotated boxes (box.hip): one counter per kernel, counted once per launch.
+// Keys box/corners, box/pairs, box/aligned, box/key, box/mask, box/reduce.
+enum BoxInst { kBoxCorners = 0, kBoxPairs, kBoxAligned, kBoxKey, kBoxMask, kBoxReduce, kBoxCount };
+extern std::atomic<long long> g_box_launches[kBoxCount];
+inline void count_box(BoxInst i) { g_box_launches[i].fetch_add(1, std::memory_order_relaxed); }
+
 // voxel serialisation (serialize.hip): keys once per spx_curve_keys call, sort once per sorted order, offsets once per
 // spx_serialize call, plan once per spx_patch_plan call, bwd once per spx_patch_rows_bwd call.
 // Keys serialize/keys, serialize/sort, serialize/offsets, serialize/plan, serialize/bwd.

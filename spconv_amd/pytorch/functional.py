@@ -607,6 +607,12 @@ from spconv_amd.pytorch._sample import (PointSamples, ball_query, ball_query_int
 from spconv_amd.pytorch._knn import (PointKNN, knn_interpolate, knn_query, knn_query_into,  # noqa: E402,F401
                                      three_nn)
 
+# rotated boxes (csrc/box.hip; not part of the reference): corners, pairwise overlap / IoU in the plane and in space, and
+# a non-maximum suppression that stays on the device -- the iou3d_nms extension of OpenPCDet / mmdet3d
+from spconv_amd.pytorch._box import (BoxCorners, BoxNMS, boxes_iou3d, boxes_iou3d_aligned,  # noqa: E402,F401
+                                     boxes_iou_bev, boxes_overlap_bev, boxes_to_corners, nms_rotated,
+                                     nms_rotated_into, nms_ws_bytes)
+
 # voxel serialisation (csrc/serialize.hip; not part of the reference): rows ordered along Z-order / Hilbert curves and
 # cut into fixed-size patches, for the serialised point / voxel transformers
 from spconv_amd.pytorch import _serialize  # noqa: E402

@@ -3,7 +3,8 @@ from a 3-D backbone to a sparse 2-D head on the kernels of csrc/collapse.hip; ``
 ``TrilinearDevoxelize``: a sparse level read out at points (csrc/interp.hip); ``VoxelQueryAndGroup``: the voxels around
 query points, gathered (csrc/query.hip); ``FarthestPointSample`` / ``BallQueryAndGroup``: keypoints of a raw cloud and the
 raw points around query points, gathered (csrc/sample.hip); ``KNNInterpolate`` / ``KNNQueryAndGroup``: features carried
-to many points from their nearest few, and the nearest raw points of query points, gathered (csrc/knn.hip)."""
+to many points from their nearest few, and the nearest raw points of query points, gathered (csrc/knn.hip);
+``RotatedNMS``: rotated non-maximum suppression that stays on the device (csrc/box.hip)."""
 from typing import Optional, Sequence
 
 import torch
@@ -320,3 +321,34 @@ class KNNQueryAndGroup(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return f"k={self.k}, use_xyz={self.use_xyz}, ndim={self.ndim}"
+
+
+class RotatedNMS(torch.nn.Module):
+    """Rotated non-maximum suppression per scene, wholly on the device (``functional.nms_rotated``, the kernels of
+    csrc/box.hip): the ``nms_gpu`` every OpenPCDet / mmdet3d head ends in.  Not part of the reference.
+
+    ``thresh``: a box is dropped when a kept, higher-scored box of its scene (with ``class_ids``: and class) overlaps it
+    with a bird's-eye IoU above it; ``pre_max`` (1 .. 16384) candidates per scene take part, ``post_max`` (1 ..
+    pre_max) are kept at most; ``score_thresh``: only scores above it are candidates.
+    ``forward(boxes, scores, batch_ids=None, batch_size=1, class_ids=None, n_boxes=None) -> BoxNMS(keep [batch_size,
+    post_max], count [batch_size])``: boxes fp32 [N, >= 7] = (x, y, z, dx, dy, dz, heading) or a ``BoxCorners``, scores
+    fp32 [N], ids int32 [N] or None.  Nothing is read back, so the module can sit inside a captured graph once its
+    buffers are owned by the caller (``functional.nms_rotated_into``).  There is no gradient."""
+
+    def __init__(self, thresh: float, pre_max: int = 4096, post_max: int = 512, score_thresh: Optional[float] = None):
+        super().__init__()
+        from spconv_amd.pytorch import _box
+        _box._check_nms("RotatedNMS", thresh, pre_max, post_max, score_thresh, 1)
+        self.thresh, self.pre_max, self.post_max = float(thresh), int(pre_max), int(post_max)
+        self.score_thresh = None if score_thresh is None else float(score_thresh)
+
+    def forward(self, boxes, scores: torch.Tensor, batch_ids: Optional[torch.Tensor] = None, batch_size: int = 1,
+                class_ids: Optional[torch.Tensor] = None, n_boxes: Optional[torch.Tensor] = None):
+        from spconv_amd.pytorch import functional as F
+        return F.nms_rotated(boxes, scores, self.thresh, batch_ids=batch_ids, batch_size=batch_size, class_ids=class_ids,
+                             pre_max=self.pre_max, post_max=self.post_max, score_thresh=self.score_thresh,
+                             n_boxes=n_boxes)
+
+    def extra_repr(self) -> str:
+        return (f"thresh={self.thresh}, pre_max={self.pre_max}, post_max={self.post_max}, "
+                f"score_thresh={self.score_thresh}")
