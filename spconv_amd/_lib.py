@@ -289,6 +289,16 @@ def check(status: int) -> None:
         raise RuntimeError(f"spconv_amd native error ({status}): {msg}")
 
 
+def launch_counts(keys) -> dict:
+    """{key: spx_launch_count(key)} for every key; KeyError for a key the library does not know."""
+    lib = load()
+    out = {k: int(lib.spx_launch_count(k.encode())) for k in keys}
+    for k, v in out.items():
+        if v < 0:
+            raise KeyError(k)
+    return out
+
+
 def ints(values):
     return (ctypes.c_int * len(values))(*[int(v) for v in values])
 

@@ -457,7 +457,7 @@ int spx_boxes_to_corners(const float *boxes, int nfeat, int n, const int32_t *n_
   hipLaunchKernelGGL(box_corners_kernel, dim3(div_up(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), boxes,
                      nfeat, n, n_boxes_dev, bev, zrange);
   SPX_LAUNCH_CHECK();
-  count_box(kBoxCorners);
+  spx::count(kBoxCorners);
   return 0;
 }
 
@@ -478,7 +478,7 @@ int spx_boxes_overlap(const float *bev_a, const float *zrange_a, int m, const in
   else
     hipLaunchKernelGGL(box_pairs_kernel<kModeIou3d>, grid, dim3(kBoxBlock), 0, s, a);
   SPX_LAUNCH_CHECK();
-  count_box(kBoxPairs);
+  spx::count(kBoxPairs);
   return 0;
 }
 
@@ -499,7 +499,7 @@ int spx_boxes_overlap_aligned(const float *bev_a, const float *zrange_a, const i
   else
     hipLaunchKernelGGL(box_aligned_kernel<kModeIou3d>, grid, dim3(kBoxBlock), 0, s, a);
   SPX_LAUNCH_CHECK();
-  count_box(kBoxAligned);
+  spx::count(kBoxAligned);
   return 0;
 }
 
@@ -537,7 +537,7 @@ int spx_nms_rotated(const float *bev, const float *scores, const int32_t *batch_
   if (n > 0) {
     hipLaunchKernelGGL(nms_key_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, a);
     SPX_LAUNCH_CHECK();
-    count_box(kBoxKey);
+    spx::count(kBoxKey);
   }
   if (stages == 1) return 0;
   // (n = 0: the bisection writes the offsets -- all 0 -- and touches neither keys nor order)
@@ -552,7 +552,7 @@ int spx_nms_rotated(const float *bev, const float *scores, const int32_t *batch_
     SPX_CHECK(rbs < 0x7fffffffLL, "too many row blocks");
     hipLaunchKernelGGL(nms_mask_kernel, dim3(static_cast<unsigned>(rbs), w.W), dim3(kWave), 0, s, a);
     SPX_LAUNCH_CHECK();
-    count_box(kBoxMask);
+    spx::count(kBoxMask);
   }
   if (stages == 3) return 0;
   if (w.W <= 64)
@@ -562,7 +562,7 @@ int spx_nms_rotated(const float *bev, const float *scores, const int32_t *batch_
   else
     hipLaunchKernelGGL(nms_reduce_kernel<4>, dim3(batch), dim3(kWave), 0, s, a);
   SPX_LAUNCH_CHECK();
-  count_box(kBoxReduce);
+  spx::count(kBoxReduce);
   return 0;
 }
 

@@ -303,10 +303,10 @@ int number_cells(const Build &b, const int32_t *indices, int n, const int32_t *n
     hipLaunchKernelGGL(collapse_mark_kernel, dim3(div_up(n, kBlock)), dim3(kBlock), 0, s, indices, n, n_live, b.g,
                        w.occupied, w.counters + 1);
     SPX_LAUNCH_CHECK();
-    count_collapse(kCollapseMark);
+    count(kCollapseMark);
   }
   SPX_HIP(number_level(w, b.W, rankmap, cap, counters, s));
-  count_collapse(kCollapsePrefix);
+  count(kCollapsePrefix);
   return 0;
 }
 
@@ -322,14 +322,14 @@ int list_rows(const Build &b, const int32_t *indices, int n, const int32_t *n_li
                        static_cast<const uint2 *>(rm), static_cast<const int32_t *>(rank_blockoff(rm, b.W)), cap, capkey, rows,
                        w.sortkey, out_indices, w.counters + 3);
     SPX_LAUNCH_CHECK();
-    count_collapse(kCollapseRank);
+    count(kCollapseRank);
     if (int rc = radix_argsort(w.sortkey, n, key_bits(capkey), list, w.sort, s)) return rc;
   }
   const long long items = n > cap + 1 ? n : static_cast<long long>(cap) + 1;
   hipLaunchKernelGGL(collapse_list_kernel, dim3(static_cast<unsigned>((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                      w.sortkey, list, n, cap, capkey, found, w.counters + 3, offsets);
   SPX_LAUNCH_CHECK();
-  count_collapse(kCollapseList);
+  count(kCollapseList);
   return 0;
 }
 
@@ -431,7 +431,7 @@ int spx_collapse_fwd(const void *feat, int n, const int32_t *offsets, const int3
     });
   });
   SPX_LAUNCH_CHECK();
-  count_collapse(kCollapseFwd);
+  count(kCollapseFwd);
   return 0;
 }
 
@@ -457,7 +457,7 @@ int spx_collapse_bwd(const void *feat, const void *out, const void *dout, const 
     });
   });
   SPX_LAUNCH_CHECK();
-  count_collapse(kCollapseBwd);
+  count(kCollapseBwd);
   return 0;
 }
 

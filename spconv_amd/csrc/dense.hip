@@ -501,7 +501,7 @@ int spx_dense_map(const int32_t *indices, int n, const int32_t *n_live, int ndim
                        n_live, g, map);
     SPX_LAUNCH_CHECK();
   }
-  spx::count_dense(spx::kDenseMap);
+  spx::count(spx::kDenseMap);
   return 0;
 }
 
@@ -524,7 +524,7 @@ int spx_to_dense(const void *rows, int n, long long row_stride, const int32_t *m
     const int v = spx::piece_bytes(elem_bytes, {row_bytes, ld_bytes}, {rows, out});
     SPX_BY_PIECE(v, spx::launch_scatter_cl<P>(rows, ld_bytes, map, out, row_bytes, g.cells, fill8, n, s));
     SPX_LAUNCH_CHECK();
-    spx::count_dense(spx::kDenseScatterCl);
+    spx::count(spx::kDenseScatterCl);
     return 0;
   }
   SPX_CHECK(spx::div_up(C, spx::kChunkBytes / elem_bytes) <= 65535, "too many channels: %d", C);
@@ -536,7 +536,7 @@ int spx_to_dense(const void *rows, int n, long long row_stride, const int32_t *m
     default: spx::launch_scatter_cf<8>(rows, row_stride, rows_vec, map, out, C, g, fill8, n, s); break;
   }
   SPX_LAUNCH_CHECK();
-  spx::count_dense(spx::kDenseScatterCf);
+  spx::count(spx::kDenseScatterCf);
   return 0;
 }
 
@@ -560,7 +560,7 @@ int spx_dense_gather(const void *dense, const int32_t *map, void *rows, int n, i
     const int v = spx::piece_bytes(elem_bytes, {row_bytes}, {rows, dense});
     SPX_BY_PIECE(v, spx::launch_gather_cl<P>(dense, map, rows, row_bytes, g.cells, n, s));
     SPX_LAUNCH_CHECK();
-    spx::count_dense(spx::kDenseGatherCl);
+    spx::count(spx::kDenseGatherCl);
     return 0;
   }
   SPX_CHECK(spx::div_up(C, spx::kChunkBytes / elem_bytes) <= 65535, "too many channels: %d", C);
@@ -572,7 +572,7 @@ int spx_dense_gather(const void *dense, const int32_t *map, void *rows, int n, i
     default: spx::launch_gather_cf<8>(dense, map, rows, rows_vec, C, g, n, s); break;
   }
   SPX_LAUNCH_CHECK();
-  spx::count_dense(spx::kDenseGatherCf);
+  spx::count(spx::kDenseGatherCf);
   return 0;
 }
 
@@ -609,7 +609,7 @@ int spx_from_dense_count(const void *dense, int C, int elem_bytes, int is_float,
   SPX_LAUNCH_CHECK();
   SPX_HIP(hipMemcpyAsync(n_active_h, w.total, sizeof(int), hipMemcpyDeviceToHost, s));
   SPX_HIP(hipStreamSynchronize(s));
-  spx::count_dense(spx::kDenseCompact);
+  spx::count(spx::kDenseCompact);
   return 0;
 }
 
@@ -638,7 +638,7 @@ int spx_from_dense_fill(const void *dense, int C, int elem_bytes, int ndim, int 
                                      static_cast<const P *>(dense), row_bytes / static_cast<int>(sizeof(P)), g, w.flags,
                                      w.blockoff, indices, static_cast<P *>(rows), map));
   SPX_LAUNCH_CHECK();
-  spx::count_dense(spx::kDenseCompact);
+  spx::count(spx::kDenseCompact);
   return 0;
 }
 

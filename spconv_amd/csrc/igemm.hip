@@ -123,7 +123,7 @@ int run_gather_gemm_single(const GemmParams &p, int dtype, hipStream_t s) {
   }
   const long long total = static_cast<long long>(p.n_dst) * p.COUT;
   const dim3 grid(static_cast<unsigned>((total + kThreads - 1) / kThreads));
-  count_launch(kFamGeneric);
+  count(kFamGeneric);
   if (int rc = with_elem_type(dtype, [&](auto t, auto slot) {
         count_inst<inst::generic(decltype(slot)::value)>();
         hipLaunchKernelGGL(gather_gemm_generic_kernel<decltype(t)>, grid, dim3(kThreads), 0, s, p);

@@ -389,12 +389,12 @@ int launch_bwd(const GemmParams &p, const Wgrad2Params &q, int n_wgrad_blocks, h
   rr.napp = p.cls ? napp : -1;
   if (exact.napp >= 0) {
     rr.acc_mode = pack_app_shape(p.acc_mode, p.app_m, exact);
-    count_hint(kHintBwd);
+    count(kHintBwd);
   }
   constexpr int wgrad_first = 1;           // (the longer chains are dispatched first: settled A/B)
   GemmParams pl = p;
   pl.lpt = p.tile_order && n_dgrad + n_wgrad_blocks > 1024;           // (see launch_v4)
-  count_launch(kFamBwdFused);
+  count(kFamBwdFused);
 #define SPX_LAUNCH_BWD(NKSV, PKV)                                                                                  \
   do {                                                                                                               \
     count_inst<inst::bwd(COUT, MB, DT, NKSV, PKV)>();                                                                \

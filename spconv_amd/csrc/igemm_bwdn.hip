@@ -432,7 +432,7 @@ int spx_igemm_bwd_rows(const void *feat, const void *dout, const void *weight_t,
   // occupancy nor a deeper ring, fewer barriers or fewer LDS reads moved them.
   // 8 waves at C = K = 16 only; the 8-wave forms of the 32-channel shapes spilled (12-16 bytes of scratch per lane)
   // and are no longer instantiated: every instantiation of this kernel runs without scratch
-  count_launch(kFamBwdRows);
+  count(kFamBwdRows);
 #define SPX_BWDN(BF, CC, KK, W8)                                                                                \
   do {                                                                                                          \
     count_inst<inst::bwd_rows(CC, KK, BF ? 1 : 0, W8)>();                                                       \

@@ -283,8 +283,8 @@ int run_gather_gemm_f64(const GemmParams &p0, bool dgrad, hipStream_t s) {
   drop_rows_layout(p);          // the rows layout's appendix tables are walked by row, as by the generic kernel
   SPX_CHECK(p.CIN > 0 && p.COUT > 0 && p.kv > 0, "bad sizes");
   const dim3 grid(static_cast<unsigned>(div_up(p.n_dst, kF64TM)), static_cast<unsigned>(div_up(p.COUT, kF64TN)));
-  count_launch(kFamF64);
-  count_f64(dgrad ? kF64Dgrad : kF64Fwd);
+  count(kFamF64);
+  count(dgrad ? kF64Dgrad : kF64Fwd);
   hipLaunchKernelGGL(gemm_f64_kernel, grid, dim3(kF64Threads), 0, s, p);
   SPX_LAUNCH_CHECK();
   return 0;
@@ -320,7 +320,7 @@ int wgrad_f64(const void *feat, const void *dout, void *dw, const int32_t *pair_
   SPX_CHECK(kv <= 65535 && q.tiles_c * q.tiles_k <= 65535, "kernel volume / channel counts beyond the launch grid");
   const dim3 grid(static_cast<unsigned>(q.nchunks), static_cast<unsigned>(kv),
                   static_cast<unsigned>(q.tiles_c * q.tiles_k));
-  count_f64(kF64Wgrad);
+  count(kF64Wgrad);
   hipLaunchKernelGGL(wgrad_f64_kernel, grid, dim3(kF64Threads), 0, s, q);
   SPX_LAUNCH_CHECK();
   const long long total = static_cast<long long>(K) * C * kv;

@@ -875,12 +875,12 @@ int launch_v4(const GemmParams &p, hipStream_t s) {
   r.napp = p.cls ? napp : -1;
   if (exact.napp >= 0) {
     r.acc_mode = pack_app_shape(p.acc_mode, p.app_m, exact);
-    count_hint(kHintV4);
+    count(kHintV4);
   }
   constexpr int es = DT == 2 ? 1 : (DT == 3 ? 4 : 2);
   const bool half = p.CIN * es <= 64;        // narrow rows: only the first 64 bytes of a piece exist
   const int pk = v4_pack(p, DT, es);         // ... <= 32 / 16 bytes: 2 / 4 offsets per step (igemm_v4_body, PK)
-  count_launch(kFamV4);
+  count(kFamV4);
 #define SPX_LAUNCH_V4(BTV, NKSV, PKV)                                                                \
   do {                                                                                                 \
     count_inst<inst::v4(COUT, MB, DT, BTV, NKSV, PKV)>();                                              \
@@ -1075,7 +1075,7 @@ int launch_i8_sparse(const GemmParams &p, hipStream_t s) {
   q.lpt = false;
   GemmRest r = rest_of(p);
   r.napp = napp;
-  count_launch(kFamI8Stream);
+  count(kFamI8Stream);
   hipLaunchKernelGGL((igemm_i8_sparse_kernel<COUT>), dim3(napp + nmain), dim3(kThreads), (v4_smem_bytes<COUT, 1, 2>()), s,
                      p.A, p.B, p.mask, p.argsort, p.pair, p.n_dst, p.n_src, p.CIN, p.kv, p.identity_k, v4_flags(q), r);
   SPX_LAUNCH_CHECK();

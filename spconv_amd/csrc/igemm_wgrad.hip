@@ -712,7 +712,7 @@ int launch_reduce2(const Wgrad2Params &q, void *dw, int dtype, int ntile, hipStr
     return 0;
   }
   const dim3 rgrid2(reduce2_blocks(q.kv), ntile);   // block-stride over the work list
-  count_launch(kFamStage2);
+  count(kFamStage2);
   if (int rc = with_elem_type(dtype, [&](auto t, auto) {
         using T = decltype(t);
         hipLaunchKernelGGL(wgrad_reduce2_kernel<T>, rgrid2, dim3(kRedThreads), 0, s, q, static_cast<T *>(dw));
@@ -913,7 +913,7 @@ int spx_wgrad_stage2_batch(const void *jobs, int njobs, spx_stream_t stream) {
       gx = gx < 32 ? 32 : gx;
       gx = gx > reduce2_blocks(kvmax) ? reduce2_blocks(kvmax) : gx;
       const dim3 grid(gx, b.ybase[b.n]);
-      count_launch(kFamStage2Batch);
+      count(kFamStage2Batch);
       if (int rc = with_elem_type(dtype, [&](auto t, auto) {
             hipLaunchKernelGGL(wgrad_reduce2_batch_kernel<decltype(t)>, grid, dim3(kRedThreads), 0, s, b);
           }))

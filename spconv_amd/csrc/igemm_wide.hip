@@ -57,7 +57,7 @@ int launch_v4w(const GemmParams &p, hipStream_t s) {
   const bool half = p.CIN * es <= 64;
   int pk = v4_pack(p, DT, es);
   if (pk >= 8) pk = pk == 32 ? 4 : (pk == 16 ? 2 : 1);       // (SPX_PK = 3: the one-piece forms are what exists here)
-  count_launch(kFamV4w);
+  count(kFamV4w);
 #define SPX_LAUNCH_V4W(BTV, NKSV, PKV)                                                                       \
   do {                                                                                                       \
     count_inst<inst::v4w(DT, BTV, NKSV, PKV)>();                                                             \

@@ -400,7 +400,7 @@ int launch_ws_one(const WsArgs &a, hipStream_t s, int *grid_out) {
   SPX_HIP(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), static_cast<int>(lds), attr_done));
   WsArgs q = a;
   q.ntiles = div_up(a.n_dst, NW * 32);
-  count_launch(kFamWs);
+  count(kFamWs);
   count_inst<inst::ws(BF16 ? 1 : 0)>();
   hipLaunchKernelGGL(kern, dim3(q.ntiles), dim3(NW * 64), lds, s, q);
   if (grid_out) *grid_out = q.stats ? q.ntiles : 0;

@@ -270,7 +270,7 @@ int spx_point_corners(const float *points, int nfeat, const int32_t *batch_ids, 
     });
   });
   SPX_LAUNCH_CHECK();
-  count_interp(ranked ? kInterpCornersRanked : kInterpCornersHash);
+  count(ranked ? kInterpCornersRanked : kInterpCornersHash);
   return 0;
 }
 
@@ -294,7 +294,7 @@ int spx_interp_fwd(const void *vfeat, int n, const int32_t *corner_rows, const f
     });
   });
   SPX_LAUNCH_CHECK();
-  count_interp(kInterpFwd);
+  count(kInterpFwd);
   return 0;
 }
 
@@ -316,7 +316,7 @@ int spx_interp_bwd(const void *dout, int n_cap, int ndim, const float *corner_w,
                        dim3(kBlock), 0, s, dout, n_cap, ndim, corner_w, offsets, list, n, pieces, gshift, n_live, dvfeat);
   });
   SPX_LAUNCH_CHECK();
-  count_interp(kInterpBwd);
+  count(kInterpBwd);
   return 0;
 }
 

@@ -214,7 +214,7 @@ int spx_knn_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids,
   else
     launch_knn<2>(a, grid, s);
   SPX_LAUNCH_CHECK();
-  count_sample(kSampleKnnQuery);
+  spx::count(kSampleKnnQuery);
   return 0;
 }
 

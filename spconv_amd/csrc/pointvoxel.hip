@@ -215,7 +215,7 @@ int spx_point_groups(const void *ids, int id_bytes, int n_cap, const int32_t *n_
   hipLaunchKernelGGL(pv_offsets_kernel, dim3(static_cast<unsigned>((static_cast<long long>(num_voxels) + kBlock) / kBlock)),
                      dim3(kBlock), 0, s, w.sortkey, list, n_cap, num_voxels, offsets);
   SPX_LAUNCH_CHECK();
-  count_pointvoxel(kPvGroups);
+  count(kPvGroups);
   return 0;
 }
 
@@ -233,7 +233,7 @@ int spx_voxel_to_point(const void *vfeat, int num_voxels, const int32_t *rows, i
   unsigned char fill16[16];
   for (int b = 0; b < 16; ++b) fill16[b] = static_cast<unsigned char>((static_cast<unsigned long long>(fill_bits) >> (8 * (b % elem_bytes))) & 0xffu);
   if (int rc = gather_rows(vfeat, num_voxels, rows, n_cap, C, elem_bytes, fill16, out, static_cast<hipStream_t>(stream))) return rc;
-  count_pointvoxel(kPvGather);
+  count(kPvGather);
   return 0;
 }
 
@@ -272,7 +272,7 @@ int spx_point_decorate(const float *points, int nfeat, int n_cap, const int32_t 
                        total, pieces, rows, indices, g, cluster_mean, flags, out);
   });
   SPX_LAUNCH_CHECK();
-  count_pointvoxel(kPvDecorate);
+  count(kPvDecorate);
   return 0;
 }
 

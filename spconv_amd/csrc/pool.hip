@@ -182,7 +182,7 @@ template <typename T, int OP>
 int launch_pool(const PoolParams &p, hipStream_t s) {
   constexpr int V = 16 / static_cast<int>(sizeof(T));
   if (p.n_dst == 0) return 0;
-  if (std::is_same<T, double>::value) count_f64(kF64Pool);     // (counted where the launch happens, like the others)
+  if (std::is_same<T, double>::value) count(kF64Pool);     // (counted where the launch happens, like the others)
   if (p.C % V == 0) {
     count_pool(OP, Elem<T>::kDt, false);
     const long long total = static_cast<long long>(p.n_dst) * (p.C / V);

@@ -422,7 +422,7 @@ int spx_voxel_query(const float *queries, int nfeat, const int32_t *batch_ids, i
       hipLaunchKernelGGL((query_ranked_kernel<nd>), grid(a.wshift), block, 0, s, a, g, look);
     });
     SPX_LAUNCH_CHECK();
-    count_query(kQueryRanked);
+    spx::count(kQueryRanked);
     return 0;
   }
   if (int rc = build_level_table(ws, ws_bytes, indices, n, n_live, g.level, &look.table, s)) return rc;
@@ -431,7 +431,7 @@ int spx_voxel_query(const float *queries, int nfeat, const int32_t *batch_ids, i
     hipLaunchKernelGGL((query_hash_kernel<nd>), grid(a.wshift), block, 0, s, a, g, look);
   });
   SPX_LAUNCH_CHECK();
-  count_query(kQueryHash);
+  spx::count(kQueryHash);
   return 0;
 }
 
@@ -447,7 +447,7 @@ int spx_group_fwd(const void *vfeat, int n, const int32_t *rows, int n_cap, int 
   if (int rc = gather_rows(vfeat, n, rows, static_cast<long long>(n_cap) * nsample, C, eb, zeros, out,
                            static_cast<hipStream_t>(stream)))
     return rc;
-  count_query(kQueryGroupFwd);
+  spx::count(kQueryGroupFwd);
   return 0;
 }
 
@@ -467,7 +467,7 @@ int spx_group_bwd(const void *dout, int n_cap, int nsample, const int32_t *offse
                        dim3(kBlock), 0, s, dout, n_cap * nsample, offsets, list, n, pieces, gshift, n_live, dvfeat);
   });
   SPX_LAUNCH_CHECK();
-  count_query(kQueryGroupBwd);
+  spx::count(kQueryGroupBwd);
   return 0;
 }
 

@@ -407,12 +407,12 @@ struct ConvWs {
 };
 
 // Launch counter (rulebook/conv3/<mj> | rulebook/conv_generic) of the passes conv3_cands picked.
-RulebookPass conv_pass_counter(int mj) {
+Counter conv_pass_counter(int mj) {
   return mj == 0 ? kRbConvGeneric : (mj == 1 ? kRbConv3_1 : (mj == 2 ? kRbConv3_2 : (mj == 4 ? kRbConv3_4 : kRbConv3_8)));
 }
 
 // Launch counter (rulebook/conv3_shares/<s>) of the grid.y a compact pass is launched with.
-RulebookPass conv_shares_counter(int shares) {
+Counter conv_shares_counter(int shares) {
   return shares <= 1 ? kRbShares1 : (shares == 2 ? kRbShares2 : (shares == 4 ? kRbShares4 : kRbShares8));
 }
 
@@ -502,7 +502,7 @@ int conv_count_impl(const ConvProblem &p, void *ws, size_t ws_bytes, int *n_out_
   if (mj && expect_out > 0) {            // (the later passes of this form never touch the table)
     const uint32_t cap = table_capacity(expect_out);
     if (cap < w.t.mask + 1u) {
-      count_rulebook(kRbConvShrunk);
+      count(kRbConvShrunk);
       table_shrink(w.t, cap);
     }
   }
@@ -515,10 +515,10 @@ int conv_count_impl(const ConvProblem &p, void *ws, size_t ws_bytes, int *n_out_
     if (mj) fills.add(w.firstbits, sizeof(uint32_t) * static_cast<size_t>(g.kv) * w.nblk * (kItems / 32), 0u);
     SPX_HIP(fills.launch(s));
   }
-  count_rulebook(conv_pass_counter(mj));
+  count(conv_pass_counter(mj));
   if (mj) {
     const int shares = conv3_shares(n_in, mj);
-    count_rulebook(conv_shares_counter(shares));
+    count(conv_shares_counter(shares));
     SPX_CONV3_LAUNCH(conv3_insert_kernel, mj, dim3(div_up(n_in, kBlock), shares), dim3(kBlock), 0, s, p.indices, n_in, g,
                      w.t, w.slot_of, w.d_nout + 1);
     SPX_CONV3_LAUNCH(conv3_first_kernel, mj, dim3(div_up(n_in, kBlock), shares), dim3(kBlock), 0, s, p.indices, n_in, g,
@@ -558,10 +558,10 @@ int conv_fill_impl(const ConvProblem &p, const ConvOutputs &o, void *ws, size_t 
   if (n_in == 0) return 0;
   ConvWs w = carve_conv_ws(ws, p, keys_fit_u32(g.batch, g.out_dims, 4));   // as the count pass
   const int mj = conv3_cands(p);
-  count_rulebook(conv_pass_counter(mj));
+  count(conv_pass_counter(mj));
   if (mj) {
     const int shares = conv3_shares(n_in, mj);                 // (as the count pass: it wrote one flag plane per share)
-    count_rulebook(conv_shares_counter(shares));
+    count(conv_shares_counter(shares));
     SPX_CONV3_LAUNCH(conv3_assign_kernel, mj, dim3(div_up(n_in, kBlock), shares), dim3(kBlock), 0, s, p.indices, n_in, g,
                      static_cast<const int32_t *>(w.slot_of), w.nblk, static_cast<const uint32_t *>(w.firstbits),
                      static_cast<const uint8_t *>(w.firstflags), static_cast<const int32_t *>(w.wordpre),
@@ -591,7 +591,7 @@ int conv_fill_impl(const ConvProblem &p, const ConvOutputs &o, void *ws, size_t 
   }
   if (o.pair_native) {
     SPX_CHECK(o.num_per_loc, "num_per_loc is required with pair_native");
-    count_rulebook(kRbConvListsV1);
+    count(kRbConvListsV1);
   }
   if (o.num_per_loc && launch_native_lists(o.pair_bwd, 1, kv, n_in, kv, w.nblk, w.blockcount, w.blockoff, o.pair_native,
                                            o.num_per_loc, s))
@@ -625,7 +625,7 @@ int spx_conv_rulebook_count(const int32_t *indices, int n_in, int ndim, int batc
   int rc = conv_count_impl(p, ws, ws_bytes, n_out_h, &overflow, expect, s);
   if (rc) return rc;
   if (overflow && expect > 0) {          // the expectation was too small: once more, at the bound
-    count_rulebook(kRbConvRetry);
+    count(kRbConvRetry);
     rc = conv_count_impl(p, ws, ws_bytes, n_out_h, &overflow, 0, s);
     if (rc) return rc;
   }

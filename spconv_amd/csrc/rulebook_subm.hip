@@ -533,7 +533,7 @@ int spx_subm_rulebook(const int32_t *indices, int n, int ndim, int batch_size, c
                        mask_pass ? static_cast<uint32_t *>(nullptr) : mask, words, pair_fwd, pair_bwd,
                        probe5 ? w.occupied : static_cast<uint32_t *>(nullptr));
     const bool lists = pair_native || num_per_loc;
-    count_rulebook(probe5 ? kRbSubmProbe5 : kRbSubmProbe4);
+    count(probe5 ? kRbSubmProbe5 : kRbSubmProbe4);
     if (probe5) {
       const int fwords = static_cast<int>(cap / 32);
       const size_t lds = static_cast<size_t>(fwords) * 4 + static_cast<size_t>(kv / 2) * (16 + 8 + 16);
@@ -547,11 +547,11 @@ int spx_subm_rulebook(const int32_t *indices, int n, int ndim, int batch_size, c
                          mask_pass);
     }
     if (mask_pass) {
-      count_rulebook(kRbSubmMaskPass);
+      count(kRbSubmMaskPass);
       hipLaunchKernelGGL(mask_from_table_kernel, grid, dim3(kBlock), 0, s, pair_fwd, kv, n, words, mask);
     }
     if (lists) {
-      count_rulebook(kRbSubmLists);
+      count(kRbSubmLists);
       if (subm_lists(pair_fwd, kv, n, w.groupcount, pair_native, num_per_loc, w.scratch_totals, s)) return -1;
     }
     SPX_LAUNCH_CHECK();
@@ -571,13 +571,13 @@ int spx_subm_rulebook(const int32_t *indices, int n, int ndim, int batch_size, c
   }
   SPX_HIP(fills.launch(s));
   hipLaunchKernelGGL(subm_insert_kernel, grid, dim3(kBlock), 0, s, indices, n, g, w.t, w.slot_of);
-  count_rulebook(kRbSubmProbe3);
+  count(kRbSubmProbe3);
   hipLaunchKernelGGL(subm_probe3_kernel, dim3(w.nblk256, kv / 2 + 1), dim3(kBlock), 0, s, indices, n, g, w.t,
                      w.slot_of, pair_fwd, pair_bwd, mask, words, pair_native);
   SPX_LAUNCH_CHECK();
   if (pair_native) {
     SPX_CHECK(num_per_loc || kv / 2 <= 64, "num_per_loc required for kv > 128");
-    if (kv / 2 > 0) count_rulebook(kRbNativeListsV1);
+    if (kv / 2 > 0) count(kRbNativeListsV1);
   }
   // num_per_loc: counts only for k < kv/2 (indices.py:1685,1692)
   if ((pair_native || num_per_loc) &&

@@ -438,7 +438,7 @@ int spx_fps(const float *points, int nfeat, int n_cap, int ndim, const int32_t *
     hipLaunchKernelGGL((fps_kernel<2>), dim3(batch), dim3(kFpsBlock), 0, s, points, nfeat, n_cap, offsets, list, num_samples,
                        idx, count, recs);
   SPX_LAUNCH_CHECK();
-  count_sample(kSampleFps);
+  spx::count(kSampleFps);
   return 0;
 }
 
@@ -460,7 +460,7 @@ int spx_ball_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids
   else
     hipLaunchKernelGGL((ball_query_kernel<2>), grid, dim3(kSceneBlock), 0, s, a);
   SPX_LAUNCH_CHECK();
-  count_sample(kSampleBallQuery);
+  spx::count(kSampleBallQuery);
   return 0;
 }
 

@@ -374,12 +374,12 @@ int count_rows(const SelRows &r, const SelectWs &w, int cap, int32_t *n_out_dev,
   if (r.n > 0) {
     hipLaunchKernelGGL(select_count_kernel, dim3(w.nblk), dim3(kBlock), 0, s, r, w.blockcount, w.counters + 1);
     SPX_LAUNCH_CHECK();
-    count_select(kSelCount);
+    count(kSelCount);
   }
   hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kBlock), 0, s, w.blockcount, w.blockoff, w.nblk, cap, w.counters,
                      n_out_dev);
   SPX_LAUNCH_CHECK();
-  count_select(kSelScan);
+  count(kSelScan);
   return 0;
 }
 
@@ -390,13 +390,13 @@ int scatter_rows(const SelRows &r, const SelectWs &w, int cap, int32_t *out_indi
     hipLaunchKernelGGL(select_scatter_kernel, dim3(static_cast<unsigned>((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                        r, w.blockoff, w.nblk, w.counters, cap, rows, src, out_indices);
     SPX_LAUNCH_CHECK();
-    count_select(kSelScatter);
+    count(kSelScatter);
   }
   if (rankmap) {
     if (int rc = spx_rankmap_from_sorted(out_indices, cap, r.g.ndim, r.g.batch, spatial_h, rankmap, rankmap_bytes,
                                          violation, s))
       return rc;
-    count_select(kSelMap);
+    count(kSelMap);
   }
   return 0;
 }
@@ -426,7 +426,7 @@ int spx_row_score(const void *feat, int n, int C, int dtype, int op, const int32
     });
   });
   SPX_LAUNCH_CHECK();
-  count_select(kSelScore);
+  count(kSelScore);
   return 0;
 }
 
@@ -459,12 +459,12 @@ int spx_topk_flags(const float *score, const int32_t *indices, int n, const int3
       hipLaunchKernelGGL(topk_hist_kernel, dim3(stream_blocks(n, kBlock)), dim3(kBlock), 0, s, r, d, w.state,
                          w.hist + d * kBins);
       SPX_LAUNCH_CHECK();
-      count_select(kSelHist);
+      count(kSelHist);
     }
     hipLaunchKernelGGL(topk_pick_kernel, dim3(1), dim3(kBlock), 0, s, w.hist + d * kBins, d, k_abs, ratio, w.state,
                        sel_dev);
     SPX_LAUNCH_CHECK();
-    count_select(kSelPick);
+    count(kSelPick);
   }
   if (n == 0) return 0;
   hipLaunchKernelGGL(topk_flags_kernel<false>, dim3(w.nblk), dim3(kBlock), 0, s, r, w.state, w.blockties, w.blockoff,
@@ -472,11 +472,11 @@ int spx_topk_flags(const float *score, const int32_t *indices, int n, const int3
   hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScanThreads), 0, s, w.blockties, w.blockoff, w.nblk,
                      static_cast<int32_t *>(nullptr));
   SPX_LAUNCH_CHECK();
-  count_select(kSelTies);
+  count(kSelTies);
   hipLaunchKernelGGL(topk_flags_kernel<true>, dim3(w.nblk), dim3(kBlock), 0, s, r, w.state, w.blockties, w.blockoff,
                      keep);
   SPX_LAUNCH_CHECK();
-  count_select(kSelFlags);
+  count(kSelFlags);
   return 0;
 }
 

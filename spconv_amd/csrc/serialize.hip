@@ -386,7 +386,7 @@ int spx_curve_keys(const int32_t *indices, int n, const int32_t *n_live, int ndi
                        indices, n, n_live, spec, reinterpret_cast<unsigned long long *>(keys));
   });
   SPX_LAUNCH_CHECK();
-  count_serialize(kSerKeys);
+  count(kSerKeys);
   return 0;
 }
 
@@ -422,12 +422,12 @@ int spx_serialize(const uint64_t *keys, int n, int n_orders, int key_bits, int b
     if (int rc = radix_argsort64(keys, n, n_orders, key_bits, order, inverse, w.sort, s)) return rc;
   }
   if (n > 0)
-    for (int k = 0; k < n_orders; ++k) count_serialize(kSerSort);
+    for (int k = 0; k < n_orders; ++k) count(kSerSort);
   // (n = 0: the bisection touches neither the keys nor the order)
   hipLaunchKernelGGL(scene_offsets_kernel, dim3(div_up(batch + 1, kBlock)), dim3(kBlock), 0, s, k64, order, n, batch,
                      batch_shift, offsets);
   SPX_LAUNCH_CHECK();
-  count_serialize(kSerOffsets);
+  count(kSerOffsets);
   return 0;
 }
 
@@ -456,7 +456,7 @@ int spx_patch_plan(const int32_t *order, const int32_t *offsets, int n, int batc
                      batch, patch_size, pad == SPX_PAD_BORROW ? 1 : 0, slots, patch_rows, patch_rows_canon, row_slot,
                      row_slot2, patch_scene);
   SPX_LAUNCH_CHECK();
-  count_serialize(kSerPlan);
+  count(kSerPlan);
   return 0;
 }
 
@@ -478,7 +478,7 @@ int spx_patch_rows_bwd(const void *g, int slots, const int32_t *row_slot, const 
                        row_slot, row_slot2, total, pieces, g_feat);
   });
   SPX_LAUNCH_CHECK();
-  count_serialize(kSerBwd);
+  count(kSerBwd);
   return 0;
 }
 

@@ -299,10 +299,10 @@ int number_union(const Build &b, void *rankmap, const UnionWs &w, int32_t *count
   if (b.n_total > 0) {
     hipLaunchKernelGGL(union_mark_kernel, dim3(div_up(b.n_total, kBlock)), dim3(kBlock), 0, s, b.ops, b.g, w.occupied);
     SPX_LAUNCH_CHECK();
-    count_union(kUnionMark);
+    count(kUnionMark);
   }
   SPX_HIP(number_level(w, b.W, rankmap, cap, counters, s));
-  count_union(kUnionPrefix);
+  count(kUnionPrefix);
   return 0;
 }
 
@@ -341,7 +341,7 @@ int spx_union_count(const int32_t *const *indices_h, const int *n_h, const int32
                        static_cast<const uint2 *>(rankmap), static_cast<const int32_t *>(rank_blockoff(rankmap, b.W)),
                        w.owner, b.n_total, b.n_total, w.counters, w.counters + 4, static_cast<int32_t *>(nullptr));
     SPX_LAUNCH_CHECK();
-    count_union(kUnionClaim);
+    count(kUnionClaim);
   }
   int32_t host[kCounters];
   SPX_HIP(hipMemcpyAsync(host, w.counters, sizeof(host), hipMemcpyDeviceToHost, s));
@@ -380,7 +380,7 @@ int spx_union_fill(const int32_t *const *indices_h, const int *n_h, const int32_
                      b.ops, b.g, static_cast<const uint2 *>(rm), static_cast<const int32_t *>(rank_blockoff(rm, b.W)),
                      static_cast<const int32_t *>(w.owner), b.n_total, n_out, base, out_indices, src);
   SPX_LAUNCH_CHECK();
-  count_union(kUnionFill);
+  count(kUnionFill);
   return 0;
 }
 
@@ -411,7 +411,7 @@ int spx_union_static(const int32_t *const *indices_h, const int *n_h, const int3
                        static_cast<const uint2 *>(rankmap), static_cast<const int32_t *>(rank_blockoff(rankmap, b.W)), src,
                        n_out_cap, n_out_cap, n_out_dev, w.counters + 4, out_indices);
     SPX_LAUNCH_CHECK();
-    count_union(kUnionClaim);
+    count(kUnionClaim);
   }
   return 0;
 }
@@ -447,7 +447,7 @@ int spx_union_add_fwd(const void *const *feat_h, const int *n_h, int T, const in
                        dim3(kBlock), 0, s, ops, src, n_out, pieces, out, n_live);
   });
   SPX_LAUNCH_CHECK();
-  count_union(kUnionAddFwd);
+  count(kUnionAddFwd);
   return 0;
 }
 
@@ -492,7 +492,7 @@ int spx_union_add_bwd(const void *dout, int n_out, void *const *din_h, const int
     default: launch_add_bwd<uint16_t>(ops, dout, n_out, pieces, s); break;
   }
   SPX_LAUNCH_CHECK();
-  count_union(kUnionAddBwd);
+  count(kUnionAddBwd);
   return 0;
 }
 

@@ -35,7 +35,7 @@ def count_of(cuda, n):
 
 def launches():
     from spconv_amd import _lib
-    return {k: _lib.load().spx_launch_count(k.encode()) for k in KEYS}
+    return _lib.launch_counts(KEYS)
 
 
 def device_table(cuda, boxes, n_boxes=None):

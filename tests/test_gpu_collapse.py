@@ -24,8 +24,7 @@ HALF_MIN_STEP = {"float16": 2.0 ** -25, "bfloat16": 2.0 ** -134, "float32": 2.0 
 
 def counts():
     from spconv_amd import _lib
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
+    return _lib.launch_counts(KEYS)
 
 
 def bits(t):

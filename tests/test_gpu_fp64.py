@@ -39,10 +39,6 @@ def assert_f64_close(got, ref, A, name):
                              f"{i}: got {a[i]!r}, want {r[i]!r}, A {A[i]:.6g}")
 
 
-def _counts(L, keys):
-    return {k: int(L.spx_launch_count(k.encode())) for k in keys}
-
-
 def _act(x, act):
     return {"none": x, "relu": torch.relu(x), "leaky": torch.where(x > 0, x, x * ALPHA),
             "sigmoid": torch.sigmoid(x)}[act]
@@ -101,7 +97,6 @@ def test_entries_match_fp64_reference(case):
     kernels ran (their counters moved), no other gather-GEMM did."""
     from spconv_amd import _lib
     from spconv_amd.pytorch import ops
-    L = _lib.load()
     name, geom, (shape, n, bs), C, K, table, inverse, act = case
     ks, st, pd, dl, subm, tr = GEOMS[geom]
     kv = int(np.prod(ks))
@@ -135,7 +130,7 @@ def test_entries_match_fp64_reference(case):
     fwd_which = "bwd" if inverse else "fwd"
     bwd_which = "fwd" if (subm or inverse) else "bwd"
     native = rb.native_swapped() if inverse else rb.pair_native
-    before = _counts(L, F64_KEYS + OTHER_KEYS)
+    before = _lib.launch_counts(F64_KEYS + OTHER_KEYS)
     t = _tables(rb, fwd_which, K, table)
     out = ops.igemm_fwd(f, w, t[0], t[1], t[2], n_out, kv // 2 if subm else -1, bias=bias,
                         act_type={None: 0, "none": 0, "relu": ops.Activation.ReLU, "sigmoid": ops.Activation.Sigmoid,
@@ -146,7 +141,7 @@ def test_entries_match_fp64_reference(case):
     din2, dw2 = ops.igemm_bwd(f, d, w, t[0], t[1], t[2], native, rb.num_per_loc, subm, ops._plan_of(rb),
                               tile_order=t[3])
     torch.cuda.synchronize()
-    after = _counts(L, F64_KEYS + OTHER_KEYS)
+    after = _lib.launch_counts(F64_KEYS + OTHER_KEYS)
 
     want, A = ref.out, ref.out_abs
     if bias is not None:
@@ -199,13 +194,13 @@ def test_capi_bwd_float64(name):
                                rb.pair_native.data_ptr(), rb.num_per_loc.data_ptr(), None, rb.n_in, rb.n_out, C, K, kv,
                                _lib.DTYPE_F64, int(subm), ws.data_ptr(), nbytes, stream)
 
-    before = _counts(L, F64_KEYS + OTHER_KEYS)
+    before = _lib.launch_counts(F64_KEYS + OTHER_KEYS)
     assert call(ws_bytes - 256) != 0 and b"workspace too small" in L.spx_last_error()
     torch.cuda.synchronize()
-    assert _counts(L, F64_KEYS + OTHER_KEYS) == before, "a refused call launched"
+    assert _lib.launch_counts(F64_KEYS + OTHER_KEYS) == before, "a refused call launched"
     _lib.check(call(ws_bytes))
     torch.cuda.synchronize()
-    moved = {k: v - before[k] for k, v in _counts(L, F64_KEYS + OTHER_KEYS).items()}
+    moved = {k: v - before[k] for k, v in _lib.launch_counts(F64_KEYS + OTHER_KEYS).items()}
     assert moved["igemm_f64/dgrad"] == 1 and moved["wgrad_f64"] == 1 and moved["igemm_f64/fwd"] == 0, moved
     assert all(moved[k] == 0 for k in OTHER_KEYS), moved
     assert_f64_close(din, ref.din, ref.din_abs, "din")

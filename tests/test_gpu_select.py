@@ -22,8 +22,7 @@ DTYPES = [torch.float16, torch.bfloat16, torch.float32, torch.float64]
 
 def counts():
     from spconv_amd import _lib
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
+    return _lib.launch_counts(KEYS)
 
 
 def delta(before):

@@ -54,8 +54,7 @@ def lattice_scene(shape, n, seed):
 
 def _counts():
     from spconv_amd import _lib
-    L = _lib.load()
-    return tuple(int(L.spx_launch_count(k)) for k in (b"sparse_hint/v4", b"sparse_hint/bwd", b"igemm_v4", b"igemm_bwd"))
+    return tuple(_lib.launch_counts(("sparse_hint/v4", "sparse_hint/bwd", "igemm_v4", "igemm_bwd")).values())
 
 
 def _delta(before):

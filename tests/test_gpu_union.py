@@ -19,8 +19,7 @@ KEYS = ("union/mark", "union/prefix", "union/claim", "union/fill", "union/add_fw
 
 def counts():
     from spconv_amd import _lib
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
+    return _lib.launch_counts(KEYS)
 
 
 def bits(t):

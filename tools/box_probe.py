@@ -68,11 +68,6 @@ def timed(fn, repeats, warmup=2, wall=False):
     return {"median_us": round(statistics.median(times), 1), "min_us": round(min(times), 1)}
 
 
-def launches():
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
-
-
 # ------------------------------------------------------------------------------------------- the torch composite
 def composite_corners(boxes):
     c, s = torch.cos(boxes[:, 6:7]), torch.sin(boxes[:, 6:7])
@@ -174,9 +169,9 @@ def nms_case(dev, per_scene, post_max, repeats, res, name):
 
     def native():
         Fsp.nms_rotated_into(corners, scores, THRESH, keep, count, ws, batch_ids=bid, batch_size=BATCH, pre_max=per_scene)
-    before = launches()
+    before = _lib.launch_counts(KEYS)
     native()
-    res[f"launches_of_{name}"] = {k: v - before[k] for k, v in launches().items()}
+    res[f"launches_of_{name}"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
     torch.cuda.synchronize()
     ref = composite_nms(boxes, scores, bid, per_scene, post_max)
     same = sum(int(count[b]) == len(ref[b]) and torch.equal(keep[b, :len(ref[b])].long(), ref[b]) for b in range(BATCH))

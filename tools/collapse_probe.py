@@ -59,11 +59,6 @@ def timed(fn, repeats, warmup=5):
     return {"median_us": round(statistics.median(times), 1), "min_us": round(min(times), 1)}
 
 
-def launches():
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
-
-
 class Composite:
     """unique of the projected keys (the count is read back) + index_add_ (float atomics); backward: a row gather"""
 
@@ -97,9 +92,9 @@ def probe(name, cfg, dev, repeats):
     shape, B, C = cfg["shape"], cfg["batch"], cfg["C"]
     res = {"shape": shape, "batch": B, "rows": int(idx.shape[0]), "C": C, "dtype": "f16", "axes": list(AXES), "reduce": "sum"}
     comp = Composite(cfg)
-    before = launches()
+    before = _lib.launch_counts(KEYS)
     c = _collapse.sparse_collapse_build(idx, B, shape, AXES)
-    res["launches_of_one_build"] = {k: v - before[k] for k, v in launches().items()}
+    res["launches_of_one_build"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
     out_idx, inverse = comp.build(idx)
     assert torch.equal(out_idx, c.out_indices) and torch.equal(inverse.int(), c.rows)
     res["out_rows"] = c.n_out

@@ -68,11 +68,6 @@ def timed(fn, repeats, warmup=5):
     return {"median_us": round(statistics.median(times), 1), "min_us": round(min(times), 1)}
 
 
-def launches():
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
-
-
 class Composite:
     """the torch form: a hash table over the level's keys, 8 queries, the weights in torch, index_select / mul / sum"""
 
@@ -159,9 +154,9 @@ def probe(dev, repeats):
     x_rank, x_hash = level(ranked_idx, dummy), level(plain_idx, dummy)
     native_corners = lambda x, groups=False: Fsp.point_corners(pts, bids, x, VSIZE, RANGE, with_groups=groups)
 
-    before = launches()
+    before = _lib.launch_counts(KEYS)
     c = native_corners(x_rank, True)
-    res["launches_of_corners_with_groups"] = {k: v - before[k] for k, v in launches().items()}
+    res["launches_of_corners_with_groups"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
     c_hash = native_corners(x_hash)
     assert torch.equal(c.rows, c_hash.rows) and torch.equal(c.weights, c_hash.weights)
     rows_c, w_c = comp.corners()

@@ -58,11 +58,6 @@ def timed(fn, repeats, warmup=3):
     return {"median_us": round(statistics.median(times), 1), "min_us": round(min(times), 1)}
 
 
-def launches():
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
-
-
 def composite_knn(q, p, k, chunk):
     """q [B, m, 3], p [B, n, 3] -> rows int64 [B * m, k] (point index in the whole cloud), d2 [B * m, k]: a distance
     matrix per chunk of queries and topk of the smallest (ties: whatever topk does)"""
@@ -116,9 +111,9 @@ def probe(dev, repeats):
     # (a) three-NN interpolation: unknown = the cloud, known = the keypoints
     feat = torch.randn((BATCH * KEYPOINTS, C), device=dev).half()
     dout = torch.randn((BATCH * N_CLOUD, C), device=dev).half()
-    before = launches()
+    before = _lib.launch_counts(KEYS)
     knn = Fsp.three_nn(pts, bid, kp, keys.batch_ids, BATCH, groups=kp_groups, with_groups=True)
-    res["launches_of_three_nn_with_groups"] = {k: v - before[k] for k, v in launches().items()}
+    res["launches_of_three_nn_with_groups"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
     rows_c, d2_c = composite_knn(p3, k3, 3, 8192)
     w_c = composite_weights(d2_c)
     res["three_nn"] = dict(agreement(knn, rows_c, 3), known_per_scene=KEYPOINTS, unknown_per_scene=N_CLOUD,
@@ -139,9 +134,9 @@ def probe(dev, repeats):
         lambda: torch.autograd.grad(composite_blend(feat_g, rows_c, w_c), feat_g, dout))
 
     # (b) k = 16 grouping of the keypoints over the cloud
-    before = launches()
+    before = _lib.launch_counts(KEYS)
     nb = Fsp.knn_query(kp, keys.batch_ids, pts, bid, BATCH, K_GROUP, groups=groups)
-    res["launches_of_knn_query_k16"] = {k: v - before[k] for k, v in launches().items()}
+    res["launches_of_knn_query_k16"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
     res["knn_k16_keypoints_over_cloud"] = dict(agreement(nb, composite_knn(k3, p3, K_GROUP, 256)[0], K_GROUP),
                                                points_per_scene=N_CLOUD)
     stages["knn_k16_keypoints_over_cloud"] = (

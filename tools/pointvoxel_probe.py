@@ -64,11 +64,6 @@ def timed(fn, repeats, warmup=5):
     return {"median_us": round(statistics.median(times), 1), "min_us": round(min(times), 1)}
 
 
-def launches():
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
-
-
 class Composite:
     """the torch forms: ids int64 [N] (every point has a voxel), nv voxels"""
 
@@ -135,9 +130,9 @@ def probe(dev, repeats):
     res = {"grid": GRID, "batch": BATCH, "points": N, "voxels": nv, "C": C, "dtype": "f16"}
     comp = Composite(ids, nv, indices)
 
-    before = launches()
+    before = _lib.launch_counts(KEYS)
     g = Fsp.point_groups(ids, nv)
-    res["launches_of_one_groups_build"] = {k: v - before[k] for k, v in launches().items()}
+    res["launches_of_one_groups_build"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
     order, ends = comp.groups()
     assert torch.equal(order.int(), g.list) and torch.equal(ends.int(), g.offsets[1:])
 
@@ -149,10 +144,10 @@ def probe(dev, repeats):
     assert torch.equal(Fsp.voxels_to_points(vfeat, g), comp.gather(vfeat))
     torch.manual_seed(0)
     vfe = DynamicVFE(4, (64, 64)).to(dev).half().eval()
-    before = launches()
+    before = _lib.launch_counts(KEYS)
     with torch.no_grad():
         ref = vfe(pts, g, indices, VSIZE, RANGE)
-    res["launches_of_one_vfe_pass"] = {k: v - before[k] for k, v in launches().items()}
+    res["launches_of_one_vfe_pass"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
     with torch.no_grad():
         alt = comp.vfe(vfe, pts)
     res["vfe_max_abs_difference_from_composite"] = float((ref.float() - alt.float()).abs().max())

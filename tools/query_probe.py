@@ -70,11 +70,6 @@ def timed(fn, repeats, warmup=3):
     return {"median_us": round(statistics.median(times), 1), "min_us": round(min(times), 1)}
 
 
-def launches():
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
-
-
 class Composite:
     """the torch form: a hash table over the level's keys, one query per window cell, topk over the hit flags"""
 
@@ -165,9 +160,9 @@ def probe(dev, repeats, composite_repeats):
     x_hash = spconv.SparseConvTensor(dummy, plain_idx, GRID, BATCH)
     native = lambda x, radius, groups=False: Fsp.voxel_query(pts, bids, x, VSIZE, RANGE, QRANGE, NSAMPLE, radius,
                                                             with_groups=groups)
-    before = launches()
+    before = _lib.launch_counts(KEYS)
     nb = native(x_rank, None, True)
-    res["launches_of_query_with_groups"] = {k: v - before[k] for k, v in launches().items()}
+    res["launches_of_query_with_groups"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
     stages = {}
     for name, radius in (("no_radius", None), ("radius", RADIUS)):
         a, b = native(x_rank, radius), native(x_hash, radius)

@@ -60,11 +60,6 @@ def timed(fn, repeats, warmup=3):
     return {"median_us": round(statistics.median(times), 1), "min_us": round(min(times), 1)}
 
 
-def launches():
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
-
-
 def composite_fps(xyz, K):
     """xyz [B, n, 3] -> idx int64 [B, K] (positions inside the scene): the batched loop"""
     Bn, n, _ = xyz.shape
@@ -118,9 +113,9 @@ def probe(dev, repeats, fps_composite_repeats):
         clouds[name] = (pts, bid, n)
         groups = Fsp.scene_groups(bid, BATCH * n, BATCH)
         xyz = pts[:, :3].reshape(BATCH, n, 3).contiguous()
-        before = launches()
+        before = _lib.launch_counts(KEYS)
         s = Fsp.farthest_point_sample(pts, bid, BATCH, K, groups=groups)
-        res[f"launches_of_fps_{name}"] = {k: v - before[k] for k, v in launches().items()}
+        res[f"launches_of_fps_{name}"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
         comp = composite_fps(xyz, K) + torch.arange(BATCH, device=dev).unsqueeze(1) * n
         assert bool((s.count == K).all())
         res[f"fps_{name}"] = {"points_per_scene": n, "samples": K,
@@ -136,9 +131,9 @@ def probe(dev, repeats, fps_composite_repeats):
     feat = torch.randn((BATCH * n, C), device=dev).half()
     p3, q3 = pts[:, :3].reshape(BATCH, n, 3).contiguous(), q[:, :3].reshape(BATCH, KEYPOINTS, 3).contiguous()
     for ns in NSAMPLES:
-        before = launches()
+        before = _lib.launch_counts(KEYS)
         nb = Fsp.ball_query(q, keys.batch_ids, pts, bid, BATCH, RADIUS, ns, groups=groups)
-        res[f"launches_of_ball_query_nsample{ns}"] = {k: v - before[k] for k, v in launches().items()}
+        res[f"launches_of_ball_query_nsample{ns}"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
         rows_c, count_c = composite_ball(q3, p3, ns)
         res[f"ball_query_nsample{ns}"] = {
             "queries": BATCH * KEYPOINTS, "points_per_scene": n, "mean_count": round(float(nb.count.float().mean()), 3),

@@ -59,11 +59,6 @@ def timed(fn, repeats, warmup=5):
     return {"median_us": round(statistics.median(times), 1), "min_us": round(min(times), 1)}
 
 
-def launches():
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
-
-
 def probe(C, dev, repeats):
     idx, feat = scene(C, dev)
     n = int(idx.shape[0])
@@ -74,9 +69,9 @@ def probe(C, dev, repeats):
     x = spconv.SparseConvTensor(feat, tagged, SHAPE, BATCH)
     plain = spconv.SparseConvTensor(feat, idx, SHAPE, BATCH)
 
-    before = launches()
+    before = _lib.launch_counts(KEYS)
     kept = Fsp.sparse_prune(x, ratio=RATIO)
-    res["launches_of_one_prune"] = {key: v - before[key] for key, v in launches().items()}
+    res["launches_of_one_prune"] = {key: v - before[key] for key, v in _lib.launch_counts(KEYS).items()}
     score = _select.row_score(feat)
     keep, sel = _select.topk_flags(score, None, RATIO)
     res["sel"] = sel.cpu().tolist()

@@ -135,10 +135,10 @@ def probe(dev, repeats):
     bits = _serialize.key_bits(ndim, depth, BATCH)
     res = {"shape": SHAPE, "batch": BATCH, "rows": n, "depth": depth, "key_bits": bits, "C": C, "dtype": "f16",
            "patch_size": PATCH}
-    before = {k: L.spx_launch_count(k.encode()) for k in KEYS}
+    before = _lib.launch_counts(KEYS)
     ser = Fsp.serialize(idx, SHAPE, BATCH)
     plan = Fsp.patch_plan(ser, PATCH)
-    res["launches_of_serialize_and_plan"] = {k: L.spx_launch_count(k.encode()) - before[k] for k in KEYS}
+    res["launches_of_serialize_and_plan"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()}
     want = keys_torch(idx, depth, ORDERS)
     res["codes_equal_the_composite"] = bool(torch.equal(ser.code, want))
     c_order, c_inverse, c_offsets = sort_torch(want, BATCH)

@@ -55,11 +55,6 @@ def timed(fn, repeats, warmup=5):
     return {"median_us": round(statistics.median(times), 1), "min_us": round(min(times), 1)}
 
 
-def launches():
-    L = _lib.load()
-    return {k: L.spx_launch_count(k.encode()) for k in KEYS}
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -89,10 +84,10 @@ def main():
     if native:
         forms["composite"] = lambda t: Fsp._sparse_add_hash_composite(*t)
     gout = torch.randn((2 * ROWS, C), device=dev).half()
-    before = launches()
+    before = _lib.launch_counts(KEYS)
     first = module(tensors(False))
     res["union_rows"] = int(first.features.shape[0])
-    res["launches_of_one_forward"] = {k: v - before[k] for k, v in launches().items()} if native else "composite"
+    res["launches_of_one_forward"] = {k: v - before[k] for k, v in _lib.launch_counts(KEYS).items()} if native else "composite"
     for rnd in range(2):                                                 # alternate the forms: two rounds each
         for name, fn in forms.items():
             res[f"{name}_fwd_round{rnd}"] = timed(run(fn, False), args.repeats)
