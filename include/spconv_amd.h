@@ -1517,7 +1517,8 @@ int spx_patch_rows_bwd(const void *g, int slots, const int32_t *row_slot, const 
  *   for arguments that are refused.  The workspace may be handed over dirty; ws must be 256-byte aligned.
  *   Measurement only: the option SPX_TEST_NMS_STAGES = 1 | 2 | 3 (spx_set_option) ends the call behind its key / sort /
  *   mask step and leaves keep and count unwritten (tools/box_probe.py times the prefixes against each other).
- * Not here: gradients, the axis-aligned nms_normal_gpu, points_in_boxes, more than 16384 candidates per scene. */
+ * Not here: gradients, the axis-aligned nms_normal_gpu, more than 16384 candidates per scene (points in boxes: the
+ * next section). */
 #define SPX_BOX_OVERLAP_BEV 0
 #define SPX_BOX_IOU_BEV 1
 #define SPX_BOX_IOU_3D 2
@@ -1534,6 +1535,87 @@ int spx_nms_rotated(const float *bev, const float *scores, const int32_t *batch_
                     const int32_t *n_boxes_dev, int batch, float thresh, int use_score_thresh, float score_thresh,
                     int pre_max, int post_max, int32_t *keep, int32_t *count, void *ws, size_t ws_bytes,
                     spx_stream_t stream);
+
+/* ---- points in rotated boxes: frames, the point-major and the box-major query (csrc/roi.hip) --------------------
+ * The geometric test of the roiaware_pool3d / roipoint_pool3d extensions of OpenPCDet / mmdet3d: points_in_boxes_gpu
+ * (foreground labels of keypoints and points, ground-truth sampling, "drop boxes with fewer than k points"), the
+ * point stage of roipoint_pool3d (PointRCNN's second stage) and the point-to-cell stage of roiaware_pool3d (Part-A2's).
+ * The pooling itself is spx_group_fwd / spx_group_bwd over rows and spx_collapse_fwd / spx_collapse_bwd over the
+ * spx_point_groups of cells.  Every call: the caller allocates, every grid depends on host-known sizes only
+ * (hipGraph-safe), nothing is read back, nothing synchronises, no atomics (identical run to run), and the argument
+ * checks that need no pointer come before any pointer is looked at.  Every fp32 operation is rounded on its own, in
+ * the order written (no FMA; the divide correctly rounded), so a host loop reproduces every output bit for bit from
+ * the same frames (tests/refroi.py).  No gradient of any kind.  No launch counter.
+ *
+ * FRAMES.  spx_boxes_to_frames: boxes fp32 [n, nfeat >= 7] = (x, y, z, dx, dy, dz, heading), z the centre; n_boxes_dev
+ * NULL or a device int32; ex, ey, ez host floats, finite and >= 0 (OpenPCDet's pool_extra_width / enlarge_box3d).
+ * frames fp32 [n, 8] = (x, y, z, hx, hy, hz, c, s), 16-byte aligned: hx = dx * 0.5f + ex, hy = dy * 0.5f + ey, hz = dz
+ * * 0.5f + ez, c = cosf(heading), s = sinf(heading).  A box is VALID by the rule of spx_boxes_to_corners: it lies
+ * below min(*n_boxes, n), its seven numbers are finite and dx, dy, dz > 0 (before enlargement); an invalid box gets
+ * eight NaNs.  One launch, one lane per box (none for n = 0), every element written.  A frame table may as well be
+ * the caller's own.
+ *
+ * THE TEST of a point (px, py, pz), whose three coordinates must be finite, against a frame:
+ *   sx = px - x;  sy = py - y;  lz = pz - z;  lx = sx * c + sy * s;  ly = sy * c - sx * s
+ *   inside = |lz| <= hz && lx > -hx && lx < hx && ly > -hy && ly < hy
+ * OpenPCDet's check_pt_in_box3d: inclusive in z, strict in the plane.  A frame with a NaN fails every comparison: an
+ * invalid box contains nothing.
+ *
+ * POINT MAJOR.  spx_points_in_boxes: points fp32 [n_cap, nfeat >= 3] (x, y, z first), p_batch_ids int32 [n_cap] or
+ * NULL (all scene 0), n_points_dev NULL or a device int32; frames [m_cap, 8]; box_offsets int32 [batch + 1] /
+ * box_list int32 [m_cap]: the scene list over the BOX batch ids (spx_point_groups: scene b = box_list[box_offsets[b]
+ * : box_offsets[b + 1]] in ascending box index; boxes at or beyond a device count and boxes with a foreign batch id
+ * are in no scene).  out int32 [n_cap]: for every point the LOWEST box index of its own scene whose frame contains
+ * it; -1 for no box, for a point with a coordinate that is not finite, at or beyond *n_points, or with a batch id
+ * outside [0, batch).  Every element is written.  One lane per point, workgroups of 256 consecutive points that walk
+ * the scenes of their points in ascending order (points may arrive in any scene order) and stage the frames of a
+ * scene's boxes in LDS, spx_points_in_boxes_tile() = 128 at a time, read back as broadcasts; a lane that has its box
+ * stops testing, a scene's remaining tiles are skipped once every lane of the workgroup is done.  One launch; n_cap =
+ * 0 does nothing, m_cap = 0 runs no walk: one fill writes -1.
+ *
+ * BOX MAJOR.  spx_box_query: frames [m_cap, 8], b_batch_ids int32 [m_cap] or NULL, n_boxes_dev NULL or a device
+ * int32; points as above with offsets int32 [batch + 1] / list int32 [n_cap], the scene list over the POINT batch ids
+ * (points at or beyond a device count are not in it).  nsample in 1 .. spx_box_query_max_nsample() = 16384, m_cap *
+ * nsample < 2^31.  Per box m, over the points of its scene in ASCENDING POINT INDEX:
+ *     rows   int32 [m_cap, nsample]      the first nsample points inside it
+ *     count  int32 [m_cap]               min(hits, nsample)
+ *     hits   int32 [m_cap]               all points inside it, uncapped
+ *     local  fp32 [m_cap, nsample, 3]    (lx, ly, lz) of each kept point: PointRCNN's canonical transform; or NULL
+ *     cells  int32 [m_cap, nsample]      with a grid (ox, oy, oz), each in 1 .. 64 -- (0, 0, 0): none, cells NULL --
+ *                                        wx = (hx + hx) / float(ox), ix = min(max(int((lx + hx) / wx), 0), ox - 1),
+ *                                        likewise iy and iz, and the entry is the GLOBAL cell id m * (ox * oy * oz) +
+ *                                        (ix * oy + iy) * oz + iz; needs m_cap * ox * oy * oz < 2^31
+ * Slots at or beyond count hold -1 in rows and cells and 0 in local; with flags = SPX_ROI_PAD_FIRST and count > 0 they
+ * repeat slot 0, with SPX_ROI_PAD_CYCLE and count > 0 slot s holds slot s % count (roipoint_pool3d).  A box that is
+ * invalid (a NaN frame), at or beyond *n_boxes or with a batch id outside [0, batch) has count = hits = 0.  Every
+ * element of every table given is written.  A box per wave, spx_box_query_waves() = 4 boxes per workgroup: the 64
+ * lanes test consecutive entries of the scene's list, a ballot and the popcount of the lanes below give each hit its
+ * slot, slots go straight to global memory (no per-lane lists, no scratch); the walk does not stop at nsample because
+ * hits is the total.  With a pad flag a second launch, one lane per slot, writes the padded slots: it reads what other
+ * lanes of the first launch stored, and the end of a kernel orders that.  Brute force per scene, no spatial index.
+ * m_cap = 0 does nothing; n_cap = 0 runs no walk: one fill writes -1 / 0.
+ *
+ * WHAT THE KERNELS MAY BE HANDED.  Every output in any state (each element is written, none is read before it is
+ * written); boxes, frames and points with NaN / Inf anywhere (an invalid box or point, as above -- never a fault,
+ * never a hit); batch ids of any value; rows of boxes, points and ids at or beyond the device counts in any state
+ * (unnamed rows are not read by the queries: the lists do not name them, and the frames kernel reads no box at or
+ * beyond *n_boxes); offsets and list entries are clamped / checked, not trusted.
+ * Not here: a fused RoI-aware kernel, a cap per cell, the points_in_boxes_all matrix, gradients, a spatial index. */
+#define SPX_ROI_PAD_NONE 0
+#define SPX_ROI_PAD_FIRST 2
+#define SPX_ROI_PAD_CYCLE 4
+int spx_box_query_max_nsample(void);
+int spx_box_query_waves(void);
+int spx_points_in_boxes_tile(void);
+int spx_boxes_to_frames(const float *boxes, int nfeat, int n, const int32_t *n_boxes_dev, float ex, float ey, float ez,
+                        float *frames, spx_stream_t stream);
+int spx_points_in_boxes(const float *points, int nfeat, const int32_t *p_batch_ids, int n_cap, const int32_t *n_points_dev,
+                        const float *frames, int m_cap, const int32_t *box_offsets, const int32_t *box_list, int batch,
+                        int32_t *out, spx_stream_t stream);
+int spx_box_query(const float *frames, const int32_t *b_batch_ids, int m_cap, const int32_t *n_boxes_dev,
+                  const float *points, int nfeat, int n_cap, const int32_t *offsets, const int32_t *list, int batch,
+                  int nsample, int flags, int ox, int oy, int oz, int32_t *rows, int32_t *count, int32_t *hits,
+                  float *local, int32_t *cells, spx_stream_t stream);
 
 #ifdef __cplusplus
 }

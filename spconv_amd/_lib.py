@@ -236,6 +236,15 @@ SIGNATURES = {
     "spx_nms_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "spx_nms_rotated": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                        ctypes.c_float, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]),
+    "spx_box_query_max_nsample": (ctypes.c_int, []),
+    "spx_box_query_waves": (ctypes.c_int, []),
+    "spx_points_in_boxes_tile": (ctypes.c_int, []),
+    "spx_boxes_to_frames": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_float, ctypes.c_float,
+                                           ctypes.c_float, vp, vp]),
+    "spx_points_in_boxes": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int,
+                                           vp, vp]),
+    "spx_box_query": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int]
+                      + [ctypes.c_int] * 5 + [vp] * 6),
 }
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_I8, DTYPE_F64 = 0, 1, 2, 3, 4

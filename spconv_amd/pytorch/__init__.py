@@ -14,6 +14,7 @@ from spconv_amd.pytorch.spatial import SparseCollapse, SparsePrune, TrilinearDev
 from spconv_amd.pytorch.spatial import BallQueryAndGroup, FarthestPointSample
 from spconv_amd.pytorch.spatial import KNNInterpolate, KNNQueryAndGroup
 from spconv_amd.pytorch.spatial import RotatedNMS
+from spconv_amd.pytorch.spatial import RoIAwarePool3d, RoIPointPool3d
 from spconv_amd.pytorch.vfe import DynamicVFE
 from spconv_amd.pytorch.functional import point_groups, points_to_voxels, voxels_to_points
 from spconv_amd.pytorch.functional import point_corners, voxels_to_points_trilinear
@@ -22,6 +23,8 @@ from spconv_amd.pytorch.functional import ball_query, farthest_point_sample, gat
 from spconv_amd.pytorch.functional import knn_interpolate, knn_query, three_nn
 from spconv_amd.pytorch.functional import (boxes_iou3d, boxes_iou3d_aligned, boxes_iou_bev, boxes_overlap_bev,
                                            boxes_to_corners, nms_rotated)
+from spconv_amd.pytorch.functional import (box_query, boxes_to_frames, points_in_boxes, roi_aware_pool,
+                                           roi_point_pool)
 from spconv_amd.pytorch.tables import AddTable, AddTableMisaligned, ConcatTable, JoinTable
 from spconv_amd.pytorch.pool import (SparseAvgPool1d, SparseAvgPool2d, SparseAvgPool3d,
                                      SparseGlobalAvgPool, SparseGlobalMaxPool, SparseMaxPool1d,

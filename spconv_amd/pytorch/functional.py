@@ -613,6 +613,12 @@ from spconv_amd.pytorch._box import (BoxCorners, BoxNMS, boxes_iou3d, boxes_iou3
                                      boxes_iou_bev, boxes_overlap_bev, boxes_to_corners, nms_rotated,
                                      nms_rotated_into, nms_ws_bytes)
 
+# points in rotated boxes (csrc/roi.hip; not part of the reference): the frames of boxes, the box of every point, the
+# points of every box, and RoI point / RoI-aware pooling composed from them with group_voxels, point_groups and
+# points_to_voxels -- the roiaware_pool3d / roipoint_pool3d extensions of OpenPCDet / mmdet3d
+from spconv_amd.pytorch._roi import (BoxFrames, BoxPoints, box_query, box_query_into,  # noqa: E402,F401
+                                     boxes_to_frames, points_in_boxes, roi_aware_pool, roi_point_pool)
+
 # voxel serialisation (csrc/serialize.hip; not part of the reference): rows ordered along Z-order / Hilbert curves and
 # cut into fixed-size patches, for the serialised point / voxel transformers
 from spconv_amd.pytorch import _serialize  # noqa: E402

@@ -4,7 +4,8 @@ from a 3-D backbone to a sparse 2-D head on the kernels of csrc/collapse.hip; ``
 query points, gathered (csrc/query.hip); ``FarthestPointSample`` / ``BallQueryAndGroup``: keypoints of a raw cloud and the
 raw points around query points, gathered (csrc/sample.hip); ``KNNInterpolate`` / ``KNNQueryAndGroup``: features carried
 to many points from their nearest few, and the nearest raw points of query points, gathered (csrc/knn.hip);
-``RotatedNMS``: rotated non-maximum suppression that stays on the device (csrc/box.hip)."""
+``RotatedNMS``: rotated non-maximum suppression that stays on the device (csrc/box.hip); ``RoIPointPool3d`` /
+``RoIAwarePool3d``: the points of every RoI, gathered or reduced per cell of a grid over the box (csrc/roi.hip)."""
 from typing import Optional, Sequence
 
 import torch
@@ -352,3 +353,65 @@ class RotatedNMS(torch.nn.Module):
     def extra_repr(self) -> str:
         return (f"thresh={self.thresh}, pre_max={self.pre_max}, post_max={self.post_max}, "
                 f"score_thresh={self.score_thresh}")
+
+
+class RoIPointPool3d(torch.nn.Module):
+    """The points of every RoI with their features, a fixed number per box (``functional.roi_point_pool``: the kernels
+    of csrc/roi.hip and csrc/query.hip): the ``roipoint_pool3d`` of PointRCNN's second stage.  Not part of the
+    reference.
+
+    ``num_sampled_points`` (1 .. 16384) slots per box; ``pool_extra_width`` (a float or a 3-tuple, >= 0) enlarges every
+    box per side.  ``forward(points, p_batch_ids, feats, boxes, b_batch_ids, batch_size) -> (pooled [M, S, 3 + C],
+    empty int32 [M])``: points fp32 [N, >= 3], feats [N, C], boxes fp32 [M, >= 7] = (x, y, z, dx, dy, dz, heading),
+    batch ids int32 or None.  The first S points inside a box in ascending point index, repeated cyclically when there
+    are fewer; a box without a point is zeros with empty = 1.  The gradient goes to feats only, added in a fixed order
+    without atomics; there is no gradient with respect to coordinates or boxes."""
+
+    def __init__(self, num_sampled_points: int = 512, pool_extra_width=0.):
+        super().__init__()
+        from spconv_amd.pytorch import _roi
+        self.num_sampled_points = _roi._check_nsample("RoIPointPool3d", num_sampled_points, 1)
+        self.pool_extra_width = _roi._extra("RoIPointPool3d", pool_extra_width)
+
+    def forward(self, points: torch.Tensor, p_batch_ids: Optional[torch.Tensor], feats: torch.Tensor, boxes: torch.Tensor,
+                b_batch_ids: Optional[torch.Tensor], batch_size: int, n_points: Optional[torch.Tensor] = None,
+                n_boxes: Optional[torch.Tensor] = None, groups=None):
+        from spconv_amd.pytorch import functional as F
+        return F.roi_point_pool(points, p_batch_ids, feats, boxes, b_batch_ids, batch_size, self.num_sampled_points,
+                                self.pool_extra_width, n_points=n_points, n_boxes=n_boxes, groups=groups)
+
+    def extra_repr(self) -> str:
+        return f"num_sampled_points={self.num_sampled_points}, pool_extra_width={self.pool_extra_width}"
+
+
+class RoIAwarePool3d(torch.nn.Module):
+    """The features of the points of every RoI reduced per cell of a grid over the box (``functional.roi_aware_pool``:
+    the kernels of csrc/roi.hip, csrc/query.hip, csrc/pointvoxel.hip and csrc/collapse.hip): the ``roiaware_pool3d``
+    of Part-A2's second stage.  Not part of the reference.
+
+    ``out_size`` (an int or three ints in 1 .. 64) cells per box; ``max_pts_per_box`` (1 .. 16384): the first so many
+    points of a box in ascending point index take part (OpenPCDet caps 128 per cell instead); ``reduce``: "max" or
+    "mean".  ``forward(points, p_batch_ids, feats, boxes, b_batch_ids, batch_size) -> [M, ox, oy, oz, C]``, zeros in an
+    empty cell.  The gradient goes to feats only, in a fixed order without atomics (a max tie: to every point that
+    attains it); there is no gradient with respect to coordinates or boxes."""
+
+    def __init__(self, out_size, max_pts_per_box: int = 2048, reduce: str = "max"):
+        super().__init__()
+        from spconv_amd.pytorch import _roi
+        if out_size is None:
+            raise ValueError("RoIAwarePool3d: the grid is an int or three ints in 1 .. 64, got None")
+        self.out_size = _roi._check_grid("RoIAwarePool3d", out_size, 1)
+        self.max_pts_per_box = _roi._check_nsample("RoIAwarePool3d", max_pts_per_box, 1)
+        if reduce not in ("max", "mean"):
+            raise ValueError(f"RoIAwarePool3d: reduce must be 'max' or 'mean', got {reduce!r}")
+        self.reduce = reduce
+
+    def forward(self, points: torch.Tensor, p_batch_ids: Optional[torch.Tensor], feats: torch.Tensor, boxes: torch.Tensor,
+                b_batch_ids: Optional[torch.Tensor], batch_size: int, n_points: Optional[torch.Tensor] = None,
+                n_boxes: Optional[torch.Tensor] = None, groups=None):
+        from spconv_amd.pytorch import functional as F
+        return F.roi_aware_pool(points, p_batch_ids, feats, boxes, b_batch_ids, batch_size, self.out_size,
+                                self.max_pts_per_box, self.reduce, n_points=n_points, n_boxes=n_boxes, groups=groups)
+
+    def extra_repr(self) -> str:
+        return f"out_size={self.out_size}, max_pts_per_box={self.max_pts_per_box}, reduce={self.reduce}"
