@@ -1,5 +1,5 @@
-"""CPU: the C-ABI library loads and exports every symbol include/spconv_amd.h declares;
-host-only entry points behave (no kernel is launched in this file)."""
+"""CPU: the C-ABI library loads and exports every symbol include/spconv_amd.h declares, and the binding is that header
+read by _lib.parse_header; host-only entry points behave (no kernel is launched in this file)."""
 import ctypes
 import os
 import re
@@ -7,15 +7,10 @@ import subprocess
 
 import pytest
 
+import capi
 from spconv_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared():
-    text = open(os.path.join(ROOT, "include", "spconv_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(spx_[a-z0-9_]+)\s*\(", text)))
 
 
 @pytest.fixture(scope="module")
@@ -26,16 +21,74 @@ def lib():
 
 
 def test_header_and_binding_agree():
-    assert _declared() == sorted(_lib.SIGNATURES)
+    """Every declaration of the header parses (parse_header raises for one that does not), and the binding holds exactly
+    the names the header puts before a `(`."""
+    assert capi.declared() == sorted(_lib.parse_header(capi.HEADER)) == sorted(_lib.signatures())
+    assert len(capi.declared()) >= 138
 
 
 def test_every_declared_symbol_is_exported(lib):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    missing = [s for s in _declared() if s not in exported]
+    missing = [s for s in capi.declared() if s not in capi.exported()]
     assert not missing, missing
-    for s in _declared():
+    for s in capi.declared():
         assert getattr(lib, s) is not None
+
+
+def test_parser_against_signatures_written_out_by_hand():
+    """One declaration at least for every branch of the mapping, each list as the hand-kept table bound it: size_t /
+    const char * / long long returned, (void), double / float / long long / const char * arguments, a host `const int *`,
+    device `const int32_t *`, `const void *`, pointers to pointers and spx_stream_t."""
+    c_int, c_size_t, c_longlong, c_float, vp, ip = (ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_float,
+                                                    ctypes.c_void_p, _lib.c_int_p)
+    want = {
+        "spx_last_error": (ctypes.c_char_p, []),
+        "spx_launch_count": (c_longlong, [ctypes.c_char_p]),
+        "spx_knn_max_k": (c_int, []),
+        "spx_topk_flags": (c_int, [vp, vp, c_int, vp, c_int, c_int, c_int, ctypes.c_double, vp, vp, vp, c_size_t, vp]),
+        "spx_pad_rows": (c_int, [vp, vp, c_longlong, c_int, c_int, vp]),
+        "spx_conv_out_shape": (c_int, [c_int] + [ip] * 6 + [c_int, ip]),
+        "spx_boxes_to_frames": (c_int, [vp, c_int, c_int, vp, c_float, c_float, c_float, vp, vp]),
+        "spx_box_query": (c_int, [vp, vp, c_int, vp, vp, c_int, c_int, vp, vp, c_int] + [c_int] * 5 + [vp] * 6),
+        "spx_union_ws_bytes": (c_size_t, [c_int, c_int, ip, c_int, c_longlong]),
+        "spx_union_add_bwd": (c_int, [vp, c_int, vp, vp, ip, c_int, c_int, c_int, vp]),
+    }
+    got = _lib.signatures()
+    for name, sig in want.items():
+        assert got[name] == sig, name
+    assert _lib.parse_header("/* spx_gone(int n); */\nconst int *spx_a(const void *const *p_h, // spx_b(\n long long n);") \
+        == {"spx_a": (ip, [vp, c_longlong])}
+    assert _lib.signatures() is got                               # parsed once
+
+
+@pytest.mark.parametrize("text, word", [
+    ("int spx_f(int n, unsigned m);", "argument 2"),              # a type the mapping does not know: never bound as int
+    ("int spx_f(int32_t n);", "int32_t"),
+    ("int spx_f(long n);", "'long'"),
+    ("char spx_f(void);", "return type"),
+    ("int spx_f(int);", "spx_f"),                                 # no name: the type would be read as one
+    ("int spx_f(int n,);", "spx_f"),
+    ("int spx_ok(void);\nint spx_f(int n, float x", "spx_f"),    # half-formed: no `);`
+    ("int spx_f(int n)\nint spx_ok(void);", "spx_f"),             # no `;`
+    ("int spx_f(int (*cb)(int), int n);", "spx_f"),
+    ("#define SPX_CALL spx_f(3)", "spx_f"),
+], ids=["unsigned", "int32_t-scalar", "long", "char-returned", "no-name", "empty-argument", "no-closing-paren",
+        "no-semicolon", "function-pointer", "macro"])
+def test_parser_refuses_what_it_cannot_read(text, word):
+    with pytest.raises(ValueError, match=re.escape(word)):
+        _lib.parse_header(text)
+
+
+def test_the_header_is_not_read_at_import():
+    import sys
+    code = ("import builtins, sys; real = builtins.open\n"
+            "def spy(f, *a, **k):\n"
+            "    assert not str(f).endswith('spconv_amd.h'), 'header read at import'\n"
+            "    return real(f, *a, **k)\n"
+            "builtins.open = spy\n"
+            "import spconv_amd, spconv_amd._lib as L\n"
+            "assert L.signatures.cache_info().currsize == 0\n"
+            "builtins.open = real; assert len(L.signatures()) >= 138 and L.signatures.cache_info().currsize == 1")
+    subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
 
 
 def test_no_torch_or_oracle_dependency():

@@ -25,7 +25,7 @@ def test_collapse_unit_is_linked():
     assert "collapse" in units
     L = _lib.load()
     for name in NAMES:
-        assert name in _lib.SIGNATURES and getattr(L, name) is not None
+        assert getattr(L, name) is not None
 
 
 @pytest.mark.parametrize("batch,shape,axes,fits", [

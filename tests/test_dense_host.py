@@ -24,7 +24,6 @@ def test_entries_are_declared_bound_and_built(lib):
     header = open(os.path.join(ROOT, "include", "spconv_amd.h")).read()
     for name in ENTRIES:
         assert re.search(r"\b%s\s*\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
         assert getattr(lib, name) is not None
     units = {os.path.splitext(os.path.basename(o))[0] for o in _lib.linked_objects()}
     assert "dense" in units

@@ -1,55 +1,17 @@
-"""CPU: the k-nearest-neighbour entry points (csrc/knn.hip) are declared, exported and bound with the declared
-signatures; their argument checks come before any pointer is looked at (no kernel is launched in this file); the Python
-layer has the new names and refuses bad arguments."""
-import ctypes
+"""CPU: the argument checks of the k-nearest-neighbour entry points (csrc/knn.hip) come before any pointer is looked at
+(no kernel is launched in this file); the Python layer has the new names and refuses bad arguments.  (Declared,
+exported and bound as declared: test_capi.py, for the whole header.)"""
 import inspect
-import os
-import re
-import subprocess
 
 import pytest
 
+from capi import fails as _fails
 from spconv_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("spx_knn_max_k", "spx_knn_query")
-C_TYPES = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "spx_stream_t": ctypes.c_void_p}
-
-
-def _declaration(name):
-    text = open(os.path.join(ROOT, "include", "spconv_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"(\w[\w ]*?)\s*\b%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, name
-    args = [" ".join(a.split()) for a in m.group(2).split(",")]
-    return m.group(1).strip(), [] if args == ["void"] else args
-
-
-@pytest.mark.parametrize("name", NAMES)
-def test_declared_exported_and_bound_with_the_declared_signature(name):
-    ret, args = _declaration(name)
-    restype, argtypes = _lib.SIGNATURES[name]
-    assert restype is C_TYPES[ret]
-    assert len(argtypes) == len(args), (args, argtypes)
-    for arg, bound in zip(args, argtypes):          # (every pointer of this unit is a device pointer: void *)
-        assert bound is (ctypes.c_void_p if "*" in arg else C_TYPES[" ".join(arg.split()[:-1])]), (arg, bound)
-    assert getattr(_lib.load(), name) is not None
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)
-    assert any(line.split()[-1] == name and " T " in line for line in out.splitlines()), name
-
-
-def test_knn_unit_is_in_the_one_list_of_translation_units():
-    assert "knn.o" in {os.path.basename(o) for o in _lib.linked_objects()}
 
 
 def test_max_k():
     from spconv_amd.pytorch import _knn
     assert _lib.load().spx_knn_max_k() == 64 == _knn.MAX_K == _knn.max_k()
-
-
-def _fails(rc, word):
-    assert rc != 0
-    assert word in _lib.load().spx_last_error().decode(), _lib.load().spx_last_error()
 
 
 def test_argument_checks_need_no_pointer():

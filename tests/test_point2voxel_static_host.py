@@ -17,7 +17,6 @@ def test_entry_points_are_declared_exported_and_bound():
     L = _lib.load()
     for name in NAMES:
         assert name + "(" in header, name
-        assert name in _lib.SIGNATURES, name
         assert getattr(L, name) is not None, name
 
 

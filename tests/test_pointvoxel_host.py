@@ -1,44 +1,13 @@
-"""CPU: the point <-> voxel entry points (csrc/pointvoxel.hip) are declared, exported and bound with the declared
-signatures; their argument checks come before any pointer is looked at (no kernel is launched in this file); the
-Python layer has the new names."""
+"""CPU: the argument checks of the point <-> voxel entry points (csrc/pointvoxel.hip) come before any pointer is looked
+at (no kernel is launched in this file); the Python layer has the new names.  (Declared, exported and bound as
+declared: test_capi.py, for the whole header.)"""
 import ctypes
 import inspect
-import os
-import re
 
 import pytest
 
+from capi import fails as _fails
 from spconv_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("spx_point_groups_ws_bytes", "spx_point_groups", "spx_voxel_to_point", "spx_point_decorate")
-C_TYPES = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "long long": ctypes.c_longlong, "spx_stream_t": ctypes.c_void_p}
-
-
-def _declaration(name):
-    text = open(os.path.join(ROOT, "include", "spconv_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"(\w[\w ]*?)\s*\b%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, name
-    return m.group(1).strip(), [a.strip() for a in m.group(2).split(",")]
-
-
-def _ctypes_of(arg):
-    """what an argument may be bound as: a device pointer travels as void *, a host float array as float *"""
-    if "*" in arg:
-        return (ctypes.c_void_p, _lib.c_float_p) if arg.startswith("const float *") else (ctypes.c_void_p,)
-    return (C_TYPES[" ".join(arg.split()[:-1])],)
-
-
-@pytest.mark.parametrize("name", NAMES)
-def test_declared_exported_and_bound_with_the_declared_signature(name):
-    ret, args = _declaration(name)
-    restype, argtypes = _lib.SIGNATURES[name]
-    assert restype is C_TYPES[ret]
-    assert len(argtypes) == len(args), (args, argtypes)
-    for arg, bound in zip(args, argtypes):
-        assert bound in _ctypes_of(arg), (arg, bound)
-    assert getattr(_lib.load(), name) is not None
 
 
 def test_ws_bytes_is_monotone_and_rejects_bad_sizes():
@@ -53,11 +22,6 @@ def test_ws_bytes_is_monotone_and_rejects_bad_sizes():
     for n in ns:
         sizes = [L.spx_point_groups_ws_bytes(n, v) for v in vs]
         assert sizes == sorted(sizes) and sizes[0] > 0, (n, sizes)
-
-
-def _fails(rc, word):
-    assert rc != 0
-    assert word in _lib.load().spx_last_error().decode(), _lib.load().spx_last_error()
 
 
 def test_argument_checks_need_no_pointer():

@@ -1,56 +1,13 @@
-"""CPU: the voxel-query entry points (csrc/query.hip) are declared, exported and bound with the declared signatures;
-their argument checks come before any pointer is looked at (no kernel is launched in this file); the Python layer has
-the new names and refuses bad arguments."""
+"""CPU: the argument checks of the voxel-query entry points (csrc/query.hip) come before any pointer is looked at (no
+kernel is launched in this file); the Python layer has the new names and refuses bad arguments.  (Declared, exported
+and bound as declared: test_capi.py, for the whole header.)"""
 import ctypes
 import inspect
-import os
-import re
-import subprocess
 
 import pytest
 
+from capi import fails as _fails
 from spconv_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("spx_voxel_query_ws_bytes", "spx_voxel_query", "spx_group_fwd", "spx_group_bwd")
-C_TYPES = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "long long": ctypes.c_longlong, "float": ctypes.c_float,
-           "spx_stream_t": ctypes.c_void_p}
-
-
-def _declaration(name):
-    text = open(os.path.join(ROOT, "include", "spconv_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"(\w[\w ]*?)\s*\b%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, name
-    return m.group(1).strip(), [" ".join(a.split()) for a in m.group(2).split(",")]
-
-
-def _ctypes_of(arg):
-    """what an argument may be bound as: a device pointer travels as void *, a host array as a typed pointer"""
-    if "*" in arg:
-        if arg.startswith("const float *v") or arg.startswith("const float *coors"):
-            return (_lib.c_float_p,)                # host arrays
-        if arg.startswith("const int *"):
-            return (_lib.c_int_p,)
-        return (ctypes.c_void_p,)
-    return (C_TYPES[" ".join(arg.split()[:-1])],)
-
-
-@pytest.mark.parametrize("name", NAMES)
-def test_declared_exported_and_bound_with_the_declared_signature(name):
-    ret, args = _declaration(name)
-    restype, argtypes = _lib.SIGNATURES[name]
-    assert restype is C_TYPES[ret]
-    assert len(argtypes) == len(args), (args, argtypes)
-    for arg, bound in zip(args, argtypes):
-        assert bound in _ctypes_of(arg), (arg, bound)
-    assert getattr(_lib.load(), name) is not None
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)
-    assert any(line.split()[-1] == name and " T " in line for line in out.splitlines()), name
-
-
-def test_query_unit_is_in_the_one_list_of_translation_units():
-    assert "query.o" in {os.path.basename(o) for o in _lib.linked_objects()}
 
 
 def test_ws_bytes_is_zero_for_the_ranked_form_and_grows_with_n():
@@ -65,11 +22,6 @@ def test_ws_bytes_is_zero_for_the_ranked_form_and_grows_with_n():
     assert ws(-1, 16, 3, 10, 0) == 0 and ws(10, 16, 3, -1, 0) == 0 and ws(10, 16, 3, (1 << 30) + 1, 0) == 0
     assert ws(10, 0, 3, 10, 0) == 0 and ws(10, 129, 3, 10, 0) == 0
     assert ws(1 << 24, 128, 3, 10, 0) == 0 and ws((1 << 24) - 1, 128, 3, 10, 0) > 0      # n_cap * nsample >= 2^31
-
-
-def _fails(rc, word):
-    assert rc != 0
-    assert word in _lib.load().spx_last_error().decode(), _lib.load().spx_last_error()
 
 
 def test_argument_checks_need_no_pointer():

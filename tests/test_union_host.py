@@ -11,9 +11,6 @@ from spconv_amd import _lib
 def test_union_unit_is_linked():
     units = {os.path.splitext(os.path.basename(o))[0] for o in _lib.linked_objects()}
     assert "union" in units
-    for name in ("spx_union_ws_bytes", "spx_union_count", "spx_union_fill", "spx_union_static", "spx_union_add_fwd",
-                 "spx_union_add_bwd"):
-        assert name in _lib.SIGNATURES
 
 
 @pytest.mark.parametrize("batch,shape,fits", [
