@@ -1455,7 +1455,8 @@ int spx_patch_rows_bwd(const void *g, int slots, const int32_t *row_slot, const 
  * caller allocates, every grid depends on host-known sizes only (hipGraph-safe), nothing is read back, nothing
  * synchronises, and the argument checks that need no pointer come before any pointer is looked at.  Every fp32
  * operation is rounded on its own (no FMA; the divide correctly rounded), so a host loop reproduces every output bit
- * for bit from the same corners (tests/refbox.py).  No gradient of any kind.
+ * for bit from the same corners (tests/refbox.py).  No entry of this section has a gradient; aligned pairs have one
+ * in the next section.
  *
  * CORNERS.  spx_boxes_to_corners: boxes fp32 [n, nfeat >= 7] = (x, y, z, dx, dy, dz, heading), z the centre;
  * n_boxes_dev NULL or a device int32.  bev fp32 [n, 4, 2], zrange fp32 [n, 2].  With c = cosf(heading), s =
@@ -1517,8 +1518,8 @@ int spx_patch_rows_bwd(const void *g, int slots, const int32_t *row_slot, const 
  *   for arguments that are refused.  The workspace may be handed over dirty; ws must be 256-byte aligned.
  *   Measurement only: the option SPX_TEST_NMS_STAGES = 1 | 2 | 3 (spx_set_option) ends the call behind its key / sort /
  *   mask step and leaves keep and count unwritten (tools/box_probe.py times the prefixes against each other).
- * Not here: gradients, the axis-aligned nms_normal_gpu, more than 16384 candidates per scene (points in boxes: the
- * next section). */
+ * Not here: the axis-aligned nms_normal_gpu, more than 16384 candidates per scene (gradients of aligned pairs: the
+ * next section; points in boxes: the one after it). */
 #define SPX_BOX_OVERLAP_BEV 0
 #define SPX_BOX_IOU_BEV 1
 #define SPX_BOX_IOU_3D 2
@@ -1535,6 +1536,67 @@ int spx_nms_rotated(const float *bev, const float *scores, const int32_t *batch_
                     const int32_t *n_boxes_dev, int batch, float thresh, int use_score_thresh, float score_thresh,
                     int pre_max, int post_max, int32_t *keep, int32_t *count, void *ws, size_t ws_bytes,
                     spx_stream_t stream);
+
+/* ---- differentiable rotated IoU: value and gradients of aligned pairs, the corners backward (csrc/boxgrad.hip) ----
+ * What a rotated-IoU regression loss trains through: mmcv's diff_iou_rotated_3d under mmdet3d's RotatedIoU3DLoss, the
+ * IoU-aware heads, the IoU-guided second stages.  Two launches, the rules of the section above: the caller allocates,
+ * host-sized grids, nothing read back, no launch counter.  Every fp32 operation is rounded on its own (no FMA, the
+ * divide correctly rounded): tests/refboxgrad.py reproduces every output bit for bit from the same corners.
+ *
+ * PAIRS.  spx_boxes_iou_aligned_grad over two corner tables of n boxes each (bev [n, 4, 2], zrange [n, 2] or NULL in the
+ * plane, device counts or NULL), mode SPX_BOX_IOU_BEV or SPX_BOX_IOU_3D, penalty SPX_BOX_PENALTY_NONE or _DIOU, grad_out
+ * fp32 [n] or NULL (all 1).  Outputs, each NULL or written in every element: value [n], gbev_a [n, 4, 2], gz_a [n, 2],
+ * gbev_b [n, 4, 2], gz_b [n, 2]: grad_out[i] times the derivative of value[i] with respect to the corners and the z
+ * range of pair i.  With all four gradient pointers NULL the launch is a forward.  A pair with an invalid box (the
+ * rule of the section above, the counts included) has value 0 and zero gradients.  One lane per pair.
+ *   RECORDS A and B as above: counter-clockwise (reversed when the signed sum is negative), area, bounding rectangle.
+ *   Gradients are computed per record corner k and written at the CALLER's index: 3 - k for a reversed quad.
+ *   garea(P)_k = ((y_{k+1} - y_{k-1}) * 0.5f, (x_{k-1} - x_{k+1}) * 0.5f), indices cyclic.
+ *   small = min(area(A), area(B)).  Rectangles apart: inter = 0, ginter = 0.  Else clip = the Sutherland-Hodgman area
+ *   above, inter = min(clip, small), and
+ *     clip > small (the clamp binds): ginter = garea of A when area(A) <= area(B), else garea of B; 0 for the other.
+ *     otherwise the EDGE INTEGRAL, A's edges against B, then B's edges against A, ginter from 0: for k = 0 .. 3, edge
+ *       p = P[k] -> q = P[k + 1]: t0 = 0, t1 = 1; for e = 0 .. 3 of the other quad, a = Q[e], ex, ey and d() as in
+ *       the clip, dp = d(p), dq = d(q): both < 0: the edge is dead; one < 0: t = dp / (dp - dq), t0 = max(t0, t) when
+ *       it is dp, else t1 = min(t1, t).  A live edge with t0 < t1 gives, with nx = q.y - p.y, ny = p.x - q.x, w1 =
+ *       (t1 * t1 - t0 * t0) * 0.5f, w0 = (t1 - t0) - w1: g[k].x += nx * w0, g[k].y += ny * w0, g[k + 1].x += nx * w1,
+ *       g[k + 1].y += ny * w1, in this order.  (Not a derivative of the clip: no polygon, nothing indexed at run time.)
+ *   In the plane h = ha = hb = 1 and the floor is 1e-8f; in space hraw = min(zmaxA, zmaxB) - max(zminA, zminB), h =
+ *   max(hraw, 0), ha = zmaxA - zminA, hb likewise, the floor 1e-6f.  i3 = inter * h, sa = area(A) * ha, sb = area(B) *
+ *   hb (the plane: inter and the areas themselves), s = sa + sb, uraw = s - i3, u = max(uraw, floor), iou = i3 / u.
+ *   uraw > floor: u2 = u * u, ci = s / u2, cs = i3 / u2; else (the floor binds: the U term carries no gradient) ci =
+ *   1 / u, cs = 0.  go = grad_out[i] or 1; ki = go * ci, ks = go * cs; in space kin = ki * h, kh = ki * inter, kaa = ks *
+ *   ha, kab = ks * hb, kha = ks * area(A), khb = ks * area(B); in the plane kin = ki, kaa = kab = ks.
+ *     gA_k = kin * ginterA_k - kaa * gareaA_k, gB_k = kin * ginterB_k - kab * gareaB_k    (x and y alike)
+ *     th = kh when hraw > 0 else 0; the top is A's when zmaxA <= zmaxB, the bottom A's when zminA >= zminB (ties: A)
+ *     gzA = (kha - (bottom is A's ? th : 0), (top is A's ? th : 0) - kha), gzB likewise with khb and the complement
+ *   SPX_BOX_PENALTY_DIOU: centres ((x0 + x2) * 0.5f, (y0 + y2) * 0.5f) of the records, in space (zmin + zmax) * 0.5f;
+ *   dx, dy, dz = centre(A) - centre(B), rho2 = (dx * dx + dy * dy) + dz * dz; x0 = min(minxA, minxB), x1 = max(maxxA,
+ *   maxxB), w = x1 - x0, v likewise in y, d = max(zmaxA, zmaxB) - min(zminA, zminB), c2 = (w * w + v * v) + d * d; c =
+ *   max(c2, 1e-12f); value = iou - rho2 / c.  kr = go / c, kc = go * (rho2 / (c * c)) when c2 > 1e-12f else 0.  Then, in
+ *   this order: corners 0 and 2 of A get - kr * dx in x and - kr * dy in y, those of B get +; in x, then in y, walking
+ *   A's corners 0 .. 3 and then B's, the FIRST corner equal to the upper end gets + kc * (w + w) (y: v + v) and the
+ *   first equal to the lower end gets - it; gzA -= kr * dz in both ends, gzB += it; + kc * (d + d) to the zmax of A
+ *   when zmaxA >= zmaxB, else of B, and - it to the zmin of A when zminA <= zminB, else of B.  The penalty is computed
+ *   for pairs whose rectangles are apart as well.
+ *   With penalty 0 value has the bits of spx_boxes_overlap_aligned.
+ *
+ * CORNERS, BACKWARD.  spx_boxes_to_corners_bwd: boxes [n, nfeat >= 7] and n_boxes_dev as in spx_boxes_to_corners, gbev
+ * fp32 [n, 4, 2], gzrange fp32 [n, 2] or NULL (zeros); gboxes fp32 [n, nfeat], every element written: columns beyond
+ * the seventh 0, the row of an invalid box 0.  With c, s, lx, ly of the forward and (gx_k, gy_k) = gbev[k]: x = sum
+ * gx_k, y = sum gy_k, dx = 0.5f * sum +-(gx_k * c + gy_k * s) by the sign of lx, dy = 0.5f * sum +-(gy_k * c - gx_k * s)
+ * by the sign of ly, heading = sum (gy_k * (lx * c - ly * s) - gx_k * (lx * s + ly * c)), all over k = 0 .. 3 in order;
+ * z = gzmin + gzmax, dz = (gzmax - gzmin) * 0.5f.  One launch, one lane per box.
+ * Not here: GIoU and a minimum-area enclosing box, gradients of the [m, n] matrix forms, second derivatives, half
+ * precision, a gradient through the NMS. */
+#define SPX_BOX_PENALTY_NONE 0
+#define SPX_BOX_PENALTY_DIOU 1
+int spx_boxes_iou_aligned_grad(const float *bev_a, const float *zrange_a, const int32_t *n_a_dev, const float *bev_b,
+                               const float *zrange_b, const int32_t *n_b_dev, int n, int mode, int penalty,
+                               const float *grad_out, float *value, float *gbev_a, float *gz_a, float *gbev_b,
+                               float *gz_b, spx_stream_t stream);
+int spx_boxes_to_corners_bwd(const float *boxes, int nfeat, int n, const int32_t *n_boxes_dev, const float *gbev,
+                             const float *gzrange, float *gboxes, spx_stream_t stream);
 
 /* ---- points in rotated boxes: frames, the point-major and the box-major query (csrc/roi.hip) --------------------
  * The geometric test of the roiaware_pool3d / roipoint_pool3d extensions of OpenPCDet / mmdet3d: points_in_boxes_gpu

@@ -13,7 +13,7 @@ from spconv_amd.pytorch.identity import Identity
 from spconv_amd.pytorch.spatial import SparseCollapse, SparsePrune, TrilinearDevoxelize, VoxelQueryAndGroup
 from spconv_amd.pytorch.spatial import BallQueryAndGroup, FarthestPointSample
 from spconv_amd.pytorch.spatial import KNNInterpolate, KNNQueryAndGroup
-from spconv_amd.pytorch.spatial import RotatedNMS
+from spconv_amd.pytorch.spatial import RotatedIoU3DLoss, RotatedNMS
 from spconv_amd.pytorch.spatial import RoIAwarePool3d, RoIPointPool3d
 from spconv_amd.pytorch.vfe import DynamicVFE
 from spconv_amd.pytorch.functional import point_groups, points_to_voxels, voxels_to_points
@@ -23,6 +23,7 @@ from spconv_amd.pytorch.functional import ball_query, farthest_point_sample, gat
 from spconv_amd.pytorch.functional import knn_interpolate, knn_query, three_nn
 from spconv_amd.pytorch.functional import (boxes_iou3d, boxes_iou3d_aligned, boxes_iou_bev, boxes_overlap_bev,
                                            boxes_to_corners, nms_rotated)
+from spconv_amd.pytorch.functional import boxes_iou3d_diff, boxes_iou_bev_diff
 from spconv_amd.pytorch.functional import (box_query, boxes_to_frames, points_in_boxes, roi_aware_pool,
                                            roi_point_pool)
 from spconv_amd.pytorch.tables import AddTable, AddTableMisaligned, ConcatTable, JoinTable

@@ -11,7 +11,8 @@ build); the code bases users port call them as the ``iou3d_nms`` CUDA extension 
   * overlap / IoU    one launch over the (M, N) grid, every element written; the subject is the first argument
   * ``nms_rotated``  key, sort (``spx_serialize``), mask and reduce launches; nothing read back: capturable
 
-There is no gradient of any kind.  tests/refbox.py restates every output in numpy float32.
+No function of this module has a gradient; the IoU of aligned pairs has one in _boxgrad.py (``boxes_iou3d_diff``, DESIGN
+section 3.36).  tests/refbox.py restates every output in numpy float32.
 """
 from __future__ import annotations
 

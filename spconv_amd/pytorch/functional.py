@@ -613,6 +613,11 @@ from spconv_amd.pytorch._box import (BoxCorners, BoxNMS, boxes_iou3d, boxes_iou3
                                      boxes_iou_bev, boxes_overlap_bev, boxes_to_corners, nms_rotated,
                                      nms_rotated_into, nms_ws_bytes)
 
+# differentiable rotated IoU (csrc/boxgrad.hip; not part of the reference): the IoU of aligned pairs in the plane and in
+# space, with or without the DIoU penalty, and its gradient -- mmcv's diff_iou_rotated_3d
+from spconv_amd.pytorch._boxgrad import (boxes_iou3d_diff, boxes_iou_aligned_grad_into,  # noqa: E402,F401
+                                         boxes_iou_bev_diff, boxes_to_corners_bwd_into)
+
 # points in rotated boxes (csrc/roi.hip; not part of the reference): the frames of boxes, the box of every point, the
 # points of every box, and RoI point / RoI-aware pooling composed from them with group_voxels, point_groups and
 # points_to_voxels -- the roiaware_pool3d / roipoint_pool3d extensions of OpenPCDet / mmdet3d

@@ -4,7 +4,8 @@ from a 3-D backbone to a sparse 2-D head on the kernels of csrc/collapse.hip; ``
 query points, gathered (csrc/query.hip); ``FarthestPointSample`` / ``BallQueryAndGroup``: keypoints of a raw cloud and the
 raw points around query points, gathered (csrc/sample.hip); ``KNNInterpolate`` / ``KNNQueryAndGroup``: features carried
 to many points from their nearest few, and the nearest raw points of query points, gathered (csrc/knn.hip);
-``RotatedNMS``: rotated non-maximum suppression that stays on the device (csrc/box.hip); ``RoIPointPool3d`` /
+``RotatedNMS``: rotated non-maximum suppression that stays on the device (csrc/box.hip); ``RotatedIoU3DLoss``: the
+rotated-IoU regression loss of aligned boxes, with a gradient (csrc/boxgrad.hip); ``RoIPointPool3d`` /
 ``RoIAwarePool3d``: the points of every RoI, gathered or reduced per cell of a grid over the box (csrc/roi.hip)."""
 from typing import Optional, Sequence
 
@@ -353,6 +354,49 @@ class RotatedNMS(torch.nn.Module):
     def extra_repr(self) -> str:
         return (f"thresh={self.thresh}, pre_max={self.pre_max}, post_max={self.post_max}, "
                 f"score_thresh={self.score_thresh}")
+
+
+class RotatedIoU3DLoss(torch.nn.Module):
+    """``1 - IoU`` of aligned (prediction, target) boxes, rotated, with a gradient (``functional.boxes_iou3d_diff`` /
+    ``boxes_iou_bev_diff``: the kernels of csrc/boxgrad.hip): mmdet3d's ``RotatedIoU3DLoss`` over mmcv's
+    ``diff_iou_rotated_3d``, the regression loss of FCAF3D / TR3D-style heads.  Not part of the reference.
+
+    ``mode``: "iou", or "diou" (minus the squared centre distance over the squared diagonal of the enclosing
+    axis-aligned box: pairs that do not overlap still move); ``plane``: the bird's-eye IoU instead of the IoU in
+    space; ``reduction``: "none", "mean" or "sum"; ``loss_weight`` scales the result.
+    ``forward(pred, target, weight=None, avg_factor=None)``: pred / target fp32 [N, >= 7] = (x, y, z, dx, dy, dz,
+    heading) or ``BoxCorners``; weight: None or [N], multiplied in before the reduction; avg_factor: with "mean" the
+    sum is divided by ``avg_factor + eps`` (eps of float32) instead of N, with "none" it is ignored, with "sum" it is
+    refused -- mmdet's ``weight_reduce_loss``.  The reduction is plain torch.  A pair with an invalid box has loss 1
+    and no gradient."""
+
+    def __init__(self, mode: str = "iou", plane: bool = False, reduction: str = "mean", loss_weight: float = 1.0):
+        super().__init__()
+        if mode not in ("iou", "diou"):
+            raise ValueError(f"RotatedIoU3DLoss: mode must be 'iou' or 'diou', got {mode!r}")
+        if reduction not in ("none", "mean", "sum"):
+            raise ValueError(f"RotatedIoU3DLoss: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
+        self.mode, self.plane, self.reduction, self.loss_weight = mode, bool(plane), reduction, float(loss_weight)
+
+    def forward(self, pred, target, weight: Optional[torch.Tensor] = None, avg_factor=None):
+        from spconv_amd.pytorch import functional as F
+        if avg_factor is not None and self.reduction == "sum":
+            raise ValueError("RotatedIoU3DLoss: avg_factor can not be used with reduction='sum'")
+        iou = (F.boxes_iou_bev_diff if self.plane else F.boxes_iou3d_diff)(
+            pred, target, penalty="diou" if self.mode == "diou" else "none")
+        if weight is not None and tuple(weight.shape) != tuple(iou.shape):
+            raise ValueError(f"RotatedIoU3DLoss: weight is None or {list(iou.shape)}, got {list(weight.shape)}")
+        loss = 1.0 - iou
+        if weight is not None:
+            loss = loss * weight
+        if self.reduction == "sum":
+            loss = loss.sum()
+        elif self.reduction == "mean":
+            loss = loss.mean() if avg_factor is None else loss.sum() / (avg_factor + torch.finfo(torch.float32).eps)
+        return self.loss_weight * loss
+
+    def extra_repr(self) -> str:
+        return f"mode={self.mode}, plane={self.plane}, reduction={self.reduction}, loss_weight={self.loss_weight}"
 
 
 class RoIPointPool3d(torch.nn.Module):
