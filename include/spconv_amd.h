@@ -1258,6 +1258,69 @@ int spx_ball_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids
                    const int32_t *offsets, const int32_t *list, int batch, int nsample, float r2, int flags,
                    int32_t *rows, int32_t *count, float *out_offsets, spx_stream_t stream);
 
+/* ---- sectorised keypoint sampling: segmented farthest-point sampling (csrc/sample.hip) ------------------------
+ * PV-RCNN++'s sectorized_proposal_centric_sampling and pointnet2_stack's stack_farthest_point_sample: keep the points
+ * near the first stage's RoIs, cut every scene into azimuth sectors, give each sector a share of K in proportion to
+ * its points and sample every sector on its own -- batch * S workgroups on batch * S CUs, none waiting for another.
+ * A SEGMENT is a group of spx_point_groups over the segment ids written here (num_voxels = batch * S); the sampling
+ * rule, the validity of a point, d2 and the scratch are those of spx_fps.  Every call: the caller allocates, nothing
+ * is read back, nothing synchronises, every grid depends on host-known sizes only (hipGraph-safe), no atomics.  The
+ * argument checks that need no pointer come before any pointer is looked at.  All float32 operations are rounded on
+ * their own (no FMA; sqrt correctly rounded).  The three launches are not counted by spx_launch_count (as the entries of
+ * csrc/roi.hip and csrc/boxgrad.hip): its key inventory stays as it is.
+ *
+ *   spx_sector_ids: seg int32 [n_cap] = b * S + sector for a valid point of scene b, else -1.  A point is in no
+ *   segment when it lies at or beyond *n_points_dev (NULL: n_cap), its batch id (batch_ids NULL: 0) is outside
+ *   [0, batch), one of its first ndim coordinates is not finite, or the RoI filter turns it down.
+ *   SECTOR, S = num_sectors in 1 .. spx_sector_max() = 64, about the centre (cx, cy): with a = -(x - cx), b = -(y - cy),
+ *   boundary k < S has the direction (c_k, s_k) = (cos, sin)(2 pi k / S) -- computed in float64 and rounded to float32,
+ *   exactly (1, 0) (0, 1) (-1, 0) (0, -1) where 4 k % S == 0: spx_sector_table writes the S pairs to a HOST array
+ *   float [S, 2] -- and the half-turn bit h_k = (2 k >= S).  The point's half turn is 0 when b > 0 or (b == 0 and
+ *   a > 0), else 1; it is at or past boundary k when half > h_k, or half == h_k and c_k * b - s_k * a >= 0; sector =
+ *   max((boundaries at or past) - 1, 0); a == 0 and b == 0 is sector 0.  No transcendental function runs on the device.
+ *   This is OpenPCDet's floor((atan2(y, x) + pi) / (2 pi / S)) but for two cases: a point on the negative x axis with
+ *   y = +0 gets index S there (which its loop never visits: the point is dropped) and sector 0 here; the origin is
+ *   sector 0 here, S / 2 there.
+ *   ROI FILTER (roi_filter = 1; ndim 3): boxes fp32 [m_cap, box_nfeat >= 7] = (x, y, z, dx, dy, dz, heading);
+ *   box_offsets int32 [batch + 1] and box_list int32 [m_cap] are spx_point_groups over the BOX batch ids with the
+ *   device box count (boxes beyond it and ids outside [0, batch) are in no scene).  A box is additionally INVALID when
+ *   one of its seven values is not finite or a size is not > 0.  With d_j = centre_j - p_j over the valid boxes of the
+ *   point's scene, the NEAREST box is the one with the lowest d2 (< +inf), ties to the lowest box index; the point is
+ *   kept when  sqrt(d2_nearest) < sqrt(d2 of (0.5 * dx, 0.5 * dy, 0.5 * dz) of the nearest) + radius  (radius finite,
+ *   >= 0) -- OpenPCDet's sample_points_with_roi, its quirk included: only the nearest centre's size counts.  A scene
+ *   without a valid box keeps nothing.  One lane per point, workgroups of 256 consecutive points which walk the scenes
+ *   of their points and stage that scene's boxes in LDS, spx_sector_box_tile() = 128 at a time.  One launch (none for
+ *   n_cap = 0).
+ *
+ *   spx_fps_quota: offsets int32 [batch * S + 1] = spx_point_groups over seg.  With n_k the size of segment k of a
+ *   scene and n their sum:  quota = n == 0 ? 0 : min(n_k, (n_k * K + n - 1) / n)  in 64-bit integers (the ceiling of
+ *   the segment's share of K = num_samples in 1 .. 65536), slot = the exclusive prefix of the quotas inside the scene,
+ *   count[b] = their sum <= K + S - 1.  quota, slot int32 [batch * S], count int32 [batch].  A wave per scene.  One
+ *   launch.
+ *
+ *   spx_fps_segments: spx_fps per segment with K read from the device.  Segment g of `groups` (offsets int32
+ *   [groups + 1], list int32 [n_cap]) samples k = min(quota[g], max_quota, its valid points) points into
+ *       idx[(g / groups_per_row) * row_stride + slot[g] + 0 .. k)              (slot NULL: 0)
+ *   in sampling order, and count[g] = k.  idx int32 [groups / groups_per_row, row_stride] holds -1 wherever no segment
+ *   writes (a fill launch in front); quota[g] and slot[g] are clamped so that no store leaves the row: with the
+ *   quotas and slots of spx_fps_quota, groups_per_row = S and row_stride = K + S - 1 a row is packed, sector by sector,
+ *   without holes below count[b].  With slot NULL, groups_per_row 1 and quota = K everywhere it is spx_fps.  max_quota
+ *   in 1 .. 65536; groups a multiple of groups_per_row; rows * row_stride < 2^31.  One workgroup of 1024 lanes per
+ *   segment, the tier chosen from the segment's own count; a segment without points or quota leaves before its first
+ *   barrier.  ws: spx_fps_ws_bytes(n_cap, groups, ndim), needed for n_cap > spx_fps_resident_points().  Two launches. */
+int spx_sector_max(void);
+int spx_sector_box_tile(void);
+int spx_sector_table(int num_sectors, float *table_h);
+int spx_sector_ids(const float *points, int nfeat, const int32_t *batch_ids, int n_cap, const int32_t *n_points_dev,
+                   int ndim, int batch, int num_sectors, float cx, float cy, int roi_filter, const float *boxes,
+                   int box_nfeat, int m_cap, const int32_t *box_offsets, const int32_t *box_list, float radius,
+                   int32_t *seg, spx_stream_t stream);
+int spx_fps_quota(const int32_t *offsets, int n_cap, int batch, int num_sectors, int num_samples, int32_t *quota,
+                  int32_t *slot, int32_t *count, spx_stream_t stream);
+int spx_fps_segments(const float *points, int nfeat, int n_cap, int ndim, const int32_t *offsets, const int32_t *list,
+                     int groups, const int32_t *quota, const int32_t *slot, int groups_per_row, int row_stride,
+                     int max_quota, int32_t *idx, int32_t *count, void *ws, size_t ws_bytes, spx_stream_t stream);
+
 /* ---- k-nearest-neighbour query and inverse-distance weights over raw points (csrc/knn.hip) ------------------
  * The way back from few points to many, and grouping by nearest neighbours instead of by radius: three_nn +
  * three_interpolate of pointnet2's feature propagation (PointNet++, PointRCNN, 3DSSD, IA-SSD, the point heads of the

@@ -11,7 +11,7 @@ from spconv_amd.pytorch.conv import (SparseConv1d, SparseConv2d, SparseConv3d, S
 from spconv_amd.pytorch.core import ConvAlgo, SparseConvTensor
 from spconv_amd.pytorch.identity import Identity
 from spconv_amd.pytorch.spatial import SparseCollapse, SparsePrune, TrilinearDevoxelize, VoxelQueryAndGroup
-from spconv_amd.pytorch.spatial import BallQueryAndGroup, FarthestPointSample
+from spconv_amd.pytorch.spatial import BallQueryAndGroup, FarthestPointSample, SectorFPS
 from spconv_amd.pytorch.spatial import KNNInterpolate, KNNQueryAndGroup
 from spconv_amd.pytorch.spatial import RotatedIoU3DLoss, RotatedNMS
 from spconv_amd.pytorch.spatial import RoIAwarePool3d, RoIPointPool3d
@@ -20,6 +20,7 @@ from spconv_amd.pytorch.functional import point_groups, points_to_voxels, voxels
 from spconv_amd.pytorch.functional import point_corners, voxels_to_points_trilinear
 from spconv_amd.pytorch.functional import group_voxels, voxel_query
 from spconv_amd.pytorch.functional import ball_query, farthest_point_sample, gather_samples
+from spconv_amd.pytorch.functional import farthest_point_sample_segments, sector_fps, sector_ids
 from spconv_amd.pytorch.functional import knn_interpolate, knn_query, three_nn
 from spconv_amd.pytorch.functional import (boxes_iou3d, boxes_iou3d_aligned, boxes_iou_bev, boxes_overlap_bev,
                                            boxes_to_corners, nms_rotated)

@@ -601,6 +601,13 @@ from spconv_amd.pytorch._query import (VoxelNeighbors, group_voxels, voxel_query
 from spconv_amd.pytorch._sample import (PointSamples, ball_query, ball_query_into,  # noqa: E402,F401
                                         farthest_point_sample, fps_into, gather_samples, scene_groups)
 
+# sectorised keypoint sampling (csrc/sample.hip; not part of the reference): segment ids by scene, RoI filter and azimuth
+# sector, a quota per segment and farthest-point sampling with K read per segment -- PV-RCNN++'s
+# sectorized_proposal_centric_sampling, pointnet2_stack's stack_farthest_point_sample
+from spconv_amd.pytorch._sample import (SectorBuffers, farthest_point_sample_segments,  # noqa: E402,F401
+                                        fps_quota_into, fps_segments_into, sector_buffers, sector_fps,
+                                        sector_fps_into, sector_ids, sector_ids_into, sector_table)
+
 # k-nearest-neighbour query and inverse-distance interpolation over raw points (csrc/knn.hip; not part of the reference):
 # the k points that come first under (squared distance, point index), as the tables group_voxels gathers and
 # voxels_to_points_trilinear blends

@@ -216,6 +216,41 @@ class FarthestPointSample(torch.nn.Module):
         return f"num_samples={self.num_samples}, ndim={self.ndim}"
 
 
+class SectorFPS(torch.nn.Module):
+    """Keypoints of a raw cloud by sectorised (and, with RoIs, proposal-centric) farthest-point sampling
+    (``functional.sector_fps``, the kernels of csrc/sample.hip): PV-RCNN++'s ``sectorized_proposal_centric_sampling``.
+    Not part of the reference.
+
+    ``num_samples`` in 1 .. 65 536: K per scene, shared among ``num_sectors`` (1 .. 64) azimuth sectors about ``center``
+    in proportion to their points; ``roi_radius`` (None: no filter) keeps the points within the nearest RoI's half
+    diagonal plus that radius.  ``forward(points, batch_ids, batch_size, rois=None, roi_batch_ids=None, n_points=None,
+    n_rois=None) -> PointSamples(idx [B, K + S - 1], count [B], batch_ids [B * (K + S - 1)])``, packed sector by sector;
+    `rois` are required exactly when ``roi_radius`` is set.  One workgroup per sector.  No gradient with respect to
+    coordinates."""
+
+    def __init__(self, num_samples: int, num_sectors: int = 6, roi_radius: Optional[float] = None, center=(0., 0.)):
+        super().__init__()
+        from spconv_amd.pytorch import _sample
+        self.center = _sample._check_sectors("SectorFPS", num_sectors, center)
+        _sample._check_sector_fps("SectorFPS", 1, num_samples, num_sectors)
+        if roi_radius is not None and not 0. <= float(roi_radius) < float("inf"):
+            raise ValueError(f"SectorFPS: roi_radius must be finite and >= 0, got {roi_radius!r}")
+        self.num_samples, self.num_sectors = int(num_samples), int(num_sectors)
+        self.roi_radius = None if roi_radius is None else float(roi_radius)
+
+    def forward(self, points: torch.Tensor, batch_ids: Optional[torch.Tensor], batch_size: int,
+                rois: Optional[torch.Tensor] = None, roi_batch_ids: Optional[torch.Tensor] = None,
+                n_points: Optional[torch.Tensor] = None, n_rois: Optional[torch.Tensor] = None):
+        from spconv_amd.pytorch import functional as F
+        return F.sector_fps(points, batch_ids, batch_size, self.num_samples, self.num_sectors, center=self.center,
+                            rois=rois, roi_batch_ids=roi_batch_ids, roi_radius=self.roi_radius, n_points=n_points,
+                            n_rois=n_rois)
+
+    def extra_repr(self) -> str:
+        return (f"num_samples={self.num_samples}, num_sectors={self.num_sectors}, roi_radius={self.roi_radius}, "
+                f"center={self.center}")
+
+
 class BallQueryAndGroup(torch.nn.Module):
     """The raw points around query points, gathered for a shared MLP (``functional.ball_query`` +
     ``functional.group_voxels``, the kernels of csrc/sample.hip and csrc/query.hip): the ``ball_query`` /
