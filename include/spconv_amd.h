@@ -718,12 +718,27 @@ int spx_point2voxel_static(const float *points, const int32_t *point_batch, int 
 /* Fixed-size hash table over caller-owned storage.  Replaces
  * spconv/csrc/hash/core.py HashTable as driven by spconv/pytorch/hash.py:29-170.
  *   table_keys [capacity] (4- or 8-byte integers, all-ones = empty; initialise with
- *   spx_hash_clear), table_vals [capacity] (4- or 8-byte items, copied bit for bit)
- *   insert: values may be NULL (key only); query: is_empty[i] = 1 where the key is absent;
- *   insert_exist: writes values only where the key is already present;
- *   assign_arange: every present key gets its rank in SLOT order as value, *count_out (an integer
- *   of the key width) receives the number of keys; items: entries in the same order.
- * ws >= spx_hash_ws_bytes(capacity) for assign_arange / items. */
+ *   spx_hash_clear), table_vals [capacity] (4- or 8-byte items, copied bit for bit).  Linear probing from the home slot
+ *   of a key; a slot, once taken, is never emptied.
+ * The contract:
+ *   - The all-ones key marks an empty slot and is never a member: insert ignores it (no slot claimed, no value written),
+ *     query and insert_exist report it absent (is_empty = 1, nothing copied).
+ *   - insert: values may be NULL (key only: table_vals is not written).  A key that finds no free slot is dropped and
+ *     later reported absent: a table never holds more than `capacity` keys and never holds one twice.  Copies of one
+ *     key within one call take one slot, and its value is one of the values given for that key.
+ *   - query: is_empty[i] = 1 where the key is absent, 0 where it is present; values_out[i] is written only where the key
+ *     is present -- the rows of absent keys keep the caller's bytes.
+ *   - insert_exist: writes values only where the key is already present; is_empty as for query.
+ *   - assign_arange: every present key gets as value its rank among the occupied slots in ascending SLOT index; items:
+ *     the entries in the same order.  Two calls on an unchanged table agree bit for bit.  Which of two colliding keys
+ *     holds the earlier slot is decided by the order the inserts arrive in, so the numbering depends on the slot
+ *     contents, hence on insertion and arrival order -- not on the key set alone.
+ *   - *count_out (may be NULL) is an integer of the KEY width and receives the number of keys, also when max_out is
+ *     smaller; items writes nothing at or beyond min(count, max_out).
+ *   - Refused before any device work: key_bytes / val_bytes other than 4 or 8, NULL table storage, capacity <= 0, n < 0,
+ *     keys = NULL with n > 0, values_out = NULL (query) or values = NULL (insert_exist) with n > 0, max_out < 0,
+ *     keys_out or vals_out = NULL with max_out > 0, ws = NULL or ws_bytes < spx_hash_ws_bytes(capacity) for
+ *     assign_arange / items (ws need not be initialised).  n = 0 is a valid call that does nothing. */
 size_t spx_hash_ws_bytes(int capacity);
 int spx_hash_clear(void *table_keys, int capacity, int key_bytes, spx_stream_t stream);
 int spx_hash_insert(void *table_keys, void *table_vals, int capacity, int key_bytes, int val_bytes,

@@ -2,10 +2,12 @@
 //
 // Fixed-size open-addressing table over caller-owned key / value arrays (SURVEY.md section 8f
 // row 4; replaces spconv/csrc/hash/core.py HashTable as used by spconv/pytorch/hash.py).  Keys
-// are 32- or 64-bit integers (all-ones = empty), values are opaque 4- or 8-byte items.
-// assign_arange / items walk the table in SLOT order (count -> scan -> assign), so their result
-// is a pure function of the set of keys -- the reference's GPU table numbers entries in atomic
-// arrival order.
+// are 32- or 64-bit integers, values are opaque 4- or 8-byte items.  The contract is the hash section of
+// include/spconv_amd.h; in short: the all-ones key marks an empty slot and is never a member; a key that finds no free
+// slot is dropped; query writes values_out only where the key is present; assign_arange / items walk the table in
+// ascending SLOT index (count -> scan -> assign), so their result is a function of the slot contents -- which of two
+// colliding keys holds the earlier slot is decided by the order the inserts arrive in; every argument is checked
+// before any device work.
 #include "common.h"
 #include "scan.h"
 #include "table.h"      // hash_key
@@ -53,6 +55,10 @@ user_hash_kernel(K *__restrict__ tkeys, V *__restrict__ tvals, int cap, const K 
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const K key = keys[i];
+  if (key == UKey<K>::empty()) {  // the empty marker is never a member: nothing claimed, nothing copied
+    if (op != 0 && is_empty) is_empty[i] = 1;
+    return;
+  }
   if (op == 0) {
     const int slot = user_find(tkeys, cap, key, true);
     if (slot >= 0 && values) tvals[slot] = values[i];
@@ -157,7 +163,18 @@ static int user_hash_call(int what, void *tkeys, void *tvals, int cap, int key_b
   SPX_CHECK(tkeys && tvals && cap > 0, "hash table storage required");
   SPX_CHECK((key_bytes == 4 || key_bytes == 8) && (val_bytes == 4 || val_bytes == 8),
             "keys and values must be 4 or 8 bytes wide");
-  if (what >= 3) SPX_CHECK(ws && ws_bytes >= spx_hash_ws_bytes(cap), "workspace too small");
+  if (what <= 2) {
+    SPX_CHECK(n >= 0, "hash: n must not be negative");
+    SPX_CHECK(n == 0 || keys, "hash: keys is NULL");
+    SPX_CHECK(n == 0 || what == 0 || values, "hash %s is NULL", what == 1 ? "query: values_out" : "insert_exist: values");
+    if (n == 0) return 0;  // a valid call that does nothing: no launch, no look at the device
+  } else {
+    SPX_CHECK(ws && ws_bytes >= spx_hash_ws_bytes(cap), "workspace too small");
+    if (what == 4) {
+      SPX_CHECK(max_out >= 0, "hash items: max_out must not be negative");
+      SPX_CHECK(max_out == 0 || (keys_out && vals_out), "hash items: keys_out / vals_out is NULL");
+    }
+  }
 #define SPX_UH(KT, VT) \
   return user_hash_dispatch2<KT, VT>(what, tkeys, tvals, cap, keys, values, is_empty, n, keys_out, vals_out, \
                                      max_out, count_out, ws, s)

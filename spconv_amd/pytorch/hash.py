@@ -1,7 +1,13 @@
 """Fixed-size GPU hash table for 32 / 64 bit keys and values (reference:
 ``spconv/pytorch/hash.py:29-170``).  Same constructor and methods; storage is two torch tensors
-owned by this object, the operations run in ``spx_hash_*``.  ``assign_arange_`` / ``items``
-enumerate the table in slot order, i.e. deterministically for a given key set."""
+owned by this object, the operations run in ``spx_hash_*``.
+
+The contract is the hash section of ``include/spconv_amd.h``.  In short: the all-ones key (-1) marks an empty slot and
+is never a member -- ``insert`` ignores it, ``query`` / ``insert_exist_keys`` report it absent; a key that finds no free
+slot is dropped and later reported absent; ``query`` writes a value only where the key is present; ``assign_arange_`` /
+``items`` enumerate the occupied slots in ascending slot index -- two calls on an unchanged table agree bit for bit, and
+the numbering depends on the slot contents, hence on insertion and arrival order.  Every ``keys`` / ``values`` operand
+goes through ``check_operand`` before a kernel sees its pointer."""
 from __future__ import annotations
 
 from typing import Optional
@@ -28,6 +34,29 @@ def _on_table_device(method):
     return guarded
 
 _ITEMSIZE = {torch.int32: 4, torch.int64: 8, torch.float32: 4, torch.float64: 8}
+
+
+def check_operand(name: str, t, dtype: torch.dtype, device: torch.device, length: Optional[int] = None,
+                  in_place: bool = False) -> torch.Tensor:
+    """The operand a kernel may be handed: a 1-d tensor of `dtype` on `device` (the table's) with `length` elements
+    (None: any), contiguous.  ValueError naming the operand otherwise.  A strided operand is made contiguous, except
+    one the kernel writes for the caller (in_place): that one is refused, a copy would be filled in its stead.
+    Pure: looks at the tensor's metadata only, needs no GPU."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must have dtype {dtype} (the table's), got {t.dtype}")
+    if t.ndim != 1:
+        raise ValueError(f"{name} must be 1-d, got shape {tuple(t.shape)}")
+    if length is not None and t.shape[0] != length:
+        raise ValueError(f"{name} must have length {length}, got {t.shape[0]}")
+    if t.device != torch.device(device):
+        raise ValueError(f"{name} must be on the table's device {device}, got {t.device}")
+    if not t.is_contiguous():
+        if in_place:
+            raise ValueError(f"{name} must be contiguous (it is written in place), got stride {tuple(t.stride())}")
+        t = t.contiguous()
+    return t
 
 
 class HashTable:
@@ -59,27 +88,33 @@ class HashTable:
         return (self.keys_data.data_ptr(), self.values_data.data_ptr(), self.keys_data.shape[0],
                 self.key_itemsize, self.value_itemsize)
 
-    def _check_keys(self, keys: torch.Tensor) -> torch.Tensor:
-        assert keys.dtype == self.key_dtype and keys.ndim == 1, "keys must be 1-d with the table's key dtype"
-        return keys.contiguous()
+    def _keys(self, keys: torch.Tensor) -> torch.Tensor:
+        return check_operand("keys", keys, self.key_dtype, self.keys_data.device)
+
+    def _values(self, values: torch.Tensor, n: int, in_place: bool = False) -> torch.Tensor:
+        return check_operand("values", values, self.value_dtype, self.keys_data.device, n, in_place)
 
     @_on_table_device
     def insert(self, keys: torch.Tensor, values: Optional[torch.Tensor] = None):
-        """insert keys (and values; without values the stored value is undefined)"""
-        keys = self._check_keys(keys)
+        """insert keys (and values; without values the value storage is not written).  -1 is ignored; a key that finds
+        no free slot is dropped"""
+        keys = self._keys(keys)
         if values is not None:
-            assert values.dtype == self.value_dtype and values.shape[0] == keys.shape[0]
-            values = values.contiguous()
+            values = self._values(values, keys.shape[0])
         _lib.check(self._L.spx_hash_insert(*self._args(), keys.data_ptr(),
                                            None if values is None else values.data_ptr(),
                                            keys.shape[0], self._stream()))
 
     @_on_table_device
     def query(self, keys: torch.Tensor, values: Optional[torch.Tensor] = None):
-        """-> (values, bool tensor that is True where the key was NOT found)"""
-        keys = self._check_keys(keys)
+        """-> (values, bool tensor that is True where the key was NOT found).  A row of `values` is written only where
+        the key was found: with a caller's `values` (filled in place, never replaced by a copy) the other rows keep
+        their content, without one they are uninitialised"""
+        keys = self._keys(keys)
         if values is None:
             values = torch.empty([keys.shape[0]], dtype=self.value_dtype, device=keys.device)
+        else:
+            values = self._values(values, keys.shape[0], in_place=True)
         is_empty = torch.empty([keys.shape[0]], dtype=torch.uint8, device=keys.device)
         _lib.check(self._L.spx_hash_query(*self._args(), keys.data_ptr(), values.data_ptr(),
                                           is_empty.data_ptr(), keys.shape[0], self._stream()))
@@ -88,11 +123,11 @@ class HashTable:
     @_on_table_device
     def insert_exist_keys(self, keys: torch.Tensor, values: torch.Tensor):
         """overwrite the values of keys that exist; -> uint8 tensor, 1 where the key was missing"""
-        keys = self._check_keys(keys)
-        assert values.dtype == self.value_dtype and values.shape[0] == keys.shape[0]
+        keys = self._keys(keys)
+        values = self._values(values, keys.shape[0])
         is_empty = torch.empty([keys.shape[0]], dtype=torch.uint8, device=keys.device)
         _lib.check(self._L.spx_hash_insert_exist(*self._args(), keys.data_ptr(),
-                                                 values.contiguous().data_ptr(), is_empty.data_ptr(),
+                                                 values.data_ptr(), is_empty.data_ptr(),
                                                  keys.shape[0], self._stream()))
         return is_empty
 
@@ -102,7 +137,8 @@ class HashTable:
 
     @_on_table_device
     def assign_arange_(self):
-        """every key gets a distinct value in [0, count); -> count (1-element tensor)"""
+        """every key gets its rank among the occupied slots, in ascending slot index, as value; -> count (1-element
+        tensor of the key dtype)"""
         assert self.value_dtype in (torch.int32, torch.int64)
         count = torch.zeros([1], dtype=self.key_dtype, device=self.keys_data.device)
         ws = self._ws()
@@ -112,9 +148,13 @@ class HashTable:
 
     @_on_table_device
     def items(self, max_size: int = -1):
-        """-> (keys, values, count): the first `count` entries are the table's content"""
+        """-> (keys, values, count): the first min(count, max_size) entries are the table's content in ascending slot
+        index (the order of assign_arange_), the rest is uninitialised; count is the number of keys also when max_size
+        is smaller"""
         if max_size == -1:
             max_size = self.values_data.shape[0]
+        if max_size < 0:
+            raise ValueError(f"max_size must be -1 (the capacity) or >= 0, got {max_size}")
         dev = self.keys_data.device
         keys = torch.empty([max_size], dtype=self.key_dtype, device=dev)
         values = torch.empty([max_size], dtype=self.value_dtype, device=dev)
