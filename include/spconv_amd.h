@@ -1757,6 +1757,100 @@ int spx_box_query(const float *frames, const int32_t *b_batch_ids, int m_cap, co
                   int nsample, int flags, int ox, int oy, int oz, int32_t *rows, int32_t *count, int32_t *hits,
                   float *local, int32_t *cells, spx_stream_t stream);
 
+/* ---- centre-head targets (csrc/center.hip; not part of the reference) ----------------------------------------------
+ * The Gaussian heatmaps and index tables of the centre heads (CenterPoint, VoxelNeXt, TransFusion, DSVT, HEDNet,
+ * SAFDNet): OpenPCDet's CenterHead.assign_target_of_single_head and VoxelNeXt's sparse twin, which walk the
+ * ground-truth boxes in Python.  Every call: the caller allocates, nothing is read back, nothing synchronises, every
+ * grid depends on host-known sizes only (hipGraph-safe), every output element is written exactly once by the call
+ * that owns it, no atomics: identical run to run.  The argument checks that need no pointer come before any pointer is
+ * looked at.  All float arithmetic is fp32, every operation rounded on its own (no FMA contraction), division and
+ * square root correctly rounded: numpy float32 reproduces every table bit for bit (tests/refcenter.py).  No launch
+ * counters.
+ *
+ * THE MAP.  W x H cells (x fastest), each 1 .. 2^23; num_classes = C class planes, 1 .. SPX_CENTER_MAX_CLASSES;
+ * batch in 1 .. 65535; batch * C * H * W < 2^31.  box_offsets int32 [batch + 1] / box_list int32 [m_cap]: the scene
+ * list over the BOX batch ids (spx_point_groups with the device box count: scene b = box_list[box_offsets[b] :
+ * box_offsets[b + 1]] in ascending box index).
+ *
+ * RECORDS.  spx_box_centers: boxes fp32 [m_cap, nfeat >= 7] = (x, y, z, dx, dy, dz, heading); b_batch_ids int32
+ * [m_cap] or NULL (all scene 0); class_ids int32 / int64 [m_cap] (class_bytes 4 / 8), 0-based planes, or NULL (all
+ * class 0); n_boxes_dev NULL or a device int32.  Host parameters: voxel sizes vx, vy > 0, range minimum x0, y0,
+ * stride > 0 (all finite), max_objs >= 1, 0 < min_overlap < 1, min_radius in 0 .. 2^20.  Per box:
+ *     cx = ((x - x0) / vx) / stride, clamped to [0, W - 0.5];  cy likewise against y0, vy, H
+ *     ix = (int)cx;  iy = (int)cy                                  (truncation)
+ *     w = (dx / vx) / stride;  h = (dy / vy) / stride;  ov = min_overlap
+ *     b1 = h + w;  c1 = ((w * h) * (1 - ov)) / (1 + ov);  r1 = (b1 + sqrt(b1 * b1 - 4 * c1)) / 2
+ *     b2 = 2 * (h + w);  c2 = ((1 - ov) * w) * h;  r2 = (b2 + sqrt(b2 * b2 - 16 * c2)) / 2
+ *     a3 = 4 * ov;  b3 = (-2 * ov) * (h + w);  c3 = ((ov - 1) * w) * h;  r3 = (b3 + sqrt(b3 * b3 - (4 * a3) * c3)) / 2
+ *     ret = min(min(r1, r2), r3), NaN when one of them is;  radius = max((int)ret, min_radius)
+ *   (CornerNet's gaussian_radius(h, w, ov) as OpenPCDet carries it.)  A box has a GEOMETRY when it lies below
+ *   min(*n_boxes, m_cap), its seven numbers are finite, dx, dy, dz > 0 and |ret| < 2^20.  Its SLOT is its position among
+ *   the boxes of its scene in the list -- every box of the scene below the device count, with a geometry or not -- or
+ *   -1 when its batch id is outside [0, batch), it lies at or beyond the device count or the position is >= max_objs.
+ *   A box TAKES PART when it has a geometry, a slot and a class in [0, C).  Outputs:
+ *     center fp32 [m_cap, 2] (cx, cy), cell int32 [m_cap, 2] (ix, iy), radius int32 [m_cap]: zeros without a geometry
+ *     cls int32 [m_cap]: the class plane of a box that takes part, else -1;  slot int32 [m_cap]
+ *     box_index int32 [batch, max_objs]: the box in slot s of scene b, -1 past the scene's boxes
+ *     mask int32 [batch, max_objs]: 1 when that box takes part;  inds int32 [batch, max_objs]: iy * W + ix, 0 where
+ *     the mask is 0
+ *   One launch, max(m_cap, batch * max_objs) lanes: a lane per box (its slot by a bisection in the scene's list) and a
+ *   lane per table entry.  m_cap = 0 writes the tables only.
+ *
+ * DENSE.  spx_center_heatmap: heat fp32 [batch, C, H, W]; element (b, c, y, x) is the maximum, over the boxes of scene
+ * b with cls = c and |x - ix| <= radius and |y - iy| <= radius, of
+ *     expf(-(float)(ddx * ddx + ddy * ddy) / ((2.f * sigma) * sigma)),  sigma = (float)(2 * radius + 1) / 6.f
+ * with the integers ddx = x - ix, ddy = y - iy (their sum of squares in 64 bits, converted once); 0 where no box
+ * reaches.  The gather form: a workgroup per 16 x 16 patch of one class plane, a lane per cell; the scene's records are
+ * staged spx_center_tile() = 128 at a time and compacted to the boxes of the class whose windows meet the patch; the
+ * maximum stays in a register and is stored once.  One launch, no zero fill.  It reads cell, radius and cls only.
+ *
+ * SPARSE (2-D levels).  indices int32 [n_cap, 3] = (b, y, x); a row is LIVE when it lies below min(*n_live, n_cap), its
+ * batch id is in [0, batch) and its cell inside W x H.  row_offsets int32 [batch + 1] / row_list int32 [n_cap]: the
+ * scene list over indices[:, 0] (spx_point_groups with the device row count).
+ *   spx_center_nearest: nearest int32 [m_cap] = for a box that takes part the live row of its scene with the least
+ *   (bits of d2, row index), d2 = (float(vx) - cx)^2 + (float(vy) - cy)^2 with the x term first -- ties to the lowest
+ *   row --, -1 for a scene without a live row and for a box that takes no part.  A box to a wave (four per workgroup),
+ *   64-bit keys reduced across the wave.  A second launch, one lane per table entry, writes inds int32 [batch,
+ *   max_objs] = the nearest row of the box in that slot (a global row index; 0 where mask is 0) and mask = box_mask
+ *   && a nearest row exists, from box_index / box_mask of spx_box_centers.
+ *   spx_center_heatmap_sparse: heat fp32 [n_cap, C]; element (i, c) of a live row is the maximum over the boxes of its
+ *   scene with cls = c of expf(-d2 / ((2.f * sigma) * sigma)), sigma as above.  anchor = SPX_CENTER_ANCHOR_CENTER
+ *   (VoxelNeXt's gt_center): d2 as in spx_center_nearest, the window centred on (ix, iy).  SPX_CENTER_ANCHOR_NEAREST:
+ *   d2 = the integer squared distance to the cell of the box's nearest row, converted once, the window centred on
+ *   that cell; a box without a nearest row draws nothing.  cutoff = SPX_CENTER_CUTOFF_WINDOW keeps the dense rule
+ *   |.| <= radius on both axes; SPX_CENTER_CUTOFF_NONE (VoxelNeXt) lets a box reach every live row of its scene.  A
+ *   row that is not live gets zeros.  A lane per row on the scene walk of the point queries (workgroups of 256
+ *   consecutive rows walk the scenes of their rows in ascending order; rows may arrive in any scene order), eight
+ *   class maxima in registers; more than eight classes walk once per group of eight.  One launch.
+ *
+ * WHAT THE KERNELS MAY BE HANDED.  Every output in any state; boxes with NaN / Inf anywhere; batch ids, class ids and
+ * index rows of any value; rows at or beyond the device counts in any state (they are not read); offsets and list
+ * entries are clamped / checked, not trusted.
+ * Not here: gaussian_ratio, IoU-aware targets, 3-D heatmaps, half-precision heat, decoding, the losses, gradients. */
+#define SPX_CENTER_MAX_CLASSES 64
+#define SPX_CENTER_ANCHOR_CENTER 0
+#define SPX_CENTER_ANCHOR_NEAREST 1
+#define SPX_CENTER_CUTOFF_NONE 0
+#define SPX_CENTER_CUTOFF_WINDOW 1
+int spx_center_tile(void);
+int spx_center_max_classes(void);
+int spx_box_centers(const float *boxes, int nfeat, const int32_t *b_batch_ids, const void *class_ids, int class_bytes,
+                    int m_cap, const int32_t *n_boxes_dev, const int32_t *box_offsets, const int32_t *box_list, int batch,
+                    int W, int H, float vx, float vy, float x0, float y0, float stride, int num_classes, int max_objs,
+                    float min_overlap, int min_radius, float *center, int32_t *cell, int32_t *radius, int32_t *cls,
+                    int32_t *slot, int32_t *box_index, int32_t *mask, int32_t *inds, spx_stream_t stream);
+int spx_center_heatmap(const int32_t *cell, const int32_t *radius, const int32_t *cls, int m_cap,
+                       const int32_t *box_offsets, const int32_t *box_list, int batch, int W, int H, int num_classes,
+                       float *heat, spx_stream_t stream);
+int spx_center_nearest(const float *center, const int32_t *cls, const int32_t *b_batch_ids, int m_cap,
+                       const int32_t *indices, int n_cap, const int32_t *n_live_dev, const int32_t *row_offsets,
+                       const int32_t *row_list, int batch, int W, int H, const int32_t *box_index, const int32_t *box_mask,
+                       int max_objs, int32_t *nearest, int32_t *inds, int32_t *mask, spx_stream_t stream);
+int spx_center_heatmap_sparse(const float *center, const int32_t *cell, const int32_t *radius, const int32_t *cls,
+                              const int32_t *nearest, int m_cap, const int32_t *box_offsets, const int32_t *box_list,
+                              const int32_t *indices, int n_cap, const int32_t *n_live_dev, int batch, int W, int H,
+                              int num_classes, int anchor, int cutoff, float *heat, spx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

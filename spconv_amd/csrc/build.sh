@@ -6,7 +6,7 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../lib
-HIP_UNITS="rulebook_subm rulebook_conv rulebook_sorted rulebook_lists igemm igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_gen1 igemm_ws igemm_bwdn pool rowsort norm dense union collapse select pointvoxel interp query sample knn serialize voxelize hash box boxgrad roi"
+HIP_UNITS="rulebook_subm rulebook_conv rulebook_sorted rulebook_lists igemm igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_gen1 igemm_ws igemm_bwdn pool rowsort norm dense union collapse select pointvoxel interp query sample knn serialize voxelize hash box boxgrad roi center"
 CPP_UNITS="common counters"
 OBJS=""
 for f in $HIP_UNITS $CPP_UNITS; do OBJS="$OBJS $OUT/$f.o"; done

@@ -15,6 +15,7 @@ from spconv_amd.pytorch.spatial import BallQueryAndGroup, FarthestPointSample, S
 from spconv_amd.pytorch.spatial import KNNInterpolate, KNNQueryAndGroup
 from spconv_amd.pytorch.spatial import RotatedIoU3DLoss, RotatedNMS
 from spconv_amd.pytorch.spatial import RoIAwarePool3d, RoIPointPool3d
+from spconv_amd.pytorch.spatial import CenterHeadTargets
 from spconv_amd.pytorch.vfe import DynamicVFE
 from spconv_amd.pytorch.functional import point_groups, points_to_voxels, voxels_to_points
 from spconv_amd.pytorch.functional import point_corners, voxels_to_points_trilinear
@@ -27,6 +28,7 @@ from spconv_amd.pytorch.functional import (boxes_iou3d, boxes_iou3d_aligned, box
 from spconv_amd.pytorch.functional import boxes_iou3d_diff, boxes_iou_bev_diff
 from spconv_amd.pytorch.functional import (box_query, boxes_to_frames, points_in_boxes, roi_aware_pool,
                                            roi_point_pool)
+from spconv_amd.pytorch.functional import box_centers, center_heatmap, center_heatmap_sparse
 from spconv_amd.pytorch.tables import AddTable, AddTableMisaligned, ConcatTable, JoinTable
 from spconv_amd.pytorch.pool import (SparseAvgPool1d, SparseAvgPool2d, SparseAvgPool3d,
                                      SparseGlobalAvgPool, SparseGlobalMaxPool, SparseMaxPool1d,

@@ -631,6 +631,14 @@ from spconv_amd.pytorch._boxgrad import (boxes_iou3d_diff, boxes_iou_aligned_gra
 from spconv_amd.pytorch._roi import (BoxFrames, BoxPoints, box_query, box_query_into,  # noqa: E402,F401
                                      boxes_to_frames, points_in_boxes, roi_aware_pool, roi_point_pool)
 
+# centre-head targets (csrc/center.hip; not part of the reference): the records of the ground-truth boxes, the dense
+# Gaussian heatmaps and the heat of the rows of a sparse 2-D level -- CenterHead.assign_target_of_single_head of
+# OpenPCDet and VoxelNeXt's sparse twin, without their Python loop
+from spconv_amd.pytorch._center import (BoxCenters, CenterParams, SparseCenters, box_centers,  # noqa: E402,F401
+                                        box_centers_into, center_buffers, center_groups_ws, center_heatmap,
+                                        center_heatmap_into, center_heatmap_sparse, center_heatmap_sparse_into,
+                                        center_nearest_into, center_tile)
+
 # voxel serialisation (csrc/serialize.hip; not part of the reference): rows ordered along Z-order / Hilbert curves and
 # cut into fixed-size patches, for the serialised point / voxel transformers
 from spconv_amd.pytorch import _serialize  # noqa: E402

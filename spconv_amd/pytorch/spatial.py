@@ -6,8 +6,9 @@ raw points around query points, gathered (csrc/sample.hip); ``KNNInterpolate`` /
 to many points from their nearest few, and the nearest raw points of query points, gathered (csrc/knn.hip);
 ``RotatedNMS``: rotated non-maximum suppression that stays on the device (csrc/box.hip); ``RotatedIoU3DLoss``: the
 rotated-IoU regression loss of aligned boxes, with a gradient (csrc/boxgrad.hip); ``RoIPointPool3d`` /
-``RoIAwarePool3d``: the points of every RoI, gathered or reduced per cell of a grid over the box (csrc/roi.hip)."""
-from typing import Optional, Sequence
+``RoIAwarePool3d``: the points of every RoI, gathered or reduced per cell of a grid over the box (csrc/roi.hip);
+``CenterHeadTargets``: the Gaussian heatmaps and regression rows of a centre head (csrc/center.hip)."""
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -494,3 +495,91 @@ class RoIAwarePool3d(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return f"out_size={self.out_size}, max_pts_per_box={self.max_pts_per_box}, reduce={self.reduce}"
+
+
+class CenterTargets(NamedTuple):
+    """What ``CenterHeadTargets`` returns: heatmap fp32 [B, C, H, W] (dense) or [N, C] (over the rows of a sparse
+    level), target_boxes fp32 [B, max_objs, 8 + extra], inds int32 [B, max_objs] (``iy * W + ix``; over a sparse level
+    the GLOBAL row index of the nearest row), mask int32 [B, max_objs]."""
+    heatmap: torch.Tensor
+    target_boxes: torch.Tensor
+    inds: torch.Tensor
+    mask: torch.Tensor
+
+
+class CenterHeadTargets(torch.nn.Module):
+    """The training targets of one centre head (``functional.box_centers`` / ``center_heatmap`` /
+    ``center_heatmap_sparse``, the kernels of csrc/center.hip): OpenPCDet's ``CenterHead.assign_target_of_single_head``
+    and VoxelNeXt's sparse twin without their Python loop over the boxes.  Not part of the reference.
+
+    ``grid_size``: (W, H) of the HEAD's map (OpenPCDet's ``grid_size[:2] // stride``); ``voxel_size`` (vx, vy[, vz]) and
+    ``point_cloud_range`` (x0, y0, ...) as in the data config; ``stride``: the map's stride over the voxels;
+    ``anchor`` / ``cutoff``: the sparse form's (``center_heatmap_sparse``).  ``forward(boxes, b_batch_ids, class_ids,
+    batch_size, x=None, n_boxes=None) -> CenterTargets``: boxes fp32 [M, >= 7], class_ids 0-based planes (None: class 0);
+    with `x` (a 2-D SparseConvTensor or indices [N, 3]) the heatmap is over its rows and inds are row indices.  A row of
+    target_boxes is (offset x, offset y, z, log dx, log dy, log dz, cos heading, sin heading, any columns beyond the
+    seventh as they are) of the box in that slot, the offset being the centre in cells minus the cell (over a sparse
+    level: minus the cell of the nearest row), all multiplied by the mask: plain torch over ``box_index``.  For several
+    heads call one module per head with the class ids of the other heads mapped to -1: those boxes keep their slots with
+    mask 0.  Nothing is read back.  Targets have no gradient."""
+
+    def __init__(self, num_classes: int, grid_size, voxel_size, point_cloud_range, stride, max_objs: int = 500,
+                 min_overlap: float = 0.1, min_radius: int = 2, anchor: str = "center", cutoff: str = "none"):
+        super().__init__()
+        from spconv_amd.pytorch import _center
+        op = "CenterHeadTargets"
+
+        def first2(v):
+            """the x and y entries of a tuple, list or array as the data config has it ((x, y, z), a 6-entry range)"""
+            try:
+                return tuple(v.tolist() if hasattr(v, "tolist") else v)[:2]
+            except TypeError:
+                return v                                  # (not a sequence: check_params says what it should be)
+
+        _center.check_params(op, 1, first2(grid_size), first2(voxel_size), first2(point_cloud_range), stride, num_classes,
+                             max_objs, min_overlap, min_radius)
+        if anchor not in ("center", "nearest"):
+            raise ValueError(f"{op}: anchor is 'center' or 'nearest', got {anchor!r}")
+        if cutoff not in ("none", "window"):
+            raise ValueError(f"{op}: cutoff is 'none' or 'window', got {cutoff!r}")
+        self.num_classes, self.max_objs, self.min_radius = int(num_classes), int(max_objs), int(min_radius)
+        self.grid_size = tuple(int(v) for v in first2(grid_size))
+        self.voxel_size = tuple(float(v) for v in first2(voxel_size))
+        self.range_min = tuple(float(v) for v in first2(point_cloud_range))
+        self.stride, self.min_overlap = float(stride), float(min_overlap)
+        self.anchor, self.cutoff = anchor, cutoff
+
+    def forward(self, boxes: torch.Tensor, b_batch_ids: Optional[torch.Tensor], class_ids: Optional[torch.Tensor],
+                batch_size: int, x=None, n_boxes: Optional[torch.Tensor] = None) -> CenterTargets:
+        from spconv_amd.pytorch import _center
+        from spconv_amd.pytorch import functional as F
+        centers = F.box_centers(boxes, b_batch_ids, class_ids, batch_size, grid_size=self.grid_size,
+                                voxel_size=self.voxel_size, range_min=self.range_min, stride=self.stride,
+                                num_classes=self.num_classes, max_objs=self.max_objs, min_overlap=self.min_overlap,
+                                min_radius=self.min_radius, n_boxes=n_boxes)
+        with torch.no_grad():
+            cell = centers.cell
+            if x is None:
+                heat, inds, mask = F.center_heatmap(centers), centers.inds, centers.mask
+            else:
+                sc = F.center_heatmap_sparse(centers, x, anchor=self.anchor, cutoff=self.cutoff)
+                heat, inds, mask = sc.heat, sc.inds, sc.mask
+                indices, _ = _center._level("CenterHeadTargets", x)     # (a Tensor has an `indices` method of its own)
+                if int(indices.shape[0]) > 0:       # the cell (x, y) of every box's nearest row; unused where there is none
+                    cell = indices[sc.nearest.clamp(min=0).long()][:, [2, 1]]
+            M = int(boxes.shape[0])
+            width = 8 + int(boxes.shape[1]) - 7
+            if M == 0:
+                target = boxes.new_zeros((int(batch_size), self.max_objs, width))
+            else:
+                b = boxes.detach()
+                rows = torch.cat([centers.center - cell.to(torch.float32), b[:, 2:3], b[:, 3:6].log(), b[:, 6:7].cos(),
+                                  b[:, 6:7].sin(), b[:, 7:]], dim=1)
+                target = rows[centers.box_index.clamp(min=0).long()]
+                target = torch.where((mask != 0).unsqueeze(-1), target, torch.zeros_like(target))
+        return CenterTargets(heat, target, inds, mask)
+
+    def extra_repr(self) -> str:
+        return (f"num_classes={self.num_classes}, grid_size={self.grid_size}, voxel_size={self.voxel_size}, "
+                f"range_min={self.range_min}, stride={self.stride}, max_objs={self.max_objs}, "
+                f"min_overlap={self.min_overlap}, min_radius={self.min_radius}, anchor={self.anchor}, cutoff={self.cutoff}")
