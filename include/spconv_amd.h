@@ -1525,6 +1525,43 @@ int spx_patch_plan(const int32_t *order, const int32_t *offsets, int n, int batc
 int spx_patch_rows_bwd(const void *g, int slots, const int32_t *row_slot, const int32_t *row_slot2, int n, int C,
                        int dtype, void *g_feat, spx_stream_t stream);
 
+/* ---- serialised patch attention (csrc/attn.hip) ----------------------------------------------------------------
+ * The attention step of the serialised transformers over the patches of a plan (spx_patch_plan), which Point
+ * Transformer V3 runs through flash_attn_varlen_qkvpacked_func: per patch p and head h, softmax(scale * Q K^T) V over
+ * the patch's slots.  The rows are read THROUGH the plan -- no patch-ordered copy of Q, K or V exists, no score leaves
+ * the registers -- and results go straight back to row order.  Every call: the caller allocates, every grid depends
+ * on host-known sizes only (hipGraph-safe), nothing is read back, nothing synchronises, no atomics: results are
+ * identical run to run.  The checks that need no pointer come before any pointer is looked at.
+ *
+ * qkv = [n, 3, H, D] (row r: its query, key and value of every head), SPX_F16 or SPX_BF16, 16-byte aligned; D in
+ * {16, 32, 64}; K = patch_size, a multiple of 32; P_cap * K < 2^31; scale multiplies the scores.  The plan tables are
+ * those of spx_patch_plan.  KEYS and VALUES of a patch are its slots with 0 <= patch_rows < n (borrowed duplicates
+ * count), QUERIES its slots with 0 <= patch_rows_canon < n; patches at or beyond min(*n_patches_dev, P_cap) cost one
+ * early exit.  Every plan entry is checked against its range (rows against n, slots against P_cap * K) before it
+ * addresses anything: an entry outside counts as -1.  The softmax runs in fp32 over the valid keys; P and dS are
+ * rounded to the 16-bit type for their second product (fp32 accumulate), results are rounded once.
+ *
+ * spx_patch_attn_fwd: out = [n, H, D], written whole: row r holds the result of its canonical slot, a row whose
+ * row_slot is outside [0, P_cap * K) zeros.  lse = fp32 [P_cap * K, H], slot-major: the natural log-sum-exp of the
+ * scaled scores of every query slot (other entries are not written).  Two launches: the dead rows, the patches (a
+ * workgroup per 64 query slots and 64 / D heads, walking the patch's keys in blocks of 32 with an online softmax).
+ *
+ * spx_patch_attn_bwd: out, lse as the forward left them, d_out = [n, H, D]; dqkv = [n, 3, H, D], written whole, zeros
+ * for dead rows.  Four launches: delta = rowsum(d_out * out); dQ (a workgroup per 64 query slots, walking the keys,
+ * P recomputed from lse, written to its row); dK / dV (a workgroup per 64 key slots, walking the queries, written per
+ * SLOT in fp32 to the workspace); the rows: dK / dV of row r = ws[row_slot[r]] + ws[row_slot2[r]], the canonical term
+ * first, added in fp32 and rounded once (the rule of spx_patch_rows_bwd), and the zeros of the dead rows.
+ * spx_patch_attn_ws_bytes: the backward's scratch (fp32 [n, H] + [P_cap * K, 2, H, D]); 0 for arguments that are
+ * refused. */
+size_t spx_patch_attn_ws_bytes(int n, int P_cap, int K, int H, int D);
+int spx_patch_attn_fwd(const void *qkv, const int32_t *patch_rows, const int32_t *patch_rows_canon, const int32_t *row_slot,
+                       const int32_t *n_patches_dev, int n, int P_cap, int K, int H, int D, int dt, float scale, void *out,
+                       float *lse, spx_stream_t stream);
+int spx_patch_attn_bwd(const void *qkv, const void *out, const float *lse, const void *d_out, const int32_t *patch_rows,
+                       const int32_t *patch_rows_canon, const int32_t *row_slot, const int32_t *row_slot2,
+                       const int32_t *n_patches_dev, int n, int P_cap, int K, int H, int D, int dt, float scale, void *dqkv,
+                       void *ws, size_t ws_bytes, spx_stream_t stream);
+
 /* ---- rotated boxes: corners, overlap, IoU and non-maximum suppression (csrc/box.hip) --------------------------
  * The iou3d_nms extension of OpenPCDet / mmdet3d: boxes_iou_bev, boxes_iou3d_gpu, its aligned form and nms_gpu -- the
  * rotated NMS every detector head ends in (SECOND, PointPillars, CenterPoint, VoxelNeXt, Voxel R-CNN, PV-RCNN), the

@@ -16,6 +16,7 @@ from spconv_amd.pytorch.spatial import KNNInterpolate, KNNQueryAndGroup
 from spconv_amd.pytorch.spatial import RotatedIoU3DLoss, RotatedNMS
 from spconv_amd.pytorch.spatial import RoIAwarePool3d, RoIPointPool3d
 from spconv_amd.pytorch.spatial import CenterHeadTargets
+from spconv_amd.pytorch.spatial import PatchAttention
 from spconv_amd.pytorch.vfe import DynamicVFE
 from spconv_amd.pytorch.functional import point_groups, points_to_voxels, voxels_to_points
 from spconv_amd.pytorch.functional import point_corners, voxels_to_points_trilinear

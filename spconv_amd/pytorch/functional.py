@@ -731,3 +731,45 @@ def patches_to_rows(patches, plan):
     Differentiable in the patches; borrowed and empty slots get a zero gradient."""
     _serialize.check_patches(patches, plan, "patches_to_rows")
     return PatchesToRowsFunction.apply(patches, plan)
+
+
+# serialised patch attention (csrc/attn.hip; not part of the reference): softmax(scale * Q K^T) V per patch and head,
+# read through the plan from row-ordered qkv -- the flash_attn_varlen_qkvpacked_func step of Point Transformer V3
+from spconv_amd.pytorch import _attn  # noqa: E402
+
+
+class PatchAttentionFunction(Function):
+    """qkv [n, 3 * H * D] -> out [n, H * D] over the patches of a plan (spx_patch_attn_fwd: two launches, the scores
+    never leave the registers); the backward recomputes the probabilities from the saved log-sum-exp
+    (spx_patch_attn_bwd: four launches, no atomics).  Casts nothing under autocast."""
+
+    @staticmethod
+    @_FWD_ROWS
+    def forward(ctx, qkv, plan, H, D, scale):
+        q = qkv.detach()
+        out, lse = _attn.fwd(q, plan, H, D, scale)
+        ctx.save_for_backward(q, out, lse)
+        ctx.plan, ctx.geom = plan, (H, D, scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @_BWD
+    def backward(ctx, grad_output):
+        q, out, lse = ctx.saved_tensors
+        return _attn.bwd(q, out, lse, grad_output, ctx.plan, *ctx.geom), None, None, None, None
+
+
+def patch_attention(qkv, plan, num_heads, scale=None):
+    """Multi-head self-attention inside the patches of a PatchPlan, on the MFMA kernels of csrc/attn.hip.  qkv: [n, 3 *
+    H * D] or [n, 3, H, D] in ROW order (what a Linear(C, 3C) over the level's features gives), contiguous, float16 or
+    bfloat16 -- float32 / float64 are refused, nothing is cast, not under autocast either; D in {16, 32, 64};
+    plan.patch_size a multiple of 32; either pad.  Per patch and head the keys and values are the slots that hold a row
+    (borrowed duplicates count, as Point Transformer V3 counts them), the queries the canonical slots; the softmax runs
+    in fp32 over the valid keys; scale defaults to D ** -0.5.  Returns out [n, H * D] in row order, written whole: a
+    live row holds the result of its canonical slot, a dead row zeros.  Differentiable in qkv (dqkv in qkv's shape,
+    zeros for dead rows; identical run to run); no gradient to scale or the plan.  Nothing is read back: the call can
+    sit inside a captured graph.  Not built: relative position bias, dropout, cross-attention, an fp32 kernel, a
+    returned log-sum-exp."""
+    H, D, scale = _attn.check(qkv, plan, num_heads, scale)
+    return PatchAttentionFunction.apply(qkv, plan, H, D, scale)

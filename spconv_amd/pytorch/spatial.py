@@ -583,3 +583,40 @@ class CenterHeadTargets(torch.nn.Module):
         return (f"num_classes={self.num_classes}, grid_size={self.grid_size}, voxel_size={self.voxel_size}, "
                 f"range_min={self.range_min}, stride={self.stride}, max_objs={self.max_objs}, "
                 f"min_overlap={self.min_overlap}, min_radius={self.min_radius}, anchor={self.anchor}, cutoff={self.cutoff}")
+
+
+class PatchAttention(torch.nn.Module):
+    """Multi-head self-attention inside the patches of a ``PatchPlan`` (``functional.patch_attention``, the MFMA
+    kernels of csrc/attn.hip): the attention of a Point Transformer V3 / OctFormer / FlatFormer-style block without its
+    relative position bias and dropout.  Not part of the reference.
+
+    ``channels`` = ``num_heads`` * D with D in {16, 32, 64}; ``qkv_bias``: the bias of the ``qkv`` Linear; ``proj``: a
+    Linear(channels, channels) behind the attention; ``scale``: None = D ** -0.5.  ``forward(features, plan) -> [n,
+    channels]``: features [n, channels] in row order; ``qkv`` is cast to the autocast dtype, or to float16 outside
+    autocast (the kernels take 16-bit rows only), and the result comes back in the features' dtype.  Dead rows give
+    zeros ahead of ``proj``."""
+
+    def __init__(self, channels: int, num_heads: int, qkv_bias: bool = True, proj: bool = True,
+                 scale: Optional[float] = None):
+        super().__init__()
+        from spconv_amd.pytorch import _attn
+        if int(num_heads) < 1 or int(channels) % int(num_heads) != 0:
+            raise ValueError(f"PatchAttention: channels ({channels}) must be a multiple of num_heads ({num_heads})")
+        if int(channels) // int(num_heads) not in _attn.HEAD_SIZES:
+            raise NotImplementedError(f"PatchAttention: channels / num_heads must be one of {list(_attn.HEAD_SIZES)}, "
+                                      f"got {int(channels) // int(num_heads)}")
+        self.channels, self.num_heads = int(channels), int(num_heads)
+        self.scale = None if scale is None else float(scale)
+        self.qkv = torch.nn.Linear(self.channels, 3 * self.channels, bias=bool(qkv_bias))
+        self.proj = torch.nn.Linear(self.channels, self.channels) if proj else None
+
+    def forward(self, features: torch.Tensor, plan) -> torch.Tensor:
+        from spconv_amd.pytorch import functional as F
+        half = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float16
+        if half not in (torch.float16, torch.bfloat16):
+            half = torch.float16
+        out = F.patch_attention(self.qkv(features).to(half), plan, self.num_heads, self.scale).to(features.dtype)
+        return out if self.proj is None else self.proj(out)
+
+    def extra_repr(self) -> str:
+        return f"channels={self.channels}, num_heads={self.num_heads}, scale={self.scale}"
