@@ -1336,6 +1336,40 @@ int spx_fps_segments(const float *points, int nfeat, int n_cap, int ndim, const 
                      int groups, const int32_t *quota, const int32_t *slot, int groups_per_row, int row_stride,
                      int max_quota, int32_t *idx, int32_t *count, void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* ---- exact farthest-point sampling with bucket pruning (csrc/fps_bucket.hip) -----------------------------------
+ * spx_fps for large scenes: the SAME idx and count, bit for bit (scenes, validity, slot 0, ties, distinct indices and -1
+ * at or behind count as stated there), by a path whose step visits only the points it can change.  Every call: the
+ * caller allocates, nothing is read back, nothing synchronises, every grid depends on host-known sizes only
+ * (hipGraph-safe), no atomics.  The argument checks that need no pointer come before any pointer is looked at.  The
+ * launches of the two entries are not counted by spx_launch_count (the sort inside the build counts as spx_serialize).
+ *
+ *   spx_fps_bucket_build: points / offsets / list as spx_fps.  Writes into ws the scenes' boxes (fp32 min / max of the
+ *   valid points), a 64-bit key per list position (scene << 30 | Morton code of the coordinates quantised to 10 bits per
+ *   axis inside the scene's box, all ones for an invalid point or a position in no scene), the order of spx_serialize
+ *   over these keys with its scene offsets, and per sorted position a 16-byte {x, y, z, t} record and the point index.
+ *   The quantisation decides speed, never a result.  Four launches and the sort's (none but the offsets' for n_cap = 0).
+ *   spx_fps_bucket: samples from the ws of a build with the same n_cap, ndim and batch (it may run again, with another
+ *   num_samples).  A BUCKET is a run of spx_fps_bucket_points() << shift = 64 << shift sorted positions of a scene,
+ *   shift the smallest that keeps the scene at or under spx_fps_bucket_cap() = 1280 buckets.  One workgroup of 1024
+ *   lanes per scene keeps per bucket the box of its points, the largest candidate t with the lowest point index that has
+ *   it, and that point's coordinates in 60 KB of static LDS (no opt-in to more); a step updates the buckets whose box
+ *   lies nearer to the last sample than their largest t, and the last sample's own.
+ *   EXACTNESS: rounding is monotone, so for a point p inside a box |fl(p_j - c_j)| >= the box term of every axis (lo_j -
+ *   c_j if positive, else hi_j - c_j if negative, else 0) and fl-d2(p - c) >= the fl-box distance, both in the operation
+ *   order of d2 above with no FMA.  A box distance >= the bucket's largest t makes d2 < t false for each of its
+ *   candidates: skipping the bucket changes nothing.
+ *   visits = NULL or int32 [batch]: bucket table entries written for the scene -- every bucket once at the start, then the
+ *   buckets updated by each step --, <= count[b] * buckets, equal to it for a sampler that never prunes.
+ *   Requires n_cap <= spx_fps_bucket_cap() * (64 << 8) = 20 971 520.  One launch.
+ *   spx_fps_bucket_ws_bytes: the scratch of both; monotone in n_cap; 0 for refused arguments. */
+int spx_fps_bucket_cap(void);
+int spx_fps_bucket_points(void);
+size_t spx_fps_bucket_ws_bytes(int n_cap, int batch, int ndim);
+int spx_fps_bucket_build(const float *points, int nfeat, int n_cap, int ndim, const int32_t *offsets,
+                         const int32_t *list, int batch, void *ws, size_t ws_bytes, spx_stream_t stream);
+int spx_fps_bucket(int n_cap, int ndim, int batch, int num_samples, int32_t *idx, int32_t *count, int32_t *visits,
+                   void *ws, size_t ws_bytes, spx_stream_t stream);
+
 /* ---- k-nearest-neighbour query and inverse-distance weights over raw points (csrc/knn.hip) ------------------
  * The way back from few points to many, and grouping by nearest neighbours instead of by radius: three_nn +
  * three_interpolate of pointnet2's feature propagation (PointNet++, PointRCNN, 3DSSD, IA-SSD, the point heads of the

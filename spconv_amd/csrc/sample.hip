@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include "fill.h"
+#include "fps.h"
 #include "scenes.h"
 
 // no multiply-add pair of this unit may be contracted into an FMA (see pointvoxel.hip)
@@ -43,16 +44,10 @@
 namespace spx {
 namespace {
 
-constexpr int kFpsBlock = 1024, kFpsWaves = kFpsBlock / kWave;
 constexpr int kFpsPer = 16;                          // points per lane of the register tier
 constexpr int kFpsResident = kFpsBlock * kFpsPer;
 constexpr int kFpsAhead = 6;                         // records of a batch of the streamed tier; a lane keeps two batches
-constexpr int kMaxSamples = 1 << 16;
 constexpr int kMaxSample = 128;
-
-struct __attribute__((aligned(16))) FpsRec {
-  float x, y, z, t;
-};
 
 // -------------------------------------------------------------------------------------------- farthest-point sampling
 
@@ -82,14 +77,6 @@ __device__ __forceinline__ void consider(Best<NDIM> &best, float t, int pos, con
   best.pos = take ? pos : best.pos;
 #pragma unroll
   for (int j = 0; j < NDIM; ++j) best.c[j] = take ? p[j] : best.c[j];
-}
-
-template <int NDIM> __device__ __forceinline__ float fold(float t, const float (&p)[NDIM], const float (&c)[NDIM]) {
-  float d[NDIM];
-#pragma unroll
-  for (int j = 0; j < NDIM; ++j) d[j] = p[j] - c[j];
-  const float d2 = dist2<NDIM>(d);
-  return d2 < t ? d2 : t;                             // (false for t < 0: a non-candidate stays one)
 }
 
 // The register tier: lane `tid` holds positions tid + 1024 j, j < 16.  Every loop is unrolled with constant bounds (the
@@ -184,35 +171,6 @@ template <int NDIM> struct StreamedPoints {
     }
   }
 };
-
-// max(k, k of the lane the DPP control names): both halves move with the same control
-template <int CTRL> __device__ __forceinline__ u64 dpp_max(u64 k) {
-  const uint32_t lo = static_cast<uint32_t>(
-      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<uint32_t>(k)), CTRL, 0xf, 0xf, false));
-  const uint32_t hi = static_cast<uint32_t>(
-      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<uint32_t>(k >> 32)), CTRL, 0xf, 0xf, false));
-  const u64 o = (static_cast<u64>(hi) << 32) | lo;
-  return o > k ? o : k;
-}
-
-// The maximum over the wave, in every lane (all 64 active).  Inside a row of 16 lanes a butterfly of DPP moves -- lane ^
-// 1, lane ^ 2 (quad permutes), then the mirrored half row and the mirrored row, which reach the other quad / half row: a
-// maximum does not mind which lane of it -- and the four row results through readlane.
-__device__ __forceinline__ u64 wave_max(u64 k) {
-  k = dpp_max<0xB1>(k);                                 // quad_perm:[1,0,3,2]
-  k = dpp_max<0x4E>(k);                                 // quad_perm:[2,3,0,1]
-  k = dpp_max<0x141>(k);                                // row_half_mirror
-  k = dpp_max<0x140>(k);                                // row_mirror
-  u64 r = 0ull;
-#pragma unroll
-  for (int row = 0; row < kWave; row += 16) {
-    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(k)), row));
-    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(k >> 32)), row));
-    const u64 o = (static_cast<u64>(hi) << 32) | lo;
-    r = o > r ? o : r;
-  }
-  return r;
-}
 
 struct FpsShared {
   u64 key[2][kFpsWaves];

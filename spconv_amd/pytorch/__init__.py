@@ -21,7 +21,8 @@ from spconv_amd.pytorch.vfe import DynamicVFE
 from spconv_amd.pytorch.functional import point_groups, points_to_voxels, voxels_to_points
 from spconv_amd.pytorch.functional import point_corners, voxels_to_points_trilinear
 from spconv_amd.pytorch.functional import group_voxels, voxel_query
-from spconv_amd.pytorch.functional import ball_query, farthest_point_sample, gather_samples
+from spconv_amd.pytorch.functional import (ball_query, farthest_point_sample, farthest_point_sample_method,  # noqa: F401
+                                           gather_samples)
 from spconv_amd.pytorch.functional import farthest_point_sample_segments, sector_fps, sector_ids
 from spconv_amd.pytorch.functional import knn_interpolate, knn_query, three_nn
 from spconv_amd.pytorch.functional import (boxes_iou3d, boxes_iou3d_aligned, boxes_iou_bev, boxes_overlap_bev,

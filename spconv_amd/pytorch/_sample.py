@@ -8,6 +8,9 @@ source) call them as the ``furthest_point_sample`` / ``ball_query`` CUDA extensi
                             ready ``PointGroups`` (``scene_groups``) so a caller builds it once
   * ``farthest_point_sample``  K samples per scene (``spx_fps``: one workgroup per scene, one launch), ties to the lowest
                             point index, distinct indices, -1 past the scene's valid points
+  * ``farthest_point_sample_method``  the same samples, bit for bit, by ``method`` "scan" (the above) or "bucket"
+                            (``spx_fps_bucket_build`` + ``spx_fps_bucket``, csrc/fps_bucket.hip: the points sorted along a
+                            Z-order curve and cut into buckets, a step updating only the buckets it can change)
   * ``gather_samples``      the sampled rows, NaN in dead slots (``gather_rows``): a dead slot is an invalid query for
                             ``voxel_query``, ``point_corners`` and ``ball_query`` alike
   * ``ball_query``          per query the first ``nsample`` points of its scene inside a radius, in ascending point
@@ -114,6 +117,87 @@ def fps_into(points: torch.Tensor, groups: PointGroups, num_samples: int, ndim: 
                                    0 if ws is None else ws.numel(), _stream(points)))
 
 
+METHODS = ("scan", "bucket")
+
+
+def bucket_cap() -> int:
+    """The most buckets ``spx_fps_bucket`` cuts a scene into."""
+    return int(_lib.load().spx_fps_bucket_cap())
+
+
+def bucket_points() -> int:
+    """The records of a bucket while its scene holds up to ``bucket_cap() * bucket_points()`` points; twice as many,
+    and so on, beyond."""
+    return int(_lib.load().spx_fps_bucket_points())
+
+
+def fps_bucket_ws_bytes(n_cap: int, batch_size: int, ndim: int) -> int:
+    return int(_lib.load().spx_fps_bucket_ws_bytes(int(n_cap), int(batch_size), int(ndim)))
+
+
+def _check_method(op: str, method) -> str:
+    if method not in METHODS:
+        raise ValueError(f"{op}: method is 'scan' or 'bucket', got {method!r}")
+    return method
+
+
+def fps_bucket_into(points: torch.Tensor, groups: PointGroups, num_samples: int, ndim: int, idx: torch.Tensor,
+                    count: torch.Tensor, ws: torch.Tensor, visits: Optional[torch.Tensor] = None) -> None:
+    """The two C calls of the bucket path into buffers the caller owns (no allocation: capturable): the build (boxes,
+    keys, sort, records) and the sampling.  idx int32 [B, K], count int32 [B], ws: ``fps_bucket_ws_bytes`` bytes, visits
+    None or int32 [B] (bucket table entries written per scene)."""
+    L, n, B = _lib.load(), int(points.shape[0]), int(groups.num_voxels)
+    _lib.check(L.spx_fps_bucket_build(points.data_ptr(), int(points.shape[1]), n, int(ndim), groups.offsets.data_ptr(),
+                                      groups.list.data_ptr(), B, ws.data_ptr(), ws.numel(), _stream(points)))
+    _lib.check(L.spx_fps_bucket(n, int(ndim), B, int(num_samples), idx.data_ptr(), count.data_ptr(), _ptr(visits),
+                                ws.data_ptr(), ws.numel(), _stream(points)))
+
+
+def farthest_point_sample_method(points: torch.Tensor, batch_ids: Optional[torch.Tensor], batch_size: int,
+                                 num_samples: int, method: str = "scan", *, ndim: int = 3,
+                                 n_points: Optional[torch.Tensor] = None, groups: Optional[PointGroups] = None,
+                                 with_visits: bool = False):
+    """``farthest_point_sample`` by `method`: "scan" (``spx_fps``: every step passes over the whole scene) or "bucket"
+    (``spx_fps_bucket``: the scene's points sorted along a Z-order curve and cut into buckets of 64 or more, a step
+    updating only the buckets whose box lies nearer to the last sample than their largest t).  Both return the SAME
+    PointSamples, bit for bit: rounding is monotone, so the fp32 box distance never exceeds the fp32 distance of a point
+    inside the box, and a bucket that is skipped holds no t the step would change.  `with_visits` (bucket only) adds
+    int32 [B]: the bucket table entries written per scene, ``count[b] * buckets`` for a sampler that prunes nothing.
+    Any other method is a ValueError.  Nothing is read back.  No gradient with respect to coordinates."""
+    op = "farthest_point_sample"
+    K, B = int(num_samples), int(batch_size)
+    _check_method(op, method)
+    N = _check_cloud(op, "points", points, batch_ids, B, ndim)
+    if not 1 <= K <= MAX_SAMPLES:
+        raise ValueError(f"{op}: num_samples must be in 1 .. {MAX_SAMPLES}, got {num_samples}")
+    if B * K >= 1 << 31:
+        raise ValueError(f"{op}: {B} scenes x {K} samples do not fit 32-bit entries")
+    if with_visits and method != "bucket":
+        raise ValueError(f"{op}: with_visits needs method 'bucket', got {method!r}")
+    if groups is not None:
+        _check_groups(op, groups, N, B)
+    _require_cloud(op, "points", points, batch_ids, n_points)
+    dev = points.device
+    with torch.cuda.device(dev), torch.no_grad():
+        points = points.detach().contiguous()
+        if groups is None:
+            groups = scene_groups(None if batch_ids is None else batch_ids.contiguous(), N, B, n_points, dev)
+        idx = torch.empty((B, K), dtype=torch.int32, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        visits = None
+        if method == "bucket":
+            nbytes = fps_bucket_ws_bytes(N, B, ndim)
+            if nbytes == 0:
+                raise ValueError(f"{op}: method 'bucket' takes up to {bucket_cap() * (bucket_points() << 8)} points, got {N}")
+            visits = torch.empty((B,), dtype=torch.int32, device=dev) if with_visits else None
+            fps_bucket_into(points, groups, K, ndim, idx, count, _ws(nbytes, dev), visits)
+        else:
+            ws = _ws(fps_ws_bytes(N, B, ndim), dev) if N > resident_points() else None
+            fps_into(points, groups, K, ndim, idx, count, ws)
+        samples = PointSamples(idx, count, sample_batch_ids(B, K, dev))
+        return (samples, visits) if with_visits else samples
+
+
 def farthest_point_sample(points: torch.Tensor, batch_ids: Optional[torch.Tensor], batch_size: int, num_samples: int, *,
                           ndim: int = 3, n_points: Optional[torch.Tensor] = None,
                           groups: Optional[PointGroups] = None) -> PointSamples:
@@ -125,27 +209,11 @@ def farthest_point_sample(points: torch.Tensor, batch_ids: Optional[torch.Tensor
     and picks the not-yet-chosen point with the largest t, ties to the LOWEST point index.  A chosen point stops being a
     candidate: the indices of a scene are distinct (pointnet2 repeats one once only duplicates are left; for distinct
     points the sequences agree).  Returns PointSamples(idx [B, K] with -1 at or beyond count[b], count [B] = min(valid
-    points, K), batch_ids [B * K]).  `groups`: a ready ``scene_groups`` of the cloud.  One launch, nothing read back.
+    points, K), batch_ids [B * K]).  `groups`: a ready ``scene_groups`` of the cloud.  One launch, nothing read back
+    (``farthest_point_sample_method`` with method "scan"; its "bucket" gives the same samples faster on large scenes).
     No gradient with respect to coordinates."""
-    K, B = int(num_samples), int(batch_size)
-    N = _check_cloud("farthest_point_sample", "points", points, batch_ids, B, ndim)
-    if not 1 <= K <= MAX_SAMPLES:
-        raise ValueError(f"farthest_point_sample: num_samples must be in 1 .. {MAX_SAMPLES}, got {num_samples}")
-    if B * K >= 1 << 31:
-        raise ValueError(f"farthest_point_sample: {B} scenes x {K} samples do not fit 32-bit entries")
-    if groups is not None:
-        _check_groups("farthest_point_sample", groups, N, B)
-    _require_cloud("farthest_point_sample", "points", points, batch_ids, n_points)
-    dev = points.device
-    with torch.cuda.device(dev), torch.no_grad():
-        points = points.detach().contiguous()
-        if groups is None:
-            groups = scene_groups(None if batch_ids is None else batch_ids.contiguous(), N, B, n_points, dev)
-        idx = torch.empty((B, K), dtype=torch.int32, device=dev)
-        count = torch.empty((B,), dtype=torch.int32, device=dev)
-        ws = _ws(fps_ws_bytes(N, B, ndim), dev) if N > resident_points() else None
-        fps_into(points, groups, K, ndim, idx, count, ws)
-        return PointSamples(idx, count, sample_batch_ids(B, K, dev))
+    return farthest_point_sample_method(points, batch_ids, batch_size, num_samples, "scan", ndim=ndim, n_points=n_points,
+                                        groups=groups)
 
 
 def gather_samples(points: torch.Tensor, samples: PointSamples) -> torch.Tensor:

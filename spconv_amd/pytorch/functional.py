@@ -601,6 +601,10 @@ from spconv_amd.pytorch._query import (VoxelNeighbors, group_voxels, voxel_query
 from spconv_amd.pytorch._sample import (PointSamples, ball_query, ball_query_into,  # noqa: E402,F401
                                         farthest_point_sample, fps_into, gather_samples, scene_groups)
 
+# the same samples with a choice of path (csrc/fps_bucket.hip): "bucket" sorts a scene along a Z-order curve and lets a
+# step update only the buckets it can change
+from spconv_amd.pytorch._sample import farthest_point_sample_method, fps_bucket_into  # noqa: E402,F401
+
 # sectorised keypoint sampling (csrc/sample.hip; not part of the reference): segment ids by scene, RoI filter and azimuth
 # sector, a quota per segment and farthest-point sampling with K read per segment -- PV-RCNN++'s
 # sectorized_proposal_centric_sampling, pointnet2_stack's stack_farthest_point_sample

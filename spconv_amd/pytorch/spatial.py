@@ -196,11 +196,14 @@ class FarthestPointSample(torch.nn.Module):
     batch_size, n_points=None, groups=None) -> PointSamples(idx [B, K], count [B], batch_ids [B * K])``: points fp32
     [N, >= ndim], batch_ids int32 [N] or None.  Ties go to the lowest point index, the indices of a scene are distinct,
     slots beyond a scene's valid points hold -1.  ``functional.gather_samples(points, samples)`` gives the sampled rows
-    (NaN in dead slots).  No gradient with respect to coordinates."""
+    (NaN in dead slots).  ``method``: "scan" (every step passes over the scene) or "bucket" (csrc/fps_bucket.hip: a step
+    updates only the buckets of Z-ordered points it can change); the samples are the same, bit for bit.  No gradient
+    with respect to coordinates."""
 
-    def __init__(self, num_samples: int, ndim: int = 3):
+    def __init__(self, num_samples: int, ndim: int = 3, *, method: str = "scan"):
         super().__init__()
         from spconv_amd.pytorch import _sample
+        self.method = _sample._check_method("FarthestPointSample", method)
         if not 1 <= int(num_samples) <= _sample.MAX_SAMPLES:
             raise ValueError(f"FarthestPointSample: num_samples must be in 1 .. {_sample.MAX_SAMPLES}, got {num_samples}")
         if ndim not in (2, 3):
@@ -210,11 +213,11 @@ class FarthestPointSample(torch.nn.Module):
     def forward(self, points: torch.Tensor, batch_ids: Optional[torch.Tensor], batch_size: int,
                 n_points: Optional[torch.Tensor] = None, groups=None):
         from spconv_amd.pytorch import functional as F
-        return F.farthest_point_sample(points, batch_ids, batch_size, self.num_samples, ndim=self.ndim, n_points=n_points,
-                                       groups=groups)
+        return F.farthest_point_sample_method(points, batch_ids, batch_size, self.num_samples, self.method, ndim=self.ndim,
+                                              n_points=n_points, groups=groups)
 
     def extra_repr(self) -> str:
-        return f"num_samples={self.num_samples}, ndim={self.ndim}"
+        return f"num_samples={self.num_samples}, ndim={self.ndim}" + ("" if self.method == "scan" else f", method={self.method}")
 
 
 class SectorFPS(torch.nn.Module):
