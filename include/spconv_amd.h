@@ -1596,6 +1596,36 @@ int spx_patch_attn_bwd(const void *qkv, const void *out, const float *lse, const
                        const int32_t *n_patches_dev, int n, int P_cap, int K, int H, int D, int dt, float scale, void *dqkv,
                        void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* The same attention with Point Transformer V3's relative position bias (its RPE) inside the kernels: for query slot
+ * i and key slot j of a patch, with c the three integer grid coordinates of a slot's row and R = 2 * pos_bnd + 1,
+ *   logit[h, i, j] = scale * q_i . k_j + sum over a in 0 .. 2 of rel_bias[a * R + clamp(c_i[a] - c_j[a], -pos_bnd,
+ *   pos_bnd) + pos_bnd, h].
+ * rel_bias = fp32 [3 * R, H], axis-major (PTv3's layout); coords = int32 [n, 3] in row order, read through the plan
+ * like the rows (a borrowed key slot carries its row's coordinates); pos_bnd in 1 .. 63, given by the caller and never
+ * recomputed.  The bias is added in fp32 ahead of the running maximum; lse includes it.  Everything else -- arguments,
+ * checks, outputs, launches, the rule for dead rows and unused patches -- is as in spx_patch_attn_fwd / _bwd, whose
+ * callers are untouched.  No score, no bias matrix and no index tensor exist in memory.
+ *
+ * spx_patch_attn_bias_bwd also writes d_rel_bias = fp32 [3 * R, H] WHOLE: entry (a * R + bin, h) is the sum of dS[h,
+ * i, j] = P (dP - delta) in fp32 over every patch and every pair whose axis-a bin it is; a bin no pair reaches is +0.
+ * Here delta is NOT rowsum(d_out * out): a first walk of the dQ kernel takes it as sum_j P dP in fp32 (and leaves it to
+ * the dK / dV kernel), so a query's dS add up to zero and the rounding of the 16-bit out does not gather in the bins;
+ * the delta launch is not run.  The second walk adds dS per wave into LDS and stores one partial table per workgroup
+ * into bias_ws, and a fifth launch adds the partials of the workgroups below the device-side patch count in a fixed order: no global atomics, no
+ * memset, stale bias_ws is never read.  ws is the workspace of spx_patch_attn_ws_bytes; bias_ws holds
+ * spx_patch_attn_bias_ws_bytes (fp32 [P_cap * ceil(K / 64), 3 * R, H rounded up to a multiple of 64 / D]; 0 for
+ * arguments that are refused), 16-byte aligned.  n = 0 launches nothing and leaves d_rel_bias unwritten. */
+size_t spx_patch_attn_bias_ws_bytes(int P_cap, int K, int H, int D, int pos_bnd);
+int spx_patch_attn_bias_fwd(const void *qkv, const int32_t *patch_rows, const int32_t *patch_rows_canon,
+                            const int32_t *row_slot, const int32_t *n_patches_dev, const float *rel_bias,
+                            const int32_t *coords, int n, int P_cap, int K, int H, int D, int dt, float scale, int pos_bnd,
+                            void *out, float *lse, spx_stream_t stream);
+int spx_patch_attn_bias_bwd(const void *qkv, const void *out, const float *lse, const void *d_out, const int32_t *patch_rows,
+                            const int32_t *patch_rows_canon, const int32_t *row_slot, const int32_t *row_slot2,
+                            const int32_t *n_patches_dev, const float *rel_bias, const int32_t *coords, int n, int P_cap, int K,
+                            int H, int D, int dt, float scale, int pos_bnd, void *dqkv, float *d_rel_bias, void *ws,
+                            size_t ws_bytes, void *bias_ws, size_t bias_ws_bytes, spx_stream_t stream);
+
 /* ---- rotated boxes: corners, overlap, IoU and non-maximum suppression (csrc/box.hip) --------------------------
  * The iou3d_nms extension of OpenPCDet / mmdet3d: boxes_iou_bev, boxes_iou3d_gpu, its aligned form and nms_gpu -- the
  * rotated NMS every detector head ends in (SECOND, PointPillars, CenterPoint, VoxelNeXt, Voxel R-CNN, PV-RCNN), the

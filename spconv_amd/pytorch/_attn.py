@@ -6,7 +6,11 @@ of the reference.  There is no composite to fall back to.
   * ``fwd``  two launches (``spx_patch_attn_fwd``): out [n, H * D] in row order, and the log-sum-exp of every query slot
   * ``bwd``  four launches (``spx_patch_attn_bwd``): delta, dQ, dK / dV per slot in fp32, the rows; no atomics
 
-Not built: relative position bias, dropout, cross-attention, fp32 / fp64 kernels, a returned log-sum-exp.
+With ``rel_bias`` (Point Transformer V3's relative position encoding) the calls go to ``spx_patch_attn_bias_fwd`` /
+``_bwd``: the BIAS instances of the kernels; in the backward a first walk of the dQ kernel takes delta = sum P dP in
+place of the delta launch, and a fifth launch adds the workgroups' partial tables to the table's gradient.
+
+Not built: dropout, cross-attention, fp32 / fp64 kernels, a returned log-sum-exp, bias tables in 16 bits.
 """
 from __future__ import annotations
 
@@ -54,6 +58,33 @@ def check(qkv: torch.Tensor, plan: PatchPlan, num_heads: int, scale: Optional[fl
     return H, D, float(D ** -0.5 if scale is None else scale)
 
 
+def default_pos_bnd(patch_size: int) -> int:
+    """Point Transformer V3's bound of the relative position, computed exactly as its RPE computes it"""
+    return int((4 * patch_size) ** (1 / 3) * 2)
+
+
+def check_bias(qkv: torch.Tensor, plan: PatchPlan, H: int, rel_bias, coords, pos_bnd) -> int:
+    """pos_bnd of a biased call; the table and the coordinates are refused, never cast."""
+    op = "patch_attention"
+    if rel_bias is None or coords is None:
+        raise ValueError(f"{op}: rel_bias and coords come together (coords is normally x.indices[:, 1:])")
+    pb = default_pos_bnd(int(plan.patch_size)) if pos_bnd is None else pos_bnd
+    if not isinstance(pb, int) or isinstance(pb, bool) or not 1 <= pb <= 63:
+        raise ValueError(f"{op}: pos_bnd must be an integer in 1 .. 63, got {pb!r}")
+    n = int(qkv.shape[0])
+    if rel_bias.dtype != torch.float32 or tuple(rel_bias.shape) != (3 * (2 * pb + 1), H):
+        raise ValueError(f"{op}: rel_bias must be float32 [3 * (2 * pos_bnd + 1), H] = [{3 * (2 * pb + 1)}, {H}] (nothing "
+                         f"is cast), got {rel_bias.dtype} {tuple(rel_bias.shape)}")
+    if coords.dtype != torch.int32 or tuple(coords.shape) != (n, 3) or coords.device != qkv.device:
+        raise ValueError(f"{op}: coords must be int32 [n, 3] = [{n}, 3] on the rows' device (nothing is cast), got "
+                         f"{coords.dtype} {tuple(coords.shape)} on {coords.device}")
+    if rel_bias.device != qkv.device:
+        raise ValueError(f"{op}: rel_bias must be on the rows' device, got {rel_bias.device}")
+    if coords.requires_grad:
+        raise ValueError(f"{op}: coords takes no gradient")
+    return pb
+
+
 def _tables(plan: PatchPlan):
     return (plan.patch_rows.data_ptr(), plan.patch_rows_canon.data_ptr(), plan.row_slot.data_ptr())
 
@@ -90,3 +121,42 @@ def bwd(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, d_out: torch.Te
                                             _CODES[qkv.dtype], scale, dqkv.data_ptr(), ws.data_ptr(), ws.numel(),
                                             _stream(qkv)))
     return dqkv
+
+
+def fwd_bias(qkv: torch.Tensor, plan: PatchPlan, H: int, D: int, scale: float, rel_bias: torch.Tensor, coords: torch.Tensor,
+             pos_bnd: int):
+    """(out, lse) of the biased forward; rel_bias and coords contiguous"""
+    P_cap, K = (int(v) for v in plan.patch_rows.shape)
+    n, dev = int(qkv.shape[0]), qkv.device
+    with torch.cuda.device(dev):
+        out = torch.empty((n, H * D), dtype=qkv.dtype, device=dev)
+        lse = torch.empty((P_cap * K, H), dtype=torch.float32, device=dev)
+        if n > 0:
+            _lib.check(_lib.load().spx_patch_attn_bias_fwd(
+                qkv.data_ptr(), *_tables(plan), plan.n_patches_dev.data_ptr(), rel_bias.data_ptr(), coords.data_ptr(), n,
+                P_cap, K, H, D, _CODES[qkv.dtype], scale, pos_bnd, out.data_ptr(), lse.data_ptr(), _stream(qkv)))
+    return out, lse
+
+
+def bwd_bias(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, d_out: torch.Tensor, plan: PatchPlan, H: int, D: int,
+             scale: float, rel_bias: torch.Tensor, coords: torch.Tensor, pos_bnd: int):
+    """(dqkv, d_rel_bias fp32 in the table's shape, written whole)"""
+    P_cap, K = (int(v) for v in plan.patch_rows.shape)
+    n, dev = int(qkv.shape[0]), qkv.device
+    if d_out.dtype != qkv.dtype:
+        raise NotImplementedError(f"patch_attention: the gradient arrives as {d_out.dtype}, the rows are {qkv.dtype}")
+    d_out = d_out.contiguous()
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        dqkv = torch.empty_like(qkv)
+        if n == 0:
+            return dqkv, torch.zeros_like(rel_bias)
+        d_table = torch.empty_like(rel_bias)
+        ws = _ws(int(L.spx_patch_attn_ws_bytes(n, P_cap, K, H, D)), dev)
+        part = _ws(int(L.spx_patch_attn_bias_ws_bytes(P_cap, K, H, D, pos_bnd)), dev)
+        _lib.check(L.spx_patch_attn_bias_bwd(
+            qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), d_out.data_ptr(), *_tables(plan), plan.row_slot2.data_ptr(),
+            plan.n_patches_dev.data_ptr(), rel_bias.data_ptr(), coords.data_ptr(), n, P_cap, K, H, D, _CODES[qkv.dtype],
+            scale, pos_bnd, dqkv.data_ptr(), d_table.data_ptr(), ws.data_ptr(), ws.numel(), part.data_ptr(), part.numel(),
+            _stream(qkv)))
+    return dqkv, d_table

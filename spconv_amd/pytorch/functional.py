@@ -764,7 +764,29 @@ class PatchAttentionFunction(Function):
         return _attn.bwd(q, out, lse, grad_output, ctx.plan, *ctx.geom), None, None, None, None
 
 
-def patch_attention(qkv, plan, num_heads, scale=None):
+class PatchAttentionBiasFunction(Function):
+    """PatchAttentionFunction with Point Transformer V3's relative position bias inside the kernels
+    (spx_patch_attn_bias_fwd / _bwd): gradients to qkv and to the table, none to the coordinates."""
+
+    @staticmethod
+    @_FWD_ROWS
+    def forward(ctx, qkv, rel_bias, coords, plan, H, D, scale, pos_bnd):
+        q, table, coords = qkv.detach(), rel_bias.detach().contiguous(), coords.contiguous()
+        out, lse = _attn.fwd_bias(q, plan, H, D, scale, table, coords, pos_bnd)
+        ctx.save_for_backward(q, out, lse, table, coords)
+        ctx.plan, ctx.geom, ctx.pos_bnd = plan, (H, D, scale), pos_bnd
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @_BWD
+    def backward(ctx, grad_output):
+        q, out, lse, table, coords = ctx.saved_tensors
+        dqkv, d_table = _attn.bwd_bias(q, out, lse, grad_output, ctx.plan, *ctx.geom, table, coords, ctx.pos_bnd)
+        return dqkv, d_table, None, None, None, None, None, None
+
+
+def patch_attention(qkv, plan, num_heads, scale=None, *, rel_bias=None, coords=None, pos_bnd=None):
     """Multi-head self-attention inside the patches of a PatchPlan, on the MFMA kernels of csrc/attn.hip.  qkv: [n, 3 *
     H * D] or [n, 3, H, D] in ROW order (what a Linear(C, 3C) over the level's features gives), contiguous, float16 or
     bfloat16 -- float32 / float64 are refused, nothing is cast, not under autocast either; D in {16, 32, 64};
@@ -773,7 +795,19 @@ def patch_attention(qkv, plan, num_heads, scale=None):
     in fp32 over the valid keys; scale defaults to D ** -0.5.  Returns out [n, H * D] in row order, written whole: a
     live row holds the result of its canonical slot, a dead row zeros.  Differentiable in qkv (dqkv in qkv's shape,
     zeros for dead rows; identical run to run); no gradient to scale or the plan.  Nothing is read back: the call can
-    sit inside a captured graph.  Not built: relative position bias, dropout, cross-attention, an fp32 kernel, a
-    returned log-sum-exp."""
+    sit inside a captured graph.
+
+    rel_bias: Point Transformer V3's relative position encoding, added inside the kernels.  A float32 table [3 * (2 *
+    pos_bnd + 1), H], axis-major (PTv3's ``rpe_table``); coords int32 [n, 3] in row order, normally x.indices[:, 1:];
+    pos_bnd in 1 .. 63, by default PTv3's int((4 * patch_size) ** (1 / 3) * 2).  The logit of query i and key j gains
+    the sum over the three axes a of rel_bias[a * (2 * pos_bnd + 1) + clamp(c_i[a] - c_j[a], -pos_bnd, pos_bnd) +
+    pos_bnd, h], in fp32.  Differentiable in rel_bias too (float32, written whole, identical run to run); coords takes no
+    gradient.  A table of another dtype or shape, other coords and a pos_bnd outside 1 .. 63 are refused.  Without
+    rel_bias the call is the one it was: the same kernels and launches.
+
+    Not built: dropout, cross-attention, an fp32 kernel, a returned log-sum-exp, a 16-bit table, other than three axes."""
     H, D, scale = _attn.check(qkv, plan, num_heads, scale)
-    return PatchAttentionFunction.apply(qkv, plan, H, D, scale)
+    if rel_bias is None and coords is None and pos_bnd is None:
+        return PatchAttentionFunction.apply(qkv, plan, H, D, scale)
+    pos_bnd = _attn.check_bias(qkv, plan, H, rel_bias, coords, pos_bnd)
+    return PatchAttentionBiasFunction.apply(qkv, rel_bias, coords, plan, H, D, scale, pos_bnd)

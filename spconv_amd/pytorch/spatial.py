@@ -591,16 +591,19 @@ class CenterHeadTargets(torch.nn.Module):
 class PatchAttention(torch.nn.Module):
     """Multi-head self-attention inside the patches of a ``PatchPlan`` (``functional.patch_attention``, the MFMA
     kernels of csrc/attn.hip): the attention of a Point Transformer V3 / OctFormer / FlatFormer-style block without its
-    relative position bias and dropout.  Not part of the reference.
+    dropout.  Not part of the reference.
 
     ``channels`` = ``num_heads`` * D with D in {16, 32, 64}; ``qkv_bias``: the bias of the ``qkv`` Linear; ``proj``: a
-    Linear(channels, channels) behind the attention; ``scale``: None = D ** -0.5.  ``forward(features, plan) -> [n,
-    channels]``: features [n, channels] in row order; ``qkv`` is cast to the autocast dtype, or to float16 outside
+    Linear(channels, channels) behind the attention; ``scale``: None = D ** -0.5; ``rpe=True``: PTv3's relative position encoding for patches
+    of ``patch_size`` slots -- the module owns ``rpe_table`` (float32 ``[3 * (2 * pos_bnd + 1), num_heads]``, ``pos_bnd
+    = int((4 * patch_size) ** (1 / 3) * 2)``, zeros at first: PTv3's name, shape and layout, so its state dicts load) and
+    ``forward`` takes the level's integer coordinates (int32 ``[n, 3]``, normally ``x.indices[:, 1:]``).
+    ``forward(features, plan, coords=None) -> [n, channels]``: features [n, channels] in row order; ``qkv`` is cast to the autocast dtype, or to float16 outside
     autocast (the kernels take 16-bit rows only), and the result comes back in the features' dtype.  Dead rows give
     zeros ahead of ``proj``."""
 
     def __init__(self, channels: int, num_heads: int, qkv_bias: bool = True, proj: bool = True,
-                 scale: Optional[float] = None):
+                 scale: Optional[float] = None, rpe: bool = False, patch_size: Optional[int] = None):
         super().__init__()
         from spconv_amd.pytorch import _attn
         if int(num_heads) < 1 or int(channels) % int(num_heads) != 0:
@@ -612,14 +615,27 @@ class PatchAttention(torch.nn.Module):
         self.scale = None if scale is None else float(scale)
         self.qkv = torch.nn.Linear(self.channels, 3 * self.channels, bias=bool(qkv_bias))
         self.proj = torch.nn.Linear(self.channels, self.channels) if proj else None
+        self.rpe, self.patch_size, self.pos_bnd = bool(rpe), None, None
+        if self.rpe:
+            if patch_size is None or int(patch_size) < 32 or int(patch_size) % 32 != 0:
+                raise ValueError(f"PatchAttention: rpe=True needs patch_size, a multiple of 32, got {patch_size!r}")
+            self.patch_size, self.pos_bnd = int(patch_size), _attn.default_pos_bnd(int(patch_size))
+            if not 1 <= self.pos_bnd <= 63:
+                raise ValueError(f"PatchAttention: pos_bnd = {self.pos_bnd} of patch_size {patch_size} lies outside 1 .. 63")
+            self.rpe_table = torch.nn.Parameter(torch.zeros((3 * (2 * self.pos_bnd + 1), self.num_heads)))
 
-    def forward(self, features: torch.Tensor, plan) -> torch.Tensor:
+    def forward(self, features: torch.Tensor, plan, coords: Optional[torch.Tensor] = None) -> torch.Tensor:
         from spconv_amd.pytorch import functional as F
         half = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float16
         if half not in (torch.float16, torch.bfloat16):
             half = torch.float16
-        out = F.patch_attention(self.qkv(features).to(half), plan, self.num_heads, self.scale).to(features.dtype)
+        if self.rpe != (coords is not None):
+            raise ValueError("PatchAttention: forward takes coords with rpe=True, and only then")
+        if self.rpe and int(plan.patch_size) != self.patch_size:
+            raise ValueError(f"PatchAttention: built for patches of {self.patch_size}, the plan has {plan.patch_size}")
+        bias = dict(rel_bias=self.rpe_table, coords=coords, pos_bnd=self.pos_bnd) if self.rpe else {}
+        out = F.patch_attention(self.qkv(features).to(half), plan, self.num_heads, self.scale, **bias).to(features.dtype)
         return out if self.proj is None else self.proj(out)
 
     def extra_repr(self) -> str:
-        return f"channels={self.channels}, num_heads={self.num_heads}, scale={self.scale}"
+        return f"channels={self.channels}, num_heads={self.num_heads}, scale={self.scale}, rpe={self.rpe}"
