@@ -1626,6 +1626,45 @@ int spx_patch_attn_bias_bwd(const void *qkv, const void *out, const float *lse, 
                             int H, int D, int dt, float scale, int pos_bnd, void *dqkv, float *d_rel_bias, void *ws,
                             size_t ws_bytes, void *bias_ws, size_t bias_ws_bytes, spx_stream_t stream);
 
+/* ---- neighbour attention and neighbour aggregation over a table of rows (csrc/nattn.hip) ----------------------
+ * Attention of every query over ITS OWN neighbours, read through the table a voxel, ball or k-nearest-neighbour query
+ * returned (rows [M, S], what spx_group_fwd takes): Voxel Transformer's local and dilated attention, the
+ * attention_step1 / attention_step2 pair of Stratified Transformer and Swin3D, attention-pooled RoI grids; and with
+ * mode = 1 the aggregation of pointops (Point Transformer's vector attention behind its weight MLP).  No grouped
+ * [M, S, C] row exists in memory.  Every call: the caller allocates, every grid depends on host-known sizes only
+ * (hipGraph-safe), nothing is read back, nothing synchronises, no atomics and no memset: results are identical run to
+ * run.  The checks that need no pointer come before any pointer is looked at.
+ *
+ * dtype = SPX_F32, SPX_F16 or SPX_BF16 (q, k, v, d_out, out and the row gradients share it); D in {8, 16, 32, 64,
+ * 128}, C = H * D <= 512; S in 1 .. 128, M * S < 2^31.  q, out, d_out, dq = [M, C] and dk, dv = [n, C] contiguous; k, v
+ * = [n, C] with row strides ldk, ldv in ELEMENTS (>= C, a multiple of 16 bytes); every row pointer 16-byte aligned.
+ * Slot (m, s) is a KEY iff 0 <= rows[m, s] < live, live = min(*n_live, n) (n for n_live NULL): the value in the slot
+ * decides, duplicates count.  Per head h:
+ *   mode 0:  x[m, s] = scale * q[m, h] . k[rows[m, s], h] + bias[m, s, h] (bias fp32 [M, S, H] or NULL), P = softmax of x
+ *            over the key slots in fp32, out[m, h] = sum_s P[m, s] v[rows[m, s], h];
+ *   mode 1:  out[m, g] = sum over the key slots of w[m, s, g] v[rows[m, s], g], w = [M, S, H] of w_dt = SPX_F32 or dtype
+ *            (q, k, bias, P are not looked at).
+ * fp32 accumulation in ascending slot, one rounding; a query without a key gets +0; out is written whole.
+ * spx_neighbor_attn_fwd: one launch.  With P != NULL (fp32 [M, S, H], spx_neighbor_attn_ws_bytes) the probabilities
+ * are written whole, +0 at slots that are no keys: what the backward reads.
+ *
+ * spx_neighbor_attn_bwd: pw = that P (mode 0) or w (mode 1).  Query side, one launch: mode 0 writes ds = fp32 [M, S, H]
+ * = P (dP - delta) with dP[s] = d_out . v_s and delta = sum_s P dP in fp32 (the gradient of bias; +0 at slots that are
+ * no keys) and dq = scale * sum_s ds k_s; mode 1 writes ds = dw [M, S, H] in w_dt = dP, +0 at slots that are no keys
+ * (skipped for ds NULL), dq is not looked at.  Key side, one launch, run when dv != NULL: over the transposed list
+ * (offsets [n + 1], list [M * S] = spx_point_groups over the flattened rows), for the entries e of row r in ascending
+ * order, m = e / S: dk[r, h] = scale * sum ds[e, h] q[m, h], dv[r, h] = sum pw[e, h] d_out[m, h], fp32 accumulation,
+ * one rounding, +0 for rows at or beyond live and for rows no entry names; mode 1 writes dv only.  dk and dv come
+ * together in mode 0.  Every list entry is checked against [0, M * S) before it addresses anything. */
+size_t spx_neighbor_attn_ws_bytes(int M, int S, int H);
+int spx_neighbor_attn_fwd(const void *q, const void *k, const void *v, long long ldk, long long ldv, const int32_t *rows,
+                          const float *bias, const void *w, int w_dt, int M, int S, int n, const int32_t *n_live, int H,
+                          int D, int dtype, int mode, float scale, void *out, float *P, spx_stream_t stream);
+int spx_neighbor_attn_bwd(const void *q, const void *k, const void *v, long long ldk, long long ldv, const int32_t *rows,
+                          const void *pw, int w_dt, const void *d_out, const int32_t *offsets, const int32_t *list, int M,
+                          int S, int n, const int32_t *n_live, int H, int D, int dtype, int mode, float scale, void *dq,
+                          void *dk, void *dv, void *ds, spx_stream_t stream);
+
 /* ---- rotated boxes: corners, overlap, IoU and non-maximum suppression (csrc/box.hip) --------------------------
  * The iou3d_nms extension of OpenPCDet / mmdet3d: boxes_iou_bev, boxes_iou3d_gpu, its aligned form and nms_gpu -- the
  * rotated NMS every detector head ends in (SECOND, PointPillars, CenterPoint, VoxelNeXt, Voxel R-CNN, PV-RCNN), the

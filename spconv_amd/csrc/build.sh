@@ -6,7 +6,7 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../lib
-HIP_UNITS="rulebook_subm rulebook_conv rulebook_sorted rulebook_lists igemm igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_gen1 igemm_ws igemm_bwdn pool rowsort norm dense union collapse select pointvoxel interp query sample fps_bucket knn serialize voxelize hash box boxgrad roi center attn"
+HIP_UNITS="rulebook_subm rulebook_conv rulebook_sorted rulebook_lists igemm igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_gen1 igemm_ws igemm_bwdn pool rowsort norm dense union collapse select pointvoxel interp query sample fps_bucket knn serialize voxelize hash box boxgrad roi center attn nattn"
 CPP_UNITS="common counters"
 OBJS=""
 for f in $HIP_UNITS $CPP_UNITS; do OBJS="$OBJS $OUT/$f.o"; done
@@ -26,10 +26,10 @@ stale() {
   for d in $2 *.h ../../include/spconv_amd.h; do [ $d -nt $1 ] && return 0; done
   return 1
 }
-# flags of single units: attn is built without packed fp32 arithmetic (its softmax is scalar fp32 per lane), and so is
-# fps_bucket (every operation of a distance is rounded on its own, per lane)
+# flags of single units: attn and nattn are built without packed fp32 arithmetic (their softmax is scalar fp32 per
+# lane), and so is fps_bucket (every operation of a distance is rounded on its own, per lane)
 unit_flags() {
-  { [ "$1" = attn ] || [ "$1" = fps_bucket ]; } && echo "-Xclang -target-feature -Xclang -packed-fp32-ops"
+  { [ "$1" = attn ] || [ "$1" = nattn ] || [ "$1" = fps_bucket ]; } && echo "-Xclang -target-feature -Xclang -packed-fp32-ops"
   return 0
 }
 pids=()

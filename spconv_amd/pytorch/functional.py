@@ -811,3 +811,11 @@ def patch_attention(qkv, plan, num_heads, scale=None, *, rel_bias=None, coords=N
         return PatchAttentionFunction.apply(qkv, plan, H, D, scale)
     pos_bnd = _attn.check_bias(qkv, plan, H, rel_bias, coords, pos_bnd)
     return PatchAttentionBiasFunction.apply(qkv, rel_bias, coords, plan, H, D, scale, pos_bnd)
+
+
+# neighbour attention and aggregation (csrc/nattn.hip; not part of the reference): every query attends over its own
+# rows of a VoxelNeighbors table -- Voxel Transformer's local attention, the attention_step1 / attention_step2 pair of
+# Stratified Transformer and Swin3D, the aggregation of pointops -- without a grouped [M, S, C] copy
+from spconv_amd.pytorch._nattn import (neighbor_aggregate, neighbor_aggregate_bwd_into,  # noqa: E402,F401
+                                       neighbor_aggregate_into, neighbor_attention, neighbor_attention_bwd_into,
+                                       neighbor_attention_into)

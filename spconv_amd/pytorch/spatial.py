@@ -639,3 +639,36 @@ class PatchAttention(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return f"channels={self.channels}, num_heads={self.num_heads}, scale={self.scale}, rpe={self.rpe}"
+
+
+class NeighborAttention(torch.nn.Module):
+    """Multi-head attention of query rows over their own neighbours (``functional.neighbor_attention``, the kernels of
+    csrc/nattn.hip): the local attention of a Voxel Transformer / Stratified Transformer-style block without its
+    dropout, and the attention pooling of RoI grid points.  Not part of the reference.
+
+    ``channels`` = ``num_heads`` * D with D in {8, 16, 32, 64, 128}, at most 512; ``bias``: the bias of the ``q`` and
+    ``kv`` Linears; ``proj``: a Linear(channels, channels) behind the attention.  ``forward(q_feats, kv_feats, nb,
+    pair_bias=None) -> [M, channels]``: q_feats [M, channels] the queries' features, kv_feats [nb.num_voxels, channels]
+    the rows the table ``nb`` (a ``VoxelNeighbors`` built with ``pad="none"``, and with_groups=True for training) names;
+    the two halves of ``kv`` are read in place.  pair_bias: float32 [M, nsample, num_heads], added to the logits
+    (relative position terms).  float16, bfloat16 and float32 run as they are; queries without a key give zeros ahead
+    of ``proj``."""
+
+    def __init__(self, channels: int, num_heads: int, bias: bool = True, proj: bool = True):
+        super().__init__()
+        from spconv_amd.pytorch import _nattn
+        self.channels = int(channels)
+        self.num_heads, _ = _nattn._heads("NeighborAttention", self.channels, num_heads, "num_heads")
+        self.q = torch.nn.Linear(self.channels, self.channels, bias=bool(bias))
+        self.kv = torch.nn.Linear(self.channels, 2 * self.channels, bias=bool(bias))
+        self.proj = torch.nn.Linear(self.channels, self.channels) if proj else None
+
+    def forward(self, q_feats: torch.Tensor, kv_feats: torch.Tensor, nb, pair_bias: Optional[torch.Tensor] = None):
+        from spconv_amd.pytorch import functional as F
+        kv = self.kv(kv_feats)
+        out = F.neighbor_attention(self.q(q_feats), kv[:, :self.channels], kv[:, self.channels:], nb, self.num_heads,
+                                   bias=pair_bias)
+        return out if self.proj is None else self.proj(out)
+
+    def extra_repr(self) -> str:
+        return f"channels={self.channels}, num_heads={self.num_heads}"
