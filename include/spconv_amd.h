@@ -1665,6 +1665,68 @@ int spx_neighbor_attn_bwd(const void *q, const void *k, const void *v, long long
                           int S, int n, const int32_t *n_live, int H, int D, int dtype, int mode, float scale, void *dq,
                           void *dk, void *dv, void *ds, spx_stream_t stream);
 
+/* ---- selective scan and causal convolution over serialised rows (csrc/scan.hip) --------------------------------
+ * The state-space step of the Mamba backbones that serialise voxels along a curve (Voxel Mamba, LION, PointMamba,
+ * Mamba3D): selective_scan_fn of mamba_ssm with causal_conv1d_fn in front of it, here over RAGGED sequences of rows
+ * read THROUGH an order -- no padded, channel-first [B, Dm, L] copy exists.  Every call: the caller allocates, every
+ * grid depends on host-known sizes only (hipGraph-safe), nothing is read back, nothing synchronises, no atomics and no
+ * memset: results are identical run to run.  The checks that need no pointer come before any pointer is looked at.
+ *
+ * SEQUENCES.  order = int32 [n] or NULL (identity), offsets = int32 [S + 1].  Sequence s is the positions p in
+ * [offsets[s], offsets[s + 1]); its row is order[p].  Positions outside [offsets[0], offsets[S]) belong to no sequence.
+ * Offsets are clamped to [0, n] and to each other, every entry of order is checked against [0, n) before it addresses
+ * anything (a position whose entry is outside is skipped); order is injective over the live positions.  step = +1
+ * walks a sequence in ascending position, step = -1 in descending position.  State never crosses a sequence.
+ *
+ * SCAN.  u, delta, z, y, d_out and their gradients = [n, Dm] in ROW order, channel-last, contiguous; B, C and their
+ * gradients = [n, G, 16]; all of one dtype out of SPX_F32, SPX_F16, SPX_BF16, 16-byte aligned.  A = fp32 [Dm, 16]; D,
+ * delta_bias = fp32 [Dm] or NULL; z may be NULL.  N = 16 states; Dm a multiple of 64, at most 2048; G divides Dm and
+ * Dm / G is a multiple of 64; S >= 1; n * Dm < 2^31 elements.  Per sequence, channel d of group g, fp32 state h[0 .. 16)
+ * from +0, r the row of the position:
+ *   dt   = delta[r, d] (+ delta_bias[d]);  softplus != 0: dt = dt <= 20 ? log1p(exp(dt)) : dt
+ *   h[k] = exp(dt * A[d, k]) * h[k] + dt * B[r, g, k] * u[r, d]
+ *   y    = sum_k C[r, g, k] * h[k] (+ D[d] * u[r, d]);  z given: y *= z * sigmoid(z);  y is rounded once.
+ * Rows of no sequence get +0 (a launch of their own, ahead of the walk); y is written whole.
+ * A sequence is cut into chunks of SPX_SCAN_CHUNK positions that start on sequence boundaries: at most
+ * n / SPX_SCAN_CHUNK + S of them, the count in use stays on the device.  spx_selective_scan_fwd, five launches: the
+ * chunk table; the rows of no sequence; every (chunk, 64 channels) from a zero state, leaving sum dt and the 16 end
+ * states; the carry along every sequence (a chunk's decay is exp(A * sum dt)); every chunk again from its entry state,
+ * writing y.  ws (spx_selective_scan_ws_bytes, 0 for arguments that are refused) keeps the table, sum dt and the entry
+ * states: spx_selective_scan_bwd reads them AS THE FORWARD LEFT THEM (same arguments, same ws) and adds: the rows of
+ * no sequence (+0 in du, ddelta, dz, dB, dC); the chunks' adjoint from zero; its carry; the main walk (a lane per
+ * (channel, state): a chunk recomputed forward from its entry state, then walked back) writing du, ddelta, dz (z
+ * given), dB, dC once, rounded once; and a fixed-order sum of per-chunk fp32 partials into dA = fp32 [Dm, 16], dD
+ * (D given) and ddelta_bias (delta_bias given) = fp32 [Dm].  Every output is written whole.
+ *
+ * CONVOLUTION.  x, out, d_out, dx = [n, Dm] rows as above (Dm a multiple of 64, at most 2048); weight = [Dm, W], W in
+ * 2 .. 4, and bias = [Dm] or NULL, each of the rows' dtype or SPX_F32 (w_dt, b_dt); act 0 = none, 1 = SiLU.
+ *   out[r(p), d] = act(bias[d] + sum_j weight[d, j] * x[r(p - step * (W - 1 - j)), d]),
+ * taps outside the sequence of p are zero; fp32 accumulation in ascending j, one rounding; rows of no sequence get +0
+ * (here order is a permutation of the rows).  spx_causal_conv_rows_fwd: one launch.  spx_causal_conv_rows_bwd, four
+ * launches: d_pre = d_out * act'(pre) per position (fp32, in ws) with one fp32 partial of dweight / dbias per
+ * workgroup; dx by the transposed gather; the partials summed in a fixed order into dweight = fp32 [Dm, W] and dbias =
+ * fp32 [Dm] (dbias may be NULL).  ws holds spx_causal_conv_rows_ws_bytes. */
+#define SPX_SCAN_CHUNK 64
+#define SPX_SCAN_STATES 16
+size_t spx_selective_scan_ws_bytes(int n, int S, int Dm, int G);
+int spx_selective_scan_fwd(const void *u, const void *delta, const float *A, const void *B, const void *C, const float *D,
+                           const void *z, const float *delta_bias, const int32_t *order, const int32_t *offsets, int n,
+                           int S, int Dm, int G, int dtype, int softplus, int step, void *y, void *ws, size_t ws_bytes,
+                           spx_stream_t stream);
+int spx_selective_scan_bwd(const void *u, const void *delta, const float *A, const void *B, const void *C, const float *D,
+                           const void *z, const float *delta_bias, const void *d_out, const int32_t *order,
+                           const int32_t *offsets, int n, int S, int Dm, int G, int dtype, int softplus, int step, void *du,
+                           void *ddelta, float *dA, void *dB, void *dC, float *dD, void *dz, float *ddelta_bias, void *ws,
+                           size_t ws_bytes, spx_stream_t stream);
+size_t spx_causal_conv_rows_ws_bytes(int n, int Dm, int W);
+int spx_causal_conv_rows_fwd(const void *x, const void *weight, int w_dt, const void *bias, int b_dt, const int32_t *order,
+                             const int32_t *offsets, int n, int S, int Dm, int W, int dtype, int act, int step, void *out,
+                             spx_stream_t stream);
+int spx_causal_conv_rows_bwd(const void *x, const void *weight, int w_dt, const void *bias, int b_dt, const void *d_out,
+                             const int32_t *order, const int32_t *offsets, int n, int S, int Dm, int W, int dtype, int act,
+                             int step, void *dx, float *dweight, float *dbias, void *ws, size_t ws_bytes,
+                             spx_stream_t stream);
+
 /* ---- rotated boxes: corners, overlap, IoU and non-maximum suppression (csrc/box.hip) --------------------------
  * The iou3d_nms extension of OpenPCDet / mmdet3d: boxes_iou_bev, boxes_iou3d_gpu, its aligned form and nms_gpu -- the
  * rotated NMS every detector head ends in (SECOND, PointPillars, CenterPoint, VoxelNeXt, Voxel R-CNN, PV-RCNN), the

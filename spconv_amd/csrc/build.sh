@@ -6,7 +6,7 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../lib
-HIP_UNITS="rulebook_subm rulebook_conv rulebook_sorted rulebook_lists igemm igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_gen1 igemm_ws igemm_bwdn pool rowsort norm dense union collapse select pointvoxel interp query sample fps_bucket knn serialize voxelize hash box boxgrad roi center attn nattn"
+HIP_UNITS="rulebook_subm rulebook_conv rulebook_sorted rulebook_lists igemm igemm_wgrad igemm_bf16 igemm_f32 igemm_f64 igemm_i8 igemm_wide igemm_gen1 igemm_ws igemm_bwdn pool rowsort norm dense union collapse select pointvoxel interp query sample fps_bucket knn serialize voxelize hash box boxgrad roi center attn nattn scan"
 CPP_UNITS="common counters"
 OBJS=""
 for f in $HIP_UNITS $CPP_UNITS; do OBJS="$OBJS $OUT/$f.o"; done
@@ -27,9 +27,10 @@ stale() {
   return 1
 }
 # flags of single units: attn and nattn are built without packed fp32 arithmetic (their softmax is scalar fp32 per
-# lane), and so is fps_bucket (every operation of a distance is rounded on its own, per lane)
+# lane), and so are fps_bucket (every operation of a distance is rounded on its own, per lane) and scan (a scalar fp32
+# recurrence per lane)
 unit_flags() {
-  { [ "$1" = attn ] || [ "$1" = nattn ] || [ "$1" = fps_bucket ]; } && echo "-Xclang -target-feature -Xclang -packed-fp32-ops"
+  { [ "$1" = attn ] || [ "$1" = nattn ] || [ "$1" = fps_bucket ] || [ "$1" = scan ]; } && echo "-Xclang -target-feature -Xclang -packed-fp32-ops"
   return 0
 }
 pids=()

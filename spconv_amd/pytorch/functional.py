@@ -819,3 +819,10 @@ def patch_attention(qkv, plan, num_heads, scale=None, *, rel_bias=None, coords=N
 from spconv_amd.pytorch._nattn import (neighbor_aggregate, neighbor_aggregate_bwd_into,  # noqa: E402,F401
                                        neighbor_aggregate_into, neighbor_attention, neighbor_attention_bwd_into,
                                        neighbor_attention_into)
+
+# selective scan and causal convolution over serialised rows (csrc/scan.hip; not part of the reference): the state-space
+# step of the Mamba backbones that serialise voxels -- selective_scan_fn behind causal_conv1d_fn -- over ragged sequences
+# read through the serialisation's order, without a padded [B, Dm, L] copy
+from spconv_amd.pytorch._scan import (ScanSequences, causal_conv1d_rows, causal_conv1d_rows_bwd_into,  # noqa: E402,F401
+                                      causal_conv1d_rows_into, conv_ws_bytes, scan_sequences, scan_ws_bytes,
+                                      selective_scan, selective_scan_bwd_into, selective_scan_into)

@@ -672,3 +672,7 @@ class NeighborAttention(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return f"channels={self.channels}, num_heads={self.num_heads}"
+
+
+# a Mamba block over the serialised rows of a level (csrc/scan.hip); the class lives with its operators
+from spconv_amd.pytorch._scan import SerializedMamba  # noqa: E402,F401
