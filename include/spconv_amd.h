@@ -1411,6 +1411,61 @@ int spx_knn_query(const float *queries, int q_nfeat, const int32_t *q_batch_ids,
                   int32_t *rows, int32_t *count, float *dist2, float *weights, float *out_offsets,
                   spx_stream_t stream);
 
+/* ---- instance clustering: connected components of the radius graph (csrc/cluster.hip) ---------------------------
+ * The grouping stage of the bottom-up instance-segmentation networks (PointGroup, HAIS, SoftGroup, ISBNet's grouping
+ * branch): ballquery_batch_p + bfs_cluster of pointgroup_ops / softgroup.ops, the second of which is a breadth-first
+ * search on the CPU there.  Not part of the reference.  Every call: the caller allocates, nothing is read back, nothing
+ * synchronises, every grid depends on host-known sizes only (hipGraph-safe).  The argument checks that need no pointer
+ * come before any pointer is looked at.  The launches are not counted by spx_launch_count (as those of spx_fps_bucket).
+ *
+ * A point TAKES PART when it lies below the device point count, its batch id is in [0, batch), lo_j <= p_j < hi_j on
+ * every axis (false for NaN and Inf), valid[i] != 0 (valid given) and labels[i] >= 0 (labels given).  Two points that
+ * take part are LINKED when they share the batch id and the label (labels given) and d2 < r2 with d2 exactly
+ * spx_ball_query's: d = q - p per axis, d2 = (d0 * d0 + d1 * d1) + d2 * d2 in fp32, every operation rounded on its own.
+ * A CLUSTER is a connected component of that graph; its ROOT is its smallest point index.
+ *
+ * THE INDEX is built by the caller from existing entries: spx_point2voxel_static in key order over cells of edge
+ * float32(radius * (1 + 2^-6)) -- lows of the range, grid_zyx cells, max_voxels = n_cap -- leaves indices [n_cap, 4]
+ * ({batch, z, y, x} of every cell row) and the level's rank map; spx_point_groups over its pc_voxel_id (num_voxels =
+ * n_cap) gives cell_rows / cell_offsets [n_cap + 1] / cell_list.  The grid must cover the range (every point that takes
+ * part has a cell) and hold at most spx_cluster_max_axis_cells() = 2^14 cells per axis: within that bound the widened
+ * edge keeps two linked points at most one cell apart on every axis whatever (p - lo) / vsize rounds to.
+ *
+ *   spx_cluster_records: clears *status, fills root with -1, and writes into ws per position of cell_list the point as
+ *   a 16-byte record {x, y, z, index} (x = NaN for a point that takes no part) with its cell row, and root[i] = i for
+ *   every point that takes part.  range_xyz_h = host {lo x, y, z, hi x, y, z}; valid = uint8 / bool [n_cap] or NULL;
+ *   labels = int32 [n_cap] or NULL.  Two launches.
+ *   spx_cluster_link: one lane per record walks the half stencil of its cell (its own cell before itself and 13 of the
+ *   26 neighbours, a line of cells being one contiguous run of records found by two rank-map lookups) and unites every
+ *   linked pair in root[] -- used as the parent array of a union-find -- by atomicCAS of the larger root onto the
+ *   smaller, paths halved by atomicMin.  root[x] <= x holds at every instant: every walk descends, and carries an
+ *   explicit budget of 2 n_cap + 8 steps no sound array can spend.  One launch.
+ *   spx_cluster_roots: root[i] = the root of i's component (-1: takes no part), in place.  One launch.
+ *   status (device int32): 0, or bits 1 (a find ran out of budget), 2 (a hook did), 4 (a parent above its child),
+ *   8 (a cell row outside the grid).  Anything but 0 means the inputs of spx_cluster_link were not what is described
+ *   above; the results are then unspecified but every access stays inside the buffers.
+ *   spx_cluster_number: size_offsets int32 [n_cap + 1] = the offsets of spx_point_groups over root (num_voxels = n_cap):
+ *   the component of root r holds size_offsets[r + 1] - size_offsets[r] points.  A component is KEPT when its size is
+ *   >= min_points (min_table NULL), or when (float) size >= min_table[labels[r]] with labels[r] < num_labels (min_table =
+ *   device fp32 [num_labels]).  Kept components are numbered 0, 1, ... by ascending root while the number is below cap;
+ *   cluster_of_point [n_cap] = the number of the point's component or -1; *count = min(kept, cap).  Four launches.
+ *   spx_point_groups over cluster_of_point (num_voxels = cap) then lists every cluster's points in ascending index.
+ *   spx_cluster_ws_bytes: the scratch shared by the four (the records live in it between them); 0 for n_cap outside
+ *   0 .. 2^30 - 8.  The result does not depend on scheduling: every output is a function of the component sets. */
+int spx_cluster_max_axis_cells(void);
+size_t spx_cluster_ws_bytes(int n_cap);
+int spx_cluster_records(const float *points, int nfeat, const int32_t *batch_ids, int n_cap, const int32_t *n_points_dev,
+                        int batch, const int32_t *labels, const void *valid, const float *range_xyz_h,
+                        const int32_t *cell_rows, const int32_t *cell_offsets, const int32_t *cell_list, int32_t *root,
+                        int32_t *status, void *ws, size_t ws_bytes, spx_stream_t stream);
+int spx_cluster_link(int n_cap, int batch, const int *grid_zyx_h, const int32_t *indices, const int32_t *cell_offsets,
+                     const void *rankmap, size_t rankmap_bytes, const int32_t *labels, float r2, int32_t *root,
+                     int32_t *status, void *ws, size_t ws_bytes, spx_stream_t stream);
+int spx_cluster_roots(int n_cap, int32_t *root, int32_t *status, spx_stream_t stream);
+int spx_cluster_number(int n_cap, const int32_t *root, const int32_t *size_offsets, const int32_t *labels, int min_points,
+                       const float *min_table, int num_labels, int cap, int32_t *cluster_of_point, int32_t *count,
+                       void *ws, size_t ws_bytes, spx_stream_t stream);
+
 /* ---- voxel pruning (csrc/select.hip) ---------------------------------------------------------------------
  * Keep the most important rows of a sparse tensor and drop, or process separately, the rest: the pruned down-sampling
  * blocks of SPS-Conv and VoxelNeXt, and every sparse head that keeps its top-scoring voxels.  Stands where a torch

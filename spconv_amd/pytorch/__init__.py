@@ -13,6 +13,7 @@ from spconv_amd.pytorch.identity import Identity
 from spconv_amd.pytorch.spatial import SparseCollapse, SparsePrune, TrilinearDevoxelize, VoxelQueryAndGroup
 from spconv_amd.pytorch.spatial import BallQueryAndGroup, FarthestPointSample, SectorFPS
 from spconv_amd.pytorch.spatial import KNNInterpolate, KNNQueryAndGroup
+from spconv_amd.pytorch.spatial import ClusterPoints
 from spconv_amd.pytorch.spatial import RotatedIoU3DLoss, RotatedNMS
 from spconv_amd.pytorch.spatial import RoIAwarePool3d, RoIPointPool3d
 from spconv_amd.pytorch.spatial import CenterHeadTargets
@@ -27,6 +28,7 @@ from spconv_amd.pytorch.functional import (ball_query, farthest_point_sample, fa
                                            gather_samples)
 from spconv_amd.pytorch.functional import farthest_point_sample_segments, sector_fps, sector_ids
 from spconv_amd.pytorch.functional import knn_interpolate, knn_query, three_nn
+from spconv_amd.pytorch.functional import cluster_points
 from spconv_amd.pytorch.functional import (boxes_iou3d, boxes_iou3d_aligned, boxes_iou_bev, boxes_overlap_bev,
                                            boxes_to_corners, nms_rotated)
 from spconv_amd.pytorch.functional import boxes_iou3d_diff, boxes_iou_bev_diff

@@ -612,6 +612,12 @@ from spconv_amd.pytorch._sample import (SectorBuffers, farthest_point_sample_seg
                                         fps_quota_into, fps_segments_into, sector_buffers, sector_fps,
                                         sector_fps_into, sector_ids, sector_ids_into, sector_table)
 
+# instance clustering (csrc/cluster.hip; not part of the reference): the connected components of the radius graph of a
+# cloud, numbered and listed as PointGroups -- PointGroup's ballquery_batch_p + bfs_cluster, without the host
+from spconv_amd.pytorch._cluster import (ClusterBuffers, ClusterPlan, PointClusters,  # noqa: E402,F401
+                                         cluster_buffers, cluster_cap, cluster_plan, cluster_points,
+                                         cluster_points_into)
+
 # k-nearest-neighbour query and inverse-distance interpolation over raw points (csrc/knn.hip; not part of the reference):
 # the k points that come first under (squared distance, point index), as the tables group_voxels gathers and
 # voxels_to_points_trilinear blends

@@ -255,6 +255,39 @@ class SectorFPS(torch.nn.Module):
                 f"center={self.center}")
 
 
+class ClusterPoints(torch.nn.Module):
+    """Instance proposals of a (shifted) cloud: the connected components of its radius graph
+    (``functional.cluster_points``, the kernels of csrc/cluster.hip) -- ``ballquery_batch_p`` + ``bfs_cluster`` of
+    PointGroup / HAIS / SoftGroup, on the device.  Not part of the reference.
+
+    ``radius`` > 0, ``coors_range_xyz`` six floats (a point outside takes no part), ``min_points`` an int or a device
+    float32 table per label.  ``forward(points, batch_ids, batch_size, labels=None, valid=None, n_points=None) ->
+    PointClusters(cluster_of_point [N], root [N], count, groups, status)``; ``functional.points_to_voxels(feat,
+    clusters.groups, "max")`` pools per cluster.  Clusters are numbered by their smallest point index, members listed in
+    ascending point index.  Nothing is read back.  No gradients: every output is an integer."""
+
+    def __init__(self, radius: float, coors_range_xyz: Sequence[float], min_points=1):
+        super().__init__()
+        from spconv_amd.pytorch import _cluster
+        _cluster.cluster_plan(radius, coors_range_xyz, 1)          # (the ValueErrors of the geometry, up front)
+        if not isinstance(min_points, torch.Tensor) and int(min_points) < 1:
+            raise ValueError(f"ClusterPoints: min_points must be >= 1, got {min_points}")
+        self.radius, self.coors_range_xyz = float(radius), [float(v) for v in coors_range_xyz]
+        self.min_points = min_points
+
+    def forward(self, points: torch.Tensor, batch_ids: Optional[torch.Tensor], batch_size: int,
+                labels: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,
+                n_points: Optional[torch.Tensor] = None):
+        from spconv_amd.pytorch import functional as F
+        return F.cluster_points(points, batch_ids, batch_size, self.radius, self.coors_range_xyz, labels=labels,
+                                valid=valid, min_points=self.min_points, n_points=n_points)
+
+    def extra_repr(self) -> str:
+        table = isinstance(self.min_points, torch.Tensor)
+        return (f"radius={self.radius}, coors_range_xyz={self.coors_range_xyz}, "
+                f"min_points={'table' if table else self.min_points}")
+
+
 class BallQueryAndGroup(torch.nn.Module):
     """The raw points around query points, gathered for a shared MLP (``functional.ball_query`` +
     ``functional.group_voxels``, the kernels of csrc/sample.hip and csrc/query.hip): the ``ball_query`` /
