@@ -1466,6 +1466,60 @@ int spx_cluster_number(int n_cap, const int32_t *root, const int32_t *size_offse
                        const float *min_table, int num_labels, int cap, int32_t *cluster_of_point, int32_t *count,
                        void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* ---- cell-indexed ball query and radius-limited k-NN over raw points (csrc/cellquery.hip) ------------------------
+ * spx_ball_query and spx_knn_query with a spatial index: the same tables, bit for bit, from the records of the 27 cells
+ * round a query instead of the whole scene.  Every call: the caller allocates, there is no workspace, nothing is read
+ * back, nothing synchronises, every grid depends on host-known sizes only (hipGraph-safe), no atomics.  The argument
+ * checks that need no pointer come before any pointer is looked at.  ndim is 3.  The launches are not counted by
+ * spx_launch_count (as those of csrc/roi.hip and csrc/cluster.hip): its key inventory stays as it is.
+ *
+ * THE INDEX is THE INDEX of the clustering section above, built by the caller from the same entries for a radius R:
+ * spx_point2voxel_static in key order over cells of edge vsize = float32(R * (1 + 2^-6)) (indices, the rank map),
+ * spx_point_groups over its pc_voxel_id (cell_rows / cell_offsets [n_cap + 1] / cell_list), a grid that covers the range
+ * with at most spx_cluster_max_axis_cells() cells per axis.  It serves every query radius r with float32(r) <= R.
+ *
+ *   spx_cell_records: records [n_cap] of 16 bytes {x, y, z, index}, one per position of cell_list: the points in CELL
+ *   ORDER.  A point TAKES PART when it lies below *n_points_dev (NULL: n_cap), its batch id (batch_ids NULL: 0) is in
+ *   [0, batch) and lo_j <= p_j < hi_j on every axis (false for NaN and Inf); every other record has x = NaN.
+ *   range_xyz_h = host {lo x, y, z, hi x, y, z}.  records is aligned to 16 bytes.  One launch (none for n_cap = 0).
+ *
+ *   spx_ball_query_cells: queries, q_batch_ids, n_queries_dev, the validity of a query (NaN coordinates are turned
+ *   down, infinite ones find nothing), d2, the predicate d2 < r2, nsample in 1 .. 128, flags, rows, count and out_offsets
+ *   are spx_ball_query's.  The hits of a query are the points that TAKE PART, share its batch id and have d2 < r2; the
+ *   nsample with the lowest point index are kept, in ascending index.  For a cloud inside the range that is
+ *   spx_ball_query's result; a point outside the range is never a hit (the one difference).  A query may lie anywhere:
+ *   its cell is floorf((q_j - lo_j) / vsize) per axis, clamped in float to [-1, grid_j], and it reads the records of the
+ *   3 x 3 x 3 cells round it that exist.  r2 is >= 0 and below vsize^2; the caller keeps float32(r) <= R.
+ *   lo_xyz_h = host {lo x, y, z}; grid_zyx_h, rankmap as spx_cluster_link takes them; points [n_cap, nfeat] are read
+ *   again for out_offsets only.
+ *
+ *   spx_knn_query_cells: the same search, the validity of a query (finite coordinates), k in 1 .. 64, width, eps, flags
+ *   and every table as spx_knn_query has them.  The result of a valid query is the count = min(hits, k) smallest hits
+ *   under the total order (d2, point index), in that order: the leading entries of spx_knn_query's result that lie
+ *   inside the radius.  The weights are normalised over these count entries.
+ *
+ *   KERNEL (both): 16 lanes per query, 4 queries per wave, workgroups of 256; loops are uniform over the wave.  Lanes
+ *   0 .. 8 find the run of records of one (dz, dy) line of the stencil each (two rank-map lookups); the group walks the
+ *   runs 16 records per step, one 16-byte load per lane.  A hit appends its key (the point index; d2 bits << 32 | index
+ *   for the k-NN) to the incoming half of the group's LDS buffer (2 x 128 keys: 1 KB, 2 KB for the k-NN) at a slot taken
+ *   from a ballot; when that half is nearly full, and at the end, every key is ranked by counting the smaller keys and
+ *   moves to slot `rank` of the kept half if rank < nsample.  The result does not depend on the order in which records
+ *   are met.  Requires m_cap * nsample (width) < 2^31.  One launch each (none for m_cap = 0). */
+int spx_cell_records(const float *points, int nfeat, const int32_t *batch_ids, int n_cap, const int32_t *n_points_dev,
+                     int batch, const float *range_xyz_h, const int32_t *cell_rows, const int32_t *cell_offsets,
+                     const int32_t *cell_list, void *records, spx_stream_t stream);
+int spx_ball_query_cells(const float *queries, int q_nfeat, const int32_t *q_batch_ids, int m_cap,
+                         const int32_t *n_queries_dev, const float *points, int nfeat, int n_cap, int batch,
+                         const int *grid_zyx_h, const float *lo_xyz_h, float vsize, const int32_t *cell_offsets,
+                         const void *rankmap, size_t rankmap_bytes, const void *records, int nsample, float r2, int flags,
+                         int32_t *rows, int32_t *count, float *out_offsets, spx_stream_t stream);
+int spx_knn_query_cells(const float *queries, int q_nfeat, const int32_t *q_batch_ids, int m_cap,
+                        const int32_t *n_queries_dev, const float *points, int nfeat, int n_cap, int batch,
+                        const int *grid_zyx_h, const float *lo_xyz_h, float vsize, const int32_t *cell_offsets,
+                        const void *rankmap, size_t rankmap_bytes, const void *records, int k, int width, float r2,
+                        float eps, int flags, int32_t *rows, int32_t *count, float *dist2, float *weights,
+                        float *out_offsets, spx_stream_t stream);
+
 /* ---- voxel pruning (csrc/select.hip) ---------------------------------------------------------------------
  * Keep the most important rows of a sparse tensor and drop, or process separately, the rest: the pruned down-sampling
  * blocks of SPS-Conv and VoxelNeXt, and every sparse head that keeps its top-scoring voxels.  Stands where a torch

@@ -31,6 +31,7 @@
 // loops).  Every index read from a table is range-checked before it addresses anything.
 #include <math.h>
 
+#include "cellrec.h"
 #include "common.h"
 #include "fill.h"
 #include "piece.h"
@@ -45,18 +46,12 @@ namespace {
 
 constexpr int kClBlock = 256;
 constexpr int kClItems = 2048;                       // points of a numbering block
-constexpr int kClMaxAxis = 1 << 14;                  // cells per axis the widened edge is proven for
-constexpr int kClMaxPoints = (1 << 30) - 8;          // 2 n + 8 steps fit a 32-bit budget
+constexpr int kClMaxAxis = kCellMaxAxis;
+constexpr int kClMaxPoints = kCellMaxPoints;         // 2 n + 8 steps fit a 32-bit budget
 static_assert(kClBlock == kScanThreads, "block_rank and block_scan_loop are kScanThreads wide");
 static_assert(kClItems % kClBlock == 0, "a numbering block is whole rounds");
 
 enum : int { kStFind = 1, kStHook = 2, kStParent = 4, kStTable = 8 };
-
-struct __attribute__((aligned(16))) ClRec {
-  float x, y, z;
-  int32_t idx;
-};
-static_assert(sizeof(ClRec) == 16, "one 16-byte load per candidate");
 
 struct ClWs {
   ClRec *recs;
@@ -179,27 +174,14 @@ __device__ __forceinline__ void unite(int32_t *parent, int a, int b, int budget,
 
 // -------------------------------------------------------------------------------------------- link
 
-struct LinkArgs {
-  int n_cap, batch;
-  int dims[3];                                        // z, y, x
+struct LinkArgs : CellLookup {                        // (cellrec.h: the grid, the rank map, the cells' offsets)
   const int4 *indices;                                // {batch, z, y, x} of every cell row
-  const int32_t *cell_offsets;
-  const uint2 *cells;
-  const int32_t *blockoff;
   const int32_t *labels;
   float r2;
   const ClRec *recs;
   const int32_t *rec_cell;
   int32_t *parent, *status;
 };
-
-// occupied cells with a key below `key` (the row `key` has, or would have), and whether `key` is occupied
-__device__ __forceinline__ int rank_lower(const LinkArgs &a, unsigned long long key, bool &occupied) {
-  const uint2 cell = a.cells[key >> 5];
-  const uint32_t bit = 1u << (key & 31);
-  occupied = (cell.x & bit) != 0u;
-  return a.blockoff[key >> 16] + static_cast<int>(cell.y) + __popc(cell.x & (bit - 1u));
-}
 
 __global__ void __launch_bounds__(kClBlock)
 cluster_link_kernel(LinkArgs a) {
@@ -223,20 +205,15 @@ cluster_link_kernel(LinkArgs a) {
     const int dz = line < 3 ? -1 : 0, dy = line < 3 ? line - 1 : line - 4;
     const int zz = c.y + dz, yy = c.z + dy;
     if (zz < 0 || yy < 0 || yy >= a.dims[1]) continue;
-    const unsigned long long base =
-        ((static_cast<unsigned long long>(c.x) * a.dims[0] + zz) * a.dims[1] + yy) * static_cast<unsigned long long>(a.dims[2]);
     int beg, end;
-    bool occ;
     if (line == 4) {                                  // the cell before mine, then the records before me in my cell
-      const int first = c.w > 0 ? rank_lower(a, base + c.w - 1, occ) : v;
-      beg = a.cell_offsets[min(max(first, 0), a.n_cap)];
+      bool occ;
+      const unsigned long long base =
+          ((static_cast<unsigned long long>(c.x) * a.dims[0] + zz) * a.dims[1] + yy) * static_cast<unsigned long long>(a.dims[2]);
+      beg = cell_offset(a, c.w > 0 ? rank_lower(a, base + c.w - 1, occ) : v);
       end = static_cast<int>(pos);
     } else {
-      const int x0 = max(c.w - 1, 0), x1 = min(c.w + 1, a.dims[2] - 1);
-      const int first = rank_lower(a, base + x0, occ);
-      const int last = rank_lower(a, base + x1, occ) + (occ ? 1 : 0);
-      beg = a.cell_offsets[min(max(first, 0), a.n_cap)];
-      end = a.cell_offsets[min(max(last, 0), a.n_cap)];
+      line_run(a, c.x, zz, yy, max(c.w - 1, 0), min(c.w + 1, a.dims[2] - 1), beg, end);
     }
     beg = min(max(beg, 0), total);
     end = min(max(end, beg), total);
@@ -421,9 +398,9 @@ int spx_cluster_link(int n_cap, int batch, const int *grid_zyx_h, const int32_t 
   if (int rc = check_cluster_ws(n_cap, ws, ws_bytes)) return rc;
   const ClWs w(ws, n_cap);
   void *rm = const_cast<void *>(rankmap);
-  LinkArgs a = {n_cap, batch, {grid_zyx_h[0], grid_zyx_h[1], grid_zyx_h[2]}, reinterpret_cast<const int4 *>(indices),
-                cell_offsets, static_cast<const uint2 *>(rm), rank_blockoff(rm, W), labels, r2, w.recs, w.rec_cell, root,
-                status};
+  LinkArgs a = {{n_cap, batch, {grid_zyx_h[0], grid_zyx_h[1], grid_zyx_h[2]}, static_cast<const uint2 *>(rm),
+                 rank_blockoff(rm, W), cell_offsets},
+                reinterpret_cast<const int4 *>(indices), labels, r2, w.recs, w.rec_cell, root, status};
   hipLaunchKernelGGL(cluster_link_kernel, point_grid(n_cap), dim3(kClBlock), 0, static_cast<hipStream_t>(stream), a);
   SPX_LAUNCH_CHECK();
   return 0;

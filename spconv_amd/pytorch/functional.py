@@ -624,6 +624,13 @@ from spconv_amd.pytorch._cluster import (ClusterBuffers, ClusterPlan, PointClust
 from spconv_amd.pytorch._knn import (PointKNN, knn_interpolate, knn_query, knn_query_into,  # noqa: E402,F401
                                      three_nn)
 
+# cell-indexed ball query and radius-limited k-NN (csrc/cellquery.hip; not part of the reference): the spatial index of
+# cluster_points as an object, and ball_query / knn_query over the 27 cells round a query instead of the whole scene
+from spconv_amd.pytorch._cellquery import (CellIndexBuffers, PointCellIndex,  # noqa: E402,F401
+                                           ball_query_cells, ball_query_cells_into, cell_index_buffers,
+                                           knn_query_cells, knn_query_cells_into, point_cell_index,
+                                           point_cell_index_into)
+
 # rotated boxes (csrc/box.hip; not part of the reference): corners, pairwise overlap / IoU in the plane and in space, and
 # a non-maximum suppression that stays on the device -- the iou3d_nms extension of OpenPCDet / mmdet3d
 from spconv_amd.pytorch._box import (BoxCorners, BoxNMS, boxes_iou3d, boxes_iou3d_aligned,  # noqa: E402,F401

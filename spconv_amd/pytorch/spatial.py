@@ -288,6 +288,16 @@ class ClusterPoints(torch.nn.Module):
                 f"min_points={'table' if table else self.min_points}")
 
 
+def _cell_range(op: str, coors_range_xyz, radius, ndim: int):
+    """The range of a module's cell path as a tuple (None: brute force), with the ValueErrors of its geometry."""
+    if coors_range_xyz is None:
+        return None
+    from spconv_amd.pytorch import _cluster
+    if ndim != 3:
+        raise ValueError(f"{op}: the cell path (coors_range_xyz) needs ndim 3, got {ndim}")
+    return _cluster.cluster_plan(radius, coors_range_xyz, 1).coors_range_xyz
+
+
 class BallQueryAndGroup(torch.nn.Module):
     """The raw points around query points, gathered for a shared MLP (``functional.ball_query`` +
     ``functional.group_voxels``, the kernels of csrc/sample.hip and csrc/query.hip): the ``ball_query`` /
@@ -300,9 +310,14 @@ class BallQueryAndGroup(torch.nn.Module):
     int32 or None.  With ``use_xyz`` the offsets from the query to the points, cast to the feature dtype, come in front of
     the C feature columns.  Empty slots repeat slot 0 (pad="first"), so the caller's MLP and a plain ``max(1)`` follow
     in torch; a query without any point gets zeros and count 0.  The gradient goes to feats only, added in a fixed order
-    without atomics; there is no gradient with respect to coordinates."""
+    without atomics; there is no gradient with respect to coordinates.
 
-    def __init__(self, radius: float, nsample: int, use_xyz: bool = True, ndim: int = 3):
+    ``coors_range_xyz`` (default None: the brute-force path above, unchanged): six floats; the module then builds a
+    ``functional.point_cell_index`` of the points per call and queries it (``functional.ball_query_cells``, the kernels
+    of csrc/cellquery.hip): the same result for a cloud inside the range, a point outside it is never a hit.  It needs
+    ndim 3 and a radius > 0."""
+
+    def __init__(self, radius: float, nsample: int, use_xyz: bool = True, ndim: int = 3, coors_range_xyz=None):
         super().__init__()
         from spconv_amd.pytorch import _query, _sample
         if radius is None:
@@ -312,11 +327,18 @@ class BallQueryAndGroup(torch.nn.Module):
         if ndim not in (2, 3):
             raise ValueError(f"BallQueryAndGroup: ndim must be 2 or 3, got {ndim}")
         self.radius, self.use_xyz, self.ndim = float(radius), bool(use_xyz), int(ndim)
+        self.coors_range_xyz = _cell_range("BallQueryAndGroup", coors_range_xyz, radius, ndim)
 
     def forward(self, points: torch.Tensor, p_batch_ids: Optional[torch.Tensor], feats: torch.Tensor, queries: torch.Tensor,
                 q_batch_ids: Optional[torch.Tensor], batch_size: int, n_queries: Optional[torch.Tensor] = None,
                 n_points: Optional[torch.Tensor] = None, groups=None):
         from spconv_amd.pytorch import functional as F
+        want_groups = bool(feats.requires_grad and torch.is_grad_enabled())
+        if self.coors_range_xyz is not None:
+            index = F.point_cell_index(points, p_batch_ids, batch_size, self.radius, self.coors_range_xyz, n_points=n_points)
+            nb = F.ball_query_cells(queries, q_batch_ids, index, self.radius, self.nsample, pad="first",
+                                    with_offsets=self.use_xyz, n_queries=n_queries, with_groups=want_groups)
+            return _group(feats, nb, self.use_xyz)
         nb = F.ball_query(queries, q_batch_ids, points, p_batch_ids, batch_size, self.radius, self.nsample, ndim=self.ndim,
                           pad="first", with_offsets=self.use_xyz, n_queries=n_queries, n_points=n_points,
                           with_groups=bool(feats.requires_grad and torch.is_grad_enabled()), groups=groups)
@@ -374,20 +396,35 @@ class KNNQueryAndGroup(torch.nn.Module):
     offsets from the query to the points, cast to the feature dtype, come in front of the C feature columns.  Slots
     beyond a scene's valid points repeat slot 0 (pad="first"), mirroring ``BallQueryAndGroup``; a query without any
     point gets zeros and count 0.  The gradient goes to feats only, added in a fixed order without atomics; there is
-    no gradient with respect to coordinates."""
+    no gradient with respect to coordinates.
 
-    def __init__(self, k: int, use_xyz: bool = True, ndim: int = 3):
+    ``radius`` and ``coors_range_xyz`` (default None: the brute-force path above, unchanged) come together: the module
+    then builds a ``functional.point_cell_index`` of the points per call and keeps the k nearest INSIDE the radius
+    (``functional.knn_query_cells``, the kernels of csrc/cellquery.hip); a point outside the range is never kept.  It
+    needs ndim 3 and a radius > 0."""
+
+    def __init__(self, k: int, use_xyz: bool = True, ndim: int = 3, radius: Optional[float] = None, coors_range_xyz=None):
         super().__init__()
         from spconv_amd.pytorch import _knn
         self.k, _ = _knn._check_knn("KNNQueryAndGroup", k, None, "first", 0.0)
         if ndim not in (2, 3):
             raise ValueError(f"KNNQueryAndGroup: ndim must be 2 or 3, got {ndim}")
         self.use_xyz, self.ndim = bool(use_xyz), int(ndim)
+        if (radius is None) != (coors_range_xyz is None):
+            raise ValueError("KNNQueryAndGroup: radius and coors_range_xyz come together (the cell path) or not at all")
+        self.radius = None if radius is None else float(radius)
+        self.coors_range_xyz = _cell_range("KNNQueryAndGroup", coors_range_xyz, radius, ndim)
 
     def forward(self, points: torch.Tensor, p_batch_ids: Optional[torch.Tensor], feats: torch.Tensor, queries: torch.Tensor,
                 q_batch_ids: Optional[torch.Tensor], batch_size: int, n_queries: Optional[torch.Tensor] = None,
                 n_points: Optional[torch.Tensor] = None, groups=None):
         from spconv_amd.pytorch import functional as F
+        if self.coors_range_xyz is not None:
+            index = F.point_cell_index(points, p_batch_ids, batch_size, self.radius, self.coors_range_xyz, n_points=n_points)
+            knn = F.knn_query_cells(queries, q_batch_ids, index, self.k, self.radius, pad="first", with_offsets=self.use_xyz,
+                                    n_queries=n_queries,
+                                    with_groups=bool(feats.requires_grad and torch.is_grad_enabled()))
+            return _group(feats, knn.neighbors(), self.use_xyz)
         knn = F.knn_query(queries, q_batch_ids, points, p_batch_ids, batch_size, self.k, ndim=self.ndim, pad="first",
                           with_dist2=False, with_offsets=self.use_xyz, n_queries=n_queries, n_points=n_points,
                           with_groups=bool(feats.requires_grad and torch.is_grad_enabled()), groups=groups)
