@@ -1774,6 +1774,44 @@ int spx_neighbor_attn_bwd(const void *q, const void *k, const void *v, long long
                           int S, int n, const int32_t *n_live, int H, int D, int dtype, int mode, float scale, void *dq,
                           void *dk, void *dv, void *ds, spx_stream_t stream);
 
+/* ---- kernel point convolution over a table of rows (csrc/kpconv.hip) -------------------------------------------
+ * Rigid KPConv with the linear influence and sum aggregation (KPFCNN; the encoders of Predator, D3Feat and
+ * GeoTransformer), read through the table a voxel, ball or k-nearest-neighbour query returned: rows [M, S] and offsets
+ * fp32 [M, S, 3] = neighbour - query.  With valid(m, s) = 0 <= rows[m, s] < live (live = min(*n_live, n); the value in
+ * the slot decides, duplicates count):
+ *   h(m, s, k)  = valid ? max(0, 1 - ||offsets[m, s] - kernel_points[k]|| / sigma) : 0      fp32, rounded to dtype
+ *   WF[m, k, :] = sum_s h(m, s, k) feats[rows[m, s], :]                                      fp32 sum, rounded once
+ *   out[m, :]   = (sum_k WF[m, k, :] @ weight[k]) * (normalize ? 1 / max(1, valid slots of m) : 1), rounded once
+ * Both products run on matrix instructions; no [M, S, Cin] and no [M, S, K] tensor exists in memory.  Every call: the
+ * caller allocates, every grid depends on host-known sizes only (hipGraph-safe), nothing is read back, nothing
+ * synchronises, no atomics and no memset: results are identical run to run.  The checks that need no pointer come
+ * before any pointer is looked at.
+ *
+ * dtype = SPX_F16 or SPX_BF16 (feats, weight, out, wf, d_out, dg, dweight share it); K in 1 .. 16, kernel_points = fp32
+ * [K, 3]; Cin and Cout multiples of 16 in 16 .. 256; S in 1 .. 128, M * S * 3 < 2^31; sigma > 0.  feats = [n, Cin], weight
+ * = [K, Cin, Cout], out = [M, Cout], contiguous and 16-byte aligned.  A query at or beyond *n_queries (NULL: M) gets
+ * zeros, a query without a valid slot +0; out is written whole.
+ *
+ * spx_kpconv_fwd: two launches (the weight into fragment order in ws, spx_kpconv_ws_bytes(.., backward = 0); the
+ * convolution).  wf != NULL: WF is also written as [M, K, Cin] in dtype, whole -- what the weight side of a backward
+ * reads, 2 * K * Cin bytes per query.
+ *
+ * spx_kpconv_bwd: with dg != NULL one launch writes dg = [M, S, Cin] in dtype whole, dg[m, s, :] = sum_k h(m, s, k)
+ * dWF[m, k, :] with dWF = (d_out * norm) @ weight^T (h is recomputed; nothing but wf is kept from the forward);
+ * spx_group_bwd over the table's transposed list turns dg into the gradient of feats.  With dweight != NULL two
+ * launches write dweight[k] = sum_m WF[m, k, :]^T (d_out[m] * norm): fp32 partials per chunk of queries in ws, added in
+ * a fixed order, rounded once; with normalize the first launch also runs (for d_out * norm, kept in ws).  ws holds
+ * spx_kpconv_ws_bytes(.., backward = 1), needed for dweight only.  No gradient to kernel_points, sigma or offsets. */
+size_t spx_kpconv_ws_bytes(int M, int K, int Cin, int Cout, int backward);
+int spx_kpconv_fwd(const void *feats, const int32_t *rows, const float *offsets, const float *kernel_points,
+                   const void *weight, int M, int S, int n, const int32_t *n_queries, const int32_t *n_live, int K, int Cin,
+                   int Cout, int dtype, float sigma, int normalize, void *out, void *wf, void *ws, size_t ws_bytes,
+                   spx_stream_t stream);
+int spx_kpconv_bwd(const void *wf, const int32_t *rows, const float *offsets, const float *kernel_points,
+                   const void *weight, const void *d_out, int M, int S, int n, const int32_t *n_queries,
+                   const int32_t *n_live, int K, int Cin, int Cout, int dtype, float sigma, int normalize, void *dg,
+                   void *dweight, void *ws, size_t ws_bytes, spx_stream_t stream);
+
 /* ---- selective scan and causal convolution over serialised rows (csrc/scan.hip) --------------------------------
  * The state-space step of the Mamba backbones that serialise voxels along a curve (Voxel Mamba, LION, PointMamba,
  * Mamba3D): selective_scan_fn of mamba_ssm with causal_conv1d_fn in front of it, here over RAGGED sequences of rows

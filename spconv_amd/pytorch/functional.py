@@ -833,6 +833,12 @@ from spconv_amd.pytorch._nattn import (neighbor_aggregate, neighbor_aggregate_bw
                                        neighbor_aggregate_into, neighbor_attention, neighbor_attention_bwd_into,
                                        neighbor_attention_into)
 
+# kernel point convolution (csrc/kpconv.hip; not part of the reference): rigid KPConv with the linear influence over a
+# VoxelNeighbors table and its offsets -- KPFCNN's layer, the encoder of Predator, D3Feat and GeoTransformer -- as two
+# MFMA products per query tile, without a grouped [M, S, Cin] copy or an [M, S, K] influence tensor
+from spconv_amd.pytorch._kpconv import (KPConvFunction, kpconv, kpconv_bwd_into, kpconv_into,  # noqa: E402,F401
+                                        kpconv_ws_bytes)
+
 # selective scan and causal convolution over serialised rows (csrc/scan.hip; not part of the reference): the state-space
 # step of the Mamba backbones that serialise voxels -- selective_scan_fn behind causal_conv1d_fn -- over ragged sequences
 # read through the serialisation's order, without a padded [B, Dm, L] copy

@@ -744,5 +744,51 @@ class NeighborAttention(torch.nn.Module):
         return f"channels={self.channels}, num_heads={self.num_heads}"
 
 
+class KPConv(torch.nn.Module):
+    """Rigid kernel point convolution (``functional.kpconv``, the MFMA kernels of csrc/kpconv.hip): the ``KPConv`` layer
+    of KPConv-PyTorch with the linear influence and sum aggregation.  Not part of the reference.
+
+    ``weight`` is [K, in_channels, out_channels] -- the shape of KPConv-PyTorch's kernel weights, so a checkpoint's
+    tensor loads as it is -- with its ``kaiming_uniform_(a=sqrt(5))`` initialisation; ``kernel_points`` a float32 buffer [K, 3], K in 1 .. 16.  Without
+    kernel_points the layer takes a fixed 15-point layout scaled by ``kp_radius``: the centre, the six axis points and
+    the eight cube diagonals, all at distance kp_radius (deterministic: no optimisation, no files).  ``sigma``: the
+    extent of a kernel point's influence; ``normalize``: divide by the valid neighbours; channels are multiples of 16
+    in 16 .. 256.  ``forward(feats, nb) -> [M, out_channels]``: feats [nb.num_voxels, in_channels] in float16 or
+    bfloat16 (nothing is cast; the weight is used in feats' dtype), nb a ``VoxelNeighbors`` built with
+    with_offsets=True, and with_groups=True for training."""
+
+    def __init__(self, in_channels: int, out_channels: int, sigma: float, kernel_points: Optional[torch.Tensor] = None,
+                 kp_radius: Optional[float] = None, normalize: bool = False, bias: bool = False):
+        super().__init__()
+        from spconv_amd.pytorch import _kpconv
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        _kpconv._channels("in_channels", self.in_channels)
+        _kpconv._channels("out_channels", self.out_channels)
+        self.sigma, self.normalize = float(sigma), bool(normalize)
+        if not self.sigma > 0:
+            raise ValueError(f"KPConv: sigma must be > 0, got {sigma}")
+        if kernel_points is None:
+            if kp_radius is None or not float(kp_radius) > 0:
+                raise ValueError(f"KPConv: without kernel_points, kp_radius must be > 0, got {kp_radius!r}")
+            kernel_points = _kpconv.default_kernel_points(kp_radius)
+        kernel_points = torch.as_tensor(kernel_points, dtype=torch.float32).detach().clone()
+        if kernel_points.dim() != 2 or kernel_points.shape[1] != 3 or not 1 <= kernel_points.shape[0] <= _kpconv.MAX_POINTS:
+            raise ValueError(f"KPConv: kernel_points is [K, 3] with K in 1 .. {_kpconv.MAX_POINTS}, got "
+                             f"{tuple(kernel_points.shape)}")
+        self.register_buffer("kernel_points", kernel_points)
+        self.weight = torch.nn.Parameter(torch.zeros((kernel_points.shape[0], self.in_channels, self.out_channels)))
+        self.bias = torch.nn.Parameter(torch.zeros(self.out_channels)) if bias else None
+        torch.nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)
+
+    def forward(self, feats: torch.Tensor, nb) -> torch.Tensor:
+        from spconv_amd.pytorch import functional as F
+        out = F.kpconv(feats, nb, self.kernel_points, self.weight.to(feats.dtype), self.sigma, self.normalize)
+        return out if self.bias is None else out + self.bias.to(out.dtype)
+
+    def extra_repr(self) -> str:
+        return (f"in_channels={self.in_channels}, out_channels={self.out_channels}, K={self.kernel_points.shape[0]}, "
+                f"sigma={self.sigma}, normalize={self.normalize}")
+
+
 # a Mamba block over the serialised rows of a level (csrc/scan.hip); the class lives with its operators
 from spconv_amd.pytorch._scan import SerializedMamba  # noqa: E402,F401
