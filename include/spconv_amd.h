@@ -1812,6 +1812,50 @@ int spx_kpconv_bwd(const void *wf, const int32_t *rows, const float *offsets, co
                    const int32_t *n_live, int K, int Cin, int Cout, int dtype, float sigma, int normalize, void *dg,
                    void *dweight, void *ws, size_t ws_bytes, spx_stream_t stream);
 
+/* ---- fused set abstraction over a table of rows (csrc/groupmax.hip) --------------------------------------------
+ * Gather, position term, ReLU, one linear layer and the max over the samples: the body of PointNet++'s SA layer,
+ * pointnet2_stack's StackSAModuleMSG and Voxel R-CNN's grouped MLP, read through the table a voxel, ball or
+ * k-nearest-neighbour query returned: rows [M, S] and, with pos_weight, offsets fp32 [M, S, 3].  With valid(m, s) = 0 <=
+ * rows[m, s] < live (live = min(*n_live, n); the value in the slot decides, duplicates count) and m < *n_queries:
+ *   x[m, s, c]  = feats[rows[m, s], c] + sum_d offsets[m, s, d] pos_weight[d, c] + in_bias[c]   fp32; relu_in: max(x, 0);
+ *                                                                                               rounded to dtype once
+ *   y[m, s, :]  = x[m, s, :] @ weight                                                           fp32 sum
+ *   out[m, co]  = max over the valid s of y[m, s, co], rounded once; arg[m, co] = the LOWEST valid s that attains the
+ *                 fp32 maximum
+ * The product runs on matrix instructions with the weight resident in LDS; no [M, S, Cin] tensor exists in the forward.
+ * Every call: the caller allocates, every grid depends on host-known sizes only (hipGraph-safe), nothing is read back,
+ * nothing synchronises, no atomics and no memset: results are identical run to run.  The checks that need no pointer
+ * come before any pointer is looked at.  Rows at or beyond live are never read.
+ *
+ * dtype = SPX_F16 or SPX_BF16 (feats, weight, out, d_out, dg, dweight share it); Cin and Cout multiples of 16 in 16 ..
+ * 256; S in 1 .. 128, M * S * 3 < 2^31.  feats = [n, Cin], weight = [Cin, Cout], out = [M, Cout], contiguous and 16-byte
+ * aligned; pos_weight = fp32 [3, Cin] or NULL (then offsets is not read), in_bias = fp32 [Cin] or NULL; arg = uint8 [M,
+ * Cout], 8-byte aligned, NULL when no backward follows.  A query without a valid slot, or at or beyond *n_queries (NULL:
+ * M), gets out = +0 and arg = 255; out and arg are written whole.
+ *
+ * spx_group_linear_max_fwd: two launches (the weight into fragment order in ws, spx_group_linear_max_ws_bytes(..,
+ * backward = 0); the op).
+ *
+ * spx_group_linear_max_bwd: with dY[m, s, co] = d_out[m, co] where s == arg[m, co], else 0, and x recomputed from the
+ * table (nothing but arg is kept from the forward): dX = dY @ weight^T, zero where the fp32 x <= 0 under relu_in.  dg !=
+ * NULL: dg = [M, S, Cin] in dtype, written whole, = dX rounded once; spx_group_bwd over the table's transposed list turns
+ * dg into the gradient of feats.  dpos = fp32 [3, Cin] / dbias = fp32 [Cin] (each or NULL): sum over (m, s) of offsets[m,
+ * s, d] dX[m, s, c] / of dX[m, s, c], taken from the fp32 dX as one partial per workgroup, added in workgroup order.
+ * dweight != NULL: dweight[c, co] = sum_m x[m, arg[m, co], c] d_out[m, co], fp32 partials per chunk of queries added in
+ * chunk order, rounded once.  One launch for dg / dpos / dbias, one for the partials of dweight, one that adds the
+ * partials.  ws holds spx_group_linear_max_ws_bytes(.., backward = 1), needed for dweight, dpos or dbias.  No gradient
+ * to offsets or the table. */
+size_t spx_group_linear_max_ws_bytes(int M, int S, int Cin, int Cout, int backward);
+int spx_group_linear_max_fwd(const void *feats, const int32_t *rows, const float *offsets, const void *weight,
+                             const float *pos_weight, const float *in_bias, int M, int S, int n, const int32_t *n_queries,
+                             const int32_t *n_live, int Cin, int Cout, int dtype, int relu_in, void *out, uint8_t *arg,
+                             void *ws, size_t ws_bytes, spx_stream_t stream);
+int spx_group_linear_max_bwd(const void *feats, const int32_t *rows, const float *offsets, const void *weight,
+                             const float *pos_weight, const float *in_bias, const uint8_t *arg, const void *d_out, int M,
+                             int S, int n, const int32_t *n_queries, const int32_t *n_live, int Cin, int Cout, int dtype,
+                             int relu_in, void *dg, void *dweight, float *dpos, float *dbias, void *ws, size_t ws_bytes,
+                             spx_stream_t stream);
+
 /* ---- selective scan and causal convolution over serialised rows (csrc/scan.hip) --------------------------------
  * The state-space step of the Mamba backbones that serialise voxels along a curve (Voxel Mamba, LION, PointMamba,
  * Mamba3D): selective_scan_fn of mamba_ssm with causal_conv1d_fn in front of it, here over RAGGED sequences of rows

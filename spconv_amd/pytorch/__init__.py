@@ -19,12 +19,14 @@ from spconv_amd.pytorch.spatial import RoIAwarePool3d, RoIPointPool3d
 from spconv_amd.pytorch.spatial import CenterHeadTargets
 from spconv_amd.pytorch.spatial import NeighborAttention, PatchAttention, SerializedMamba
 from spconv_amd.pytorch.spatial import KPConv
+from spconv_amd.pytorch.spatial import GroupLinearMax
 from spconv_amd.pytorch.vfe import DynamicVFE
 from spconv_amd.pytorch.functional import point_groups, points_to_voxels, voxels_to_points
 from spconv_amd.pytorch.functional import point_corners, voxels_to_points_trilinear
 from spconv_amd.pytorch.functional import group_voxels, voxel_query
 from spconv_amd.pytorch.functional import neighbor_aggregate, neighbor_attention
 from spconv_amd.pytorch.functional import kpconv
+from spconv_amd.pytorch.functional import group_linear_max
 from spconv_amd.pytorch.functional import causal_conv1d_rows, scan_sequences, selective_scan
 from spconv_amd.pytorch.functional import (ball_query, farthest_point_sample, farthest_point_sample_method,  # noqa: F401
                                            gather_samples)

@@ -839,6 +839,12 @@ from spconv_amd.pytorch._nattn import (neighbor_aggregate, neighbor_aggregate_bw
 from spconv_amd.pytorch._kpconv import (KPConvFunction, kpconv, kpconv_bwd_into, kpconv_into,  # noqa: E402,F401
                                         kpconv_ws_bytes)
 
+# fused set abstraction (csrc/groupmax.hip; not part of the reference): gather, position term, ReLU, one linear layer and
+# the max over the samples of a VoxelNeighbors table -- the body of PointNet++'s SA layer, StackSAModuleMSG and Voxel
+# R-CNN's grouped MLP -- on MFMA kernels with the weight resident in LDS, without a grouped [M, S, Cin] copy
+from spconv_amd.pytorch._groupmax import (GroupLinearMaxFunction, group_linear_max,  # noqa: E402,F401
+                                          group_linear_max_bwd_into, group_linear_max_into, group_linear_max_ws_bytes)
+
 # selective scan and causal convolution over serialised rows (csrc/scan.hip; not part of the reference): the state-space
 # step of the Mamba backbones that serialise voxels -- selective_scan_fn behind causal_conv1d_fn -- over ragged sequences
 # read through the serialisation's order, without a padded [B, Dm, L] copy

@@ -790,5 +790,43 @@ class KPConv(torch.nn.Module):
                 f"sigma={self.sigma}, normalize={self.normalize}")
 
 
+class GroupLinearMax(torch.nn.Module):
+    """Fused set abstraction (``functional.group_linear_max``, the MFMA kernels of csrc/groupmax.hip): gather through a
+    ``VoxelNeighbors`` table, position term, ReLU, one linear layer and the max over the samples -- what stays of a
+    PointNet++ / ``StackSAModuleMSG`` / Voxel R-CNN grouped MLP once its first layer is hoisted to the rows.  Not part
+    of the reference.
+
+    ``weight`` is [in_channels, out_channels]; with use_xyz the layer also owns ``pos_weight`` [3, in_channels] and
+    ``in_bias`` [in_channels] (the first layer's xyz columns and bias).  Parameters are float32; the weight is cast to the
+    rows' dtype per call, pos_weight and in_bias are used as they are.  Channels are multiples of 16 in 16 .. 256.
+    ``forward(feats, nb) -> [M, out_channels]``: feats [nb.num_voxels, in_channels] in float16 or bfloat16 (nothing is
+    cast), nb built with with_offsets=True for use_xyz and with_groups=True for training.  A training-mode BatchNorm over
+    the grouped pre-activations is not served (``functional.group_linear_max``)."""
+
+    def __init__(self, in_channels: int, out_channels: int, use_xyz: bool = True, relu_in: bool = True):
+        super().__init__()
+        from spconv_amd.pytorch import _groupmax
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        _groupmax._channels("in_channels", self.in_channels)
+        _groupmax._channels("out_channels", self.out_channels)
+        self.use_xyz, self.relu_in = bool(use_xyz), bool(relu_in)
+        self.weight = torch.nn.Parameter(torch.zeros((self.in_channels, self.out_channels)))
+        torch.nn.init.kaiming_uniform_(self.weight.t(), a=5 ** 0.5)
+        if self.use_xyz:
+            self.pos_weight = torch.nn.Parameter(torch.zeros((3, self.in_channels)))
+            self.in_bias = torch.nn.Parameter(torch.zeros((self.in_channels,)))
+            torch.nn.init.kaiming_uniform_(self.pos_weight.t(), a=5 ** 0.5)
+        else:
+            self.pos_weight = self.in_bias = None
+
+    def forward(self, feats: torch.Tensor, nb) -> torch.Tensor:
+        from spconv_amd.pytorch import functional as F
+        return F.group_linear_max(feats, nb, self.weight.to(feats.dtype), self.pos_weight, self.in_bias, self.relu_in)
+
+    def extra_repr(self) -> str:
+        return (f"in_channels={self.in_channels}, out_channels={self.out_channels}, use_xyz={self.use_xyz}, "
+                f"relu_in={self.relu_in}")
+
+
 # a Mamba block over the serialised rows of a level (csrc/scan.hip); the class lives with its operators
 from spconv_amd.pytorch._scan import SerializedMamba  # noqa: E402,F401
